@@ -11,6 +11,11 @@ mask for the next forward.  Inputs (env state, observations, weights) are reside
 Workload at N=1: BASELINE configs[1] -- CrowdSimVarNum-v0, 20 humans, 4096 envs, HH+HR attention on.  With N ranks
 every rank owns 4096 envs (weak scaling, global env indices rank*4096.., no data-path collective in the rollout).
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, de-phases and warms up, times the K steps and prints the headline line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the script measures: the roofline of the dominant kernels (instrumented timed window), the step
+decomposition, the worst-case window, the PPO and drop-in legs, the HBM traffic, the other BASELINE configs and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed as .npy files; the inputs are seeded, so two builds compare output for output.
 """
 import argparse
 import datetime
@@ -164,7 +169,7 @@ def other_configs_leg(timeout_s=150, budget_s=330):
     this box and build (a separate process: its own simulator batch, policy and -- configs[3] -- the GST predictor + VecPretextNormalize
     in the loop), env-steps/s, ms per step and the per-kernel medians of its step."""
     import subprocess
-    common = ["--gpus", "1", "--no-cpu-baseline", "--no-ppo", "--no-worst-case", "--no-dropin", "--no-pmc-traffic", "--no-other-configs"]
+    common = ["--gpus", "1", "--full", "--no-cpu-baseline", "--no-ppo", "--no-worst-case", "--no-dropin", "--no-pmc-traffic", "--no-other-configs"]
     legs = [
         ("configs[2]: CrowdSimPred-v0, 20 humans, const_vel predictor, 4096 envs per GPU", ["--env-name", "CrowdSimPred-v0", "--envs", "4096", "--steps", "60", "--warmup", "20"]),
         ("configs[3]: CrowdSimPredRealGST-v0, 20 humans, GST predictor + wrapper in the loop, 2048 envs per GPU",
@@ -259,6 +264,30 @@ def dropin_leg(E, H, env_name, steps=24):
                     "env_step includes the per-step device-to-host transfer and synchronisation, loop_python is train.py's own per-env list building"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` (leading dimension = the env) as out_dir/<name>.npy, float64 where the source is float64
+    or a 32/64-bit integer, float32 otherwise.  Above `limit` bytes in all, every array keeps the same fixed, seeded sample of envs, whose
+    indices go to env_index.npy."""
+    import numpy as np
+    host = {}
+    for k, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        host[k] = a.astype(np.float64 if a.dtype in (np.float64, np.int32, np.int64) else np.float32)
+    E = next(iter(host.values())).shape[0]
+    per_env = sum(a.nbytes for a in host.values()) // E
+    budget = limit - 1024 * (len(host) + 1)                  # room for the .npy headers
+    if per_env * E > budget:
+        idx = np.sort(np.random.default_rng(0).choice(E, max(1, budget // (per_env + 8)), replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -287,7 +316,7 @@ def main():
                          "cn_policy_set_post_hh_hook: every kernel runs undisturbed and 5-12 us shorter, but the cross-stream event that releases the "
                          "tail costs 15-25 us and its chain ends after the robot-node kernel: 0.325-0.33 ms per step, profiles/HISTORY.md)")
     ap.add_argument("--pregen-budget-us", type=float, default=None, help="time budget of one launch of the episode pre-generation kernel (library default 40)")
-    ap.add_argument("--timeline-out", default=None, help="write the stamped timeline of the decomposition window (all kernels of 24 steps) to this file")
+    ap.add_argument("--timeline-out", default=None, help="with --full: write the stamped timeline of the decomposition window (all kernels of 24 steps) to this file")
     ap.add_argument("--no-worst-case", action="store_true", help="skip the second timed window with every human detected (all H rows live)")
     ap.add_argument("--no-pmc-traffic", action="store_true",
                     help="do not measure roofline.traffic in this run (two short rocprofv3 --pmc child runs of this script, ~1 min); the committed "
@@ -301,6 +330,15 @@ def main():
     ap.add_argument("--gemm", choices=["fused", "bf16x3", "fp32"], default="fused",
                     help="human-human block: 'fused' = one persistent kernel, bf16x3 split-precision MFMA (default); 'bf16x3' = the same arithmetic "
                          "as separate launches (round-1 path); 'fp32' = exact fp32 MFMA, separate launches")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the timed window instrumented for the roofline (HIP events and "
+                         "device-clock stamps of the dominant kernels), the step decomposition, the worst-case window, the PPO and drop-in legs, "
+                         "the HBM traffic, the other BASELINE configs and the CPU baseline; the --no-* flags drop single legs of a --full run.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed window, write what its last step computed (the sim step's observation, reward, done, info, episode "
+                         "return / length and done mask; the policy forward's value, action, log-prob and hidden state) as DIR/<name>.npy in "
+                         "float32 / float64 (rank 0; a seeded sample of the envs when the arrays exceed 64 MB)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -412,36 +450,54 @@ def main():
     # range, no resets); after a few hundred steps of sampled actions the envs are spread over their episodes
     for _ in range(args.dephase + (args.dephase & 1)):
         step(it); it += 1
-    # the measurement instruments are switched on BEFORE the warm-up so that their one-off costs (the first record of a timing event
-    # switches the queue's profiling on: some hundred microseconds; the first launches with a stamp argument) fall into it, not into
-    # the timed window; what they collected during the warm-up is dropped below
-    pol.set_profiling(ev_every)
-    stamps = StepStamps(args.steps, ("hh_fused", "rn_fused"))
+    # drain the pre-roll before the warm-up: enqueued behind a long backlog, the warm-up would not settle the runtime, and the first
+    # launches of a short timed window would pay for it (20 steps: 0.30 instead of 0.28 ms per step)
+    torch.cuda.synchronize()
+    # --full: the measurement instruments are switched on BEFORE the warm-up so that their one-off costs (the first record of a timing
+    # event switches the queue's profiling on: some hundred microseconds; the first launches with a stamp argument) fall into it, not
+    # into the timed window; what they collected during the warm-up is dropped below.  A plain run times the steps uninstrumented.
+    stamps = None
+    if args.full:
+        pol.set_profiling(ev_every)
+        stamps = StepStamps(args.steps, ("hh_fused", "rn_fused"))
     for _ in range(args.warmup + (args.warmup & 1)):
         step(it); it += 1
     torch.cuda.synchronize()
-    pol.reset_profile()
+    if stamps is not None:
+        pol.reset_profile()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        stamps.next()
+        if stamps is not None:
+            stamps.next()
         step(it + i)
     t_enq = time.perf_counter() - t0       # host time to ENQUEUE the K steps (well below `elapsed` = the host runs ahead of the device)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    stamps.close()
-    pol.set_profiling(False)
-    prof_ms, prof_n = pol.get_profile()
-    ev_samples = sorted(pol.get_profile_samples())
-    dev_hh = sorted(x * 1e-3 for x in stamps.durations_us("hh_fused"))     # ms, every launch of the window
-    dev_rn = sorted(x * 1e-3 for x in stamps.durations_us("rn_fused"))
-    dev_rows = stamps.counts("hh_fused")
-    hh_starts = [a_ for (_, k_, a_, _) in stamps.table() if k_ == "hh_fused"]
-    step_intervals = [round(b_ - a_, 1) for a_, b_ in zip(hh_starts[:-1], hh_starts[1:])]     # us between consecutive human-human launches
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before anything else runs on the batch: i = it + steps - 1 wrote masks2[i & 1] and out["hxs"]
+        last = it + args.steps - 1
+        dump = {k: obs[k] for k in ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num", "visible_masks")}
+        dump.update(reward=env.reward, done=env.done, info=env.info, episode_return=env.ep_return, episode_length=env.ep_len,
+                    not_done=masks2[last & 1], value=out["value"], action=out["action"], logp=out["logp"], hxs=out["hxs"])
+        if gst is not None:
+            dump["policy_spatial_edges"] = pol_obs["spatial_edges"]      # the GST-wrapped edges the forward read
+        dump_outputs(args.dump_outputs, dump)
+    step_intervals = []
+    if stamps is not None:
+        stamps.close()
+        pol.set_profiling(False)
+        prof_ms, prof_n = pol.get_profile()
+        ev_samples = sorted(pol.get_profile_samples())
+        dev_hh = sorted(x * 1e-3 for x in stamps.durations_us("hh_fused"))     # ms, every launch of the window
+        dev_rn = sorted(x * 1e-3 for x in stamps.durations_us("rn_fused"))
+        dev_rows = stamps.counts("hh_fused")
+        hh_starts = [a_ for (_, k_, a_, _) in stamps.table() if k_ == "hh_fused"]
+        step_intervals = [round(b_ - a_, 1) for a_, b_ in zip(hh_starts[:-1], hh_starts[1:])]     # us between consecutive human-human launches
     it += args.steps            # the hxs / masks ping-pong follows the step index: advance by exactly the steps taken
     plan_hdr = env.row_plan[:8].tolist() if (gst is None and env.row_plan.numel() >= 8) else None   # [1] workgroups [6] tiles of the last planned launch
     per_rank = None
@@ -462,7 +518,7 @@ def main():
     # step decomposition: a separate short window (NOT the timed one) in which every kernel of the step stamps the device clock --
     # per-kernel durations and, because the clock is global, where each sits on the step's timeline (gaps, side-stream overlap)
     decomp = None
-    if rank == 0:
+    if args.full and rank == 0:
         DEC = 24
         dst = StepStamps(DEC)
         for i in range(DEC):
@@ -527,7 +583,7 @@ def main():
                         s_, a_[0], a_[len(a_) // 2], a_[int(len(a_) * 0.9)], a_[-1], l_[0] if len(l_) else -1, l_[len(l_) // 2] if len(l_) else -1, l_[-1] if len(l_) else -1,
                         b_[0], b_[len(b_) // 2], b_[-1], (np.int64(pg_end) - np.int64(lane_end)) * 0.01))
     worst = None
-    if not args.no_worst_case and rank == 0:
+    if args.full and not args.no_worst_case and rank == 0:
         force_all_detected[0] = True
         pol_obs["detected_human_num"].fill_(float(H))
         for _ in range(10):
@@ -547,7 +603,7 @@ def main():
     # gradients are all-reduced once per optimiser step (one flat bucket), time = max over ranks of the last update
     ppo = None
     pol.attach_env_tail(None)
-    if not args.no_ppo and args.env_name != "CrowdSimPredRealGST-v0":
+    if args.full and not args.no_ppo and args.env_name != "CrowdSimPredRealGST-v0":
         del env, pol, net
         torch.cuda.empty_cache()
         from crowdnav_prediction_attngraph_amd.trainer import train
@@ -601,69 +657,15 @@ def main():
             dist.destroy_process_group()
         return
     dropin = None
-    if not args.no_dropin and args.env_name != "CrowdSimPredRealGST-v0":
+    if args.full and not args.no_dropin and args.env_name != "CrowdSimPredRealGST-v0":
         try:
             dropin = dropin_leg(E, H, args.env_name)
         except Exception as exc:
             dropin = {"error": "%s: %s" % (type(exc).__name__, exc)}
     total_env_steps = E * world * args.steps
     value = total_env_steps / elapsed
-    # dominant kernel: timed (a) by HIP event brackets on its stream, one per launch (median over the window; a bracket also contains
-    # the dispatch of the launch, and whatever the launch waits for when the host is not ahead), and (b) by the kernel's own stamps of
-    # the device clock (first workgroup in -> last wavefront out, every launch).  The roofline uses the MEDIAN event bracket.
-    M = (sum(dev_rows) / len(dev_rows)) if dev_rows else prof_n[1] / max(prof_n[0], 1)   # mean live (env, human) rows per launch
     fused = args.gemm == "fused"
-    # fused: the timed kernel is the whole human-human block; its algorithmic work = the three dense layers on the live rows
-    # (embedding_layer.2 128->512, folded q|k|v 512->1536, folded out_proj∘spatial_linear 512->256); the D->128 input layer and the
-    # attention core (<2 % of it) are left out of the count
-    qkv_flops = 2.0 * M * (128 * 512 + 512 * 1536 + 512 * 256) if fused else 2.0 * M * 512 * 1536
-    mid = lambda v: v[len(v) // 2] if v else 0.0    # noqa: E731  (v sorted)
-    qkv_ms = mid(ev_samples) if ev_samples else prof_ms[0] / max(prof_n[0], 1)
-    achieved = qkv_flops / (qkv_ms * 1e-3) / 1e12 if qkv_ms > 0 else 0.0
-    F = flops_per_env_step(H, D)
     split = args.gemm in ("bf16x3", "fused")
-    # the split runs 3 bf16 MFMA passes per algorithmic product, so its attainable algorithmic rate is the bf16 peak / 3
-    peak = PEAK_BF16_MFMA_TFLOPS / 3.0 if split else PEAK_F32_MFMA_TFLOPS
-    team_max = int(os.environ.get("CN_HH_TEAM_MAX", "63"))   # hh_fused.hip: the two-team kernel takes crowds of <= 63 humans (round 6), the wide one 64
-    kname = (("hh_fused_wide_kernel" if (H > team_max or os.environ.get("CN_HH_WIDE", "0") not in ("", "0")) else "hh_fused_kernel") + " (v_mfma_f32_16x16x32_bf16, 3 passes hi*hi+hi*lo+lo*hi): embedding -> q|k|v -> attention -> out_proj∘spatial_linear in one launch" if fused else
-             "gemm3_nt_kernel<128,NONE> (v_mfma_f32_32x32x16_bf16, 3 passes hi*hi+hi*lo+lo*hi): folded q|k|v projection" if split
-             else "gemm_nt_kernel<128,NONE> (v_mfma_f32_32x32x2_f32): folded q|k|v projection")
-    # HBM traffic of the dominant kernel: bench.py cannot run rocprofv3 on itself, so the number comes from the committed PMC passes of
-    # the same command (tools/profile_step.sh -> tools/mk_traffic.py) -- but only while their stamp (sha256 of csrc/hh_fused.hip at the
-    # time of the measurement) matches the kernel source of this build; a stale constant is reported as null with the reason
-    traffic = None
-    traffic_note = None
-    if fused and world == 1 and not args.no_pmc_traffic:
-        try:
-            child = ["--gpus", "1", "--steps", "10", "--warmup", "10", "--dephase", str(args.dephase), "--envs", str(E), "--humans", str(H), "--env-name", args.env_name,
-                     "--no-cpu-baseline", "--no-ppo", "--no-worst-case", "--no-dropin", "--no-pmc-traffic", "--no-other-configs", "--tail", args.tail] + (["--randomized"] if args.randomized else [])
-            tl = pmc_traffic_live(child)
-            traffic = tl["hbm_bytes_per_launch"]
-            rows_c = tl["child_live_rows"] or M
-            alg_c = rows_c * (D + 256) * 4 + 3932160
-            traffic_note = ("measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (two child runs of this script on this box, %d "
-                            "hh_fused_kernel launches each): FETCH_SIZE %.0f KB x 2 (gfx950 correction) + WRITE_SIZE %.0f KB per launch = %.2fx the algorithmic "
-                            "%.1f MB (%d live rows x (%d input + 256 output floats) + the 3.93 MB weight image once)"
-                            % (tl["launches"], tl["fetch_size_kb"], tl["write_size_kb"], traffic / alg_c, alg_c / 1e6, rows_c, D))
-        except Exception as exc:
-            traffic_note = "live PMC measurement failed (%s: %s)" % (type(exc).__name__, str(exc)[:200])
-    if traffic is None and fused and (args.env_name, E, H, args.randomized) == ("CrowdSimVarNum-v0", 4096, 20, False):
-        # fall back to the committed PMC passes of the same command (tools/profile_step.sh -> tools/mk_traffic.py) -- but only while their stamp
-        # (sha256 of csrc/hh_fused.hip at the time of the measurement) matches the kernel source of this build
-        import glob
-        import hashlib
-        src = os.path.join(ROOT, "crowdnav_prediction_attngraph_amd", "csrc", "hh_fused.hip")
-        stamp = hashlib.sha256(open(src, "rb").read()).hexdigest()[:16] if os.path.exists(src) else None
-        cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
-        tj = json.load(open(cands[-1])) if cands else None
-        prev = (traffic_note + "; ") if traffic_note else ""
-        if tj is not None and stamp is not None and tj.get("kernel_source_sha16") == stamp:
-            traffic = tj["hbm_bytes_per_launch_corrected"]
-            traffic_note = prev + ("constant from the committed passes of the same kernel source (%s, stamp %s; %.2fx the algorithmic bytes)"
-                                   % (os.path.basename(cands[-1]), stamp, tj["ratio"]))
-        else:
-            traffic_note = prev + ("null: the newest committed PMC result (%s) was measured on a different hh_fused.hip (stamp %s, this build %s)"
-                                   % (os.path.basename(cands[-1]) if cands else "none", tj.get("kernel_source_sha16") if tj else None, stamp))
     line = {
         "metric": "env-steps/sec (sim+policy fwd) at %d humans" % H, "value": round(value, 1), "unit": "env-steps/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
@@ -673,48 +675,103 @@ def main():
                                    "BASELINE configs[1]: " if (args.env_name, H, E, args.randomized) == ("CrowdSimVarNum-v0", 20, 4096, False) else ("randomized humans, " if args.randomized else ""), args.env_name, H, E),
                    "envs_per_gpu": E, "humans": H, "parallelism": "dp%d (envs sharded, no rollout collective)" % world,
                    "policy_init": "orthogonal, torch.manual_seed(425)", "sampled_actions": True, "side_stream_tail": args.tail},
-        "roofline": {"bound": "mfma", "kernel": "%s, M=%d live rows of %d%s" % (kname, M, E * H, "" if fused else ", N=1536 K=512"),
-                     "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": traffic,
-                     "note": ("achieved = algorithmic 2*M*(128*512+512*1536+512*256) / launch time (hipEvents on the kernel's stream); peak = 2500 TFLOP/s dense bf16 "
-                              "MFMA / 3 passes of the hi/lo split; executed bf16 MFMA rate = %.1f TFLOP/s" % (3 * achieved)) if fused else
-                             ("achieved = algorithmic 2*M*N*K / launch time (hipEvents on the kernel's stream); peak = 2500 TFLOP/s dense bf16 "
-                              "MFMA / 3 passes of the hi/lo split; executed bf16 MFMA rate = %.1f TFLOP/s" % (3 * achieved)) if split else
-                             "achieved = algorithmic 2*M*N*K / launch time on exact fp32 MFMA",
-                     "traffic_note": traffic_note, "launch_ms": round(qkv_ms, 4), "launches": len(ev_samples), "mean_detected_humans": round(M / E, 3),
-                     "launch_ms_events": {"median": round(mid(ev_samples), 4), "min": round(ev_samples[0], 4) if ev_samples else None,
-                                          "max": round(ev_samples[-1], 4) if ev_samples else None, "mean": round(sum(ev_samples) / max(len(ev_samples), 1), 4),
-                                          "samples": len(ev_samples), "every": ev_every,
-                                          "what": "hipEventElapsedTime of a (record, launch, record) bracket on the kernel's stream, per launch of the timed window"},
-                     "launch_ms_device": {"median": round(mid(dev_hh), 4), "min": round(dev_hh[0], 4) if dev_hh else None,
-                                          "max": round(dev_hh[-1], 4) if dev_hh else None, "samples": len(dev_hh),
-                                          "frac_at_median": round(qkv_flops / (mid(dev_hh) * 1e-3) / 1e12 / peak, 4) if dev_hh and fused else None,
-                                          "what": "the kernel's own stamps of the 100 MHz device clock: first workgroup in -> last wavefront out, every launch of the timed window"},
-                     "rn_fused_launch_ms_device": {"median": round(mid(dev_rn), 4), "min": round(dev_rn[0], 4) if dev_rn else None,
-                                                   "max": round(dev_rn[-1], 4) if dev_rn else None, "samples": len(dev_rn)},
-                     "whole_step": {"reference_graph_flops_per_env_step": F,
-                                    "reference_graph_tflops_equivalent": round(value / world * F / 1e12, 2),
-                                    "note": "env-steps/s x the FLOPs of the reference's dense, unfolded forward; NOT a hardware utilisation "
-                                            "(padded humans are not computed and affine pairs are folded)"}},
     }
     line["config"]["dephase_steps"] = args.dephase
-    if fused:
-        rl = line["roofline"]
-        step_s = elapsed / args.steps
-        rn_flops = 0.79e6 * E                                  # robot-node kernel: 0.79 MFLOP per env
-        rl["frac_of_dense_bf16_algorithmic"] = round(achieved / PEAK_BF16_MFMA_TFLOPS, 4)
-        rl["whole_step_frac"] = round((qkv_flops + rn_flops) / step_s / 1e12 / peak, 4)
-        rl["fractions_note"] = ("frac = dominant kernel against the three-pass ceiling (dense bf16 / 3); frac_of_dense_bf16_algorithmic = the same algorithmic rate "
-                                "against the dense bf16 peak itself (%.0f TFLOP/s); whole_step_frac = (human-human + robot-node FLOPs of a step) / ms_per_step "
-                                "against the three-pass ceiling: the simulator kernels and the launch gaps of the step count as time, not as work" % PEAK_BF16_MFMA_TFLOPS)
-        if plan_hdr is not None and plan_hdr[0] == 0x52504C4E and qkv_ms > 0:
-            tiles = int(plan_hdr[6])
-            rl["l2_weight_stream_TBps"] = round(tiles * 3932160 / (qkv_ms * 1e-3) / 1e12, 2)
-            rl["l2_weight_stream_note"] = "%d tiles of the last planned launch x the 3.93 MB weight image each tile streams L2 -> registers / launch time" % tiles
-        if decomp is not None:
-            rl["step_decomposition_us"] = dict(decomp.get("median_us", {}), **{"gap_" + k: v for k, v in decomp.get("median_gap_us", {}).items()})
-            if "median_step_us" in decomp:
-                rl["step_decomposition_us"]["step"] = decomp["median_step_us"]
+    if args.full:
+        # dominant kernel: timed (a) by HIP event brackets on its stream, one per launch (median over the window; a bracket also contains
+        # the dispatch of the launch, and whatever the launch waits for when the host is not ahead), and (b) by the kernel's own stamps of
+        # the device clock (first workgroup in -> last wavefront out, every launch).  The roofline uses the MEDIAN event bracket.
+        M = (sum(dev_rows) / len(dev_rows)) if dev_rows else prof_n[1] / max(prof_n[0], 1)   # mean live (env, human) rows per launch
+        # fused: the timed kernel is the whole human-human block; its algorithmic work = the three dense layers on the live rows
+        # (embedding_layer.2 128->512, folded q|k|v 512->1536, folded out_proj∘spatial_linear 512->256); the D->128 input layer and the
+        # attention core (<2 % of it) are left out of the count
+        qkv_flops = 2.0 * M * (128 * 512 + 512 * 1536 + 512 * 256) if fused else 2.0 * M * 512 * 1536
+        mid = lambda v: v[len(v) // 2] if v else 0.0    # noqa: E731  (v sorted)
+        qkv_ms = mid(ev_samples) if ev_samples else prof_ms[0] / max(prof_n[0], 1)
+        achieved = qkv_flops / (qkv_ms * 1e-3) / 1e12 if qkv_ms > 0 else 0.0
+        F = flops_per_env_step(H, D)
+        # the split runs 3 bf16 MFMA passes per algorithmic product, so its attainable algorithmic rate is the bf16 peak / 3
+        peak = PEAK_BF16_MFMA_TFLOPS / 3.0 if split else PEAK_F32_MFMA_TFLOPS
+        team_max = int(os.environ.get("CN_HH_TEAM_MAX", "63"))   # hh_fused.hip: the two-team kernel takes crowds of <= 63 humans (round 6), the wide one 64
+        kname = (("hh_fused_wide_kernel" if (H > team_max or os.environ.get("CN_HH_WIDE", "0") not in ("", "0")) else "hh_fused_kernel") + " (v_mfma_f32_16x16x32_bf16, 3 passes hi*hi+hi*lo+lo*hi): embedding -> q|k|v -> attention -> out_proj∘spatial_linear in one launch" if fused else
+                 "gemm3_nt_kernel<128,NONE> (v_mfma_f32_32x32x16_bf16, 3 passes hi*hi+hi*lo+lo*hi): folded q|k|v projection" if split
+                 else "gemm_nt_kernel<128,NONE> (v_mfma_f32_32x32x2_f32): folded q|k|v projection")
+        # HBM traffic of the dominant kernel: bench.py cannot run rocprofv3 on itself, so the number comes from the committed PMC passes of
+        # the same command (tools/profile_step.sh -> tools/mk_traffic.py) -- but only while their stamp (sha256 of csrc/hh_fused.hip at the
+        # time of the measurement) matches the kernel source of this build; a stale constant is reported as null with the reason
+        traffic = None
+        traffic_note = None
+        if fused and world == 1 and not args.no_pmc_traffic:
+            try:
+                child = ["--gpus", "1", "--steps", "10", "--warmup", "10", "--dephase", str(args.dephase), "--envs", str(E), "--humans", str(H), "--env-name", args.env_name,
+                         "--full", "--no-cpu-baseline", "--no-ppo", "--no-worst-case", "--no-dropin", "--no-pmc-traffic", "--no-other-configs", "--tail", args.tail] + (["--randomized"] if args.randomized else [])
+                tl = pmc_traffic_live(child)
+                traffic = tl["hbm_bytes_per_launch"]
+                rows_c = tl["child_live_rows"] or M
+                alg_c = rows_c * (D + 256) * 4 + 3932160
+                traffic_note = ("measured in this run: rocprofv3 --kernel-trace --pmc FETCH_SIZE / WRITE_SIZE (two child runs of this script on this box, %d "
+                                "hh_fused_kernel launches each): FETCH_SIZE %.0f KB x 2 (gfx950 correction) + WRITE_SIZE %.0f KB per launch = %.2fx the algorithmic "
+                                "%.1f MB (%d live rows x (%d input + 256 output floats) + the 3.93 MB weight image once)"
+                                % (tl["launches"], tl["fetch_size_kb"], tl["write_size_kb"], traffic / alg_c, alg_c / 1e6, rows_c, D))
+            except Exception as exc:
+                traffic_note = "live PMC measurement failed (%s: %s)" % (type(exc).__name__, str(exc)[:200])
+        if traffic is None and fused and (args.env_name, E, H, args.randomized) == ("CrowdSimVarNum-v0", 4096, 20, False):
+            # fall back to the committed PMC passes of the same command (tools/profile_step.sh -> tools/mk_traffic.py) -- but only while their stamp
+            # (sha256 of csrc/hh_fused.hip at the time of the measurement) matches the kernel source of this build
+            import glob
+            import hashlib
+            src = os.path.join(ROOT, "crowdnav_prediction_attngraph_amd", "csrc", "hh_fused.hip")
+            stamp = hashlib.sha256(open(src, "rb").read()).hexdigest()[:16] if os.path.exists(src) else None
+            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))
+            tj = json.load(open(cands[-1])) if cands else None
+            prev = (traffic_note + "; ") if traffic_note else ""
+            if tj is not None and stamp is not None and tj.get("kernel_source_sha16") == stamp:
+                traffic = tj["hbm_bytes_per_launch_corrected"]
+                traffic_note = prev + ("constant from the committed passes of the same kernel source (%s, stamp %s; %.2fx the algorithmic bytes)"
+                                       % (os.path.basename(cands[-1]), stamp, tj["ratio"]))
+            else:
+                traffic_note = prev + ("null: the newest committed PMC result (%s) was measured on a different hh_fused.hip (stamp %s, this build %s)"
+                                       % (os.path.basename(cands[-1]) if cands else "none", tj.get("kernel_source_sha16") if tj else None, stamp))
+        line["roofline"] = {"bound": "mfma", "kernel": "%s, M=%d live rows of %d%s" % (kname, M, E * H, "" if fused else ", N=1536 K=512"),
+                            "achieved": round(achieved, 2), "peak": round(peak, 1), "unit": "TFLOP/s",
+                            "frac": round(achieved / peak, 4), "traffic": traffic,
+                            "note": ("achieved = algorithmic 2*M*(128*512+512*1536+512*256) / launch time (hipEvents on the kernel's stream); peak = 2500 TFLOP/s dense bf16 "
+                                     "MFMA / 3 passes of the hi/lo split; executed bf16 MFMA rate = %.1f TFLOP/s" % (3 * achieved)) if fused else
+                                    ("achieved = algorithmic 2*M*N*K / launch time (hipEvents on the kernel's stream); peak = 2500 TFLOP/s dense bf16 "
+                                     "MFMA / 3 passes of the hi/lo split; executed bf16 MFMA rate = %.1f TFLOP/s" % (3 * achieved)) if split else
+                                    "achieved = algorithmic 2*M*N*K / launch time on exact fp32 MFMA",
+                            "traffic_note": traffic_note, "launch_ms": round(qkv_ms, 4), "launches": len(ev_samples), "mean_detected_humans": round(M / E, 3),
+                            "launch_ms_events": {"median": round(mid(ev_samples), 4), "min": round(ev_samples[0], 4) if ev_samples else None,
+                                                 "max": round(ev_samples[-1], 4) if ev_samples else None, "mean": round(sum(ev_samples) / max(len(ev_samples), 1), 4),
+                                                 "samples": len(ev_samples), "every": ev_every,
+                                                 "what": "hipEventElapsedTime of a (record, launch, record) bracket on the kernel's stream, per launch of the timed window"},
+                            "launch_ms_device": {"median": round(mid(dev_hh), 4), "min": round(dev_hh[0], 4) if dev_hh else None,
+                                                 "max": round(dev_hh[-1], 4) if dev_hh else None, "samples": len(dev_hh),
+                                                 "frac_at_median": round(qkv_flops / (mid(dev_hh) * 1e-3) / 1e12 / peak, 4) if dev_hh and fused else None,
+                                                 "what": "the kernel's own stamps of the 100 MHz device clock: first workgroup in -> last wavefront out, every launch of the timed window"},
+                            "rn_fused_launch_ms_device": {"median": round(mid(dev_rn), 4), "min": round(dev_rn[0], 4) if dev_rn else None,
+                                                          "max": round(dev_rn[-1], 4) if dev_rn else None, "samples": len(dev_rn)},
+                            "whole_step": {"reference_graph_flops_per_env_step": F,
+                                           "reference_graph_tflops_equivalent": round(value / world * F / 1e12, 2),
+                                           "note": "env-steps/s x the FLOPs of the reference's dense, unfolded forward; NOT a hardware utilisation "
+                                                   "(padded humans are not computed and affine pairs are folded)"}}
+        if fused:
+            rl = line["roofline"]
+            step_s = elapsed / args.steps
+            rn_flops = 0.79e6 * E                                  # robot-node kernel: 0.79 MFLOP per env
+            rl["frac_of_dense_bf16_algorithmic"] = round(achieved / PEAK_BF16_MFMA_TFLOPS, 4)
+            rl["whole_step_frac"] = round((qkv_flops + rn_flops) / step_s / 1e12 / peak, 4)
+            rl["fractions_note"] = ("frac = dominant kernel against the three-pass ceiling (dense bf16 / 3); frac_of_dense_bf16_algorithmic = the same algorithmic rate "
+                                    "against the dense bf16 peak itself (%.0f TFLOP/s); whole_step_frac = (human-human + robot-node FLOPs of a step) / ms_per_step "
+                                    "against the three-pass ceiling: the simulator kernels and the launch gaps of the step count as time, not as work" % PEAK_BF16_MFMA_TFLOPS)
+            if plan_hdr is not None and plan_hdr[0] == 0x52504C4E and qkv_ms > 0:
+                tiles = int(plan_hdr[6])
+                rl["l2_weight_stream_TBps"] = round(tiles * 3932160 / (qkv_ms * 1e-3) / 1e12, 2)
+                rl["l2_weight_stream_note"] = "%d tiles of the last planned launch x the 3.93 MB weight image each tile streams L2 -> registers / launch time" % tiles
+            if decomp is not None:
+                rl["step_decomposition_us"] = dict(decomp.get("median_us", {}), **{"gap_" + k: v for k, v in decomp.get("median_gap_us", {}).items()})
+                if "median_step_us" in decomp:
+                    rl["step_decomposition_us"]["step"] = decomp["median_step_us"]
     if world > 1:
         try:
             ver = ".".join(str(x) for x in torch.cuda.nccl.version())
@@ -728,7 +785,7 @@ def main():
             "rccl_ranks_equal_n_gpus": line["collectives"]["rccl_ranks"] == world,
             "one_distinct_device_per_rank": len(set(ids)) == world,
             "every_rank_reported": per_rank is not None and len(per_rank) == world and all(x > 0 for x in per_rank),
-            "gradient_allreduce_timed": (ppo or {}).get("grad_allreduce_ms_per_step") is not None or args.no_ppo,
+            "gradient_allreduce_timed": (ppo or {}).get("grad_allreduce_ms_per_step") is not None or args.no_ppo or not args.full,
             "value_is_sum_of_ranks_over_slowest_clock": True,
             "note": "weak scaling: every rank owns --envs envs (global env indices rank * E ..); value = E x N x steps / max over ranks of the timed window; "
                     "no scaling efficiency is claimed in this line -- the driver derives it from the per-N values"}
@@ -749,9 +806,9 @@ def main():
         line["worst_case_all_detected"] = worst
     if ppo is not None:
         line["ppo"] = ppo
-    if not args.no_other_configs and world == 1 and (args.env_name, H, E, args.randomized) == ("CrowdSimVarNum-v0", 20, 4096, False):
+    if args.full and not args.no_other_configs and world == 1 and (args.env_name, H, E, args.randomized) == ("CrowdSimVarNum-v0", 20, 4096, False):
         line["other_baseline_configs_1gpu"] = other_configs_leg()
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         line["cpu_baseline"] = cpu_baseline_threads(H, args.env_name, args.cpu_threads)
         line["gpu_over_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
         # SURVEY 8d CPU baseline (ii) / BASELINE.md 4.1: the REAL reference Python, timed in the build container (it cannot travel to this

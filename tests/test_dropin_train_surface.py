@@ -1,17 +1,11 @@
-"""Build-container only (skipped where /root/reference is absent, e.g. on the GPU box): the reference's own train.py / test.py
-against dropin/.
+"""The reference's own train.py / test.py / collect_data.py against dropin/, through the interface they expect of it
+(tests/golden/dropin_surface.json, names read off the scripts' syntax trees by tests/golden/make_golden_dropin_surface.py):
 
-1. Static: every `import` / `from ... import name` of the two scripts resolves with dropin/ first on sys.path, and every
-   attribute the scripts read off the objects the shims hand out exists on the mirrors.
-2. Dynamic: the reference's train.py is EXECUTED, unmodified, for one PPO update with `--no-cuda`; the only substitution is the
-   simulator behind `make_vec_envs` (the C oracle on CPU instead of the device batch, tests/oracle_vec_env.py) -- Policy,
-   RolloutStorage, PPO, arguments, Config and the crowd_sim registry are the shims' real objects.  It must write the
-   checkpoint train.py:213-219 writes, loadable by the mirror.
-The reference file itself never ships: nothing here copies it, the test only runs it where it lies."""
-import ast
+1. every `from ... import name` of the three scripts resolves with dropin/ first on sys.path;
+2. every attribute train.py reads off the objects the shims hand out exists on the mirrors."""
 import importlib
+import json
 import os
-import runpy
 import sys
 
 import pytest
@@ -19,9 +13,8 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DROPIN = os.path.join(ROOT, "dropin")
-REF = "/root/reference"
-
-pytestmark = pytest.mark.skipif(not os.path.isfile(os.path.join(REF, "train.py")), reason="needs the reference checkout (build container only)")
+with open(os.path.join(ROOT, "tests", "golden", "dropin_surface.json")) as _f:
+    SURFACE = json.load(_f)
 
 THIRD_PARTY = {"os", "shutil", "time", "collections", "numpy", "torch", "pandas", "matplotlib", "logging", "argparse", "sys", "importlib", "copy", "tqdm"}
 
@@ -39,35 +32,20 @@ def dropin_path():
 
 @pytest.mark.parametrize("script", ["train.py", "test.py", "collect_data.py"])
 def test_every_import_of_the_reference_scripts_resolves_against_dropin(script, dropin_path):
-    tree = ast.parse(open(os.path.join(REF, script)).read())
     checked = 0
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.module and node.module.split(".")[0] not in THIRD_PARTY:
-            mod = importlib.import_module(node.module)
-            assert os.path.abspath(mod.__file__).startswith(DROPIN), "%s resolved outside dropin/: %s" % (node.module, mod.__file__)
-            for alias in node.names:
-                if alias.name == "*":
-                    assert getattr(mod, "__all__", None), "%s: `import *` needs __all__" % node.module
+    for module, names in SURFACE["import_from"][script]:
+        if module.split(".")[0] not in THIRD_PARTY:
+            mod = importlib.import_module(module)
+            assert os.path.abspath(mod.__file__).startswith(DROPIN), "%s resolved outside dropin/: %s" % (module, mod.__file__)
+            for name in names:
+                if name == "*":
+                    assert getattr(mod, "__all__", None), "%s: `import *` needs __all__" % module
                     for n in mod.__all__:
                         assert hasattr(mod, n)
                 else:
-                    assert hasattr(mod, alias.name) or importlib.import_module(node.module + "." + alias.name), (node.module, alias.name)
+                    assert hasattr(mod, name) or importlib.import_module(module + "." + name), (module, name)
                 checked += 1
     assert checked >= (3 if script == "collect_data.py" else 6)
-
-
-def _attr_chains(tree, roots):
-    """dotted attribute reads `root.a.b` for the given root variable names"""
-    out = set()
-    for node in ast.walk(tree):
-        if isinstance(node, ast.Attribute):
-            parts, cur = [node.attr], node.value
-            while isinstance(cur, ast.Attribute):
-                parts.append(cur.attr)
-                cur = cur.value
-            if isinstance(cur, ast.Name) and cur.id in roots:
-                out.add((cur.id,) + tuple(reversed(parts)))
-    return out
 
 
 def test_attribute_surface_of_train_py_exists_on_the_mirrors(dropin_path):
@@ -92,8 +70,7 @@ def test_attribute_surface_of_train_py_exists_on_the_mirrors(dropin_path):
     agent = PPO(pol, args.clip_param, args.ppo_epoch, args.num_mini_batch, args.value_loss_coef, args.entropy_coef, lr=args.lr, eps=args.eps,
                 max_grad_norm=args.max_grad_norm)
     objs = {"actor_critic": pol, "rollouts": ro, "agent": agent, "algo_args": args, "config": config, "env_config": config}
-    tree = ast.parse(open(os.path.join(REF, "train.py")).read())
-    chains = _attr_chains(tree, set(objs) | {"envs"})
+    chains = {tuple(c) for c in SURFACE["train_py_attr_chains"] if c[0] in set(objs) | {"envs"}}
     assert len(chains) > 40
     for chain in sorted(chains):
         if chain[0] == "envs":
@@ -108,148 +85,3 @@ def test_attribute_surface_of_train_py_exists_on_the_mirrors(dropin_path):
             cur = getattr(cur, a)
             if callable(cur) and not isinstance(cur, torch.nn.Module):
                 break
-
-
-def test_reference_train_py_runs_unchanged_for_one_update(dropin_path, tmp_path, monkeypatch):
-    import rl.networks.envs as shim_envs
-    from tests import oracle_vec_env
-    monkeypatch.setattr(shim_envs, "make_vec_envs", oracle_vec_env.make_vec_envs)   # the ONLY substitution: simulator -> CPU oracle
-    out = tmp_path / "run"
-    monkeypatch.chdir(DROPIN)              # train.py copies crowd_nav/configs/config.py and arguments.py relative to the cwd
-    monkeypatch.setattr(sys, "argv", ["train.py", "--no-cuda", "--env-name", "CrowdSimVarNum-v0", "--num-processes", "2", "--num-mini-batch", "1",
-                                      "--num-steps", "5", "--num-env-steps", "10", "--output_dir", str(out), "--ppo-epoch", "2", "--seed", "7"])
-    nthreads = torch.get_num_threads()
-    try:
-        runpy.run_path(os.path.join(REF, "train.py"), run_name="__main__")
-    finally:
-        torch.set_num_threads(nthreads)    # train.py:61 sets 1
-    ckpt = out / "checkpoints" / "00000.pt"
-    assert ckpt.is_file() and (out / "configs" / "config.py").is_file() and (out / "arguments.py").is_file()
-    sd = torch.load(str(ckpt))
-    from crowdnav_prediction_attngraph_amd.policy import Policy, make_spaces
-    ob_space, act_space = make_spaces(20, 2)
-    torch.manual_seed(7)
-    fresh = Policy(ob_space.spaces, act_space, base_kwargs=dict(env_name="CrowdSimVarNum-v0", num_processes=2, num_mini_batch=1, seq_length=30))
-    assert list(sd) == list(fresh.state_dict())
-    moved = sum(int(not torch.equal(sd[k], v)) for k, v in fresh.state_dict().items())
-    assert moved > 30, "one PPO update must have changed (almost) every parameter tensor; changed: %d" % moved
-    fresh.load_state_dict(sd)
-
-
-def test_reference_collect_data_py_runs_unchanged_and_writes_the_collector_s_files(dropin_path, tmp_path, monkeypatch):
-    """collect_data.py's collectData(), executed where it lies, against dropin/ (make_vec_envs, Config, crowd_sim.envs); the only
-    substitution is the simulator behind make_vec_envs (C oracle instead of the device batch).  The files it writes must be the lines
-    the product's collector (crowdnav_prediction_attngraph_amd.collect.format_rows) produces from the same observations."""
-    import numpy as np
-    import rl.networks.envs as shim_envs
-    from tests import oracle_vec_env
-    from crowdnav_prediction_attngraph_amd import config as C
-    from crowdnav_prediction_attngraph_amd.collect import format_rows
-    monkeypatch.setattr(shim_envs, "make_vec_envs", oracle_vec_env.make_vec_envs)
-    monkeypatch.setattr(sys, "argv", ["collect_data.py"])
-    mod = runpy.run_path(os.path.join(REF, "collect_data.py"), run_name="collect_data_under_test")
-    cfg = C.non_randomized(**{"sim.human_num": 20, "data.tot_steps": 40, "data.num_processes": 3, "data.data_save_dir": str(tmp_path / "ds")})
-    np.random.seed(11)
-    mod["collectData"](torch.device("cpu"), False, cfg)
-    assert cfg.robot.policy == "orca"
-    np.random.seed(11)
-    seed = np.random.randint(0, np.iinfo(np.uint32).max)
-    envs = oracle_vec_env.OracleCollectVecEnv(seed, 3, "cpu", config=cfg)
-    ob = envs.reset()["pred_info"]
-    want = [[] for _ in range(3)]
-    for t in range(40):
-        for i in range(3):
-            want[i] += format_rows(ob[i])
-        ob = envs.step(None)[0]["pred_info"]
-    for i in range(3):
-        got = open(str(tmp_path / "ds" / "test" / ("%d.txt" % i))).read().split("\n")
-        assert got[-1] == "" and got[:-1] == want[i] and len(want[i]) > 100
-
-
-def test_reference_train_py_then_test_py_run_unchanged_on_baseline_config0(tmp_path, monkeypatch):
-    """BASELINE configs[0] literally -- CrowdSimVarNum-v0, 5 ORCA humans, predict_method 'none', 1 env (`--num-processes 1
-    --num-mini-batch 1 --no-cuda`, which makes the env phase 'test', rl/networks/envs.py:55-58) -- through the reference's own workflow:
-    edit config.py / arguments.py, run train.py, run test.py on the directory it wrote.  Both scripts are EXECUTED where they lie,
-    unmodified, against a working copy of dropin/ carrying the user's edits; the only substitution is the simulator behind
-    make_vec_envs (C oracle on the CPU).  test.py takes no flags that arguments.get_args() would accept (test.py:20-33 are edited by
-    hand upstream), so it runs with its built-in defaults: model_dir 'trained_models/GST_predictor_rand', weights '41665.pt',
-    visualize on.  Its log line must equal what the mirror's evaluate() returns for the same policy and envs."""
-    import re
-    import shutil
-    work = tmp_path / "work"
-    shutil.copytree(DROPIN, str(work), ignore=shutil.ignore_patterns("__pycache__"))
-    # --- the edits a user of the reference makes by hand before training (config.py:43, :22; arguments.py defaults) ---
-    cfg_py = work / "crowd_nav" / "configs" / "config.py"
-    cfg_py.write_text(cfg_py.read_text() + "        self.sim.human_num = 5\n        self.env.test_size = 4\n")
-    arg_py = work / "arguments.py"
-    txt = arg_py.read_text()
-    for a, b in (('("--env-name", dict(default="CrowdSimPredRealGST-v0"))', '("--env-name", dict(default="CrowdSimVarNum-v0"))'),
-                 ('("--no-cuda", dict(action="store_true", default=False))', '("--no-cuda", dict(action="store_true", default=True))'),
-                 ('("--num-processes", dict(type=int, default=16))', '("--num-processes", dict(type=int, default=1))'),
-                 ('("--num-mini-batch", dict(type=int, default=2))', '("--num-mini-batch", dict(type=int, default=1))'),
-                 ('("--num-steps", dict(type=int, default=30))', '("--num-steps", dict(type=int, default=6))'),
-                 ('("--seq_length", dict(type=int, default=30))', '("--seq_length", dict(type=int, default=6))'),
-                 ('("--ppo-epoch", dict(type=int, default=5))', '("--ppo-epoch", dict(type=int, default=2))'),
-                 ('("--num-env-steps", dict(type=float, default=20e6))', '("--num-env-steps", dict(type=float, default=6))'),
-                 ('("--output_dir", dict(type=str, default="trained_models/my_model"))', '("--output_dir", dict(type=str, default="trained_models/GST_predictor_rand"))')):
-        assert a in txt, a
-        txt = txt.replace(a, b)
-    arg_py.write_text(txt)
-    saved_path, saved_mods = list(sys.path), set(sys.modules)
-    sys.path.insert(0, str(work))
-    monkeypatch.chdir(str(work))
-    monkeypatch.setenv("MPLBACKEND", "Agg")
-    nthreads = torch.get_num_threads()
-    try:
-        import matplotlib
-        matplotlib.use("Agg", force=True)
-        import rl.networks.envs as shim_envs
-        from tests import oracle_vec_env
-        assert os.path.abspath(shim_envs.__file__).startswith(str(work))
-        monkeypatch.setattr(shim_envs, "make_vec_envs", oracle_vec_env.make_vec_envs)   # the ONLY substitution: simulator -> CPU oracle
-        # ---- train.py: one PPO update of 6 steps on one env ----
-        monkeypatch.setattr(sys, "argv", ["train.py"])
-        runpy.run_path(os.path.join(REF, "train.py"), run_name="__main__")
-        model_dir = work / "trained_models" / "GST_predictor_rand"
-        assert (model_dir / "checkpoints" / "00000.pt").is_file() and (model_dir / "configs" / "config.py").is_file() and (model_dir / "arguments.py").is_file()
-        os.rename(str(model_dir / "checkpoints" / "00000.pt"), str(model_dir / "checkpoints" / "41665.pt"))   # test.py:29 default weight file
-        for d in ("trained_models", "trained_models/GST_predictor_rand", "trained_models/GST_predictor_rand/configs"):
-            init = work / d / "__init__.py"           # test.py:41-60 imports <model_dir>.arguments / .configs.config as packages
-            if not init.exists():
-                init.write_text("")
-        # ---- test.py: 4 test episodes with the checkpoint train.py wrote ----
-        monkeypatch.setattr(sys, "argv", ["test.py"])
-        import logging
-        monkeypatch.setattr(logging.root, "handlers", [])     # test.py:80-82 logging.basicConfig is a no-op while pytest's capture handlers sit on the root logger
-        with pytest.warns(UserWarning, match="rendering is not implemented"):
-            runpy.run_path(os.path.join(REF, "test.py"), run_name="__main__")
-        log = (model_dir / "test" / "test_visual.log").read_text()
-        m = re.search(r"Testing success rate: ([\d.]+), collision rate: ([\d.]+), timeout rate: ([\d.]+), nav time: ([\d.]+), path length: ([\d.]+), "
-                      r"average intrusion ratio: ([\d.]+)%, average minimal distance during intrusions: ([\d.naif]+)", log)
-        assert m, log
-        # ---- the same evaluation through the mirror's API ----
-        from arguments import get_args
-        from crowd_nav.configs.config import Config
-        from rl.evaluation import evaluate
-        from rl.networks.model import Policy
-        args, config = get_args([]), None
-        monkeypatch.setattr(sys, "argv", ["x"])
-        config = Config()
-        assert (args.env_name, args.num_processes, config.sim.human_num, config.sim.predict_method, config.env.test_size) == ("CrowdSimVarNum-v0", 1, 5, "none", 4)
-        envs = oracle_vec_env.make_vec_envs(args.env_name, args.seed, 1, args.gamma, None, torch.device("cpu"), True, config=config)
-        assert envs.cfg.phase == 2 and envs.cfg.human_num == 5            # phase 'test' (one env), five humans
-        pol = Policy(envs.observation_space.spaces, envs.action_space, base_kwargs=args, base=config.robot.policy)
-        pol.load_state_dict(torch.load(str(model_dir / "checkpoints" / "41665.pt"), map_location="cpu"))
-        pol.base.nenv = 1
-        got = evaluate(pol, envs, 1, torch.device("cpu"), config.env.test_size, None, config, args, False)
-        want = [float(x) if x not in ("nan",) else float("nan") for x in m.groups()]
-        have = [got["success_rate"], got["collision_rate"], got["timeout_rate"], got["nav_time"], got["path_length"], got["intrusion_ratio"], got["min_intrusion_dist"]]
-        for w, h in zip(want, have):
-            assert (w != w and h != h) or abs(w - float("%.2f" % h)) < 1e-9, (want, have)
-        assert got["episodes"] == 4
-    finally:
-        torch.set_num_threads(nthreads)
-        sys.path[:] = saved_path
-        for mname in set(sys.modules) - saved_mods:
-            if mname.split(".")[0] in ("rl", "crowd_sim", "crowd_nav", "arguments", "trained_models"):
-                del sys.modules[mname]

@@ -46,12 +46,43 @@ def test_gst_predictor_and_wrapper_match_reference_cpu():
     _check("cpu")
 
 
-def test_reference_checkpoint_loads_when_available():
-    path = "/root/reference/gst_updated/results/100-gumbel_social_transformer-faster_lstm-lr_0.001-init_temp_0.5-edge_head_0-ebd_64-snl_1-snh_8-seed_1000_rand/sj/checkpoint/epoch_100.pt"
-    if not os.path.exists(path):
-        pytest.skip("reference checkout not present (GPU box)")
+def _save_as_numpy1(obj, path):
+    """torch.save, with numpy scalars named as numpy 1.x pickled them (numpy.core.multiarray.scalar; numpy >= 2 writes numpy._core...),
+    as in the checkpoints the reference ships.  Protocol-2 GLOBAL opcodes are newline-terminated text: the rename is a byte replacement."""
+    import io
+    import zipfile
+    buf = io.BytesIO()
+    torch.save(obj, buf)
+    src = zipfile.ZipFile(io.BytesIO(buf.getvalue()))
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_STORED) as dst:
+        for info in src.infolist():
+            data = src.read(info.filename)
+            if info.filename.endswith("/data.pkl"):
+                data = data.replace(b"cnumpy._core.multiarray\nscalar\n", b"cnumpy.core.multiarray\nscalar\n")
+                assert b"cnumpy.core.multiarray\nscalar\n" in data
+            dst.writestr(info.filename, data)
+
+
+def test_reference_checkpoint_loads_when_available(tmp_path):
+    """A checkpoint in the layout of the reference's shipped epoch_100.pt (the GST training script's dict: model / optimizer / scheduler
+    state, numpy-scalar epoch metrics, date), holding the shipped weights (the w/ arrays of gst_real_e4_h20.npz), written here and loaded."""
+    from collections import OrderedDict
+    z = np.load(os.path.join(GOLDEN, "gst_real_e4_h20.npz"))
+    keys = list(GSTPredictor().state_dict())
+    sd = OrderedDict((k, torch.from_numpy(z["w/" + k].copy())) for k in keys)
+    src = GSTPredictor()
+    src.load_state_dict(sd)
+    opt = torch.optim.Adam(src.parameters(), lr=1e-3)
+    sched = torch.optim.lr_scheduler.StepLR(opt, step_size=10, gamma=0.1)
+    ck = {"epoch": 100, "model_state_dict": sd, "optimizer_state_dict": opt.state_dict(), "lr_scheduler_state_dict": sched.state_dict(),
+          "train_loss_epoch": np.float64(-5.0), "val_loss_epoch": np.float64(-3.5), "train_aoe_epoch": np.float32(5.5),
+          "val_aoe_epoch": np.float32(5.0), "train_foe_epoch": np.float32(11.5), "val_foe_epoch": np.float32(10.5), "training_date": "211230"}
+    path = str(tmp_path / "epoch_100.pt")
+    _save_as_numpy1(ck, path)
     m = GSTPredictor.from_checkpoint(path, "cpu")
     assert sum(p.numel() for p in m.parameters()) == 67269   # SURVEY.md 8a-G3 [probed]
+    for k, v in m.state_dict().items():
+        assert torch.equal(v, sd[k]), k
 
 
 @pytest.mark.gpu

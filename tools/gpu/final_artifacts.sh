@@ -11,9 +11,9 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 bash tools/profile_step.sh $TAG --with-update > $OUT/profile_step.log 2>&1; echo "profile_step rc=$?"
 bash tools/gpu/update_profile.sh $TAG > $OUT/update_profile.log 2>&1; echo "update_profile rc=$?"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --timeline-out $OUT/step_timeline.txt > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver rc=$?"
-timeout 400 python bench.py --no-ppo --no-cpu-baseline --no-dropin --no-pmc-traffic --no-other-configs > $OUT/bench_long.json 2> $OUT/bench_long.err; echo "bench long rc=$?"
-timeout 600 python bench.py --gpus 8 --same-gpu --dist-backend gloo --envs 512 --steps 20 --warmup 5 --no-cpu-baseline --no-worst-case --no-dropin --no-pmc-traffic --no-other-configs > $OUT/bench_8rank_gloo.json 2> $OUT/bench_8rank.err; echo "bench8 rc=$?"
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --timeline-out $OUT/step_timeline.txt > $OUT/bench_driver.json 2> $OUT/bench_driver.err; echo "bench driver rc=$?"
+timeout 400 python bench.py --full --no-ppo --no-cpu-baseline --no-dropin --no-pmc-traffic --no-other-configs > $OUT/bench_long.json 2> $OUT/bench_long.err; echo "bench long rc=$?"
+timeout 600 python bench.py --full --gpus 8 --same-gpu --dist-backend gloo --envs 512 --steps 20 --warmup 5 --no-cpu-baseline --no-worst-case --no-dropin --no-pmc-traffic --no-other-configs > $OUT/bench_8rank_gloo.json 2> $OUT/bench_8rank.err; echo "bench8 rc=$?"
 timeout 300 python examples/train_ppo.py --updates 60 > $OUT/train_60_updates.jsonl 2> $OUT/train_60.err; echo "train60 rc=$?"; tail -1 $OUT/train_60_updates.jsonl | cut -c1-300
 C="--no-ppo --no-cpu-baseline --no-dropin --no-pmc-traffic --no-worst-case --no-other-configs"
 i=2

@@ -2,7 +2,7 @@
 # A/B of build flags of hh_fused.hip on the PPO leg (run through gpurun): the default build, then each quoted HHFLAGS string.
 #   gpurun -- 'bash tools/gpu/hh_ab.sh "-DHH_TRAIN_STORE_AUX=0"'
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-pmc-traffic --no-other-configs --no-worst-case"
+B="python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-pmc-traffic --no-other-configs --no-worst-case"
 run() {
   $B 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$1', 'step_ms', d['ms_per_step'], 'frac', d['roofline']['frac'], 'update_s', d['ppo']['update_s'], 'samples/s', d['ppo']['samples_per_s'])"
 }

@@ -20,6 +20,6 @@ done
 python $GRAFT_REPO_ROOT/tools/pmc_digest.py $OUT/pmc_2.txt $OUT/pmc_3.txt $OUT/pmc_4.txt > $OUT/update_pmc.txt 2>&1
 fi
 cd $GRAFT_REPO_ROOT
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-pmc-traffic --no-other-configs --no-worst-case > $OUT/bench_ppo.json 2> $OUT/bench_ppo.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-dropin --no-pmc-traffic --no-other-configs --no-worst-case > $OUT/bench_ppo.json 2> $OUT/bench_ppo.err
 head -30 $OUT/update_kernel_trace.txt | cut -c1-200
 tail -c 1500 $OUT/bench_ppo.json
