@@ -1203,16 +1203,7 @@ __device__ __forceinline__ uint32_t mt_temper(uint32_t y)
 // groups of 64 candidates one evaluating wavefront screens per round, C per lane: a pair of points is read from LDS once (a broadcast read of
 // 24 bytes per lane: 12 clocks of the CU's LDS pipe) and tested against C candidates (6 C packed instructions), so with C = 1 four busy SIMDs
 // ask for twice what the LDS delivers
-#ifndef CN_COOP_C4
-#define CN_COOP_C4 4
-#endif
-#ifndef CN_COOP_C8
-#define CN_COOP_C8 2
-#endif
-#ifndef CN_COOP_C16
-#define CN_COOP_C16 1
-#endif
-constexpr int coop_c(int W) { return W <= 4 ? CN_COOP_C4 : (W <= 8 ? CN_COOP_C8 : CN_COOP_C16); }
+constexpr int coop_c(int W) { return W <= 4 ? 4 : (W <= 8 ? 2 : 1); }
 template <int W>
 struct CoopLds {
     static constexpr int NE = W - 1;                          // evaluating wavefronts (master + helpers)
@@ -2603,10 +2594,8 @@ static int truth_rollout_and_obs(cn_env_batch *env, const cn_obs *obs, hipStream
 static bool lane_path_of(const cn_env_batch *env)
 {
     const int slots = env->d.H + (env->d.cfg.robot_visible ? 1 : 0); // candidate neighbours per agent (self included)
-    static int coop = -1; // CN_ORCA_COOP=1 forces the one-wavefront-per-agent kernel (A/B measurements)
-    if (coop < 0) { const char *v = getenv("CN_ORCA_COOP"); coop = v ? atoi(v) : 0; }
     // (a narrowed human field of view goes through the cooperative kernel: the lane kernel has no visibility test in its inner loops)
-    return env->d.cfg.humans_policy == CN_HUMANS_ORCA && slots <= 32 && !coop && env->d.cfg.human_fov >= 2.0;
+    return env->d.cfg.humans_policy == CN_HUMANS_ORCA && slots <= 32 && env->d.cfg.human_fov >= 2.0;
 }
 
 // refill the next-episode staging of the envs that just consumed theirs (rare: ~1.5 % of envs per step; a 60 us chain of serial fp64
@@ -2625,10 +2614,7 @@ static bool dense_crowd(cn_env_batch *env)
 
 static int launch_post(cn_env_batch *env, hipStream_t on)
 {
-    static const int post_waves = getenv("CN_POST_WAVES") ? atoi(getenv("CN_POST_WAVES")) : 4; // (A/B: 4, 8, 16)
-    if (post_waves == 4) hipLaunchKernelGGL(env_post_kernel<4>, dim3(env->d.E), dim3(256), 0, on, stamped(env->d, CN_K_OTHER));
-    else if (post_waves == 8) hipLaunchKernelGGL(env_post_kernel<8>, dim3(env->d.E), dim3(512), 0, on, stamped(env->d, CN_K_OTHER));
-    else hipLaunchKernelGGL(env_post_kernel<16>, dim3(env->d.E), dim3(1024), 0, on, stamped(env->d, CN_K_OTHER));
+    hipLaunchKernelGGL(env_post_kernel<4>, dim3(env->d.E), dim3(256), 0, on, stamped(env->d, CN_K_OTHER));
     CN_CHECK_LAUNCH();
 #ifdef CN_POST_DEBUG
     {
@@ -2977,16 +2963,13 @@ extern "C" int cn_env_step(cn_env_batch *env, const float *actions, const cn_obs
         if (int rc = truth_rollout_and_obs(env, obs, st)) return rc;
     } else {
         const bool coop = dense_crowd(env);
-        static const int defer_env = getenv("CN_ENV_DEFER") ? atoi(getenv("CN_ENV_DEFER")) : 1; // 0: placement loops inside the step kernel (A/B)
         // without a lane kernel the next consumer of the goals is the ORCA pass on the side stream: the updates go there, in front of it
         // (with one, that kernel follows on the caller's stream and the loops stay in the step kernel, on four wavefronts)
-        const bool defer = coop && defer_env && !lane_path_of(env) && env->d.cfg.humans_policy == CN_HUMANS_ORCA;
+        const bool defer = coop && !lane_path_of(env) && env->d.cfg.humans_policy == CN_HUMANS_ORCA;
         if (defer) {
             CN_HIP(hipMemsetAsync(env->d.post_cnt, 0, 4, st));
             hipLaunchKernelGGL((env_step_kernel<false, 1, true>), dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
             env->post_deferred = true;
-            static const int post_main = getenv("CN_POST_MAIN") ? atoi(getenv("CN_POST_MAIN")) : 0; // (measurement: the kernel on its own, behind the step)
-            if (post_main) { if (int rc = launch_post(env, st)) return rc; env->post_deferred = false; }
         }
         else if (coop) hipLaunchKernelGGL((env_step_kernel<false, 4>), dim3(env->d.E), dim3(256), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
         else hipLaunchKernelGGL(env_step_kernel<false>, dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);

@@ -9,24 +9,22 @@ namespace {
 // a*b ~= a_hi*b_hi + a_hi*b_lo + a_lo*b_hi with hi = bf16(x), lo = bf16(x - hi): the dropped terms are <= 2^-16 relative,
 // accumulation is fp32 (measured end-to-end error on the HH block: 1.5e-5, bar 1e-4).  Runs on v_mfma_f32_32x32x16_bf16
 // (16x the fp32 MFMA rate, three passes -> 5.3x).  A is fp32 in HBM and split while it is staged into LDS
-// (v_cvt_pk_bf16_f32); W is split once per weight snapshot.  LDS rows are 32 bf16 padded to 40 (80 B): the 16-byte
-// fragment reads of 16 consecutive rows then hit 16 distinct 16-B slots of the 256-B bank row (conflict-free).
+// (v_cvt_pk_bf16_f32); W is split once per weight snapshot.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-// K tile = ONE MFMA k-step (16): 24.6 KB of LDS and <= 128 VGPRs per workgroup -> FOUR workgroups (16 wavefronts) per CU.
-// The kernel is a plain two-barrier loop whose phases (global loads in flight, convert + LDS stores, MFMA, C stores) do
-// not overlap inside one workgroup; what hides them is other workgroups in other phases, so occupancy beats tile depth:
-// measured on the q|k|v shapes (stand-alone, random operands)  BK 64 / 2 per CU: 180 us | 2348 us (M = 24.5 k | 368 k),
-// BK 32 / 3 per CU: 168 | 2025,  BK 16 / 4 per CU: 161 | 1888 (307 TFLOP/s algorithmic = 920 executed).
-#ifndef CN_BK3
-#define CN_BK3 16
-#endif
-constexpr int BK3 = CN_BK3;
-constexpr int L3_STRIDE = BK3 + 8;  // +8 bf16 pad: rows 48 B apart (BK3 = 16) -> 16 consecutive rows' 16-byte reads tile all 64 banks
-constexpr int G3_OCC = BK3 <= 16 ? 4 : (BK3 <= 32 ? 3 : 2); // workgroups per CU the register budget is compiled for
+// The kernels are plain two-barrier loops whose phases (global loads in flight, convert + LDS stores, MFMA, C stores) do not
+// overlap inside one workgroup; what hides them is other workgroups in other phases.  Stand-alone, occupancy beats tile depth --
+// measured on the q|k|v shapes (random operands)  BK 64 / 2 per CU: 180 us | 2348 us (M = 24.5 k | 368 k),
+// BK 32 / 3 per CU: 168 | 2025,  BK 16 / 4 per CU: 161 | 1888 (307 TFLOP/s algorithmic = 920 executed) -- but the rollout forward
+// shares the chip with the ORCA side stream and does best with deep tiles.  Each kernel has its own K tile: NT_BK, TN_BK.
+// LDS rows are the K tile + 8 bf16 of pad: 16 consecutive rows' 16-byte fragment reads then tile all 64 banks.
+
+// K tile of gemm3_nt_kernel (the rollout forward's separate-launch mode): 64, two workgroups per CU
+constexpr int NT_BK = 64;
+constexpr int NT_STRIDE = NT_BK + 8;
 
 template <int TBM, int BN, int ACT, bool GATE>
-__global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) void gemm3_nt_kernel(int M, int N, int K, const float *__restrict__ A, int lda,
+__global__ __launch_bounds__(256, 2) void gemm3_nt_kernel(int M, int N, int K, const float *__restrict__ A, int lda,
                                                        const float *__restrict__ Agate, const __bf16 *__restrict__ Whi, const __bf16 *__restrict__ Wlo,
                                                        const float *__restrict__ bias, float *__restrict__ C, int ldc,
                                                        const int *__restrict__ m_dev)
@@ -38,16 +36,16 @@ __global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) vo
     if (row_tile * TBM >= M) return;
     constexpr int MI = TBM / 64;             // 32-row MFMA blocks per wavefront (2 x 2 wavefronts: TBM/2 rows each)
     constexpr int NB = BN / 64;
-    constexpr int AQ = BK3 / 4, ARP = 256 / AQ;  // float4 per A row of the K tile, rows staged per pass
-    constexpr int ALD = TBM / ARP;               // float4 loads of A per thread per K tile
-    constexpr int WQ = BK3 / 8;                  // 16-byte chunks per W row of the K tile
-    constexpr int WCH = BN * WQ / 256;           // chunks of each W plane per thread per K tile
+    constexpr int AQ = NT_BK / 4, ARP = 256 / AQ; // float4 per A row of the K tile, rows staged per pass
+    constexpr int ALD = TBM / ARP;                // float4 loads of A per thread per K tile
+    constexpr int WQ = NT_BK / 8;                 // 16-byte chunks per W row of the K tile
+    constexpr int WCH = BN * WQ / 256;            // chunks of each W plane per thread per K tile
     static_assert(WCH >= 1 && ALD >= 1, "tile too small for 256 staging threads");
     extern __shared__ __attribute__((aligned(16))) char smem3[];
     __bf16 *Ah = reinterpret_cast<__bf16 *>(smem3);
-    __bf16 *Al = Ah + TBM * L3_STRIDE;
-    __bf16 *Wh = Al + TBM * L3_STRIDE;
-    __bf16 *Wl = Wh + BN * L3_STRIDE;
+    __bf16 *Al = Ah + TBM * NT_STRIDE;
+    __bf16 *Wh = Al + TBM * NT_STRIDE;
+    __bf16 *Wl = Wh + BN * NT_STRIDE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int m_blk = row_tile * TBM, n_blk = col_tile * BN;
@@ -94,36 +92,36 @@ __global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) vo
                 hi[q] = (__bf16)a;
                 lo[q] = (__bf16)(a - (float)hi[q]);
             }
-            *reinterpret_cast<bf16x4 *>(&Ah[(lrow + ARP * p) * L3_STRIDE + lcol]) = hi;
-            *reinterpret_cast<bf16x4 *>(&Al[(lrow + ARP * p) * L3_STRIDE + lcol]) = lo;
+            *reinterpret_cast<bf16x4 *>(&Ah[(lrow + ARP * p) * NT_STRIDE + lcol]) = hi;
+            *reinterpret_cast<bf16x4 *>(&Al[(lrow + ARP * p) * NT_STRIDE + lcol]) = lo;
         }
 #pragma unroll
         for (int p = 0; p < WCH; ++p) {
             const int c = tid + 256 * p, r = c / WQ, col = (c % WQ) * 8;
-            *reinterpret_cast<bf16x8 *>(&Wh[r * L3_STRIDE + col]) = pwh[p];
-            *reinterpret_cast<bf16x8 *>(&Wl[r * L3_STRIDE + col]) = pwl[p];
+            *reinterpret_cast<bf16x8 *>(&Wh[r * NT_STRIDE + col]) = pwh[p];
+            *reinterpret_cast<bf16x8 *>(&Wl[r * NT_STRIDE + col]) = pwl[p];
         }
     };
 
     load_tiles(0);
     const int half = lane >> 5, l31 = lane & 31;
-    for (int k0 = 0; k0 < K; k0 += BK3) {
+    for (int k0 = 0; k0 < K; k0 += NT_BK) {
         __syncthreads();
         store_tiles();
         __syncthreads();
-        if (k0 + BK3 < K) load_tiles(k0 + BK3);
+        if (k0 + NT_BK < K) load_tiles(k0 + NT_BK);
 #pragma unroll
-        for (int ks = 0; ks < BK3 / 16; ++ks) {
+        for (int ks = 0; ks < NT_BK / 16; ++ks) {
             bf16x8 ah[MI], al[MI], bh[NB], bl[NB];
 #pragma unroll
             for (int i = 0; i < MI; ++i) {
-                const int o = (wm * (TBM / 2) + i * 32 + l31) * L3_STRIDE + ks * 16 + half * 8;
+                const int o = (wm * (TBM / 2) + i * 32 + l31) * NT_STRIDE + ks * 16 + half * 8;
                 ah[i] = *reinterpret_cast<const bf16x8 *>(&Ah[o]);
                 al[i] = *reinterpret_cast<const bf16x8 *>(&Al[o]);
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
-                const int o = (wn * (BN / 2) + j * 32 + l31) * L3_STRIDE + ks * 16 + half * 8;
+                const int o = (wn * (BN / 2) + j * 32 + l31) * NT_STRIDE + ks * 16 + half * 8;
                 bh[j] = *reinterpret_cast<const bf16x8 *>(&Wh[o]);
                 bl[j] = *reinterpret_cast<const bf16x8 *>(&Wl[o]);
             }
@@ -185,10 +183,10 @@ template <int TBM, int BN, int ACT>
 static int launch_gemm3_t(int M, int N, int K, const float *A, int lda, const __bf16 *Whi, const __bf16 *Wlo, const float *bias, float *C, int ldc,
                           hipStream_t st, const int *m_dev, const float *Agate = nullptr)
 {
-    CN_REQUIRE(N % BN == 0 && K % BK3 == 0 && lda % 4 == 0, "gemm3: unsupported shape M=%d N=%d K=%d lda=%d", M, N, K, lda);
+    CN_REQUIRE(N % BN == 0 && K % NT_BK == 0 && lda % 4 == 0, "gemm3: unsupported shape M=%d N=%d K=%d lda=%d", M, N, K, lda);
     if (M == 0) return CN_OK;
     dim3 grid(N / BN, (((M + TBM - 1) / TBM) + 7) & ~7);
-    constexpr size_t lds = (size_t)(2 * TBM + 2 * BN) * L3_STRIDE * sizeof(__bf16); // 73.7 KB at 128 x 128: needs the opt-in above 64 KB
+    constexpr size_t lds = (size_t)(2 * TBM + 2 * BN) * NT_STRIDE * sizeof(__bf16); // 73.7 KB at 128 x 128: needs the opt-in above 64 KB
     static CnLdsOptIn opt_in; // per device
     int opt_dev;
     if (opt_in.needed(&opt_dev)) {
@@ -208,19 +206,10 @@ static int launch_gemm3(int M, int N, int K, const float *A, int lda, const __bf
     return launch_gemm3_t<BM, BN, ACT>(M, N, K, A, lda, Whi, Wlo, bias, C, ldc, st, m_dev, Agate);
 }
 
-// hi/lo split of W^T: w [rows, cols] row-major -> hi, lo [cols, rows].  Lets the NT kernel compute dX = dY * W
-// (the "weight" operand of that product is W^T).  Sizes are a few hundred KB: no tiling needed.
-__global__ void split_bf16_t_kernel(int rows, int cols, const float *__restrict__ w, __bf16 *__restrict__ hi, __bf16 *__restrict__ lo)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; // index into the transposed output
-    if (i < (size_t)rows * cols) {
-        const int c = (int)(i / rows), r = (int)(i % rows);
-        const float x = w[(size_t)r * cols + c];
-        const __bf16 h = (__bf16)x;
-        hi[i] = h;
-        lo[i] = (__bf16)(x - (float)h);
-    }
-}
+// K tile of gemm3_tn_kernel (the update's weight gradients: large stand-alone products): 16 = ONE MFMA k-step, 24.6 KB of LDS and <= 128
+// VGPRs -> four workgroups per CU (three with the ReLU gate)
+constexpr int TN_BK = 16;
+constexpr int TN_STRIDE = TN_BK + 8;
 
 // Weight-gradient GEMM (TN): P[s][n][k] = sum_{m in split s} dY[m][n] * X[m][k], both operands fp32 activations with the
 // reduction index m as the SLOW axis in memory.  The MFMA wants 8 consecutive reduction elements per lane, so the tiles
@@ -231,7 +220,7 @@ __global__ void split_bf16_t_kernel(int rows, int cols, const float *__restrict_
 // by reduce_partials_kernel in a fixed order: deterministic).  Blocks of k tile 0 also produce the column sums of dY
 // (the bias gradient) from the registers they stage anyway.
 template <bool GATE>
-__global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) void gemm3_tn_kernel(int M, int N, int K, const float *__restrict__ dY, int ldy, const float *__restrict__ Ygate,
+__global__ __launch_bounds__(256, GATE ? 3 : 4) void gemm3_tn_kernel(int M, int N, int K, const float *__restrict__ dY, int ldy, const float *__restrict__ Ygate,
                                                        const float *__restrict__ X, int ldx, int rows_per_split, float *__restrict__ partials,
                                                        float *__restrict__ db_part)
 {
@@ -239,9 +228,9 @@ __global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) vo
     constexpr int NB = BN / 64;
     extern __shared__ __attribute__((aligned(16))) char smem3[];
     __bf16 *Ah = reinterpret_cast<__bf16 *>(smem3);
-    __bf16 *Al = Ah + BM * L3_STRIDE;
-    __bf16 *Wh = Al + BM * L3_STRIDE;
-    __bf16 *Wl = Wh + BN * L3_STRIDE;
+    __bf16 *Al = Ah + BM * TN_STRIDE;
+    __bf16 *Wh = Al + BM * TN_STRIDE;
+    __bf16 *Wl = Wh + BN * TN_STRIDE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
     const int n_blk = blockIdx.x * BM, k_blk = blockIdx.y * BN, split = blockIdx.z;
@@ -259,7 +248,7 @@ __global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) vo
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    constexpr int TG = BK3 / 16; // 8-row groups per thread per chunk (2 thread halves x TG groups x 8 rows = BK3 rows)
+    constexpr int TG = TN_BK / 16; // 8-row groups per thread per chunk (2 thread halves x TG groups x 8 rows = TN_BK rows)
     float pa[TG][8], pb[TG][8], pg[GATE ? TG : 1][8];
     const float *a_col = dY + n_blk + c, *b_col = X + k_blk + c;
     const float *g_col = GATE ? Ygate + n_blk + c : nullptr; // backward through a ReLU: dY gated by the forward output
@@ -289,7 +278,7 @@ __global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) vo
                 blo[u] = (__bf16)(pb[p][u] - (float)bhi[u]);
                 colsum += pa[p][u];
             }
-            const int o = c * L3_STRIDE + (g0 + 2 * p) * 8;
+            const int o = c * TN_STRIDE + (g0 + 2 * p) * 8;
             *reinterpret_cast<bf16x8 *>(&Ah[o]) = ahi;
             *reinterpret_cast<bf16x8 *>(&Al[o]) = alo;
             *reinterpret_cast<bf16x8 *>(&Wh[o]) = bhi;
@@ -299,23 +288,23 @@ __global__ __launch_bounds__(256, (GATE && G3_OCC > 2) ? G3_OCC - 1 : G3_OCC) vo
 
     load_chunk(m_begin);
     const int half = lane >> 5, l31 = lane & 31;
-    for (int m0 = m_begin; m0 < m_end; m0 += BK3) {
+    for (int m0 = m_begin; m0 < m_end; m0 += TN_BK) {
         __syncthreads();
         store_chunk();
         __syncthreads();
-        if (m0 + BK3 < m_end) load_chunk(m0 + BK3);
+        if (m0 + TN_BK < m_end) load_chunk(m0 + TN_BK);
 #pragma unroll
-        for (int ks = 0; ks < BK3 / 16; ++ks) {
+        for (int ks = 0; ks < TN_BK / 16; ++ks) {
             bf16x8 ah[2], al[2], bh[NB], bl[NB];
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int o = (wm * 64 + i * 32 + l31) * L3_STRIDE + ks * 16 + half * 8;
+                const int o = (wm * 64 + i * 32 + l31) * TN_STRIDE + ks * 16 + half * 8;
                 ah[i] = *reinterpret_cast<const bf16x8 *>(&Ah[o]);
                 al[i] = *reinterpret_cast<const bf16x8 *>(&Al[o]);
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
-                const int o = (wn * (BN / 2) + j * 32 + l31) * L3_STRIDE + ks * 16 + half * 8;
+                const int o = (wn * (BN / 2) + j * 32 + l31) * TN_STRIDE + ks * 16 + half * 8;
                 bh[j] = *reinterpret_cast<const bf16x8 *>(&Wh[o]);
                 bl[j] = *reinterpret_cast<const bf16x8 *>(&Wl[o]);
             }

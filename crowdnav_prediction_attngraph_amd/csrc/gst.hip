@@ -70,20 +70,9 @@ __global__ __launch_bounds__(256) void gst_obs_prep_kernel(int E, int H, const f
 // ------------------------------------------------------------------------------------------------------------------
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#ifndef CN_GL_RT
-#define CN_GL_RT 5
-#endif
-#ifndef CN_GL_WAVES
-#define CN_GL_WAVES 8   // wavefronts per workgroup of the encoder-layer kernel: 8 = two teams of four on alternate row tiles (one workgroup per CU);
-#endif                  // 4 = one team, and with CN_GL_RT = 3 (48 rows, 64 KB of LDS) TWO independent workgroups per CU whose phases drift apart
-#ifndef CN_GST_WGS
-#define CN_GST_WGS 1   // workgroups per CU the LSTM kernel is sized for
-#endif
-constexpr int GL_NW = CN_GL_WAVES, GL_TEAMS = GL_NW / 4, GL_THREADS = 64 * GL_NW, GL_WGS = GL_NW == 4 ? 2 : 1;
-#ifndef CN_LS_ROWS
-#define CN_LS_ROWS 0   // nodes per LSTM tile: 0 = chosen per launch between 32 and 80 (gst_lstm); 32 / 80 force one
-#endif
-constexpr int GL_RT = CN_GL_RT, GL_ROWS = 16 * GL_RT;            // row tiles / rows per workgroup tile
+// wavefronts per workgroup of the encoder-layer kernel: two teams of four on alternate row tiles, one workgroup per CU
+constexpr int GL_NW = 8, GL_TEAMS = GL_NW / 4, GL_THREADS = 64 * GL_NW;
+constexpr int GL_RT = 5, GL_ROWS = 16 * GL_RT;                   // row tiles / rows per workgroup tile
 constexpr int GL_SA = 68, GL_SQ = 196;                    // LDS row strides (floats): 16-byte aligned, lanes of a float4 read on distinct banks
 constexpr int GL_OA = 0, GL_OQ = GL_OA + GL_ROWS * GL_SA, GL_OT = GL_OQ + GL_ROWS * GL_SQ, GL_OM = GL_OT + GL_ROWS * GL_SA;
 constexpr int GL_OX = GL_OM + GL_ROWS, GL_OC = GL_OX + 2 * GL_ROWS; // staged (x, y) inputs; constants of the embedding's LayerNorm
@@ -373,7 +362,7 @@ __device__ __forceinline__ float gl_tanh(float x) { return 1.0f - 2.0f / (1.0f +
 __device__ __forceinline__ float gl_sigmoid(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }
 
 template <int LS_ROWS>
-__global__ __launch_bounds__(512, 2 * CN_GST_WGS) void gst_lstm_kernel(int E, int H, int S, GstLstmArgs a)
+__global__ __launch_bounds__(512, 2) void gst_lstm_kernel(int E, int H, int S, GstLstmArgs a)
 {
     constexpr int LS_PT = LS_ROWS / 8, LS_OX = 0, LS_OG = LS_OX + LS_ROWS * LS_SX, LS_OB = LS_OG + LS_ROWS * LS_SG;
 #ifdef GST_TIMING
@@ -783,7 +772,7 @@ static int gst_layer(cn_gst *g, int rows, const float *x2, const float *mask, hi
     const int n_tiles = (rows + TG * H - 1) / (TG * H);
     GstLayerArgs a{x2, mask, g->emb_w, g->emb_b, g->n_w, g->n_b, g->n1_w, g->n1_b, g->f_in, g->in_b, g->f_out, g->out_b, g->f_l1, g->l1_b, g->f_l2, g->l2_b,
                    xs_out ? xs_out : g->xs, listed ? g->glist : nullptr, listed ? g->gcount : nullptr, listed ? 2 * (rows / (GT * H)) : 0};
-    hipLaunchKernelGGL(gst_layer_kernel, dim3(n_tiles < 256 * GL_WGS ? n_tiles : 256 * GL_WGS), dim3(GL_THREADS), GL_LDS_FLOATS * sizeof(float), st, rows, H, TG, a);
+    hipLaunchKernelGGL(gst_layer_kernel, dim3(n_tiles < 256 ? n_tiles : 256), dim3(GL_THREADS), GL_LDS_FLOATS * sizeof(float), st, rows, H, TG, a);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -804,12 +793,11 @@ static int gst_lstm(cn_gst *g, int E, int S, const float *in_mask, const float *
                   g->acc, out_traj, g->x_sample};
     // Tile size: a pass over an 80-node tile costs ~2.25x a pass over a 32-node one (measured at 2048 envs x 20 nodes: 2 tiles of 80 per workgroup
     // 0.716 ms per step against 5 tiles of 32 0.745, 64-node tiles 0.767: 640 tiles on 256 workgroups leave a third of them idle in the last
-    // turn), so the larger tile wins where it does not cost a whole extra turn of the workgroups.  CN_LS_ROWS=32 / 80 forces one (A/B).
-    static const int forced = getenv("CN_LS_ROWS") ? atoi(getenv("CN_LS_ROWS")) : CN_LS_ROWS;
-    const int N = E * g->H, wgs = 256 * CN_GST_WGS;
+    // turn), so the larger tile wins where it does not cost a whole extra turn of the workgroups (one workgroup per CU).
+    const int N = E * g->H, wgs = 256;
     const int t32 = (N + 31) / 32, t80 = (N + 79) / 80;
     const double c32 = (double)((t32 + wgs - 1) / wgs), c80 = 2.25 * (double)((t80 + wgs - 1) / wgs);
-    const bool big = forced == 80 || (forced != 32 && c80 < c32);
+    const bool big = c80 < c32;
     if (big) hipLaunchKernelGGL(gst_lstm_kernel<80>, dim3(t80 < wgs ? t80 : wgs), dim3(512), ls_lds_floats(80) * sizeof(float), st, E, g->H, S, a);
     else hipLaunchKernelGGL(gst_lstm_kernel<32>, dim3(t32 < wgs ? t32 : wgs), dim3(512), ls_lds_floats(32) * sizeof(float), st, E, g->H, S, a);
     CN_CHECK_LAUNCH();

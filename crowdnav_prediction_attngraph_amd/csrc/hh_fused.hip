@@ -38,7 +38,7 @@
 //       q.k.v MFMA loop of another head.  Tiles of <= 48 rows give each team its own scratch region; tiles of 49..63 rows fill the
 //       LDS with X and share one scratch region in turns (namespace team, struct Layout).  The teams' partial out_sp accumulators
 //       are exchanged through the (dead) X region at the end of the tile.  DESIGN.md section 4 has the measurements behind each choice.
-//   hh_fused_wide_kernel  (crowds of 64 humans -- an env must fit one tile -- and CN_HH_WIDE=1): the round-2 schedule, 4 wavefronts (one per SIMD),
+//   hh_fused_wide_kernel  (crowds of 64 humans -- an env must fit one tile): the round-2 schedule, 4 wavefronts (one per SIMD),
 //       64-row tiles.
 #include "hh_fused.h"
 #include "row_plan.h"
@@ -56,11 +56,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // weight fragments are read once per tile by exactly one wavefront: stream them past the vector L1
 __device__ __forceinline__ bf16x8 ldw(const char *p)
 {
-#ifndef HH_NT_LOADS
     return *reinterpret_cast<const bf16x8 *>(p);
-#else
-    return __builtin_nontemporal_load(reinterpret_cast<const bf16x8 *>(p));
-#endif
 }
 __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
@@ -129,9 +125,6 @@ __device__ __forceinline__ int chunk_boundary(const int *row_off, int E, int tot
     return below < above ? e1 - 1 : e1;
 }
 
-#ifdef HH_DEBUG
-__device__ int *g_hh_dbg = nullptr;
-#endif
 #ifdef HH_TIMING
 __device__ long long *g_hh_tim = nullptr; // [block][16] phase cycle sums of wavefront 0
 #define HH_T(k) do { const long long now_ = clock64(); tacc[k] += now_ - tlast; tlast = now_; } while (0)
@@ -286,12 +279,6 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
             }
     }
 
-#ifdef HH_DEBUG
-    if (g_hh_dbg && blockIdx.x == 0 && t.e_lo == 0) {
-        int *d = g_hh_dbg + wave * 64 * 8 + lane * 8;
-        d[0] = t.my_env; d[1] = t.my_start; d[2] = (int)vmask; d[3] = t.nrows; d[4] = t.n_env; d[5] = t.r0; d[6] = NRB; d[7] = t.e_lo;
-    }
-#endif
     f32x4 acc_os[4][NRB];
 #pragma unroll
     for (int j = 0; j < 4; ++j)
@@ -333,12 +320,8 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 // The scheduling barrier pins the issue point: left alone, the scheduler sinks these loads next to their use
                 // three k-steps later and the prefetch distance collapses to one L2 round trip per k-step.
                 const int kp = ks + PF - 1 < 16 ? ks + PF - 1 : 15;
-#ifndef HH_EXP_NO_WLOAD
 #pragma unroll
                 for (int c = 0; c < 6; ++c) wf[(ku + PF - 1) % PF][c] = ldw(wp + (kp * 6 + c) * 1024);
-#else
-                asm volatile("" : "+v"(wf[(ku + PF - 1) % PF][0]) : "s"(kp));
-#endif
                 const int kn = ks + 1 < 16 ? ks + 1 : 15;
 #pragma unroll
                 for (int rb = 0; rb < NRB; ++rb) {
@@ -349,13 +332,6 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
             }
             const bf16x8 *w6 = wf[ku]; // pair block A hi, lo, pair block B hi, lo (q in even wavefronts, k in odd), v hi, v lo
             const bf16x8 *xhc = xh[ku & 1], *xlc = xl[ku & 1];
-#ifdef HH_EXP_NO_MFMA
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) {
-                aq[rb][0] += (float)w6[0][0] + (float)w6[1][0] + (float)xhc[rb][0]; ak[rb][0] += (float)w6[2][0] + (float)w6[3][0] + (float)xlc[rb][0];
-                av[rb][0] += (float)w6[4][0] + (float)w6[5][0];
-            }
-#else
 #pragma unroll
             for (int rb = 0; rb < NRB; ++rb) {
                 aq[rb] = mfma(w6[1], xhc[rb], aq[rb]);
@@ -374,7 +350,6 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 ak[rb] = mfma(w6[2], xhc[rb], ak[rb]);
                 av[rb] = mfma(xhc[rb], w6[4], av[rb]);
             }
-#endif
             __builtin_amdgcn_sched_barrier(0);
         }
         }
@@ -546,11 +521,7 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 for (int q = 0; q < 4; ++q) v[q] = fmaxf(v[q], 0.0f);
                 // streamed past this XCD's L2: the reader (rn_fused) runs on other XCDs anyway, and the 24 MB of rows would push
                 // the 3.9 MB weight image, which every tile of every WG on the XCD re-reads, out of the 4 MB L2
-#ifndef HH_NO_NT_STORE
                 __builtin_nontemporal_store(v, reinterpret_cast<f32x4 *>(out_sp + (size_t)(t.r0 + row) * 256 + f0));
-#else
-                *reinterpret_cast<f32x4 *>(out_sp + (size_t)(t.r0 + row) * 256 + f0) = v;
-#endif
             }
         }
     }
@@ -725,10 +696,6 @@ __global__ __launch_bounds__(256, 1) void hh_fused_wide_kernel(int E, int H, int
 // ===================================================== two-team kernel: 8 wavefronts, 63-row tiles (<= 63 humans) =====================
 namespace team {
 
-#ifndef HH_TEAM_PFC
-#define HH_TEAM_PFC 8   // cap on the k-steps of weight fragments requested across the attention chain (default: no cap below PF - 1)
-#endif
-
 constexpr int FR = 63;                       // rows per tile: at most 4 row blocks of 16; the last row of a fourth block is never live (see CTR)
 constexpr int LDS_BYTES = 163840;            // all of the CU's LDS
 // The LDS layout depends on the row blocks of the tile:
@@ -793,17 +760,15 @@ __device__ __forceinline__ RowBuf make_row_buf(float *base, int r0, int nrows, i
 // Stores of the TRAINING forward's saved activations (e0 / x / qkv / attn: 11.8 KB per row, 4.8 GB per launch at 405 k rows).  With the
 // default cache policy they allocate in the XCD's 4 MB L2 and evict the 3.9 MB weight image that every tile streams from there: round 6's
 // counters show 2.5 GB of fabric reads per training launch against 19 MB in the rollout (weights resident).  nt (aux bit 1) = streaming
-// stores that do not displace the weights.  HH_TRAIN_STORE_AUX=0 restores the default policy (A/B).
-#ifndef HH_TRAIN_STORE_AUX
-#define HH_TRAIN_STORE_AUX 2
-#endif
+// stores that do not displace the weights.
+constexpr int TRAIN_STORE_AUX = 2;
 __device__ __forceinline__ void st4(const RowBuf &b, int float_off, f32x4 v)
 {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), b.rs, float_off * 4, 0, HH_TRAIN_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), b.rs, float_off * 4, 0, TRAIN_STORE_AUX);
 }
 __device__ __forceinline__ void st1(const RowBuf &b, int float_off, float v)
 {
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), b.rs, float_off * 4, 0, HH_TRAIN_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), b.rs, float_off * 4, 0, TRAIN_STORE_AUX);
 }
 
 // Barrier among the four wavefronts of ONE team (gfx950 has a single s_barrier per workgroup, which would couple the teams): a
@@ -866,9 +831,11 @@ __device__ __forceinline__ void finish_rows(const TileCtx &t, const f32x4 (&acc)
     }
 }
 
-// XM: how the q.k.v loop holds its X fragments -- 1: two sets, the next k-step's read while this one is multiplied; 2: ONE set refilled in
-// place (see the loop); 0: one set, read at the top of the step
-template <int NRB, int PF, int XM, bool TRAIN>
+// PF: depth (k-steps) of the q.k.v loop's weight prefetch ring.  With <= 3 row blocks, 4 measured the same as 2, and 2 leaves registers
+// for the cross-head prefetch; with 4 row blocks, 2 is what the 256-register budget allows.
+constexpr int PF = 2;
+
+template <int NRB, bool TRAIN>
 __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const float *__restrict__ se, const HhFusedWeights &W, const WeightBuf &WB,
                                           float *__restrict__ out_sp, char *lds, int lane_in, int wave, int tm)
 {
@@ -1031,12 +998,10 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
     // head's attention chain (and, for the first head, before the X epilogue above), so that every loop starts on a warm ring instead
     // of a cold L2 round trip.
     bf16x8 wf[PF][6];
-    constexpr bool XDB = XM == 1;
-    constexpr int PFC = PF - 1 < HH_TEAM_PFC ? PF - 1 : HH_TEAM_PFC; // k-steps requested across the attention chain (they hold registers there)
     auto ring_prologue = [&](const int hh_) __attribute__((always_inline)) {
         const unsigned wp_ = WB.qkv + (unsigned)((((h0 + 2 * hh_ + tm) & 7) * 4 + wave) * 16) * 6 * 1024;
 #pragma unroll
-        for (int p = 0; p < PFC; ++p)
+        for (int p = 0; p < PF - 1; ++p)
 #pragma unroll
             for (int c = 0; c < 6; ++c) wf[p][c] = ldb(WB, wp_ + (p * 6 + c) * 1024, uoff);
     };
@@ -1051,24 +1016,13 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
         for (int rb = 0; rb < NRB; ++rb) { aq[rb] = f32x4{0.f, 0.f, 0.f, 0.f}; ak[rb] = aq[rb]; av[rb] = aq[rb]; }
         const unsigned wp = WB.qkv + (unsigned)((h * 4 + wave) * 16) * 6 * 1024;
         f32x4 bq_pf, bk_pf; float bv_pf; // this head's biases: requested under the last k-step instead of behind the loop
-        constexpr int NXB = XDB ? 2 : 1;
-        bf16x8 xh[NXB][NRB], xl[NXB][NRB];
-        if (XDB) {
+        // X fragments are double buffered: step ks+1 is read from LDS while the MFMAs of step ks run
+        bf16x8 xh[2][NRB], xl[2][NRB];
 #pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) {
-                xh[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + rb * 1024 + loff);
-                xl[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + rb * 1024 + loff);
-            }
+        for (int rb = 0; rb < NRB; ++rb) {
+            xh[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + rb * 1024 + loff);
+            xl[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + rb * 1024 + loff);
         }
-        if (XM == 2) {
-#pragma unroll
-            for (int rb = 0; rb < NRB; ++rb) xl[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + rb * 1024 + loff);
-        }
-        // the rest of the ring's head start (steps PFC .. PF-2), requested here rather than across the chain
-#pragma unroll
-        for (int p = PFC; p < PF - 1; ++p)
-#pragma unroll
-            for (int c = 0; c < 6; ++c) wf[p][c] = ldb(WB, wp + (p * 6 + c) * 1024, uoff);
         static_assert(16 % PF == 0, "the ring position must be compile-time inside the unrolled group");
         // a group of PF k-steps; the last group is a separate instance whose prefetches end at compile time (a run-time test would
         // cut the k-step into basic blocks and the loads could no longer be interleaved with the MFMAs)
@@ -1084,29 +1038,13 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
 #pragma unroll
                     for (int c = 0; c < 6; ++c) wf[(ku + PF - 1) % PF][c] = ldb(WB, wp + ((ks + PF - 1) * 6 + c) * 1024, uoff);
                 }
-                if (XM == 2) {
-                    // ONE set of X fragments, refilled in place: the lo plane is only used by the first third of the step (w_hi . x_lo),
-                    // the hi plane by the other two.  x_hi of THIS step is read during the first third (its registers died with the previous
-                    // step), x_lo of the NEXT step during the second third (its registers died with the first).  Same latency hiding as two
-                    // sets, 8 * NRB registers less -- they pay for a deeper weight ring.
-#pragma unroll
-                    for (int rb = 0; rb < NRB; ++rb) xh[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + (ks * RB + rb) * 1024 + loff);
-                } else if (XDB) {
-                    if (!TAIL || ku + 1 < PF) {
-#pragma unroll
-                        for (int rb = 0; rb < NRB; ++rb) {
-                            xh[(ku + 1) & (NXB - 1)][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + ((ks + 1) * RB + rb) * 1024 + loff);
-                            xl[(ku + 1) & (NXB - 1)][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + ((ks + 1) * RB + rb) * 1024 + loff);
-                        }
-                    }
-                } else {
+                if (!TAIL || ku + 1 < PF) {
 #pragma unroll
                     for (int rb = 0; rb < NRB; ++rb) {
-                        xh[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + (ks * RB + rb) * 1024 + loff);
-                        xl[0][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + (ks * RB + rb) * 1024 + loff);
+                        xh[(ku + 1) & 1][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + ((ks + 1) * RB + rb) * 1024 + loff);
+                        xl[(ku + 1) & 1][rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + ((ks + 1) * RB + rb) * 1024 + loff);
                     }
                 }
-                if (XM == 0) __builtin_amdgcn_sched_barrier(0); // this step's own X fragments: nothing to interleave them with
             }
             if (TAIL && ku == PF - 1) {
                 // aq / ak: the two feature blocks of this wavefront's pair, of q (even wavefronts) or k (odd) -- see bake_qkv_kernel
@@ -1116,36 +1054,7 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 bv_pf = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(BB.rs, 4u * (unsigned)i, bo + 4096u, 0));
             }
             const bf16x8 *w6 = wf[ku]; // pair block A hi, lo, pair block B hi, lo (q in even wavefronts, k in odd), v hi, v lo
-            const bf16x8 *xhc = xh[ku & (NXB - 1)], *xlc = xl[ku & (NXB - 1)];
-            if (XM == 2) {
-#pragma unroll
-                for (int rb = 0; rb < NRB; ++rb) {
-                    aq[rb] = mfma(w6[0], xl[0][rb], aq[rb]);
-                    ak[rb] = mfma(w6[2], xl[0][rb], ak[rb]);
-                    av[rb] = mfma(xl[0][rb], w6[4], av[rb]);
-                }
-                bf16x8 xn[NRB];
-                if (!TAIL || ku + 1 < PF) {
-#pragma unroll
-                    for (int rb = 0; rb < NRB; ++rb) xn[rb] = *reinterpret_cast<const bf16x8 *>(lds + LDS_X + X_PLANE + ((ks + 1) * RB + rb) * 1024 + loff);
-                }
-#pragma unroll
-                for (int rb = 0; rb < NRB; ++rb) {
-                    aq[rb] = mfma(w6[1], xh[0][rb], aq[rb]);
-                    ak[rb] = mfma(w6[3], xh[0][rb], ak[rb]);
-                    av[rb] = mfma(xh[0][rb], w6[5], av[rb]);
-                }
-#pragma unroll
-                for (int rb = 0; rb < NRB; ++rb) {
-                    aq[rb] = mfma(w6[0], xh[0][rb], aq[rb]);
-                    ak[rb] = mfma(w6[2], xh[0][rb], ak[rb]);
-                    av[rb] = mfma(xh[0][rb], w6[4], av[rb]);
-                }
-                if (!TAIL || ku + 1 < PF) {
-#pragma unroll
-                    for (int rb = 0; rb < NRB; ++rb) xl[0][rb] = xn[rb];
-                }
-            } else {
+            const bf16x8 *xhc = xh[ku & 1], *xlc = xl[ku & 1];
 #pragma unroll
             for (int rb = 0; rb < NRB; ++rb) {
                 aq[rb] = mfma(w6[1], xhc[rb], aq[rb]);
@@ -1164,47 +1073,23 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 ak[rb] = mfma(w6[2], xhc[rb], ak[rb]);
                 av[rb] = mfma(xhc[rb], w6[4], av[rb]);
             }
-            }
             // Issue order inside the k-step: one memory instruction after every few MFMAs, so that it issues in the shadow of a running
             // MFMA.  Issued as one burst at the top of the step (the plain sched_barrier version) the 6 + 2*NRB memory instructions
             // cost ~170 cycles per step during which this wavefront keeps the matrix pipe empty.
-            if (XM == 2) {
-                // x_hi reads under the first MFMAs, then the weight loads, then (once the first third is through) next step's x_lo reads
-                constexpr int NM = 9 * NRB, NV = !TAIL || ku == 0 ? 6 : (ku == PF - 1 ? 3 : 0), NL = (!TAIL || ku + 1 < PF) ? NRB : 0;
+            constexpr int NM = 9 * NRB, ND = !TAIL || ku + 1 < PF ? 2 * NRB : 0, NV = !TAIL || ku == 0 ? 6 : (ku == PF - 1 ? 3 : 0);
+            constexpr int A = NM >= 12 + ND ? 2 : 1;                 // MFMAs in front of each weight load
+            constexpr int B = (NM - NV * A) / (ND ? ND : 1);         // MFMAs in front of each X fragment read (unused when ND == 0)
 #pragma unroll
-                for (int d = 0; d < NRB; ++d) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-                constexpr int GAP = 3 * NRB > NRB + NV ? 3 * NRB - NRB - NV : 0; // the rest of the first third
-                __builtin_amdgcn_sched_group_barrier(0x008, GAP, 0);
-#pragma unroll
-                for (int d = 0; d < NL; ++d) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, NM - NRB - NV - GAP - NL, 0);
-            } else {
-                constexpr int NM = 9 * NRB, ND = XDB && (!TAIL || ku + 1 < PF) ? 2 * NRB : 0, NV = !TAIL || ku == 0 ? 6 : (ku == PF - 1 ? 3 : 0);
-                constexpr int A = NM >= 12 + ND ? 2 : 1;                 // MFMAs in front of each weight load
-                constexpr int B = (NM - NV * A) / (ND ? ND : 1);         // MFMAs in front of each X fragment read (unused when ND == 0)
-#pragma unroll
-                for (int v = 0; v < NV; ++v) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, A, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                }
-#pragma unroll
-                for (int d = 0; d < ND; ++d) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, B, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x008, NM - NV * A - ND * B, 0);
+            for (int v = 0; v < NV; ++v) {
+                __builtin_amdgcn_sched_group_barrier(0x008, A, 0);
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
             }
+#pragma unroll
+            for (int d = 0; d < ND; ++d) {
+                __builtin_amdgcn_sched_group_barrier(0x008, B, 0);
+                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            }
+            __builtin_amdgcn_sched_group_barrier(0x008, NM - NV * A - ND * B, 0);
             __builtin_amdgcn_sched_barrier(0);
         });
         };
@@ -1424,19 +1309,6 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
 
 } // namespace team
 
-#ifndef HH_TEAM_PF3
-#define HH_TEAM_PF3 2   // prefetch depth (k-steps) of the bodies of <= 3 row blocks (4 measured the same; 2 leaves registers for the cross-head prefetch)
-#endif
-#ifndef HH_TEAM_PF4
-#define HH_TEAM_PF4 2   // prefetch depth of the 4-row-block body (register budget: 256)
-#endif
-#ifndef HH_TEAM_XM3
-#define HH_TEAM_XM3 1   // X fragment mode of the q.k.v loop (tile_body) for <= 3 row blocks
-#endif
-#ifndef HH_TEAM_XM4
-#define HH_TEAM_XM4 1
-#endif
-
 // TRAIN: also write e0 / x / qkv / attn (HhFusedWeights::*_out) and scale the scores by qscale -- the training forward (cn_hh_block_fwd)
 template <bool TRAIN>
 __global__ __launch_bounds__(512, 2) void hh_fused_kernel(int E, int H, int D, const float *__restrict__ se, const float *__restrict__ det,
@@ -1515,10 +1387,10 @@ __global__ __launch_bounds__(512, 2) void hh_fused_kernel(int E, int H, int D, c
         }
         const int nrb = (t.nrows + 15) >> 4;
         switch (nrb) {
-        case 1: team::tile_body<1, HH_TEAM_PF3, HH_TEAM_XM3, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
-        case 2: team::tile_body<2, HH_TEAM_PF3, HH_TEAM_XM3, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
-        case 3: team::tile_body<3, HH_TEAM_PF3, HH_TEAM_XM3, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
-        default: team::tile_body<4, HH_TEAM_PF4, HH_TEAM_XM4, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
+        case 1: team::tile_body<1, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
+        case 2: team::tile_body<2, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
+        case 3: team::tile_body<3, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
+        default: team::tile_body<4, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
         }
     }
 #ifdef HH_TIMING
@@ -1599,13 +1471,6 @@ extern "C" int cn_hh_fused_set_timing(long long *buf)
     return CN_OK;
 }
 #endif
-#ifdef HH_DEBUG
-extern "C" int cn_hh_fused_set_debug(int *buf)
-{
-    CN_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_hh_dbg), &buf, sizeof(buf)));
-    return CN_OK;
-}
-#endif
 
 int hh_fused_forward(int E, int H, int D, const float *spatial_edges, const float *det, int *row_off, unsigned long long *live_total,
                      const HhFusedWeights &w, float *out_sp, hipStream_t st, const int32_t *row_plan)
@@ -1622,19 +1487,15 @@ int hh_fused_forward(int E, int H, int D, const float *spatial_edges, const floa
     }
     // one workgroup per CU (the LDS footprint admits exactly one); small batches get fewer so that a chunk is >= one row block
     const int grid = rp_workgroups(E, H);
-    // an env must fit one tile: the two-team kernel holds 63 rows, the wide one 64 (CN_HH_WIDE=1 forces the latter: A/B measurements)
-    static int force_wide = -1;
-    if (force_wide < 0) { const char *v = getenv("CN_HH_WIDE"); force_wide = v ? atoi(v) : 0; }
+    // an env must fit one tile: the two-team kernel holds 63 rows, the wide one 64
     // (round 6: crowds of 49..63 humans also go through the two-team kernel -- an env of <= 63 rows fits its 4-row-block layout; measured at 50
-    // randomised humans x 8192 envs: 1.39 -> 1.14 ms beside the simulator's side-stream kernels.  CN_HH_TEAM_MAX=48 restores the round-5 split.)
-    static int team_max = -1;
-    if (team_max < 0) { const char *v = getenv("CN_HH_TEAM_MAX"); team_max = v ? atoi(v) : team::FR; }
+    // randomised humans x 8192 envs: 1.39 -> 1.14 ms beside the simulator's side-stream kernels.)
     const bool train = w.e0_out != nullptr;
     if (train) {
         CN_REQUIRE(H <= 48 && w.x_out && w.qkv_out && w.attn_out, "hh_fused_forward: the training outputs need H <= 48 and all four buffers");
         hipLaunchKernelGGL(hh_fused_kernel<true>, dim3(grid), dim3(512), team::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp,
                            (const int32_t *)nullptr, stamp);
-    } else if (H > team_max || force_wide > 0)
+    } else if (H > team::FR)
         hipLaunchKernelGGL(hh_fused_wide_kernel, dim3(grid), dim3(256), wide::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp, stamp);
     else
         hipLaunchKernelGGL(hh_fused_kernel<false>, dim3(grid), dim3(512), team::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp,

@@ -460,14 +460,6 @@ extern "C" int cn_linear_fwd(int M, int N, int K, const float *X, int ldx, const
     CN_REQUIRE(ldx >= K && ldy >= N, "cn_linear_fwd: leading dimension smaller than the row length");
     hipStream_t st = (hipStream_t)stream;
     const __bf16 *wh = (const __bf16 *)Whi, *wl = (const __bf16 *)Wlo;
-#ifdef CN_G3_KNOCKOUT
-    static const int ko = getenv("CN_G3KO") ? atoi(getenv("CN_G3KO")) : 0;
-    if (ko && act == 0 && !relu_gate) {
-#define KOV(k) if (ko == k) return launch_gemm3p<ACT_NONE, k>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr);
-        KOV(1) KOV(4) KOV(5) KOV(8) KOV(9) KOV(12)
-#undef KOV
-    }
-#endif
     return act == 1 ? launch_gemm3p<ACT_RELU>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, relu_gate)
                     : launch_gemm3p<ACT_NONE>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, relu_gate);
 }
@@ -522,7 +514,7 @@ extern "C" int cn_linear_wgrad_splits(int M, int N, int K)
     const long long tiles = (long long)((N + 127) / 128) * (K / 128);
     long long s = (768 + tiles - 1) / tiles;             // 1.5 resident rounds of blocks on 256 CUs (shorter blocks, small tail) ...
     if (s > 64) s = 64;                                  // ... but bounded: every split costs an [N,K] partial to write and re-read
-    const long long chunks = ((long long)M + BK3 - 1) / BK3;
+    const long long chunks = ((long long)M + TN_BK - 1) / TN_BK;
     if (s > chunks) s = chunks;
     return (int)(s < 1 ? 1 : s);
 }
@@ -536,7 +528,7 @@ extern "C" int cn_linear_wgrad(int M, int N, int K, const float *dY, int ldy, co
     CN_REQUIRE((db == nullptr) == (db_partials == nullptr), "cn_linear_wgrad: db and db_partials go together");
     CN_REQUIRE(ldy >= N && ldx >= K, "cn_linear_wgrad: leading dimension smaller than the row length");
     hipStream_t st = (hipStream_t)stream;
-    constexpr size_t lds = (size_t)(2 * BM + 2 * 128) * L3_STRIDE * sizeof(__bf16);
+    constexpr size_t lds = (size_t)(2 * BM + 2 * 128) * TN_STRIDE * sizeof(__bf16);
     static CnLdsOptIn opt_in; // per device
     int opt_dev;
     if (opt_in.needed(&opt_dev)) {
@@ -582,7 +574,7 @@ extern "C" int cn_linear_wgrad(int M, int N, int K, const float *dY, int ldy, co
         }
     } else {
         int rows = (M + splits - 1) / splits;
-        rows = (rows + BK3 - 1) / BK3 * BK3;
+        rows = (rows + TN_BK - 1) / TN_BK * TN_BK;
         used = (M + rows - 1) / rows; // <= splits, every split non-empty
         launch_tn(M, dY, relu_gate, X, rows, used, partials, db_partials);
         CN_CHECK_LAUNCH();

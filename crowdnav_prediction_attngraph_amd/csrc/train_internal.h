@@ -20,9 +20,8 @@ int rn_seq_prep_jobs(const cn_rn_weights *w, float *fwd_ws, float *bwd_ws, int T
 int rn_seq_fwd_impl(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off, const float *h0,
                     const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, float *ws, float *value, float *logp,
                     void *stream, bool prepared);
-// side != NULL: the eight weight-gradient products go to that stream behind events recorded on `stream` (ev: five events); the caller joins.
 // packed_heads != NULL: the heads' gradients stay packed there ([fc_mean.w 512 | critic_linear.w 256 | fc_mean.b 2 | critic_linear.b 1 | logstd 2])
 // instead of five device-to-device copies; prepared: the transposed split planes are already in the workspace (rn_seq_prep_jobs)
 int rn_seq_bwd_impl(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off, const float *masks,
                     const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, const float *d_value, const float *d_logp, float *ws,
-                    float *d_out_sp, float *d_h0, const cn_rn_grads *g, void *stream, hipStream_t side, hipEvent_t *ev, bool prepared, float **packed_heads);
+                    float *d_out_sp, float *d_h0, const cn_rn_grads *g, void *stream, bool prepared, float **packed_heads);

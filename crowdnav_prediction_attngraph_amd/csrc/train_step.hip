@@ -17,7 +17,6 @@
 
 #include "train_internal.h"
 
-#include <cstdlib>
 #include <cstring>
 
 namespace {
@@ -331,28 +330,6 @@ int layer_dw(int M, int N, int K, const float *dy, const float *gate, const floa
     return cn_linear_wgrad(M, N, K, dy, N, gate, inp, K, splits, reinterpret_cast<float *>(base + L.part), reinterpret_cast<float *>(base + L.dbp), dW, db, (void *)st);
 }
 
-// Library-owned side stream (one per device): carries weight-gradient products that nothing on the critical path waits for, beside the
-// dX chain on the caller's stream.  Events are record / wait pairs inside one call; the call joins before it returns its last launches.
-struct SideCtx {
-    hipStream_t s = nullptr;
-    hipEvent_t ev[8] = {};
-    bool ok = false;
-};
-SideCtx *side_ctx()
-{
-    static SideCtx ctx[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-    SideCtx &c = ctx[dev];
-    if (!c.ok) {
-        if (hipStreamCreateWithFlags(&c.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-        for (auto &e : c.ev)
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return nullptr;
-        c.ok = true;
-    }
-    return &c;
-}
-
 } // namespace
 
 extern "C" int64_t cn_ppo_minibatch_workspace_bytes(int T, int N, int H, int D, int64_t rows)
@@ -476,30 +453,16 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
     cn_rn_grads rg{g(G->robot_linear_w), g(G->robot_linear_b), F(L.d_te_w), F(L.d_te_b), g(G->edge_embed_w), g(G->edge_embed_b), g(G->gru_w_ih), g(G->gru_b_ih),
                    g(G->gru_w_hh), g(G->gru_b_hh), F(L.d_ac0_w), F(L.d_ac0_b), g(G->actor2_w), g(G->actor2_b), g(G->critic2_w), g(G->critic2_b),
                    g(G->critic_linear_w), g(G->critic_linear_b), g(G->fc_mean_w), g(G->fc_mean_b), g(G->logstd)};
-    // The weight-gradient products of the sequence (eight small split-K launches + their reductions, ~0.6 ms at 61 k samples) and the one of
-    // out_proj o spatial_linear run on the side stream beside the dX chain, the GRU, the two attention backward kernels (HBM-bound: the
-    // matrix cores are idle under them); CN_TRAIN_SIDE_STREAM=0 keeps everything on the caller's stream (A/B timing).
-    static const int use_side = getenv("CN_TRAIN_SIDE_STREAM") ? atoi(getenv("CN_TRAIN_SIDE_STREAM")) : 0; // 1: the sequence's products, 2: + out_proj o spatial_linear
-    SideCtx *sc = use_side ? side_ctx() : nullptr;
-    hipStream_t side = sc ? sc->s : nullptr;
-    if (sc) { // nothing of an earlier call may still be running there (a caller that switched streams between calls)
-        CN_HIP(hipEventRecord(sc->ev[7], st));
-        CN_HIP(hipStreamWaitEvent(side, sc->ev[7], 0));
-    }
     float *heads = nullptr; // packed head gradients: fc_mean.w [2,256] | critic_linear.w [256] | fc_mean.b [2] | critic_linear.b [1] | logstd [2]
     if ((rc = rn_seq_bwd_impl(T, N, H, F(L.rn), F(L.te), F(L.out), row_off, F(L.masks), F(L.act), &rw, &sv, F(L.d_value), F(L.d_logp), F(L.rn_bwd), F(L.d_out),
-                              F(L.d_h0), &rg, stream, side, sc ? sc->ev : nullptr, true, &heads))) return rc;
+                              F(L.d_h0), &rg, stream, true, &heads))) return rc;
 
     // ---- backward of the human-human block: the per-layer kernels on the saved activations, in reverse order ----
-    // out = relu(attn Wos^T + b): d_out is complete since the sequence's attention backward, i.e. before the side stream's last wait
-    if ((rc = layer_dw(R, 256, 512, F(L.d_out), F(L.out), F(L.attn), F(L.d_os_w), F(L.d_os_b), base, L, side && use_side >= 2 ? side : st))) return rc;
+    // out = relu(attn Wos^T + b): d_out is complete since the sequence's attention backward
+    if ((rc = layer_dw(R, 256, 512, F(L.d_out), F(L.out), F(L.attn), F(L.d_os_w), F(L.d_os_b), base, L, st))) return rc;
     if ((rc = layer_dx(R, 256, 512, F(L.d_out), F(L.out), F(L.wT_os), F(L.d_attn), st))) return rc;
     if ((rc = cn_hh_attention_bwd(B, H, F(L.qkv), row_off, F(L.d_attn), 0.125f, F(L.d_qkv), reinterpret_cast<int *>(base + L.cls), 0, stream))) return rc;
     if ((rc = layer_dx(R, 1536, 512, F(L.d_qkv), nullptr, F(L.wT_qkv), F(L.d_x), st))) return rc;                                                   // qkv = x Wc^T + bc
-    if (sc) { // join: the next weight gradient reuses the partial-sum buffers, and from here on everything is on the caller's stream again
-        CN_HIP(hipEventRecord(sc->ev[6], side));
-        CN_HIP(hipStreamWaitEvent(st, sc->ev[6], 0));
-    }
     if ((rc = layer_dw(R, 1536, 512, F(L.d_qkv), nullptr, F(L.x), F(L.d_qkv_w), F(L.d_qkv_b), base, L, st))) return rc;
     if ((rc = layer_dx(R, 512, 128, F(L.d_x), F(L.x), F(L.wT_emb2), F(L.d_e0), st))) return rc;                                                     // x = relu(e0 W2^T + b2)
     if ((rc = layer_dw(R, 512, 128, F(L.d_x), F(L.x), F(L.e0), g(G->emb2_w), g(G->emb2_b), base, L, st))) return rc;

@@ -14,7 +14,6 @@ Parameter construction order follows the reference so that `torch.manual_seed(s)
 initial weights (tests/test_host_policy.py checks this against checksums captured from the reference).
 """
 import math
-import os
 from collections import OrderedDict
 
 import numpy as np
@@ -172,7 +171,7 @@ class AttnGraphBase(nn.Module):
     train_fused_hh = True
     # everything behind the human-human block (robot node, robot-human attention, GRU sequence, trunks, heads, log-prob) as ONE call forward and
     # ONE backward (hip.RnSequence: cn_rn_seq_fwd / cn_rn_seq_bwd) instead of torch modules with HIP Functions spliced in
-    train_fused_rn = os.environ.get("CN_TRAIN_FUSED_RN", "1") != "0"   # (the environment switch is for A/B timing: bench.py's PPO leg)
+    train_fused_rn = True
 
     def counted_inputs(self, inputs):
         """sort_humans = True: the inputs as they are.  sort_humans = False (selfAttn_srnn_temp_node.py:378-383, :410-414): both attention modules

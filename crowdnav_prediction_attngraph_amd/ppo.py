@@ -143,13 +143,12 @@ class PPO():
     # ---- one boundary call per minibatch (default network on the GPU) -------------------------------------------------
     # cn_ppo_minibatch_step gathers the minibatch from the storage by env index, runs the train-mode forward, the losses and the whole
     # backward, and WRITES every parameter gradient into the flat bucket: no autograd graph, no framework kernel between the rollout
-    # storage and the Adam step.  use_minibatch_step = False (or CN_PPO_MINIBATCH_STEP=0) keeps the autograd-joined path below, which
-    # the non-default variants (use_self_attn / sort_humans off, fp32 arithmetic, CPU tensors) always take.
+    # storage and the Adam step.  use_minibatch_step = False keeps the autograd-joined path below, which the non-default variants
+    # (use_self_attn / sort_humans off, fp32 arithmetic, CPU tensors) always take.
     use_minibatch_step = True
 
     def _fast_path(self, rollouts):
-        import os
-        if not self.use_minibatch_step or os.environ.get("CN_PPO_MINIBATCH_STEP", "1") == "0":
+        if not self.use_minibatch_step:
             return False
         if not self.actor_critic.is_recurrent or not hasattr(self.actor_critic, "base"):
             return False

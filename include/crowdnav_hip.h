@@ -574,11 +574,9 @@ int cn_adam_clip_step(int64_t n, float *param, float *grad, float *exp_avg, floa
  *   value_loss / action_loss / entropy           rl/ppo/ppo.py:66-86
  *   optimizer.zero_grad(); total.backward()      rl/ppo/ppo.py:87-88
  * by: gather -> affine folds -> cn_hh_block_fwd -> cn_rn_seq_fwd -> cn_ppo_loss_fwd/bwd -> cn_rn_seq_bwd -> the per-layer backward of
- * the human-human block -> chain rule of the folds, all on `stream` (+ a library-owned side stream that carries weight-gradient
- * products off the critical path and is joined before the call returns its last launch), with NO framework kernel in between: every
- * parameter gradient is WRITTEN (not accumulated) to grads-><same field>; parameters the loss does not reach
- * (attn.spatial_edge_layer.bias) get an exact zero.  The caller then runs its gradient all-reduce (data parallel) and
- * cn_adam_clip_step on the flat bucket the pointers live in.
+ * the human-human block -> chain rule of the folds, everything on `stream`, with NO framework kernel in between: every parameter gradient
+ * is WRITTEN (not accumulated) to grads-><same field>; parameters the loss does not reach (attn.spatial_edge_layer.bias) get an exact
+ * zero.  The caller then runs its gradient all-reduce (data parallel) and cn_adam_clip_step on the flat bucket the pointers live in.
  *
  * storage tensors (float32, contiguous, device; T = num_steps, E = envs in storage):
  *   robot_node [T+1,E,1,7], temporal_edges [T+1,E,1,2], spatial_edges [T+1,E,H,D], detected_human_num [T+1,E,1], h0 = recurrent_hidden_states

@@ -1,15 +1,12 @@
 """Stand-alone probe of the PPO update's split-precision products (run on the GPU box).
 
     python tools/bench_update_gemms.py                 # the six NT shapes + the three weight-gradient shapes, M = 400 000 rows
-    python tools/bench_update_gemms.py --knockout      # NT q|k|v shape with parts of the kernel compiled out (needs a library built with
-                                                       #   make -C crowdnav_prediction_attngraph_amd/csrc G3FLAGS=-DCN_G3_KNOCKOUT)
 
 Every line: time per launch (5 launches between two events), algorithmic TFLOP/s, and the error against fp64 on a slice of the rows
 (NT) or on the whole product (weight gradient).  Operands are uniform-random on purpose: constant fills run ~20 % faster on this part
-(clock / power), see DESIGN.md section 4.  Knock-out bits (CN_G3KO): 1 = no C stores, 4 = no MFMA, 8 = no global loads in the loop."""
+(clock / power), see DESIGN.md section 4."""
 import argparse
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,20 +83,8 @@ def tn(M, shapes):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--rows", type=int, default=400000)
-    ap.add_argument("--knockout", action="store_true")
-    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
-    if a.child is not None:              # one process per knock-out value: the library reads CN_G3KO once
-        print("CN_G3KO=%s" % a.child, flush=True)
-        nt(a.rows, NT_SHAPES[:1])
-        return
-    if a.knockout:
-        for ko in ("0", "1", "4", "5", "8", "9", "12"):
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--rows", str(a.rows), "--child", ko], env=dict(os.environ, CN_G3KO=ko),
-                               capture_output=True, text=True, timeout=600)
-            print(r.stdout.strip() or r.stderr[-800:], flush=True)
-        return
     nt(a.rows, NT_SHAPES)
     tn(a.rows, TN_SHAPES)
     tn(a.rows - 23, TN_SHAPES[:1])       # a row count that is not a multiple of 32: the tail split

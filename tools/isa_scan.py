@@ -19,13 +19,12 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "crowdnav_prediction_attngraph_amd", "csrc")
-FLAGS = {"policy": ["-DCN_BK3=64"]}
 
 
 def assembly(name):
     out = os.path.join(tempfile.gettempdir(), "cn_isa_%s.s" % name)
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
-           os.path.join(CSRC, name + ".hip"), "-o", out] + FLAGS.get(name, [])
+           os.path.join(CSRC, name + ".hip"), "-o", out]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     return open(out).read().split("\n")
 
