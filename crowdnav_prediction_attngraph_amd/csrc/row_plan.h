@@ -12,7 +12,7 @@
 // own.  ~28 us per wavefront stand-alone, all groups in parallel (round 3: one wavefront, longest-processing-time-first through a
 // water-filling level search of ~8 DPP reductions per class and a per-env placement chain, ~50 us).  The wavefronts also write the row
 // offsets (prefix sum of the row counts by env index), so the consuming kernel needs no scan of its own.  They run as the first workgroups
-// of the simulator's ORCA lane kernel (env_sim.hip), i.e. beside work that is on the step's critical path anyway.  Everything they touch
+// of the simulator's ORCA lane kernel (orca.h), i.e. beside work that is on the step's critical path anyway.  Everything they touch
 // more than once lives in registers or LDS (a global round trip costs a lone wavefront 1-2 us, a ds_bpermute 100+ cycles: the scans are DPP).
 //
 // Layout (int32 words): header | row_off[E + 1] | tile_cnt[RP_TMAX] | items[RP_TMAX][64], item = env | rows << 16, a tile's list ends with

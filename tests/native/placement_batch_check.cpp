@@ -18,7 +18,7 @@ static void serial(Rng &R, int max_att, double &ox, double &oy) {
     for (int attempt = 0;; ++attempt) { double u0 = dbl(R), u1 = dbl(R), u2 = dbl(R); double x, y; make(u0, u1, u2, x, y); if (!collides(x, y) || attempt >= max_att) { ox = x; oy = y; return; } }
 }
 static void batch(Rng &R, int max_att, double &ox, double &oy) {
-    // the device loop of place_by_rejection (csrc/env_sim.hip): passes of up to 64 candidates inside the current block; a candidate whose
+    // the device loop of place_by_rejection (csrc/episode.h): passes of up to 64 candidates inside the current block; a candidate whose
     // six words straddle the end of the block is lane 0 of the first pass over the regenerated block
     int attempt = 0;
     for (;;) {

@@ -202,7 +202,7 @@ def test_hip_env_matches_oracle_bit_exact(name):
 
 @pytest.mark.parametrize("after", [0, 5, 100])
 def test_cooperative_placement_is_bit_exact_wherever_the_helpers_join(after):
-    """BASELINE configs[4]'s dense crowds run their long placement loops on four wavefronts per env (env_sim.hip, place_by_rejection<4>):
+    """BASELINE configs[4]'s dense crowds run their long placement loops on four wavefronts per env (episode.h, place_by_rejection<4>):
     the accepted candidate and the stream position behind it must not depend on WHEN the three helpers join.  The library reads the
     switches once per process, so the oracle comparisons above are re-run in a child with the cooperative kernel forced on for every
     crowd and the joining point at the first candidate (0), inside the first pass (5) and behind it (100)."""

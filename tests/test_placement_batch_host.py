@@ -1,4 +1,4 @@
-"""The attempt-parallel placement loop of csrc/env_sim.hip (place_by_rejection: 64 candidates of a rejection-sampling loop per pass, read
+"""The attempt-parallel placement loop of csrc/episode.h (place_by_rejection: 64 candidates of a rejection-sampling loop per pass, read
 straight out of the staged MT19937 block) must consume the stream exactly like the reference's one-candidate-at-a-time loop
 (crowd_sim_var_num.py:116-146, crowd_sim.py:415-485): same accepted candidate, same stream position, same regenerated state -- for any
 stream offset, for loops that straddle the 624-word block, and when the attempt bound ends the loop.  tests/native/placement_batch_check.cpp

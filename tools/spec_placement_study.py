@@ -2,7 +2,7 @@
 
 generate_circle_crossing_human (crowd_sim_var_num.py:116-146) places the humans of an episode one after another; every attempt draws
 three doubles from the legacy MT19937 stream and is rejected when it is too close to the robot's start / goal or to an earlier human's
-position / goal.  The device generator (env_sim.hip: gen_human) walks that chain attempt by attempt: ~26 attempts per episode at 20
+position / goal.  The device generator (episode.h: gen_human) walks that chain attempt by attempt: ~26 attempts per episode at 20
 humans, each a dependent chain of tempering, fp64 sin / cos and distance tests.
 
 Speculation: the stream position of human i's FIRST attempt is known if no earlier attempt is rejected.  One pass computes the first
