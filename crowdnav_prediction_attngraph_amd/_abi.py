@@ -11,7 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CN_HIP_LIB") or os.path.join(_PKG, "libcrowdnav_hip.so")   # CN_HIP_LIB: another build of the same ABI (A/B measurements)
 
 CN_MAX_HUMANS = 64
-ABI_VERSION = 404          # CN_ABI_VERSION of include/crowdnav_hip.h this binding was written against
+ABI_VERSION = 405          # CN_ABI_VERSION of include/crowdnav_hip.h this binding was written against
 PROF_KERNELS, PROF_SLOT_WORDS = 8, 2048
 PROF_KERNEL_IDS = {"env_step": 0, "orca_lane": 1, "hh_fused": 2, "rn_fused": 3, "orca_lp3": 4, "env_pregen": 5, "row_plan": 6, "other": 7}
 ENV_KINDS = {"CrowdSimVarNum-v0": 0, "CrowdSimPred-v0": 1, "CrowdSimPredRealGST-v0": 2, "CrowdSimVarNumCollect-v0": 3}
@@ -142,7 +142,7 @@ ABI_SYMBOLS = [
     "cn_gst_wrapper_reset", "cn_gst_wrapper_step", "cn_gst_wrapper_set_interval", "cn_gst_wrapper_history_len", "cn_gst_wrapper_save", "cn_gst_wrapper_load", "cn_gae", "cn_adv_stats", "cn_adv_normalize", "cn_episode_stats_update",
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
     "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
-    "cn_gst_train_workspace_bytes", "cn_gst_train_step",
+    "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
 ]
 
 _lib = None
@@ -259,6 +259,9 @@ def lib():
         L.cn_gst_train_workspace_bytes.restype = C.c_int64
         L.cn_gst_train_workspace_bytes.argtypes = [i32, i32]
         L.cn_gst_train_step.argtypes = [i32, i32, vp, vp, vp, C.POINTER(GstWeights), C.POINTER(GstWeights), f32, C.c_uint64, vp, i64, vp, vp, vp]
+        L.cn_gst_eval_workspace_bytes.restype = C.c_int64
+        L.cn_gst_eval_workspace_bytes.argtypes = [i32, i32, i32]
+        L.cn_gst_eval_step.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(GstWeights), vp, vp, i64, vp, vp, vp, vp]
         L.cn_ppo_minibatch_workspace_bytes.restype = C.c_int64
         L.cn_ppo_minibatch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
         L.cn_ppo_row_totals.argtypes = [i32, i32, i32, vp, vp, vp]

@@ -13,27 +13,14 @@
 // Dropout (the reference's four sites: attention probabilities, out_proj output, FFN hidden, FFN output; p = 0.1 in training) draws its
 // masks from a counter-based hash of (seed, layer pass, site, element), regenerated in the backward pass -- its own stream, not torch's.
 #include "common.h"
+#include "gst_model.h"
 
 #include <cmath>
 
 namespace {
 
-constexpr int GT = 5, GP = 5, TT = GT + GP;   // observed / predicted steps
-constexpr int NCALL = GT + GP - 1;            // encoder-layer passes: 5 observed slices + 4 decode steps
-constexpr int NSTEP = GT + GP - 1;            // LSTM steps
-constexpr int NT = 256;                       // threads per workgroup
-constexpr int NPARAM = 20;
-constexpr int PSIZE[NPARAM] = {128, 64, 192 * 64, 192, 64 * 64, 64, 64, 64, 64, 64, 128 * 64, 128, 64 * 128, 64, 256 * 64, 256 * 64, 256, 256, 320, 5};
-enum { P_EW = 0, P_EB, P_INW, P_INB, P_OW, P_OB, P_NW, P_NB, P_N1W, P_N1B, P_L1W, P_L1B, P_L2W, P_L2B, P_WIH, P_WHH, P_BIH, P_BHH, P_HW, P_HB };
-constexpr int param_total()
-{
-    int s = 0;
-    for (int i = 0; i < NPARAM; ++i) s += PSIZE[i];
-    return s;
-}
-constexpr int NPARAMS = param_total(); // 67 269
+using namespace gst_model;
 
-struct Wts { const float *p[NPARAM]; };
 struct Grd { float *p[NPARAM]; };
 
 // ---- per-sequence scratch layout (floats), N = pedestrians (padded count of the batch) ----
@@ -79,8 +66,6 @@ __device__ __forceinline__ float drop_scale(unsigned long long seed, int call, i
     const float u = (float)(x >> 40) * (1.0f / 16777216.0f);
     return u < p ? 0.0f : 1.0f / (1.0f - p);
 }
-
-__device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // y[r][f] = b[f] + sum_k W[f][k] x[r][k]
 __device__ void lin_fwd(int N, int K, int F, const float *x, int ldx, const float *__restrict__ W, const float *__restrict__ b, float *y, int ldy)

@@ -63,11 +63,7 @@ class GSTPredictor(nn.Module):
     @staticmethod
     def from_checkpoint(path, device):
         """path: <model_dir>/checkpoint/epoch_100.pt as shipped with the reference (config.pred.model_dir)."""
-        import numpy
-        safe = [(numpy.core.multiarray.scalar, "numpy.core.multiarray.scalar"), (numpy.dtype, "numpy.dtype")]
-        safe += [getattr(numpy.dtypes, n) for n in dir(numpy.dtypes) if n.endswith("DType")]
-        with torch.serialization.safe_globals(safe):
-            ck = torch.load(path, map_location=device, weights_only=True)
+        ck = load_checkpoint(path, device)
         m = GSTPredictor().to(device)
         m.load_state_dict(ck["model_state_dict"] if "model_state_dict" in ck else ck)
         return m
@@ -211,6 +207,15 @@ class PretextProcessor:
         order = torch.argsort(se[:, :, :2].norm(dim=-1), dim=1, stable=True)
         se = torch.gather(se, 1, order.unsqueeze(-1).expand(E, H, se.shape[2]))
         return se, rews
+
+
+def load_checkpoint(path, device):
+    """The dict of an epoch_<n>.pt (weights, optimiser state, the epoch's losses as numpy scalars), loaded with weights_only = True."""
+    import numpy
+    safe = [(numpy.core.multiarray.scalar, "numpy.core.multiarray.scalar"), (numpy.dtype, "numpy.dtype")]
+    safe += [getattr(numpy.dtypes, n) for n in dir(numpy.dtypes) if n.endswith("DType")]
+    with torch.serialization.safe_globals(safe):
+        return torch.load(path, map_location=device, weights_only=True)
 
 
 def load_predictor(config, device):

@@ -8,7 +8,10 @@ Two execution paths of the training step (train.py:121-146: forward, negative lo
     reverse pass, one workgroup per sequence, the reference's four dropout sites) and cn_adam_clip_step, through the C ABI;
   * the torch-op graph below under autograd (backend 'torch'): what CPU tensors use (unit tests, pinned to the reference's numbers) and the
     independent cross-check of the kernels (tests/test_gpu_gst_train.py holds the two against each other).
-The dataset, the rotation augmentation, the learning-rate schedule, evaluation and the checkpoint format are host code either way, and the
+Evaluation (eval.py's `inference`: the per-epoch validation pass and the sampled test protocol) has the same two paths: HipGstEvaluator --
+cn_gst_eval_step (csrc/gst_eval.hip), batches of sequences per boundary call, one read-back per pass -- behind evaluate(backend='hip') / test(), and
+the torch-op graph (evaluate's default, the CPU tests' path and the cross-check of the kernel).
+The dataset, the rotation augmentation, the learning-rate schedule and the checkpoint format are host code either way, and the
 producer of the data is the batched simulator (collect.py: thousands of simulated crowds per GPU).
 
 Scope note: the reference trains on `<dataset>_dset_<split>_batch_trajectories.pt` files produced by scripts/data/create_*datasets*.py,
@@ -171,10 +174,12 @@ def _transformer_train(model, x, attn_mask, p_drop):
     return x + F.dropout(L.linear2(x2), p_drop, tr)
 
 
-def forward_train(model, v_obs, attn_mask_obs, loss_mask_rel, p_drop=0.1):
-    """st_model.py:271-455 (faster_lstm, recursive, only_observe_full_period = False, sampling = False).
+def forward_train(model, v_obs, attn_mask_obs, loss_mask_rel, p_drop=0.1, noise=None):
+    """st_model.py:271-455 (faster_lstm, recursive, only_observe_full_period = False).
     v_obs [1,T,N,2], attn_mask_obs [1,T,N,N] (neighbour, target), loss_mask_rel [1,N,T+P] ->
-    (mu [1,P,N,2], sx, sy, corr [1,P,N,1]), x_sample_pred [1,P,N,2], info{'loss_mask_rel_full_partial', 'loss_mask_per_pedestrian'}."""
+    (mu [1,P,N,2], sx, sy, corr [1,P,N,1]), x_sample_pred [1,P,N,2], info{'loss_mask_rel_full_partial', 'loss_mask_per_pedestrian'}.
+    noise None: sampling = False, the mean is fed back.  noise [1,P,N,2] (standard-normal draws): sampling = True with sample_gaussian's
+    arithmetic (st_model.py:235-240) on the caller's draws instead of torch.empty(...).normal_()."""
     B, T, N, _ = v_obs.shape
     P = model.pred_len
     dev = v_obs.device
@@ -182,7 +187,7 @@ def forward_train(model, v_obs, attn_mask_obs, loss_mask_rel, p_drop=0.1):
     am = attn_mask_obs.permute(0, 1, 3, 2).reshape(B * T, N, N)                       # (target, neighbour)
     xs = _transformer_train(model, v_obs.reshape(B * T, N, 2), am, p_drop).view(B, T, N, 64)
     xs = xs * loss_mask_rel[:, :, :T].permute(0, 2, 1).unsqueeze(-1)
-    h = torch.zeros(B * N, 64, device=dev)
+    h = torch.zeros(B * N, 64, device=dev, dtype=xs.dtype)
     c = torch.zeros_like(h)
     for t in range(T):
         h, c = model._lstm_cell(xs[:, t].reshape(B * N, 64), h, c)
@@ -201,6 +206,9 @@ def forward_train(model, v_obs, attn_mask_obs, loss_mask_rel, p_drop=0.1):
         raw = model.hidden2pos(h).view(B, N, 5).unsqueeze(1)
         mu = raw[..., :2]
         mus.append(mu); sxs.append(raw[..., 2:3].exp()); sys_.append(raw[..., 3:4].exp()); cors.append(raw[..., 4:5].tanh())
+        if noise is not None:
+            sx, sy, corr, ex, ey = sxs[-1], sys_[-1], cors[-1], noise[:, tt:tt + 1, :, 0:1], noise[:, tt:tt + 1, :, 1:2]
+            mu = torch.cat((sx * ex, corr * sy * ex + ((1. - corr ** 2.) ** 0.5) * sy * ey), dim=3) + mu
         x_sample = mu * lm_fp.unsqueeze(1).unsqueeze(-1)
         samples.append(x_sample)
     gp = (torch.cat(mus, 1), torch.cat(sxs, 1), torch.cat(sys_, 1), torch.cat(cors, 1))
@@ -247,11 +255,12 @@ def rotate_graph(vtx, theta):
     return torch.cat((vtx[..., 0:1] * c - vtx[..., 1:2] * s, vtx[..., 0:1] * s + vtx[..., 1:2] * c), dim=-1)
 
 
-def sequence_loss(model, item, device, p_drop=0.1):
-    """One step's loss exactly as train.py:113-137 computes it (non-deterministic branch: NLL / number of valid (step, pedestrian))."""
+def sequence_loss(model, item, device, p_drop=0.1, noise=None):
+    """One step's loss exactly as train.py:113-137 computes it (non-deterministic branch: NLL / number of valid (step, pedestrian)).
+    noise: see forward_train (the test protocol's sampled decode)."""
     obs_traj, pred_gt, obs_rel, pred_rel_gt, lm_rel, lm, v_obs, A_obs, v_pred_gt, A_pred_gt, am_obs, am_pred = item
     v_obs, v_pred_gt, am_obs, lm_rel = v_obs.to(device), v_pred_gt.to(device), am_obs.to(device), lm_rel.to(device)
-    gp, xs, info = forward_train(model, v_obs, am_obs, lm_rel, p_drop)
+    gp, xs, info = forward_train(model, v_obs, am_obs, lm_rel, p_drop, noise)
     prob_loss, elm = negative_log_likelihood_full_partial(gp, v_pred_gt, info["loss_mask_rel_full_partial"], lm_rel[:, :, -model.pred_len:])
     return prob_loss.sum() / elm.sum(), gp, xs, info, v_pred_gt
 
@@ -335,9 +344,125 @@ def temperature(epoch, total_epochs, base_temp, temp_min=0.03):
     return max((1 - epoch / total_epochs) * (base_temp - temp_min) + temp_min, temp_min)
 
 
-def evaluate(model, loader, device):
-    """eval.py's `inference` in 'val' mode: mean loss over the sequences, aoe / foe over the fully observed pedestrians."""
+class HipGstEvaluator:
+    """Evaluation of the predictor on the MI355X through the C ABI: cn_gst_eval_step (csrc/gst_eval.hip) runs, for a batch of sequences in one
+    boundary call, what eval.py:63-117 does per sequence -- the forward with dropout off, the masked negative log-likelihood and the
+    average / final offset errors; validation (the mean fed back) or the test protocol (S sampled decodes per sequence on the caller's draws).
+    The kernels read the model's parameters where they are (also when they are views of a HipGstTrainer's flat bucket): nothing is copied."""
+
+    MAX_PEDS, MAX_SAMPLES = 64, 64
+
+    def __init__(self, model):
+        from . import _abi as A
+        self.A = A
+        self.model = model
+        params = self._params()
+        if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+            raise A.CnError("HipGstEvaluator: the predictor must live on the GPU in float32 (there is no CPU fallback of the HIP path)")
+        self.dev = params[0].device
+        self.ws = None
+
+    def _params(self):
+        named = dict(self.model.named_parameters())
+        return [named[k] for _, k in self.A.GST_WEIGHT_KEYS]
+
+    def evaluate_batch(self, v_obs, v_pred, loss_mask_rel, noise=None):
+        """v_obs, v_pred [B,5,N,2], loss_mask_rel [B,N,10] (any device), or lists of B per-sequence tensors ([5,N_b,2] / [N_b,10], a leading
+        axis of one allowed) of different crowd sizes; noise None (validation) or [B,S,5,N,2] / a list of [S,5,N_b,2] (test: S decodes per
+        sequence on these standard-normal draws).  Crowds are padded to the batch's largest (at least four) with absent pedestrians.
+        -> seq [B,R,4] (NLL sum, valid pairs, sum of masked aoe, sum of masked foe), ped [B,R,N,3] (aoe, foe, loss_mask_per_pedestrian),
+        gauss [B,R,5,N,5] (mu_x, mu_y, sigma_x, sigma_y, corr), R = max(S, 1), all on the device (nothing is read back here)."""
+        A = self.A
+        C = A.C
+        vo, vp, lm, nz = self._stack(v_obs, 3, 1), self._stack(v_pred, 3, 1), self._stack(loss_mask_rel, 2, 0), None if noise is None else self._stack(noise, 4, 2)
+        B, T, N, _ = vo.shape
+        if T != 5 or vp.shape[1] != 5 or N > self.MAX_PEDS:
+            raise A.CnError("HipGstEvaluator: 5 observed + 5 predicted steps and at most 64 pedestrians per sequence (got %d + %d steps, %d pedestrians)" % (T, vp.shape[1], N))
+        S = 0 if nz is None else int(nz.shape[1])
+        if nz is not None and (S < 1 or S > self.MAX_SAMPLES or tuple(nz.shape) != (B, S, 5, N, 2)):
+            raise A.CnError("HipGstEvaluator: noise must be [B,S,5,N,2] with 1 <= S <= 64 (got %s for B=%d, N=%d)" % (tuple(nz.shape), B, N))
+        Np = max(N, 4)
+        if Np != N:
+            pad = torch.nn.functional.pad
+            vo, vp, lm = pad(vo, (0, 0, 0, Np - N)), pad(vp, (0, 0, 0, Np - N)), pad(lm, (0, 0, 0, Np - N))
+            nz = None if nz is None else pad(nz, (0, 0, 0, Np - N))
+        f = lambda t: None if t is None else t.to(self.dev, torch.float32, non_blocking=True).contiguous()   # noqa: E731
+        vo, vp, lm, nz = f(vo), f(vp), f(lm), f(nz)
+        w = A.GstWeights()
+        for (field, _), p in zip(A.GST_WEIGHT_KEYS, self._params()):
+            setattr(w, field, p.data_ptr())
+        need = int(A.lib().cn_gst_eval_workspace_bytes(B, Np, S))
+        if self.ws is None or self.ws.numel() < need:
+            self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        R = max(S, 1)
+        seq, ped, gauss = torch.empty(B, R, 4, device=self.dev), torch.empty(B, R, Np, 3, device=self.dev), torch.empty(B, R, 5, Np, 5, device=self.dev)
+        with torch.cuda.device(self.dev):
+            A.check(A.lib().cn_gst_eval_step(B, Np, S, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(w), A.ptr(nz), C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()),
+                                             A.ptr(seq), A.ptr(ped), A.ptr(gauss), A.stream_ptr()), "cn_gst_eval_step")
+        return seq, ped[:, :, :N], gauss[:, :, :, :N]
+
+    @staticmethod
+    def _stack(x, rank, ax):
+        """A tensor as it is; a list of per-sequence tensors of `rank` axes (a leading axis of one allowed) padded along the pedestrian axis `ax`
+        with zeros (absent pedestrians) and stacked."""
+        if torch.is_tensor(x):
+            return x
+        xs = [t[0] if t.dim() == rank + 1 else t for t in x]
+        n = max(t.shape[ax] for t in xs)
+        out = []
+        for t in xs:
+            if t.shape[ax] != n:
+                shape = list(t.shape)
+                shape[ax] = n - t.shape[ax]
+                t = torch.cat((t, torch.zeros(shape, dtype=t.dtype, device=t.device)), dim=ax)
+            out.append(t)
+        return torch.stack(out, 0)
+
+
+def _eval_backend(model, backend):
+    if backend is None:
+        return "torch"
+    if backend not in ("torch", "hip"):
+        raise ValueError("backend must be None, 'torch' or 'hip' (got %r)" % (backend,))
+    return backend
+
+
+def _evaluate_hip(model, loader, device, batch_size):
+    """The validation pass in batches of sequences through cn_gst_eval_step: per-sequence results stay on the device, one read-back per pass."""
+    ev = HipGstEvaluator(model)
+    rows, pend = [], []
+
+    def flush():
+        if pend:
+            seq, ped, _ = ev.evaluate_batch([it[6] for it in pend], [it[8] for it in pend], [it[4] for it in pend])
+            rows.append(torch.stack((seq[:, 0, 0] / seq[:, 0, 1], seq[:, 0, 2], seq[:, 0, 3], ped[:, 0, :, 2].sum(1)), 1))
+            del pend[:]
+
+    with torch.no_grad():
+        for item in loader:
+            n = item[6].shape[2]
+            if n > 128:
+                continue
+            if n > HipGstEvaluator.MAX_PEDS:      # the kernels stop at 64 pedestrians: the op graph takes the sequence
+                loss, gp, xs, info, v_pred_gt = sequence_loss(model, item, device, 0.0)
+                lm = info["loss_mask_per_pedestrian"]
+                rows.append(torch.stack((loss, average_offset_error(xs, v_pred_gt, lm).sum(), final_offset_error(xs, v_pred_gt, lm).sum(), lm.sum())).view(1, 4))
+                continue
+            pend.append(item)
+            if len(pend) == batch_size:
+                flush()
+        flush()
+    r = torch.cat(rows, 0).double().cpu().numpy()
+    m = max(float(r[:, 3].sum()), 1.0)
+    return float(r[:, 0].mean()), float(r[:, 1].sum() / m), float(r[:, 2].sum() / m)
+
+
+def evaluate(model, loader, device, backend=None, batch_size=32):
+    """eval.py's `inference` in 'val' mode: mean loss over the sequences, aoe / foe over the fully observed pedestrians.
+    backend None / 'torch': the op graph, one sequence at a time.  'hip': cn_gst_eval_step on up to batch_size sequences per call."""
     model.eval()
+    if _eval_backend(model, backend) == "hip":
+        return _evaluate_hip(model, loader, device, batch_size)
     losses, aoes, foes, ms = [], [], [], []
     with torch.no_grad():
         for item in loader:
@@ -352,8 +477,67 @@ def evaluate(model, loader, device):
     return float(np.mean(losses)), float(np.concatenate(aoes).sum() / m), float(np.concatenate(foes).sum() / m)
 
 
+def test_sequence(model, item, noise, device):
+    """eval.py:89-107 for one sequence on the op graph: noise [S,5,N,2] -> per-sample (loss [S], sum of masked aoe [S], sum of masked foe [S]) and
+    the number of fully present pedestrians."""
+    losses, aoes, foes = [], [], []
+    with torch.no_grad():
+        for s in range(noise.shape[0]):
+            loss, gp, xs, info, v_pred_gt = sequence_loss(model, item, device, 0.0, noise[s:s + 1].to(device))
+            lm = info["loss_mask_per_pedestrian"]
+            losses.append(loss); aoes.append(average_offset_error(xs, v_pred_gt, lm).sum()); foes.append(final_offset_error(xs, v_pred_gt, lm).sum())
+    return torch.stack(losses), torch.stack(aoes), torch.stack(foes), lm.sum()
+
+
+def _test_row(loss, aoe, foe, m):
+    """eval.py:108-117 for sequences stacked on axis 0: loss, aoe, foe [n,S], m [n] -> [n,8]: mean loss, aoe mean / std / min, foe mean / std / min, m."""
+    return torch.stack((loss.mean(1), aoe.mean(1), aoe.std(1), aoe.min(1).values, foe.mean(1), foe.std(1), foe.min(1).values, m), 1)
+
+
+def test(model, loader, device, num_samples=20, seed=1000, backend=None, batch_size=32, draws=None):
+    """eval.py's `inference` in 'test' mode (:84-117, :148-157): num_samples decodes per sequence with the Gaussian sampled and fed back;
+    per sequence the mean / unbiased std / min over the samples of the summed masked aoe and foe and the mean of the losses; over the pass those
+    sums divided by the number of fully present pedestrians.  -> (loss, aoe, foe, aoe_std, foe_std, aoe_min, foe_min).
+    The draws come from a CPU torch.Generator seeded with `seed`: torch.randn [num_samples,5,N,2] per sequence in loader order, the same for
+    both backends; `draws` (an iterable of one [S,5,N,2] tensor per sequence) replaces them with recorded ones.  backend None: 'hip' for a model
+    on the GPU, 'torch' otherwise."""
+    model.eval()
+    if backend is None:
+        backend = "hip" if next(model.parameters()).is_cuda else "torch"
+    backend = _eval_backend(model, backend)
+    gen = torch.Generator().manual_seed(int(seed))
+    draws = iter(draws) if draws is not None else None
+    ev = HipGstEvaluator(model) if backend == "hip" else None
+    rows, pend = [], []
+
+    def flush():
+        if pend:
+            seq, ped, _ = ev.evaluate_batch([it[6] for it, _ in pend], [it[8] for it, _ in pend], [it[4] for it, _ in pend], [nz for _, nz in pend])
+            rows.append(_test_row(seq[:, :, 0] / seq[:, :, 1], seq[:, :, 2], seq[:, :, 3], ped[:, 0, :, 2].sum(1)))
+            del pend[:]
+
+    with torch.no_grad():
+        for item in loader:
+            n = item[6].shape[2]
+            if n > 128:
+                continue
+            noise = torch.randn(num_samples, 5, n, 2, generator=gen) if draws is None else next(draws)
+            if ev is None or n > HipGstEvaluator.MAX_PEDS:
+                loss, aoe, foe, m = test_sequence(model, item, noise, device)
+                rows.append(_test_row(loss.view(1, -1), aoe.view(1, -1), foe.view(1, -1), m.view(1)))
+                continue
+            pend.append((item, noise))
+            if len(pend) == batch_size:
+                flush()
+        flush()
+    r = torch.cat(rows, 0).double().cpu().numpy()
+    m = max(float(r[:, 7].sum()), 1.0)
+    return (float(r[:, 0].mean()), float(r[:, 1].sum() / m), float(r[:, 4].sum() / m), float(r[:, 2].sum() / m), float(r[:, 5].sum() / m),
+            float(r[:, 3].sum() / m), float(r[:, 6].sum() / m))
+
+
 def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad=10.0, rotation_pattern="random", save_epochs=10, init_temp=0.5,
-          random_seed=1000, device=None, num_workers=0, log=print, backend=None):
+          random_seed=1000, device=None, num_workers=0, log=print, backend=None, val_backend=None):
     """gst_updated/scripts/experiments/train.py:49-195 for the shipped configuration.  data_dir holds the text files of collect.py /
     collect_data.py; the first 80 % of every file's windows train, the rest validate (TrajectoriesDataset modes).  Writes
     <out_dir>/checkpoint/{epoch_<n>.pt, args.pickle, train_hist.pickle} in the reference's format (+ args.json / train_hist.json): the
@@ -374,6 +558,9 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
         backend = "hip" if device.type == "cuda" else "torch"
     if backend == "hip" and clip_grad is None:
         raise ValueError("backend='hip' clips the gradient norm in its fused Adam step: pass a clip_grad (the reference's default is 10)")
+    # the per-epoch validation follows the training step's backend (cn_gst_eval_step with 'hip'); val_backend forces one ('torch': the op graph)
+    if val_backend is None:
+        val_backend = backend
     hip_tr = HipGstTrainer(model, lr=lr, clip_grad=clip_grad, seed=random_seed, optimizer=optimizer) if backend == "hip" else None
     ckpt_dir = os.path.join(out_dir, "checkpoint")
     os.makedirs(ckpt_dir, exist_ok=True)
@@ -429,7 +616,7 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
         scheduler.step()
         m = max(float(np.concatenate(ms).sum()), 1.0)
         tr = (float(np.mean(losses)), float(np.concatenate(aoes).sum() / m), float(np.concatenate(foes).sum() / m))
-        va = evaluate(model, loader_val, device)
+        va = evaluate(model, loader_val, device, backend=val_backend)
         for k, a, b in (("loss", tr[0], va[0]), ("aoe", tr[1], va[1]), ("foe", tr[2], va[2])):
             hist["train_%s_task" % k].append(a); hist["val_%s_task" % k].append(b)
         hist["epoch"] = epoch
@@ -445,3 +632,41 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
                 pickle.dump(hist, f)
     model.eval()
     return model, hist
+
+
+def eval_run(run_dir, data_dir, num_samples=20, seed=1000, device=None, backend=None, log=print):
+    """gst_updated/scripts/experiments/eval.py:12-43 for a run directory of train(): the checkpoint's stored validation loss, the validation
+    loss recomputed from the loaded model, and the test protocol's line, on the last 20 % of every file's windows of data_dir."""
+    from .gst import GSTPredictor, find_checkpoint, load_checkpoint
+    device = torch.device(device if device is not None else ("cuda:0" if torch.cuda.is_available() else "cpu"))
+    if backend is None:
+        backend = "hip" if device.type == "cuda" else "torch"
+    path = find_checkpoint(run_dir)
+    model = GSTPredictor.from_checkpoint(path, device)
+    stored = load_checkpoint(path, "cpu").get("val_loss_epoch")
+    loader_val = DataLoader(TrajectoriesDataset(data_dir, mode="val"), batch_size=1, shuffle=False)
+    loader_test = DataLoader(TrajectoriesDataset(data_dir, mode="test"), batch_size=1, shuffle=False)
+    log("The best validation losses printed below should be the same.")
+    log("Validation loss in the checkpoint:  %s" % (stored,))
+    val = evaluate(model, loader_val, device, backend=backend)
+    log("Validation loss from loaded model:  %s" % (val[0],))
+    t = test(model, loader_test, device, num_samples=num_samples, seed=seed, backend=backend)
+    log("Test loss from loaded model:  %s" % (t[0],))
+    log("dataset: %s | test aoe: %.4f | test aoe std: %.4f | test foe: %.4f | test foe std: %.4f | min aoe: %.4f, min foe: %.4f"
+        % (os.path.basename(os.path.normpath(data_dir)), t[1], t[3], t[2], t[4], t[5], t[6]))
+    return val, t
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m crowdnav_prediction_attngraph_amd.gst_train")
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    ev = sub.add_parser("eval", help="validation loss and the sampled test protocol of a trained run (the reference's scripts/experiments/eval.py)")
+    ev.add_argument("run_dir"); ev.add_argument("data_dir")
+    ev.add_argument("--samples", type=int, default=20); ev.add_argument("--seed", type=int, default=1000)
+    ev.add_argument("--device", default=None); ev.add_argument("--backend", default=None, choices=("torch", "hip"))
+    a = ap.parse_args(argv)
+    eval_run(a.run_dir, a.data_dir, num_samples=a.samples, seed=a.seed, device=a.device, backend=a.backend)
+
+
+if __name__ == "__main__":
+    main()

@@ -147,7 +147,7 @@ typedef struct cn_policy cn_policy;
 
 /* Bumped whenever a struct layout, a signature or the snapshot format changes (round 4: cn_obs.row_plan, cn_env_config.robot_fov /
  * human_fov, the profiling entry points, snapshot layout CNENV004); the ctypes binding refuses a library that reports another number. */
-#define CN_ABI_VERSION 404
+#define CN_ABI_VERSION 405
 const char *cn_last_error(void);
 int cn_version(void);
 int cn_device_count(void);
@@ -524,6 +524,25 @@ int cn_gst_wrapper_step(cn_gst *g, int E, const cn_obs *obs, float robot_plus_hu
 int64_t cn_gst_train_workspace_bytes(int B, int N);
 int cn_gst_train_step(int B, int N, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const cn_gst_weights *grads,
                       float p_drop, uint64_t seed, void *workspace, int64_t workspace_bytes, float *loss_out, float *gauss_out, void *stream);
+
+/* ---- GST predictor EVALUATION step: validation (decode on the mean) and the sampled test protocol, B sequences per call ----
+ * Replaces, per sequence, the body of gst_updated/scripts/experiments/eval.py:63-117 (`inference`): st_model.forward (st_model.py:271-455, dropout
+ * off) with sampling = False (mode 'val', eval.py:69-82) or S times with sampling = True (mode 'test', eval.py:84-107), negative_log_likelihood_
+ * full_partial (st_model.py:62-112) and average_offset_error / final_offset_error (mgnn/utils.py:8-28) under loss_mask_per_pedestrian.
+ * v_obs, v_pred, loss_mask_rel, w, the bounds on N and the padding rule: as cn_gst_train_step; every weight pointer 16-byte aligned.
+ *   S = 0: one decode per sequence that feeds the mean back; noise must be NULL.
+ *   1 <= S <= 64: S decodes per sequence; decode step t of sample s feeds back mu + (sx e_x, corr sy e_x + sqrt(1 - corr^2) sy e_y)
+ *     (st_model.py:235-240) times loss_mask_rel_full_partial, (e_x, e_y) = noise[b, s, t, n] -- noise [B,S,5,N,2]: standard-normal draws supplied
+ *     by the CALLER.  The library draws nothing: equal arguments give equal bits.  The five observed encoder passes / LSTM steps do not depend
+ *     on the draws and run once per sequence; all B x S decodes of a call are in flight together.
+ * Outputs, R = max(S, 1) rows per sequence:
+ *   seq_out   [B,R,4]      sum of the masked NLL, number of valid (step, pedestrian) pairs, sum of the masked aoe, sum of the masked foe
+ *   ped_out   [B,R,N,3]    (optional) aoe, foe, loss_mask_per_pedestrian; a pedestrian not present at all ten steps has aoe = foe = 0 exactly
+ *   gauss_out [B,R,5,N,5]  (optional) mu_x, mu_y, sigma_x, sigma_y, corr of every predicted step
+ * eval.py's per-sequence loss is seq_out[.,.,0] / seq_out[.,.,1]. */
+int64_t cn_gst_eval_workspace_bytes(int B, int N, int S);
+int cn_gst_eval_step(int B, int N, int S, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const float *noise,
+                     void *workspace, int64_t workspace_bytes, float *seq_out, float *ped_out, float *gauss_out, void *stream);
 
 /* ---- rollout math ---- */
 /* rewards [T,N], values [T+1,N], masks [T+1,N] -> returns[t][n] for t < T (row T untouched).  fp32, torch op order. */
