@@ -1,0 +1,219 @@
+"""Host reference of cn_gst_train_step with dropout ON: the kernel's own counter-based masks recomputed in numpy and applied inside a plain
+torch graph of the training step (tests/test_gst_dropout_ref.py checks this module on the CPU, tests/test_gpu_gst_train.py holds the kernel
+against it).
+
+The masks are a pure function of (seed, sequence, encoder pass, site, element) -- csrc/gst_train.hip, drop_scale and `sd` in gst_train_kernel:
+    sd   = seed + 0x632BE59BD9B4E019 * (b + 1)                                                   (mod 2^64, b = sequence of the batch)
+    x    = sd ^ (0x9E3779B97F4A7C15 * (call * 4 + site + 1)) ^ (idx * 0xD1B54A32D192ED03)       (mod 2^64)
+    x   ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+    u    = (x >> 40) / 2^24            keep <=> u >= float32(p); survivors are scaled by float32(1) / (float32(1) - float32(p))
+call = t for the observed slice t = 0..4 and 5 + tt - 1 for decode step tt = 1..4; site 0 = attention probabilities [8, Np, Np] at
+(h * Np + i) * Np + j (i = target row, j = neighbour), site 1 = out_proj output [Np, 64], site 2 = FFN hidden [Np, 128], site 3 = FFN output
+[Np, 64], all row-major; Np = max(N, 4) is the padded pedestrian count the kernel sees.
+
+The graph is the op graph of gst_train._transformer_train / forward_train / negative_log_likelihood_full_partial, one sequence at a time,
+with the four F.dropout calls replaced by a multiplication with those arrays; the loss is pooled over the batch like the kernel's (sum of
+masked NLL / valid pairs of the whole batch)."""
+import copy
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+M64 = (1 << 64) - 1
+NCALL = 9                                   # 5 observed slices + 4 decode steps
+SEQ_MUL, SITE_MUL, IDX_MUL = 0x632BE59BD9B4E019, 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03
+STEP_SEED_STRIDE = 7919                     # HipGstTrainer: seed + 7919 * step_no when no seed is passed
+
+
+def site_shapes(Np):
+    return ((8, Np, Np), (Np, 64), (Np, 128), (Np, 64))
+
+
+def seq_seed(seed, b):
+    """The kernel's per-sequence seed `sd`."""
+    return (int(seed) + SEQ_MUL * (int(b) + 1)) & M64
+
+
+def decode_call(tt):
+    """Encoder pass index of decode step tt = 1..4 (the observed slice t is pass t)."""
+    return 5 + tt - 1
+
+
+def drop_scale(seed, call, site, idx, p):
+    """The kernel's drop_scale for an array of element indices: 0 where dropped, 1 / (1 - p) (float32 arithmetic, held as a double) where kept."""
+    idx = np.asarray(idx, dtype=np.uint64)
+    if p <= 0:
+        return np.ones(idx.shape, dtype=np.float64)
+    x0 = (int(seed) & M64) ^ ((SITE_MUL * (int(call) * 4 + int(site) + 1)) & M64)
+    with np.errstate(over="ignore"):
+        x = np.uint64(x0) ^ (idx * np.uint64(IDX_MUL))
+        x ^= x >> np.uint64(33); x *= np.uint64(0xff51afd7ed558ccd)
+        x ^= x >> np.uint64(33); x *= np.uint64(0xc4ceb9fe1a85ec53)
+        x ^= x >> np.uint64(33)
+    u = (x >> np.uint64(40)).astype(np.float64) / 16777216.0          # 24 bits: exact in float32, so comparing doubles is the kernel's comparison
+    p32 = np.float32(p)
+    keep = float(np.float32(1.0) / (np.float32(1.0) - p32))
+    return np.where(u < float(p32), 0.0, keep)
+
+
+def site_mask(sd, call, site, shape, p):
+    """One site's array under the per-sequence seed sd: element k of the row-major `shape` is drop_scale(sd, call, site, k)."""
+    return drop_scale(sd, call, site, np.arange(int(np.prod(shape)), dtype=np.uint64), p).reshape(shape)
+
+
+def masks(seed, b, call, Np, p):
+    """The four site arrays of encoder pass `call` of sequence b: [8,Np,Np], [Np,64], [Np,128], [Np,64]."""
+    sd = seq_seed(seed, b)
+    return [site_mask(sd, call, s, shp, p) for s, shp in enumerate(site_shapes(Np))]
+
+
+def _layer(model, x, attn_mask, mks, records=None):
+    """gst_train._transformer_train on x [S,H,2] (S slices of one sequence), the F.dropout calls replaced by the arrays mks[s] (the four site
+    arrays of slice s, sliced to the unpadded crowd)."""
+    g = model.gumbel_social_transformer
+    L = g.node_encoder_layers[0]
+    B, H, _ = x.shape
+    m0, m1, m2, m3 = [torch.stack([torch.from_numpy(np.ascontiguousarray(mk[s])) for mk in mks], 0).to(x.dtype) for s in range(4)]
+    m0, m1, m2, m3 = m0[:, :, :H, :H], m1[:, :H], m2[:, :H], m3[:, :H]
+    x = g.node_embedding(x)
+    ped = (attn_mask.sum(-1) > 0).to(x.dtype).unsqueeze(-1)
+    x = L.norm_node(x) * ped
+    q, k, v = [t.view(B, H, 8, 8).transpose(1, 2) for t in F.linear(x, L.self_attn.in_proj_weight, L.self_attn.in_proj_bias).chunk(3, dim=-1)]
+    p = torch.softmax((q * 8 ** -0.5) @ k.transpose(-1, -2), dim=-1)
+    p = p * attn_mask.unsqueeze(1)
+    p = p / (p.sum(-1, keepdim=True) + 1e-10)
+    p = p * m0
+    o = (p @ v).transpose(1, 2).reshape(B, H, 64)
+    x = x + L.self_attn.out_proj(o) * m1
+    hidden = F.relu(L.linear1(L.norm1_node(x)))
+    if records is not None:
+        for s, r in enumerate(records):
+            r["relu_active"] = (hidden[s] > 0).detach().numpy()
+    x2 = hidden * m2
+    return x + L.linear2(x2) * m3
+
+
+def _forward(model, v_obs, attn_mask_obs, loss_mask_rel, mask_fn, b, record=None):
+    """gst_train.forward_train (noise None) for ONE sequence b (leading axis of one): mask_fn(b, call, Np) gives the four arrays of a pass."""
+    B, T, N, _ = v_obs.shape
+    Np = max(N, 4)
+    P = model.pred_len
+    rec = (lambda calls: None) if record is None else (lambda calls: [record.setdefault((b, call), {}) for call in calls])
+    am = attn_mask_obs.permute(0, 1, 3, 2).reshape(B * T, N, N)                        # (target, neighbour)
+    xs = _layer(model, v_obs.reshape(B * T, N, 2), am, [mask_fn(b, t, Np) for t in range(T)], rec(range(T))).view(B, T, N, 64)
+    xs = xs * loss_mask_rel[:, :, :T].permute(0, 2, 1).unsqueeze(-1)
+    h = torch.zeros(B * N, 64, dtype=xs.dtype)
+    c = torch.zeros_like(h)
+    for t in range(T):
+        h, c = model._lstm_cell(xs[:, t].reshape(B * N, 64), h, c)
+    lm_fp = loss_mask_rel[:, :, T - 1]
+    mk = lm_fp.reshape(B * N, 1)
+    h, c = h * mk, c * mk
+    attn_pred = (lm_fp.unsqueeze(2) * lm_fp.unsqueeze(1)).permute(0, 2, 1)
+    mus, sxs, sys_, cors = [], [], [], []
+    x_sample = None
+    for tt in range(P):
+        if tt > 0:
+            call = decode_call(tt)
+            xt = _layer(model, x_sample.reshape(B, N, 2), attn_pred, [mask_fn(b, call, Np)], rec([call])).reshape(B * N, 64) * mk
+            hp, cp = model._lstm_cell(xt, h, c)
+            h = hp * mk + h * (1 - mk)
+            c = cp * mk + c * (1 - mk)
+        raw = model.hidden2pos(h).view(B, N, 5).unsqueeze(1)
+        mu = raw[..., :2]
+        mus.append(mu); sxs.append(raw[..., 2:3].exp()); sys_.append(raw[..., 3:4].exp()); cors.append(raw[..., 4:5].tanh())
+        x_sample = mu * lm_fp.unsqueeze(1).unsqueeze(-1)
+    return (torch.cat(mus, 1), torch.cat(sxs, 1), torch.cat(sys_, 1), torch.cat(cors, 1)), lm_fp
+
+
+def _nll(gaussian_params, x_target, loss_mask_ped, loss_mask_pred_seq):
+    """gst_train.negative_log_likelihood_full_partial."""
+    mu, sx, sy, corr = gaussian_params
+    m_t = loss_mask_pred_seq.permute(0, 2, 1).unsqueeze(-1)
+    m_p = loss_mask_ped.unsqueeze(1).unsqueeze(-1)
+    mu = mu * m_t * m_p
+    corr = corr * m_t * m_p
+    x_target = x_target * m_t * m_p
+    sx = (sx * m_t + (1. - m_t)) * m_p + (1. - m_p)
+    sy = (sy * m_t + (1. - m_t)) * m_p + (1. - m_p)
+    sigma = torch.cat((sx, sy), dim=3)
+    xn = (x_target - mu) / sigma
+    nx, ny = xn[..., 0:1], xn[..., 1:2]
+    t1 = torch.log(1. - corr ** 2.) / 2. + torch.log(sx) + torch.log(sy)
+    t2 = (nx ** 2. - 2. * corr * nx * ny + ny ** 2.) / (2. * (1. - corr ** 2.))
+    prob_loss = (t1 + t2).squeeze(3).squeeze(0)
+    elm = m_t[0, :, :, 0] * loss_mask_ped[0]
+    return prob_loss * elm, elm
+
+
+def masked_loss_and_grads(model, v_obs, v_pred, lm, seed, p, dtype=torch.float64, mask_fn=None, record=None):
+    """v_obs, v_pred [B,5,N,2], lm [B,N,10] -> (pooled loss, valid pairs, Gaussian parameters [B,5,N,5], {parameter name: gradient}) of the
+    training step under the kernel's masks for (seed, p), on a CPU copy of `model` in `dtype` (the model itself is not touched).
+    mask_fn(b, call, Np) -> four arrays replaces the masks (the sensitivity tests' mutants); record: a dict that receives, per (b, call),
+    {'relu_active': [N,128] bool} (which FFN units a site-2 element acts on)."""
+    if mask_fn is None:
+        mask_fn = lambda b, call, Np: masks(seed, b, call, Np, p)   # noqa: E731
+    m = copy.deepcopy(model).to("cpu", dtype)
+    m.zero_grad()
+    v_obs, v_pred, lm = v_obs.to("cpu", dtype), v_pred.to("cpu", dtype), lm.to("cpu", dtype)
+    num, den, gps = 0.0, 0.0, []
+    for b in range(v_obs.shape[0]):
+        l1 = lm[b:b + 1]
+        am = (l1[0].t().unsqueeze(2) * l1[0].t().unsqueeze(1))[:5].unsqueeze(0)
+        gp, lm_fp = _forward(m, v_obs[b:b + 1], am, l1, mask_fn, b, record)
+        pl, elm = _nll(gp, v_pred[b:b + 1], lm_fp, l1[:, :, 5:])
+        num, den = num + pl.sum(), den + elm.sum()
+        gps.append(torch.cat(gp, -1))
+    loss = num / den
+    loss.backward()
+    return loss.detach(), den.detach(), torch.cat(gps, 0).detach(), {k: q.grad.detach().clone() for k, q in m.named_parameters()}
+
+
+def ragged_case(B, N, seed):
+    """The ragged generator of the training / evaluation kernel tests with the weights drawn on the CPU (the same on every machine): B sequences
+    of N pedestrians, one present throughout, one without a last observed step, one never present, -999 where missing.
+    -> (model on the CPU, lm [B,N,10], v_obs [B,5,N,2], v_pred [B,5,N,2])."""
+    from crowdnav_prediction_attngraph_amd.gst import GSTPredictor
+    gw = torch.Generator().manual_seed(100 + seed)
+    torch.manual_seed(100 + seed)
+    model = GSTPredictor()
+    with torch.no_grad():
+        for q in model.parameters():
+            q.add_(0.05 * torch.randn(q.shape, generator=gw))
+    g = torch.Generator().manual_seed(seed)
+    lm = (torch.rand(B, N, 10, generator=g) > 0.25).float()
+    lm[:, 0] = 1.0
+    lm[:, 1, 4] = 0.0
+    if N > 2:
+        lm[:, 2, :] = 0.0
+    v_obs = torch.where(lm[:, :, :5].permute(0, 2, 1).unsqueeze(-1) > 0, 0.4 * torch.randn(B, 5, N, 2, generator=g), torch.full((B, 5, N, 2), -999.0))
+    v_pred = torch.where(lm[:, :, 5:].permute(0, 2, 1).unsqueeze(-1) > 0, 0.4 * torch.randn(B, 5, N, 2, generator=g), torch.full((B, 5, N, 2), -999.0))
+    return model, lm, v_obs, v_pred
+
+
+# ---- the bars of the GPU comparison (what the kernel holds with dropout off) and the distance of two results in units of them ----
+BAR, BAR_GRAD, BAR_GRAD_ABS = 2e-5, 1e-4, 1e-7
+
+
+def bars(ref):
+    """ref = masked_loss_and_grads(...) -> {'loss': bar, 'gauss': bar, parameter name: bar}."""
+    loss, _, gauss, grads = ref
+    out = {"loss": BAR * max(1.0, abs(float(loss))), "gauss": BAR * max(1.0, float(gauss.abs().max()))}
+    for k, g in grads.items():
+        out[k] = BAR_GRAD * max(float(g.abs().max()), 1e-6) + BAR_GRAD_ABS
+    return out
+
+
+def errors(res, ref):
+    """Largest absolute difference per compared quantity, same keys as bars()."""
+    out = {"loss": abs(float(res[0]) - float(ref[0])), "gauss": float((res[2].double() - ref[2].double()).abs().max())}
+    for k, g in ref[3].items():
+        out[k] = float((res[3][k].double() - g.double()).abs().max())
+    return out
+
+
+def ratios(res, ref):
+    """errors / bars of the reference, per quantity."""
+    e, b = errors(res, ref), bars(ref)
+    return {k: e[k] / b[k] for k in b}
