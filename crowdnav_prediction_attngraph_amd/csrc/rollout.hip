@@ -85,7 +85,61 @@ __global__ __launch_bounds__(1024) void episode_stats_kernel(int E, const uint8_
     }
 }
 
+// The per-step bookkeeping of the evaluation protocol (rl/evaluation.py:49-110) for one vec-env step, one lane per env, from the outputs of
+// cn_env_step as they are.  State layout: CN_EVAL_* of crowdnav_hip.h.  An env whose first episode is over is skipped, so steps fed after
+// every env has finished change nothing.  One workgroup striding over E: the count of the envs still active is a fixed-order sum, no atomics.
+__global__ __launch_bounds__(1024) void eval_accumulate_kernel(int E, const uint8_t *__restrict__ done, const uint8_t *__restrict__ info,
+                                                               const double *__restrict__ ep_ret, const float *__restrict__ robot_node,
+                                                               const double *__restrict__ danger_dist, int64_t *state, float *masks)
+{
+    __shared__ int part[16];
+    int64_t *active = state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_ACTIVE * E, *steps = state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_STEPS * E;
+    int64_t *dsteps = state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_DANGER_STEPS * E, *outcome = state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_OUTCOME * E;
+    double *dsum = reinterpret_cast<double *>(state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_DANGER_SUM * E);
+    double *path = reinterpret_cast<double *>(state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_PATH_LENGTH * E);
+    double *ret = reinterpret_cast<double *>(state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_RETURN * E);
+    float2 *last = reinterpret_cast<float2 *>(state + CN_EVAL_HEADER_WORDS + (size_t)CN_EVAL_LAST_POS * E);
+    int left = 0;
+    for (int e = threadIdx.x; e < E; e += 1024) {
+        const int d = done[e];
+        if (masks) masks[e] = d ? 0.0f : 1.0f;
+        if (!active[e]) continue;
+        const float px = robot_node[(size_t)e * 7], py = robot_node[(size_t)e * 7 + 1];
+        const float2 lp = last[e];
+        const float dx = px - lp.x, dy = py - lp.y;         // float32 like the observation the reference measures the path on
+        path[e] += (double)sqrtf(dx * dx + dy * dy);
+        last[e] = make_float2(px, py);
+        steps[e] += 1;
+        const int c = info[e];
+        if (c == CN_INFO_DANGER) { dsteps[e] += 1; dsum[e] += danger_dist[e]; }
+        if (d) { outcome[e] = c; ret[e] = ep_ret[e]; active[e] = 0; }
+        else left += 1;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) left += __shfl_xor(left, o, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = left;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int k = 0; k < 16; ++k) n += part[k];
+        state[CN_EVAL_N_ACTIVE] = n;
+    }
+}
+
 } // namespace
+
+extern "C" int64_t cn_eval_state_words(int E) { return E > 0 ? (int64_t)CN_EVAL_HEADER_WORDS + (int64_t)CN_EVAL_FIELDS * E : 0; }
+
+extern "C" int cn_eval_accumulate(int E, const uint8_t *done, const uint8_t *info, const double *ep_return, const float *robot_node,
+                                  const double *danger_dist, int64_t *state, float *masks, void *stream)
+{
+    if (int rc = cn_require_device()) return rc;
+    CN_REQUIRE(E > 0 && done && info && ep_return && robot_node && danger_dist && state, "cn_eval_accumulate: bad argument");
+    CN_REQUIRE(((uintptr_t)state & 7) == 0, "cn_eval_accumulate: the state buffer must be 8-byte aligned");
+    hipLaunchKernelGGL(eval_accumulate_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, E, done, info, ep_return, robot_node, danger_dist, state, masks);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
 
 extern "C" int cn_episode_stats_update(int E, const uint8_t *done, const uint8_t *info, const double *ep_return, const int32_t *ep_len, double *acc,
                                        void *stream)

@@ -14,8 +14,14 @@ from . import info as I
 from .config import to_env_config
 
 
-def _summarise(outcomes, steps, path_len, too_close, min_dists, ep_rewards, time_limit, time_step, logging):
+def _summarise(outcomes, steps, path_len, too_close, min_dists, ep_rewards, time_limit, time_step, logging, danger_sums=None):
+    """min_dists: the Danger distances of all episodes as one flat list, or None with danger_sums = their sum per episode (too_close = count)."""
     test_size = len(outcomes)
+    if min_dists is None:
+        n_close = sum(too_close)
+        min_intrusion = float(sum(danger_sums) / n_close) if n_close else float("nan")
+    else:
+        min_intrusion = float(np.mean(min_dists)) if len(min_dists) else float("nan")
     success = [k for k, o in enumerate(outcomes) if o == 3]
     collision = [k for k, o in enumerate(outcomes) if o == 2]
     timeout = [k for k, o in enumerate(outcomes) if o == 1]
@@ -24,7 +30,7 @@ def _summarise(outcomes, steps, path_len, too_close, min_dists, ep_rewards, time
     m = dict(success_rate=len(success) / test_size, collision_rate=len(collision) / test_size, timeout_rate=len(timeout) / test_size,
              nav_time=sum(success_times) / len(success_times) if success_times else time_limit,
              path_length=float(np.mean(path_len)), intrusion_ratio=float(np.mean([100.0 * c / s for c, s in zip(too_close, steps)])),
-             min_intrusion_dist=float(np.mean(min_dists)) if len(min_dists) else float("nan"),
+             min_intrusion_dist=min_intrusion,
              collision_cases=collision, timeout_cases=timeout, mean_reward=float(np.mean(ep_rewards)), episodes=test_size)
     if logging is not None:
         logging.info('Testing success rate: {:.2f}, collision rate: {:.2f}, timeout rate: {:.2f}, '
@@ -114,24 +120,94 @@ def _evaluate(actor_critic, eval_envs, num_processes, device, test_size, logging
     return _summarise(outcomes, steps, path_lens, too_closes, min_dists, ep_rewards, time_limit, time_step, logging)
 
 
-def evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, *, batch_invariant=False):
+class EvalAccumulator(object):
+    """The bookkeeping of the evaluation protocol for the first episode of each of E envs, fed with the step outputs of HipEnvBatch as they are.
+    The state is ONE int64 buffer laid out as include/crowdnav_hip.h describes (CN_EVAL_*): on the GPU an update is one launch of
+    cn_eval_accumulate and nothing is read back until `n_active()` / `results()`; the torch-op form below works on the same buffer -- it is
+    what CPU tensors use and the cross-check of the kernel (use_kernel=False on the GPU)."""
+    HEADER, FIELDS = 8, 8
+    ACTIVE, STEPS, DANGER_STEPS, OUTCOME, DANGER_SUM, PATH_LENGTH, RETURN, LAST_POS = range(8)
+
+    def __init__(self, num_envs, device, use_kernel=None):
+        self.E, self.device = int(num_envs), torch.device(device)
+        self.use_kernel = (self.device.type == "cuda") if use_kernel is None else bool(use_kernel)
+        self.state = torch.zeros(self.HEADER + self.FIELDS * self.E, dtype=torch.int64, device=self.device)
+        f = self.state[self.HEADER:].view(self.FIELDS, self.E)
+        self.active, self.steps, self.danger_steps, self.outcome = f[self.ACTIVE], f[self.STEPS], f[self.DANGER_STEPS], f[self.OUTCOME]
+        self.danger_sum, self.path_length, self.ep_return = (f[k].view(torch.float64) for k in (self.DANGER_SUM, self.PATH_LENGTH, self.RETURN))
+        self.last_pos = f[self.LAST_POS].view(torch.float32).view(self.E, 2)
+        self.masks = torch.zeros(self.E, 1, device=self.device)
+
+    def start(self, robot_node):
+        """robot_node: the [E,1,7] rows of the reset observation."""
+        self.state.zero_()
+        self.active.fill_(1)
+        self.state[0] = self.E
+        self.last_pos.copy_(robot_node.reshape(self.E, 7)[:, :2])
+        self.masks.zero_()
+
+    def update(self, done, info, ep_return, robot_node, danger_dist):
+        """One vec-env step.  Returns the masks of the next forward (done == 0 as float32 [E,1])."""
+        E = self.E
+        if self.use_kernel:
+            from . import _abi as A
+            if (done.dtype != torch.uint8 or info.dtype != torch.uint8 or ep_return.dtype != torch.float64 or robot_node.dtype != torch.float32
+                    or danger_dist.dtype != torch.float64 or done.numel() != E or info.numel() != E or ep_return.numel() != E
+                    or robot_node.numel() != 7 * E or danger_dist.numel() != E):
+                raise A.CnError("EvalAccumulator.update: done / info u8 [E], ep_return / danger_dist f64 [E], robot_node f32 [E,1,7] expected (E = %d)" % E)
+            with torch.cuda.device(self.device):
+                A.check(A.lib().cn_eval_accumulate(E, A.ptr(done), A.ptr(info), A.ptr(ep_return), A.ptr(robot_node), A.ptr(danger_dist), A.ptr(self.state),
+                                                   A.ptr(self.masks), A.stream_ptr()), "cn_eval_accumulate")
+            return self.masks
+        act = self.active != 0
+        pos = robot_node.reshape(E, 7)[:, :2]
+        # the reference measures the path on the float32 observation tensors, episode-end jump to the auto-reset start included
+        self.path_length += torch.where(act, torch.linalg.norm((pos - self.last_pos).float(), dim=1).double(), torch.zeros_like(self.path_length))
+        self.last_pos.copy_(torch.where(act.unsqueeze(1), pos, self.last_pos))
+        self.steps += act.long()
+        danger = act & (info == 4)
+        self.danger_steps += danger.long()
+        self.danger_sum += torch.where(danger, danger_dist, torch.zeros_like(danger_dist))
+        fin = act & (done != 0)
+        self.outcome.copy_(torch.where(fin, info.long(), self.outcome))
+        self.ep_return.copy_(torch.where(fin, ep_return, self.ep_return))
+        self.active.copy_((act & ~fin).long())
+        self.state[0] = self.active.sum()
+        self.masks.copy_((done == 0).float().view(E, 1))
+        return self.masks
+
+    def n_active(self):
+        """Envs whose first episode is still running (one host synchronisation)."""
+        return int(self.state[0].item())
+
+    def results(self):
+        """dict of per-env host lists: outcome, steps, danger_steps, danger_sum, path_length, ep_return."""
+        h = self.state.cpu()[self.HEADER:].view(self.FIELDS, self.E)
+        return dict(outcome=h[self.OUTCOME].tolist(), steps=h[self.STEPS].tolist(), danger_steps=h[self.DANGER_STEPS].tolist(),
+                    danger_sum=h[self.DANGER_SUM].view(torch.float64).tolist(), path_length=h[self.PATH_LENGTH].view(torch.float64).tolist(),
+                    ep_return=h[self.RETURN].view(torch.float64).tolist())
+
+
+def evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, *, batch_invariant=False, predictor=None):
     """The same protocol with every distinct test case as one env of one batch (all tensors stay on the GPU).  batch_invariant=True on both
     this and evaluate() makes the two report bit-identical episodes (tests/test_gpu_eval.py); by default both run the fused kernels and
-    agree to the policy's 1e-7-level sensitivity to its tile neighbours (which can flip a chaotic episode's outcome)."""
-    if env_name == "CrowdSimPredRealGST-v0":
-        # the raw env observation carries placeholder futures; the policy needs the VecPretextNormalize processing (GST predictions,
-        # distance sort, social penalty), which this function does not run
-        raise NotImplementedError("evaluate_batched does not run the GST wrapper: evaluate CrowdSimPredRealGST-v0 with "
-                                  "evaluate(actor_critic, make_vec_envs(..., pretext_wrapper=True), ...)")
+    agree to the policy's 1e-7-level sensitivity to its tile neighbours (which can flip a chaotic episode's outcome).
+    CrowdSimPredRealGST-v0 runs behind the VecPretextNormalize processing (gst.PretextProcessor over the batch): predictor = a
+    gst.GSTPredictor, or None to load config.pred.model_dir."""
     with _batch_invariant(actor_critic, batch_invariant):
-        return _evaluate_batched(actor_critic, env_name, config, seed, test_size, device, logging)
+        return _evaluate_batched(actor_critic, env_name, config, seed, test_size, device, logging, predictor=predictor)
 
 
-def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None):
+def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, predictor=None, poll_every=16, act_fn=None,
+                      hip_policy=None, use_kernel=True, per_env=None):
+    """poll_every: the count of running episodes is read back (the loop's only host synchronisation) every that many steps; steps taken after
+    the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
+    hip_policy: a HipPolicy handle to run instead of actor_critic's own (train() evaluates through a second handle so that the training
+    rollout finds its handle as it left it); use_kernel=False: the torch-op bookkeeping; per_env: a dict that receives the per-env results."""
     from .hip import HipEnvBatch
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = to_env_config(config, env_name, 1, "test")          # nenv = 1: case counters advance by one, as in the sequential run
-    scripted = actor_critic is None
+    scripted = actor_critic is None and act_fn is None
     if scripted and int(cfg.robot_policy) == 0:
         raise ValueError("actor_critic is None but config.robot.policy is not 'orca'")
     if int(cfg.robot_policy) == 1 and int(cfg.randomize_attributes):
@@ -144,57 +220,60 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     env = HipEnvBatch(cfg, E, int(seed), device=device)
     # env e draws seed offset + counter[e] + (seed + e): counter[e] = case - e  (cases are distinct and sorted, so case >= e)
     env.set_case_counters(torch.tensor([c - e for e, c in enumerate(cases)], dtype=torch.int64))
+    pretext = None
+    if env_name == "CrowdSimPredRealGST-v0":
+        # VecPretextNormalize over the batch: GST predictions into spatial_edges[:, :, 2:], rows sorted by distance.  Every episode evaluated
+        # here is the first one after the wrapper's reset(), i.e. starts from the dummy history, as every episode of the sequential run does
+        from .gst import PretextProcessor, load_predictor
+        pred = predictor if predictor is not None else load_predictor(config, device)
+        data = getattr(config, "data", None)
+        interval = int(float(getattr(data, "pred_timestep", cfg.time_step)) // float(cfg.time_step))   # as BatchedCrowdSim.__init__
+        pretext = PretextProcessor(pred.to(device), E, env.H, int(cfg.predict_steps), float(cfg.robot_radius), float(cfg.human_radius),
+                                   float(cfg.collision_penalty), device, pred_interval=interval)
+        zero_reward = torch.zeros(E, device=device)
     obs = env.reset()
-    pol = None if scripted else actor_critic._hip_policy(E, device)
+    pol = None
+    if act_fn is None and not scripted:
+        pol = hip_policy if hip_policy is not None else actor_critic._hip_policy(E, device)
     zero_action = torch.zeros(E, 2, device=device)
-    H = env.H
     hx = [torch.zeros(E, 1, 128, device=device), torch.zeros(E, 1, 128, device=device)]
-    masks = torch.zeros(E, 1, device=device)
-    active = torch.ones(E, dtype=torch.bool, device=device)
-    steps = torch.zeros(E, dtype=torch.int64, device=device)
-    too_close = torch.zeros(E, dtype=torch.int64, device=device)
-    path_len = torch.zeros(E, dtype=torch.float64, device=device)
-    outcome = torch.zeros(E, dtype=torch.int64, device=device)
-    ep_reward = torch.zeros(E, dtype=torch.float64, device=device)
-    last_pos = obs["robot_node"].view(E, 7)[:, :2].clone()
-    md_steps = []                                              # (env, step, min_dist) of every Danger step of a first episode
+    acc = EvalAccumulator(E, device, use_kernel=use_kernel)
+    acc.start(obs["robot_node"])
+    masks = acc.masks
+    danger_dist = torch.zeros(E, dtype=torch.float64, device=device)
     max_steps = int(round(float(cfg.time_limit) / float(cfg.time_step))) + 1
+    poll_every = max(1, int(poll_every))
     for t in range(max_steps):
         if scripted:
             action = zero_action
         else:
             pobs = {k: obs[k] for k in ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num")}
-            out = pol.act(pobs, hx[t & 1], masks, eps=None)      # deterministic: dist.mode() (model.py:66-67)
-            hx[(t + 1) & 1] = out["hxs"].view(E, 1, 128)
-            action = out["action"]
+            if pretext is not None:
+                # the social penalty lands in the env's own reward buffer, as in BatchedCrowdSim.step_device: no metric reads it (the episode
+                # reward is the Monitor's sum of the raw reward)
+                pobs["spatial_edges"], _ = pretext.process(obs, zero_reward if t == 0 else rew)
+            if act_fn is not None:
+                action = act_fn(t, pobs)
+            else:
+                out = pol.act(pobs, hx[t & 1], masks, eps=None)      # deterministic: dist.mode() (model.py:66-67)
+                hx[(t + 1) & 1] = out["hxs"].view(E, 1, 128)
+                action = out["action"]
         obs, rew, done, info, ep_ret, _ = env.step(action)
-        pos = obs["robot_node"].view(E, 7)[:, :2]
-        # the reference measures the path on the float32 observation tensors, episode-end jump to the auto-reset start included
-        path_len += torch.where(active, torch.linalg.norm((pos - last_pos).float(), dim=1).double(), torch.zeros_like(path_len))
-        last_pos = pos.clone()
-        steps += active.long()
-        danger = active & (info == 4)
-        if bool(danger.any()):
-            md = env.get_danger_min_dist()
-            idx = danger.nonzero().squeeze(1)
-            md_steps.append(torch.stack([idx.double(), torch.full_like(idx, t).double(), md[idx]], 1))
-        too_close += danger.long()
-        fin = active & (done != 0)
-        outcome = torch.where(fin, info.long(), outcome)
-        ep_reward = torch.where(fin, ep_ret, ep_reward)
-        active = active & ~fin
-        masks = (done == 0).float().view(E, 1)
-        if not bool(active.any()):
+        env.get_danger_min_dist(out=danger_dist)
+        masks = acc.update(done, info, ep_ret, obs["robot_node"], danger_dist)
+        if (t + 1) % poll_every == 0 and acc.n_active() == 0:
             break
     env.close()
-    outcome_h, steps_h, path_h, close_h = outcome.cpu().tolist(), steps.cpu().tolist(), path_len.cpu().tolist(), too_close.cpu().tolist()
-    rew_h = [round(x, 6) for x in ep_reward.cpu().tolist()]
-    md = torch.cat(md_steps).cpu().numpy() if md_steps else np.zeros((0, 3))
+    if pretext is not None and pretext.hip is not None:
+        pretext.hip.close()
+    r = acc.results()
+    if per_env is not None:
+        per_env.update(r, cases=cases)
+    if any(o == 0 for o in r["outcome"]):
+        raise ValueError("Invalid end signal from environment")
+    rew_h = [round(x, 6) for x in r["ep_return"]]
     e_of = {c: e for e, c in enumerate(cases)}
-    outcomes, steps_l, paths, closes, mins, rewards = [], [], [], [], [], []
-    for k in range(test_size):                                  # sequential episode k == first episode of the env of its case
-        e = e_of[case_of[k]]
-        outcomes.append(outcome_h[e]); steps_l.append(steps_h[e]); paths.append(path_h[e]); closes.append(close_h[e]); rewards.append(rew_h[e])
-        rows = md[md[:, 0] == e]
-        mins.extend(rows[np.argsort(rows[:, 1]), 2].tolist())
-    return _summarise(outcomes, steps_l, paths, closes, mins, rewards, float(cfg.time_limit), float(cfg.time_step), logging)
+    order = [e_of[case_of[k]] for k in range(test_size)]       # sequential episode k == first episode of the env of its case
+    pick = lambda xs: [xs[e] for e in order]
+    return _summarise(pick(r["outcome"]), pick(r["steps"]), pick(r["path_length"]), pick(r["danger_steps"]), None, pick(rew_h), float(cfg.time_limit),
+                      float(cfg.time_step), logging, danger_sums=pick(r["danger_sum"]))

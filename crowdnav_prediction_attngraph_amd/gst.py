@@ -184,13 +184,15 @@ class PretextProcessor:
         self.mask = sd["mask"].to(self.device).to(torch.bool).view(self.buffer_len, self.E, self.H, 1).clone()
 
     @torch.no_grad()
-    def process(self, obs, rews):
+    def process(self, obs, rews, out=None):
         """obs: dict with robot_node [E,1,7], spatial_edges [E,H,2(P+1)] (unsorted, by human id), visible_masks [E,H] bool.
-        rews [E] or [E,1] device tensor.  Returns (new spatial_edges [E,H,2(P+1)] sorted by distance, rews + social penalty)."""
+        rews [E] or [E,1] device tensor.  Returns (new spatial_edges [E,H,2(P+1)] sorted by distance, rews + social penalty).
+        out: optional [E,H,2(P+1)] float32 tensor that receives the new spatial edges (a rollout-storage row); on the GPU a contiguous
+        float32 `rews` is then updated where it is."""
         E, H, P = self.E, self.H, self.P
         if self.hip is not None:
             rews = rews.reshape(E).float().contiguous()
-            se = self.hip.wrapper_step(obs, rews, self.dist, self.collision_penalty)
+            se = self.hip.wrapper_step(obs, rews, self.dist, self.collision_penalty, out=out)
             return se, rews
         robot_xy = obs["robot_node"][:, :, :2]
         se = obs["spatial_edges"].clone()
@@ -206,6 +208,8 @@ class PretextProcessor:
         se[:, :, 2:] = torch.where(out_mask.expand(E, H, 2 * P), rel.reshape(E, H, 2 * P), se[:, :, 2:])
         order = torch.argsort(se[:, :, :2].norm(dim=-1), dim=1, stable=True)
         se = torch.gather(se, 1, order.unsqueeze(-1).expand(E, H, se.shape[2]))
+        if out is not None:
+            se = out.copy_(se)
         return se, rews
 
 

@@ -161,9 +161,12 @@ class HipEnvBatch:
             A.check(A.lib().cn_env_load(self._h, A.ptr(buf), A.stream_ptr()), "cn_env_load")
         self.row_plan[:8].zero_()   # the plan belongs to an observation of the state that was just replaced
 
-    def get_danger_min_dist(self):
-        """Danger.min_dist of the last step per env (float64 [E]); non-zero only in the test phase."""
-        out = torch.zeros(self.E, dtype=torch.float64, device=self.device)
+    def get_danger_min_dist(self, out=None):
+        """Danger.min_dist of the last step per env (float64 [E]); non-zero only in the test phase.  out: optional tensor to write into."""
+        if out is None:
+            out = torch.zeros(self.E, dtype=torch.float64, device=self.device)
+        elif out.dtype != torch.float64 or out.numel() != self.E or not out.is_contiguous():
+            raise A.CnError("out must be a contiguous float64 tensor of %d elements" % self.E)
         with torch.cuda.device(self.device):
             A.check(A.lib().cn_env_get_danger_min_dist(self._h, A.ptr(out), A.stream_ptr()), "cn_env_get_danger_min_dist")
         return out

@@ -79,18 +79,39 @@ def collect_rollout(envs, actor_critic, rollouts, stats=None, generator=None):
             _, reward, done, info, ep_ret, ep_len = env.step(rollouts.actions[t], obs=obs_n, not_done=rollouts.masks[t + 1],
                                                              reward=rollouts.rewards[t])   # rows written in place
         else:
-            # GST wrapper in the loop: predictions / sort / social penalty post-process the raw observation
-            o, reward, done, info, ep_ret, ep_len = envs.step_device(rollouts.actions[t])
-            for k in obs_t:
-                rollouts.obs[k][t + 1].copy_(o[k].view_as(rollouts.obs[k][t + 1]))
-            if "visible_masks" in rollouts.obs:
-                rollouts.obs["visible_masks"][t + 1].copy_(o["visible_masks"].to(torch.bool))
-        if envs._pretext is not None:
-            rollouts.rewards[t].copy_(reward.view(E, 1))
-            rollouts.masks[t + 1].copy_((done == 0).view(E, 1))
+            # GST wrapper in the loop, in place as well: the simulator writes every row but the spatial edges, which the wrapper needs raw
+            # (by human id): those go to the batch's own buffer, and the wrapper writes predictions / distance sort into the storage row and
+            # adds the social penalty to the reward row
+            raw = dict(obs_n, spatial_edges=env.obs["spatial_edges"])
+            if raw["visible_masks"] is None:
+                raw["visible_masks"] = env.obs["visible_masks"]
+            _, reward, done, info, ep_ret, ep_len = env.step(rollouts.actions[t], obs=raw, not_done=rollouts.masks[t + 1], reward=rollouts.rewards[t])
+            envs._pretext.process(raw, rollouts.rewards[t].view(E), out=rollouts.obs["spatial_edges"][t + 1])
         if stats is not None:
             stats.update(done, info, ep_ret, ep_len)
     rollouts.step = 0
+
+
+def evaluate_policy(actor_critic, env_name, config, seed, eval_cases=None, device=None, predictor=None, logging=None):
+    """The batched test protocol on the current weights through a policy handle of its OWN: Policy._hip_policy hands out one handle per
+    policy, and what the training rollout has set on it (weight snapshot, gemm mode, a post-hh hook) stays as it is.  No torch RNG draw."""
+    from .config import Config
+    from .evaluation import _evaluate_batched
+    from .hip import HipPolicy
+    config = config if config is not None else Config()
+    if eval_cases is None:
+        eval_cases = int(config.env.test_size)
+    E = len(set((2 * k) % int(config.env.test_size) for k in range(eval_cases)))     # distinct cases = envs of the batch (evaluation.py)
+    base = actor_critic.base
+    pol = HipPolicy(base.human_num, base.edge_width, E, device=device)
+    try:
+        pol.set_self_attention(base.use_self_attn)
+        pol.set_taps(False)
+        pol.set_gemm_mode(actor_critic.rollout_gemm_mode)
+        pol.set_weights(actor_critic.state_dict())
+        return _evaluate_batched(actor_critic, env_name, config, seed, eval_cases, device, logging, predictor=predictor, hip_policy=pol)
+    finally:
+        pol.close()
 
 
 def bootstrap_value(actor_critic, rollouts):
@@ -161,14 +182,25 @@ def update_flops(live_rows, samples, ppo_epoch):
 
 def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_updates=10, seed=425, config=None, ppo_epoch=5,
           num_mini_batch=2, lr=4e-5, eps=1e-5, clip_param=0.2, value_loss_coef=0.5, entropy_coef=0.0, max_grad_norm=0.5, gamma=0.99,
-          gae_lambda=0.95, log=print, device=None, save_dir=None, save_interval=0, resume=None, use_self_attn=True, sort_humans=None):
+          gae_lambda=0.95, log=print, device=None, save_dir=None, save_interval=0, resume=None, use_self_attn=True, sort_humans=None,
+          pretext_wrapper=None, predictor=None, eval_interval=0, eval_cases=None):
     """Returns a list of per-update dicts (losses, timings, episode stats).  Works single- or multi-GPU (one process per
     GPU, torch.distributed initialised by the caller).  save_dir / save_interval: write checkpoints like train.py:213-219 (every
     `save_interval` updates and after the last one); resume = path of a `NNNNN.pt` written by this function: continue that run
-    (updates NNNNN+1 .. num_updates-1) with results bit-identical to the uninterrupted run."""
+    (updates NNNNN+1 .. num_updates-1) with results bit-identical to the uninterrupted run.
+    pretext_wrapper: train CrowdSimPredRealGST-v0 behind the VecPretextNormalize processing (GST predictions in the observation, social
+    penalty in the reward); None follows config.env.use_wrapper, as the reference's train.py:86 does.  predictor: a gst.GSTPredictor instead
+    of the checkpoint under config.pred.model_dir.
+    eval_interval: every that many updates and after the last one, run the batched test protocol (evaluation.evaluate_batched: eval_cases
+    episodes, default config.env.test_size, phase 'test', same config / seed / predictor) on the current weights and put its metrics under
+    rec["eval"].  The training run itself -- losses, statistics, checkpoints, weights -- is bit-identical with and without it: the evaluation
+    owns its simulator, wrapper and policy handle and draws from no torch RNG stream.  Under torch.distributed rank 0 evaluates."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
-    envs = make_vec_envs(env_name, seed, num_processes, gamma, None, device, False, config=config, phase="train")
+    if pretext_wrapper is None:
+        pretext_wrapper = bool(getattr(getattr(config, "env", None), "use_wrapper", False))
+    envs = make_vec_envs(env_name, seed, num_processes, gamma, None, device, False, config=config, phase="train", pretext_wrapper=bool(pretext_wrapper),
+                         predictor=predictor)
     # arguments.py:189, :206: use_self_attn, and sort_humans -- by default whatever the config's args say (it also decides the simulator's row order)
     if sort_humans is None:
         sort_humans = bool(getattr(getattr(config, "args", None), "sort_humans", True))
@@ -216,6 +248,12 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
         rec = dict(update=j, value_loss=value_loss, action_loss=action_loss, entropy=dist_entropy, rollout_s=t1 - t0, update_s=t2 - t1,
                    allreduce_ms=getattr(agent, "last_allreduce_ms", None), live_rows=int(live_rows.item()),
                    samples_per_s=num_steps * num_processes / (t2 - t0), **stats.pop())
+        if eval_interval and ((j + 1) % eval_interval == 0 or j == num_updates - 1):
+            rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+            if rank == 0:     # the other ranks go on to the next rollout and meet this one at its first collective
+                t3 = time.perf_counter()
+                rec["eval"] = evaluate_policy(actor_critic, env_name, config, seed, eval_cases, device, predictor=envs._pretext.pred if envs._pretext is not None else predictor)
+                rec["eval_s"] = time.perf_counter() - t3
         history.append(rec)
         if log:
             log(rec)

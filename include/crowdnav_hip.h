@@ -147,7 +147,7 @@ typedef struct cn_policy cn_policy;
 
 /* Bumped whenever a struct layout, a signature or the snapshot format changes (round 4: cn_obs.row_plan, cn_env_config.robot_fov /
  * human_fov, the profiling entry points, snapshot layout CNENV004); the ctypes binding refuses a library that reports another number. */
-#define CN_ABI_VERSION 405
+#define CN_ABI_VERSION 406
 const char *cn_last_error(void);
 int cn_version(void);
 int cn_device_count(void);
@@ -557,6 +557,24 @@ int cn_adv_normalize(int64_t n, const float *returns, const float *values, const
  * device) += {finished episodes, sum of their returns, sum of their lengths, timeouts, collisions, goals reached, -, -}.  One launch with a
  * fixed summation order instead of two dozen small reductions per rollout step. */
 int cn_episode_stats_update(int E, const uint8_t *done, const uint8_t *info, const double *ep_return, const int32_t *ep_len, double *acc, void *stream);
+
+/* The per-step bookkeeping of the evaluation protocol (rl/evaluation.py:49-110) for the FIRST episode of each of E envs, from the outputs of
+ * cn_env_step as they are: done / info [E] u8, ep_return [E] f64, robot_node = the [E,1,7] float32 rows of the NEW observation (auto-reset start
+ * of the next episode where done), danger_dist [E] f64 = cn_env_get_danger_min_dist of that step.  One launch, one workgroup, no atomics: a rerun
+ * gives the same bits.  state: caller-owned, 8-byte words, cn_eval_state_words(E) = CN_EVAL_HEADER_WORDS + CN_EVAL_FIELDS * E of them:
+ *   word CN_EVAL_N_ACTIVE (int64): envs whose first episode is still running after this call (OUTPUT; the other header words are reserved)
+ *   then CN_EVAL_FIELDS arrays of E words each, array f at word CN_EVAL_HEADER_WORDS + f * E:
+ *     ACTIVE int64 0/1 | STEPS int64 | DANGER_STEPS int64 | OUTCOME int64 (CN_INFO_* of the final step) |
+ *     DANGER_SUM f64 (sum of danger_dist over the Danger steps, in step order) | PATH_LENGTH f64 (sum of the float32 norm of the float32 position
+ *     difference, jump to the auto-reset start included) | RETURN f64 (ep_return at the final step) | LAST_POS 2 x float32 (x, y).
+ * The caller starts an evaluation with ACTIVE = 1, LAST_POS = the robot position of the reset observation and everything else 0.  An env with
+ * ACTIVE = 0 is left alone, so steps fed after every env has finished change nothing.  masks (optional, [E] float32) <- done == 0. */
+enum { CN_EVAL_HEADER_WORDS = 8, CN_EVAL_N_ACTIVE = 0, CN_EVAL_FIELDS = 8 };
+enum { CN_EVAL_ACTIVE = 0, CN_EVAL_STEPS = 1, CN_EVAL_DANGER_STEPS = 2, CN_EVAL_OUTCOME = 3, CN_EVAL_DANGER_SUM = 4, CN_EVAL_PATH_LENGTH = 5,
+       CN_EVAL_RETURN = 6, CN_EVAL_LAST_POS = 7 };
+int64_t cn_eval_state_words(int E);
+int cn_eval_accumulate(int E, const uint8_t *done, const uint8_t *info, const double *ep_return, const float *robot_node, const double *danger_dist,
+                       int64_t *state, float *masks, void *stream);
 
 /* ---- PPO losses (rl/ppo/ppo.py:66-84) ----
  * values, logp (new policy), old_logp, adv (normalised advantages), value_preds, returns: [n] float32 (the [T*N,1] minibatch
