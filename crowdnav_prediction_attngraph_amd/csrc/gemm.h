@@ -1,4 +1,6 @@
-// gemm.h -- exact-fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32) shared by policy.hip and gst.hip.
+// gemm.h -- exact-fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32) of policy.hip: the rollout's per-env layers, its big layers in gemm mode 0, and
+// edge_attention_embed's forward in cn_rn_seq_fwd.  The MFMA vector types, the ACT_* enum, the XCD tile mappings and BM are also what
+// the split-precision GEMMs build on (gemm3.h in policy.hip; gemm3p.h and gemm3_tn.h in linear.hip).
 #pragma once
 #include "common.h"
 
@@ -8,8 +10,8 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2,
-       // backward epilogues (training path, rn_train in policy.hip): the product is a gradient w.r.t. an activation whose forward VALUE y is
-       // handed over in GemmBatch::resid -- multiply by relu'(y) = [y > 0] or tanh'(.) = 1 - y^2 instead of adding a residual
+       // backward epilogues, gemm3p_nt_kernel only (gemm3p.h; cn_rn_seq_bwd reaches it through cn_linear_fwd_act): the product is a gradient
+       // w.r.t. an activation whose forward VALUE y is handed over in `aux` -- multiply by relu'(y) = [y > 0] or tanh'(.) = 1 - y^2
        ACT_MUL_DRELU = 3, ACT_MUL_DTANH = 4 };
 
 // XCD-aware tile mapping.  Workgroups are dispatched round-robin over the 8 XCDs (linear id L -> XCD L % 8), each with a
@@ -142,15 +144,12 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(int M, int N, int K, const
                     float v = acc[i][j][r] + b;
                     if (ACT == ACT_RELU || extra_relu) v = fmaxf(v, 0.0f);
                     if (ACT == ACT_TANH) v = tanhf(v);
-                    if (ACT == ACT_MUL_DRELU) v = gb.resid[(size_t)row * gb.ldr + col] > 0.0f ? v : 0.0f;
-                    else if (ACT == ACT_MUL_DTANH) { const float y = gb.resid[(size_t)row * gb.ldr + col]; v *= 1.0f - y * y; }
-                    else if (gb.resid) v += gb.resid[(size_t)row * gb.ldr + col];
+                    if (gb.resid) v += gb.resid[(size_t)row * gb.ldr + col];
                     C[(size_t)row * ldc + col] = v;
                 }
             }
         }
 }
-
 
 template <int TBM, int BN, int ACT>
 static int launch_gemm_t(int M, int N, int K, const float *A, int lda, const float *W, const float *bias, float *C, int ldc, hipStream_t st,

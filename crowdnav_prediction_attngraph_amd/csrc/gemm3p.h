@@ -1,7 +1,8 @@
-// gemm3p.h -- the split-precision ("bf16x3") NT GEMM of gemm3.h for the PPO update's row counts (M = 3e5 .. 5e5 live rows).
+// gemm3p.h -- the split-precision ("bf16x3", split_bf16.h) NT GEMM for the PPO update's row counts (M = 3e5 .. 5e5 live rows) and the
+// fragment-order split of its weights.  Only linear.hip includes it (cn_linear_fwd, cn_linear_fwd_act, cn_split_bf16*).
 //
-// Why a second kernel.  Knock-out runs of the 128 x 128 / two-barrier kernel on the q|k|v shape (M = 400 k, N = 1536, K = 512;
-// 2.83 ms) showed its four components adding up instead of overlapping: MFMA 0.95 ms + LDS / convert / barrier skeleton 0.81
+// Why not the rollout's kernel (gemm3_nt_kernel, gemm3.h).  Knock-out runs of that 128 x 128 / two-barrier kernel on the q|k|v shape
+// (M = 400 k, N = 1536, K = 512; 2.83 ms) showed its four components adding up instead of overlapping: MFMA 0.95 ms + LDS / convert / barrier skeleton 0.81
 // + global loads 0.65 + C stores 0.45.  Neither more workgroups per CU, larger tiles nor a double-buffered K loop changed the
 // sum (all within 7 %): every wavefront of a workgroup is in the same phase at the same time and a wavefront that is issuing
 // MFMAs issues nothing else; and the stores sat one per basic block behind an s_waitcnt vmcnt(0) (see the epilogue).
@@ -15,7 +16,9 @@
 //     k-step 0, W fragment loads two tiles ahead }; groups of three MFMAs fenced with sched_barrier keep the side work spread.
 // LDS traffic per K tile: 16 KB written + 64 KB read for 48 MFMAs (1536 cycles) per wavefront = 40 % of the LDS peak.
 #pragma once
-#include "gemm3.h"
+#include "common.h"
+#include "gemm.h"
+#include "split_bf16.h"
 
 namespace {
 
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, 
                                                            const float *__restrict__ bias, float *__restrict__ C, int ldc,
                                                            const float *__restrict__ aux, int ldaux, int relu_from)
 {
-    // Epilogues (ACT, gemm.h): none / ReLU / tanh on the sum, or -- backward products of the robot-node sequence -- the sum times the
+    // Epilogues (the ACT_* enum of gemm.h): none / ReLU / tanh on the sum, or -- backward products of the robot-node sequence -- the sum times the
     // derivative of the activation whose forward VALUE y sits in aux [M, ldaux]: [y > 0] (ACT_MUL_DRELU) or 1 - y^2 (ACT_MUL_DTANH).
     // Columns >= relu_from get a ReLU on top of ACT (one launch produces [u | relu(enc)]); pass relu_from >= N for none.
     constexpr int TBM = 128, MI = 4, BN = 128 * NB;
@@ -283,10 +286,14 @@ __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, 
     }
 }
 
+// Agate (optional): backward through a ReLU, A = dY gated by the forward output (same shape / leading dimension).  The gated kernels exist
+// for ACT_NONE and ACT_RELU only -- what cn_linear_fwd, the one caller with a gate, admits.
 template <int ACT>
 static int launch_gemm3p(int M, int N, int K, const float *A, int lda, const __bf16 *Whi, const __bf16 *Wlo, const float *bias, float *C, int ldc,
                          hipStream_t st, const float *Agate, const float *aux = nullptr, int ldaux = 0, int relu_from = 1 << 30)
 {
+    constexpr bool CAN_GATE = ACT == ACT_NONE || ACT == ACT_RELU;
+    CN_REQUIRE(CAN_GATE || !Agate, "gemm3p: no gated kernel for act %d (a ReLU gate on A goes with act 0 or 1)", ACT);
     CN_REQUIRE(N % 128 == 0 && K % 64 == 0 && lda % 4 == 0, "gemm3p: unsupported shape M=%d N=%d K=%d lda=%d", M, N, K, lda);
     CN_REQUIRE((long long)M * lda < (1LL << 31) && (long long)N * K < (1LL << 31), "gemm3p: operand too large for 32-bit element offsets (M=%d lda=%d)", M, lda);
     if (M == 0) return CN_OK;
@@ -295,183 +302,18 @@ static int launch_gemm3p(int M, int N, int K, const float *A, int lda, const __b
     const int nb = N % 256 == 0 ? 2 : 1;
     const int per_xcd = N / (128 * nb) * gy / 8;                 // output tiles per XCD
     const dim3 grid(8 * (per_xcd < 32 ? per_xcd : 32));          // persistent: one workgroup per CU, 32 CUs per XCD
-    if (nb == 2) {
-        if (Agate) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
-        else hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
-    } else {
-        if (Agate) hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
-        else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
+    if constexpr (CAN_GATE) {
+        if (Agate) {
+            if (nb == 2) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
+            else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
+            CN_CHECK_LAUNCH();
+            return CN_OK;
+        }
     }
+    if (nb == 2) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
+    else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
     CN_CHECK_LAUNCH();
     return CN_OK;
-}
-
-// ---- weight gradient: P[s][n][k] = sum_{m in split s} dY[m][n] X[m][k] (see gemm3_tn_kernel in gemm3.h for the contract) ----
-// Same division of labour as gemm3p_nt_kernel: the 128 dY columns of the tile are shared by the four wavefronts and go through
-// the LDS (transposed on the way in: a thread loads 8 consecutive m of ONE column with 8 coalesced dword loads and stores them as
-// one 16-byte fragment word per plane), the X columns belong to exactly one wavefront each (32 NB of them) and go straight from
-// global memory into fragment registers: lane (l31, half) of block j loads X[m0 + 8 half + e][k0 + 32 j + l31], e = 0..7 -- eight
-// dword loads of two full 128-byte lines each.  One barrier per 32 rows of m; no LDS traffic for X at all.  NB = 1, 2 or 4 (a wavefront
-// then owns 32 / 64 / 128 X columns and 64 / 128 / 256 accumulator registers).
-template <int NB, bool GATE>
-__global__ __launch_bounds__(256, 1) void gemm3p_tn_kernel(int M, int N, int K, const float *__restrict__ dY, int ldy, const float *__restrict__ Ygate,
-                                                           const float *__restrict__ X, int ldx, int rows_per_split, int nsplit,
-                                                           float *__restrict__ partials, float *__restrict__ db_part)
-{
-    constexpr int MI = 4, PS = 40, BUF = 2 * 128 * PS;
-    extern __shared__ __attribute__((aligned(16))) char smem3p[];
-    __bf16 *lds = reinterpret_cast<__bf16 *>(smem3p);
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6); // (uniform: the buffer resources below live in SGPRs)
-    const int half = lane >> 5, l31 = lane & 31;
-    // XCD-aware 1-D grid: workgroup L runs on XCD L % 8 (round-robin dispatch); all tiles of one split go to ONE XCD, so the rows
-    // of dY and X that the split owns stream through one L2 once (the tiles advance over m together) instead of through up to 8 of
-    // them (with x-fastest 3-D indexing every tile of a split sat on a different XCD: 14.7 GB of L2 misses for 3.3 GB of operands)
-    const int L = blockIdx.x, NX = N / 128, tiles = NX * (K / (128 * NB));
-    const int split = (L & 7) + 8 * ((L >> 3) / tiles), tile = (L >> 3) % tiles;
-    if (split >= nsplit) return;
-    const int n_blk = (tile % NX) * 128, k_blk = (tile / NX) * (128 * NB) + wave * 32 * NB;
-    // M and rows_per_split are multiples of 32 here (the launcher hands the last M % 32 rows to gemm3_tn_kernel): no row predicates,
-    // and every row offset below is wave-uniform, i.e. scalar address arithmetic (one SALU add per load instead of a 64-bit VALU chain)
-    const int m_begin = split * rows_per_split;
-    const int m_end = min(M, m_begin + rows_per_split);
-    const int T = (m_end - m_begin) / 32;
-    const bool want_db = db_part != nullptr && tile / NX == 0;
-
-    f32x16 acc[MI][NB];
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    // dY staging: thread (column c, half-tile g0) owns m groups g0 and g0 + 2 (8 rows each) of the 32-row tile
-    const int c = tid & 127, g0 = __builtin_amdgcn_readfirstlane(tid >> 7);
-    // Buffer addressing relative to the split's first row: a load is ONE instruction (per-lane byte offset register + wave-uniform
-    // scalar offset + immediate).  With flat 64-bit addresses every one of the 48 loads of a 32-row tile carried a 64-bit VALU add
-    // and three scalar multiplies / adds -- 130 of the loop's 460 instructions, on a wavefront that is alone on its SIMD.
-    // (a split spans < 2^31 bytes of either operand: rows_per_split * ld * 4)
-    const __amdgpu_buffer_rsrc_t yrs = __builtin_amdgcn_make_buffer_rsrc((void *)(dY + (size_t)m_begin * ldy + n_blk), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc((void *)((GATE ? Ygate : dY) + (size_t)m_begin * ldy + n_blk), 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc((void *)(X + (size_t)m_begin * ldx + k_blk), 0, 0x7fffffff, 0x00020000);
-    unsigned yv[8], xv[8]; // per-lane byte offsets of row e of a group: column c of dY; the lane's X column, its 8 rows start 8 * half below the k-step's first row
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { yv[e] = (unsigned)(e * ldy + c) * 4u; xv[e] = (unsigned)((half * 8 + e) * ldx + l31) * 4u; }
-    float sy[2][8], sg[GATE ? 2 : 1][8];
-    // X: raw rows of this lane's fragments, [k-step][block][e]
-    float rx[2][NB][8];
-    bf16x8 fah[2][MI], fal[2][MI], fwh[2][NB], fwl[2][NB];
-    float colsum = 0.0f;
-    // tiles past the end of the split (the pipeline runs two ahead) read its last tile again; what they stage is never multiplied
-    auto load_y = [&](int q, int tile) {
-        const unsigned so = (unsigned)((min(tile, T - 1) * 32 + (g0 + 2 * q) * 8) * ldy) * 4u; // wave-uniform
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            sy[q][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(yrs, yv[e], so, 0));
-            if (GATE) sg[GATE ? q : 0][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(grs, yv[e], so, 0));
-        }
-    };
-    auto stage_y = [&](int q, int tile, int b) {
-        const float cm = tile < T ? 1.0f : 0.0f; // the column sums count every row once
-        __bf16 *Ah = lds + b * BUF, *Al = Ah + 128 * PS;
-        bf16x8 hi, lo;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float a = sy[q][e];
-            if (GATE) a = sg[GATE ? q : 0][e] > 0.0f ? a : 0.0f;
-            colsum = fmaf(cm, a, colsum);
-            const __bf16 h = (__bf16)a;
-            hi[e] = h;
-            lo[e] = (__bf16)(a - (float)h);
-        }
-        *reinterpret_cast<bf16x8 *>(&Ah[c * PS + (g0 + 2 * q) * 8]) = hi;
-        *reinterpret_cast<bf16x8 *>(&Al[c * PS + (g0 + 2 * q) * 8]) = lo;
-    };
-    auto load_x = [&](int ks, int j, int tile) {
-        const unsigned so = (unsigned)((min(tile, T - 1) * 32 + ks * 16) * ldx) * 4u; // wave-uniform
-#pragma unroll
-        for (int e = 0; e < 8; ++e) rx[ks][j][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xv[e] + 128u * j, so, 0));
-    };
-    auto convert_x = [&](int ks, int j) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float a = rx[ks][j][e];
-            const __bf16 h = (__bf16)a;
-            fwh[ks][j][e] = h;
-            fwl[ks][j][e] = (__bf16)(a - (float)h);
-        }
-    };
-    const int a_off = l31 * PS + half * 8;
-    auto read_a = [&](int ks, int s, int b) {
-        const __bf16 *Ah = lds + b * BUF + ks * 16 + a_off, *Al = Ah + 128 * PS;
-        if (s < 4) fah[ks][s] = *reinterpret_cast<const bf16x8 *>(&Ah[s * 32 * PS]);
-        else fal[ks][s - 4] = *reinterpret_cast<const bf16x8 *>(&Al[(s - 4) * 32 * PS]);
-    };
-    auto mfma_one = [&](int ks, int s) {
-        const int t = s / (MI * NB), i = (s % (MI * NB)) / NB, j = s % NB;
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(t == 0 ? fal[ks][i] : fah[ks][i], t == 1 ? fwl[ks][j] : fwh[ks][j], acc[i][j], 0, 0, 0);
-    };
-    constexpr int G = MI * NB, RPG = 8 / G; // groups of three MFMAs per k-step; dY fragment reads per group
-
-    // prologue: dY tile 0 in LDS buffer 0, tile 1 staged; X tile 0 converted (k-step 0) / raw (k-step 1), tile 1 k-step 0 requested
-    load_y(0, 0); load_y(1, 0);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) { load_x(0, j, 0); load_x(1, j, 0); }
-    stage_y(0, 0, 0); stage_y(1, 0, 0);
-    load_y(0, 1); load_y(1, 1);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) { convert_x(0, j); load_x(0, j, 1); }
-    __syncthreads();
-#pragma unroll
-    for (int s = 0; s < 8; ++s) read_a(0, s, 0);
-    int cur = 0;
-    for (int t = 0; t < T; ++t) {
-        // Branch-free body.
-        // ---- phase A: k-step 0 | dY fragments of k-step 1; dY tile t+1 into the other buffer, tile t+2 requested; X k-step 1 of
-        //      tile t converted, of tile t+1 requested ----
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            mfma_one(0, 3 * g);
-#pragma unroll
-            for (int r = 0; r < RPG; ++r) read_a(1, g * RPG + r, cur);
-            if (RPG == 0 && g % (G / 8) == 0) read_a(1, g / (G / 8), cur);
-            mfma_one(0, 3 * g + 1);
-            if (g == 0 || g == G / 2) { const int q = g ? 1 : 0; stage_y(q, t + 1, cur ^ 1); load_y(q, t + 2); }
-            if (g % (G / NB) == G / NB - 1) { const int j = g / (G / NB); convert_x(1, j); load_x(1, j, t + 1); }
-            mfma_one(0, 3 * g + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        __syncthreads(); // dY tile t+1 is complete, the buffer of tile t is free
-        // ---- phase B: k-step 1 | dY fragments (k-step 0) of tile t+1; X k-step 0 of tile t+1 converted, of tile t+2 requested ----
-#pragma unroll
-        for (int g = 0; g < G; ++g) {
-            mfma_one(1, 3 * g);
-#pragma unroll
-            for (int r = 0; r < RPG; ++r) read_a(0, g * RPG + r, cur ^ 1);
-            if (RPG == 0 && g % (G / 8) == 0) read_a(0, g / (G / 8), cur ^ 1);
-            mfma_one(1, 3 * g + 1);
-            if (g % (G / NB) == G / NB - 1) { const int j = g / (G / NB); convert_x(0, j); load_x(0, j, t + 2); }
-            mfma_one(1, 3 * g + 2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        cur ^= 1;
-    }
-    float *P = partials + (size_t)split * N * K;
-#pragma unroll
-    for (int i = 0; i < MI; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            float *pp = P + (size_t)(n_blk + i * 32 + 4 * half) * K + k_blk + j * 32 + l31;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) pp[(size_t)((r & 3) + 8 * (r >> 2)) * K] = acc[i][j][r];
-        }
-    if (want_db) { // uniform per block
-        __syncthreads();
-        float *red = reinterpret_cast<float *>(smem3p);
-        red[tid] = colsum;
-        __syncthreads();
-        if (tid < 128) db_part[(size_t)split * N + n_blk + tid] = red[tid] + red[tid + 128];
-    }
 }
 
 } // namespace

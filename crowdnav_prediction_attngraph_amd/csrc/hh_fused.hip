@@ -14,7 +14,7 @@
 //                     out += O Wos[:, h]^T       MFMA, accumulators persist over the heads
 //   out_sp = relu(out + b)                       stored to HBM
 // Arithmetic: every product is bf16x3 split precision (hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_bf16, fp32 accumulate),
-// the same arithmetic as gemm3.h; softmax in fp32.
+// the same arithmetic as split_bf16.h describes; softmax in fp32.
 //
 // Layout tricks that keep the chain on chip:
 //   * a wavefront owns OUTPUT FEATURES (three 16-feature blocks of the head's q|k|v -- a PAIR of q blocks in the even wavefronts,

@@ -1,10 +1,11 @@
 // linear.hip -- the large Linear layers of the PPO update (forward, input gradient, weight/bias gradient) on gfx950 in
-// the same split-precision bf16x3 MFMA arithmetic as the rollout forward (gemm3.h).
+// the same split-precision bf16x3 MFMA arithmetic as the rollout forward (split_bf16.h): products in gemm3p.h, weight gradients in gemm3_tn.h.
 // Reference: the torch.nn.Linear calls of SpatialEdgeSelfAttn.forward / spatial_linear
 // (rl/networks/selfAttn_srnn_temp_node.py:63-91,408) executed under autograd by PPO.update (rl/ppo.py:60-95:
 // evaluate_actions -> loss.backward()).
 #include "common.h"
 #include "gemm3p.h"
+#include "gemm3_tn.h"
 #include "train_internal.h"
 
 namespace {

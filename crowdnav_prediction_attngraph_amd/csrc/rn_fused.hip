@@ -160,7 +160,7 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
         stage<128, 3, A_NONE>(a.f_whh, w4 + 12, 4, nullptr, R4, S128, R2, S384, 0, 0, lane);
     }
     __syncthreads();
-    // ---- robot-human attention (u-form, see hr_attention_kernel in policy.hip): wavefront w owns envs 2w, 2w+1 ----
+    // ---- robot-human attention (u-form, see hr_attention_kernel in attention.h): wavefront w owns envs 2w, 2w+1 ----
     // out_sp was written a moment ago by the human-human kernel on (mostly) other XCDs: every row read is a trip to the fabric.  A
     // row-by-row loop is a chain of such trips (two passes x nd rows x 2 envs: ~25 of them, the largest single item of this kernel),
     // so the first 8 rows of BOTH envs are fetched up front into registers; envs with more rows walk the rest in chunks of 8.

@@ -1,4 +1,5 @@
-// train_internal.h -- pieces of the training path shared between linear.hip, policy.hip and train_step.hip (not part of the C ABI).
+// train_internal.h -- pieces of the training path shared between linear.hip, policy.hip (its part 2, the training entry points) and
+// train_step.hip (not part of the C ABI).
 #pragma once
 #include "common.h"
 
@@ -12,11 +13,11 @@ struct CnSplitJob {
 };
 constexpr int CN_SPLIT_MAX_JOBS = 20;
 int cn_split_group_launch(CnSplitJob *jobs, int n, hipStream_t st);                                            // linear.hip
-// job for cn_split_bf16_padded(w, rows, cols, transpose, n_padded, planes) with hi = planes, lo = planes + n elements (policy.hip's rn_split)
+// job for cn_split_bf16_padded(w, rows, cols, transpose, n_padded, planes) with hi = planes, lo = planes + n elements (rn_split in policy.hip, part 2)
 CnSplitJob cn_split_job(const float *w, int rows, int cols, int transpose, int n_padded, float *planes);
 
 // the split jobs of one optimiser step's robot-node sequence: five for cn_rn_seq_fwd (+ the padded te bias), six for cn_rn_seq_bwd
-int rn_seq_prep_jobs(const cn_rn_weights *w, float *fwd_ws, float *bwd_ws, int T, int N, CnSplitJob *out);     // policy.hip: returns the count (12)
+int rn_seq_prep_jobs(const cn_rn_weights *w, float *fwd_ws, float *bwd_ws, int T, int N, CnSplitJob *out);     // policy.hip, part 2: returns the count (12)
 int rn_seq_fwd_impl(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off, const float *h0,
                     const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, float *ws, float *value, float *logp,
                     void *stream, bool prepared);
