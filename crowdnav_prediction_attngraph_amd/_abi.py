@@ -11,7 +11,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CN_HIP_LIB") or os.path.join(_PKG, "libcrowdnav_hip.so")   # CN_HIP_LIB: another build of the same ABI (A/B measurements)
 
 CN_MAX_HUMANS = 64
-ABI_VERSION = 406          # CN_ABI_VERSION of include/crowdnav_hip.h this binding was written against
+ABI_VERSION = 407          # CN_ABI_VERSION of include/crowdnav_hip.h this binding was written against
 PROF_KERNELS, PROF_SLOT_WORDS = 8, 2048
 PROF_KERNEL_IDS = {"env_step": 0, "orca_lane": 1, "hh_fused": 2, "rn_fused": 3, "orca_lp3": 4, "env_pregen": 5, "row_plan": 6, "other": 7}
 ENV_KINDS = {"CrowdSimVarNum-v0": 0, "CrowdSimPred-v0": 1, "CrowdSimPredRealGST-v0": 2, "CrowdSimVarNumCollect-v0": 3}
@@ -143,6 +143,7 @@ ABI_SYMBOLS = [
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
     "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
+    "cn_env_get_visibility", "cn_render_scenes",
 ]
 
 _lib = None
@@ -188,6 +189,8 @@ def lib():
         L.cn_env_set_case_counters.argtypes = [vp, vp, vp]
         L.cn_env_get_human_counts.argtypes = [vp, vp, vp]
         L.cn_env_get_human_actions.argtypes = [vp, vp, vp]
+        L.cn_env_get_visibility.argtypes = [vp, vp, vp]
+        L.cn_render_scenes.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, i32, f32, vp, vp]
         L.cn_env_snapshot_bytes.argtypes = [vp]
         L.cn_env_snapshot_bytes.restype = i64
         L.cn_env_save.argtypes = [vp, vp, vp]

@@ -521,6 +521,24 @@ __global__ void export_hact_kernel(EnvDev s, float *out)
     }
 }
 
+// the robot-side detect_visible decision on the CURRENT state (robot_sees, the function write_obs decides with), one thread per slot
+__global__ void export_visibility_kernel(EnvDev s, uint8_t *out)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int H = s.H;
+    if (idx >= s.E * H) return;
+    const int e = idx / H, j = idx % H;
+    const int n = s.nh ? s.nh[e] : H;
+    bool vis = false;
+    if (j < n) {
+        const double *r = s.rob + (size_t)e * 8;
+        const Robot rb = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+        const double *h = s.hum + (size_t)e * 8 * H + j;
+        vis = robot_sees(s.cfg, rb, true, h[0], h[(size_t)H], h[(size_t)6 * H]);
+    }
+    out[idx] = vis ? 1 : 0;
+}
+
 __global__ void fill_i32_kernel(int n, int v, int32_t *out)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1001,6 +1019,16 @@ extern "C" int cn_env_get_human_counts(cn_env_batch *env, int32_t *out, void *st
         hipLaunchKernelGGL(fill_i32_kernel, dim3((env->d.E + 255) / 256), dim3(256), 0, st, env->d.E, env->d.H, out);
         CN_CHECK_LAUNCH();
     }
+    return CN_OK;
+}
+
+extern "C" int cn_env_get_visibility(cn_env_batch *env, uint8_t *out, void *stream)
+{
+    CN_REQUIRE(env && out, "cn_env_get_visibility: null argument");
+    if (int rc = sync_side(env, (hipStream_t)stream)) return rc; // ordered like cn_env_get_state
+    const int n = env->d.E * env->d.H;
+    hipLaunchKernelGGL(export_visibility_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, env->d, out);
+    CN_CHECK_LAUNCH();
     return CN_OK;
 }
 

@@ -588,6 +588,16 @@ __device__ __forceinline__ void change_goals(const EnvDev &s, Rng &R, int lane, 
     }
 }
 
+// detect_visible(robot, human, robot1=True), crowd_sim.py:513-552: inside the robot's field of view (FOV = 2*pi: iff not coincident) and
+// within sensor range; `present`: the slot holds a human.  The observation (write_obs) and cn_env_get_visibility both decide with this function.
+__device__ __forceinline__ bool robot_sees(const cn_env_config &c, const Robot &rb, bool present, double hpx, double hpy, double hrad)
+{
+    const double dx = rb.px - hpx, dy = rb.py - hpy;
+    bool vis = present && !(dx == 0.0 && dy == 0.0) && (norm2(dx, dy) - c.robot_radius - hrad <= c.sensor_range);
+    if (c.robot_fov < 2.0) vis = vis && in_fov(c, c.robot_fov, rb.px, rb.py, rb.vx, rb.vy, rb.theta, hpx, hpy);
+    return vis;
+}
+
 // crowd_sim_var_num.py:233-279 generate_ob / crowd_sim_pred.py:62-97 / crowd_sim_pred_real_gst.py:76-93,
 // crowd_sim.py:558-572 get_num_human_in_fov, :243-273 update_last_human_states.
 __device__ __forceinline__ void write_obs(const EnvDev &s, int e, int lane, int n, bool reset, const Robot &rb, Lane &h, const cn_obs &ob, int step_counter)
@@ -595,11 +605,7 @@ __device__ __forceinline__ void write_obs(const EnvDev &s, int e, int lane, int 
     const cn_env_config &c = s.cfg;
     const int H = s.H, D = s.D, P = s.P; // H observation rows (crowd_sim_var_num.py:249, crowd_sim_pred.py:78), n humans present
     const bool isH = lane < n, isRow = lane < H;
-    // detect_visible(robot, human, robot1=True), crowd_sim.py:513-552: inside the robot's field of view (FOV = 2*pi: iff not coincident) and
-    // within sensor range
-    const double dx = rb.px - h.px, dy = rb.py - h.py;
-    bool vis = isH && !(dx == 0.0 && dy == 0.0) && (norm2(dx, dy) - c.robot_radius - h.rad <= c.sensor_range);
-    if (c.robot_fov < 2.0) vis = vis && in_fov(c, c.robot_fov, rb.px, rb.py, rb.vx, rb.vy, rb.theta, h.px, h.py);
+    const bool vis = robot_sees(c, rb, isH, h.px, h.py, h.rad);
     const uint64_t vmask = __ballot(vis);
     const int num_visible = __popcll(vmask);
     if (s.vis && isRow) s.vis[(size_t)e * H + lane] = vis ? 1 : 0; // human_visibility, read by the next step's 'truth' blanking

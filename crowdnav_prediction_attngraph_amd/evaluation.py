@@ -199,11 +199,14 @@ def evaluate_batched(actor_critic, env_name, config, seed, test_size, device=Non
 
 
 def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, predictor=None, poll_every=16, act_fn=None,
-                      hip_policy=None, use_kernel=True, per_env=None):
-    """poll_every: the count of running episodes is read back (the loop's only host synchronisation) every that many steps; steps taken after
-    the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
+                      hip_policy=None, use_kernel=True, per_env=None, frame_fn=None):
+    """test_size: the episode count of the sequential protocol (episode k runs case 2 k mod the config's test_size), or a sequence of case
+    numbers to run instead (render_episodes).  poll_every: the count of running episodes is read back (the loop's only host synchronisation)
+    every that many steps; steps taken after the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
     hip_policy: a HipPolicy handle to run instead of actor_critic's own (train() evaluates through a second handle so that the training
-    rollout finds its handle as it left it); use_kernel=False: the torch-op bookkeeping; per_env: a dict that receives the per-env results."""
+    rollout finds its handle as it left it); use_kernel=False: the torch-op bookkeeping; per_env: a dict that receives the per-env results;
+    frame_fn(t, env, obs): called once after the reset (t = 0) and once after every step (t = steps taken) with the HipEnvBatch and the
+    observation it returned, e.g. to draw the state (render_episodes); it must leave both as they are."""
     from .hip import HipEnvBatch
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = to_env_config(config, env_name, 1, "test")          # nenv = 1: case counters advance by one, as in the sequential run
@@ -214,7 +217,10 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
         raise NotImplementedError("an ORCA robot with randomised humans keeps ONE rvo2 simulator (radii / neighbour distance frozen in the "
                                   "first episode) across the whole sequential run; use evaluate() for that configuration")
     case_size = int(cfg.test_size)
-    case_of = [(2 * k) % case_size for k in range(test_size)]  # reset() + the vec-env's auto-reset: two resets per episode
+    if isinstance(test_size, (list, tuple)):
+        case_of, test_size = [int(c) for c in test_size], len(test_size)
+    else:
+        case_of = [(2 * k) % case_size for k in range(test_size)]  # reset() + the vec-env's auto-reset: two resets per episode
     cases = sorted(set(case_of))
     E = len(cases)
     env = HipEnvBatch(cfg, E, int(seed), device=device)
@@ -232,6 +238,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
                                    float(cfg.collision_penalty), device, pred_interval=interval)
         zero_reward = torch.zeros(E, device=device)
     obs = env.reset()
+    if frame_fn is not None:
+        frame_fn(0, env, obs)
     pol = None
     if act_fn is None and not scripted:
         pol = hip_policy if hip_policy is not None else actor_critic._hip_policy(E, device)
@@ -260,6 +268,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
                 action = out["action"]
         obs, rew, done, info, ep_ret, _ = env.step(action)
         env.get_danger_min_dist(out=danger_dist)
+        if frame_fn is not None:
+            frame_fn(t + 1, env, obs)
         masks = acc.update(done, info, ep_ret, obs["robot_node"], danger_dist)
         if (t + 1) % poll_every == 0 and acc.n_active() == 0:
             break
@@ -277,3 +287,41 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     pick = lambda xs: [xs[e] for e in order]
     return _summarise(pick(r["outcome"]), pick(r["steps"]), pick(r["path_length"]), pick(r["danger_steps"]), None, pick(rew_h), float(cfg.time_limit),
                       float(cfg.time_step), logging, danger_sums=pick(r["danger_sum"]))
+
+
+FRAME_BUFFER_LIMIT = 4 << 30     # bytes of device memory render_episodes may ask for
+
+
+def render_episodes(actor_critic, env_name, config, seed, cases, size=256, device=None, predictor=None, batch_invariant=False):
+    """Run the test cases `cases` exactly as evaluate_batched runs them (one env per case, its first episode; actor_critic=None: the ORCA
+    robot) and draw every state on the device (HipEnvBatch.render; CrowdSimPred-v0 also gets its predictions as dots).
+    Returns {case: dict(frames=uint8 [steps+1,size,size,3], outcome=1 timeout / 2 collision / 3 goal, steps=...)}: frame 0 is the reset
+    state, frame t the state after step t -- the last one therefore shows what the vec-env's auto-reset left.  The frames go into ONE
+    preallocated device buffer [T,n,size,size] RGBA and are read back once at the end; a request whose buffer would exceed 4 GiB is
+    refused."""
+    from .hip import prediction_dots
+    cases = sorted(set(int(c) for c in cases))
+    if not cases:
+        raise ValueError("render_episodes: no cases given")
+    size, n = int(size), len(cases)
+    cfg = to_env_config(config, env_name, 1, "test")
+    T = int(round(float(cfg.time_limit) / float(cfg.time_step))) + 2      # the reset frame + one per step of the longest episode
+    nbytes = 4 * T * n * size * size
+    if nbytes > FRAME_BUFFER_LIMIT:
+        raise ValueError("render_episodes: %d cases x %d frames of %d x %d pixels need a %.1f GiB frame buffer (limit 4 GiB): fewer cases per "
+                         "call, or a smaller size" % (n, T, size, size, nbytes / float(1 << 30)))
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    buf = torch.zeros(T, n, size, size, 4, dtype=torch.uint8, device=device)
+    with_dots = env_name == "CrowdSimPred-v0"
+
+    def draw(t, env, obs):
+        dots, counts = prediction_dots(obs) if with_dots else (None, None)
+        env.render(size=size, dots=dots, dot_counts=counts, out=buf[t])
+
+    per_env = {}
+    with _batch_invariant(actor_critic, batch_invariant):
+        _evaluate_batched(actor_critic, env_name, config, seed, cases, device, None, predictor=predictor, per_env=per_env, frame_fn=draw)
+    last = max(per_env["steps"])
+    frames = buf[:last + 1, :, :, :, :3].contiguous().cpu().numpy()
+    return {c: dict(frames=frames[:per_env["steps"][e] + 1, e].copy(), outcome=per_env["outcome"][e], steps=per_env["steps"][e])
+            for e, c in enumerate(per_env["cases"])}

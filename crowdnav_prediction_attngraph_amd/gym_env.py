@@ -16,7 +16,7 @@ import torch
 from . import _abi as A
 from . import info as I
 from .config import to_env_config
-from .hip import HipEnvBatch
+from .hip import HipEnvBatch, prediction_dots
 from .policy import make_spaces
 
 _KEYS = ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num", "visible_masks")
@@ -114,7 +114,16 @@ class _SingleCrowdSim(object):
         self.gst_out_traj = data          # crowd_sim_pred_real_gst.py:64-74 (render aid)
         return True
 
-    def render(self, mode="human"):
+    def render(self, mode="human", size=128):
+        """mode='rgb_array': the current state as numpy uint8 [size,size,3], drawn on the device (HipEnvBatch.render; the predictions of
+        the last observation as dots where the env has them).  There is no viewer window: mode='human' raises."""
+        if mode == "rgb_array":
+            if self._env is None:
+                raise A.CnError("render() before reset()")
+            dots = counts = None
+            if self._env.cfg.env_kind in (1, 2) and self._env.D > 2:
+                dots, counts = prediction_dots(self._env.obs)
+            return self._env.render(size=size, dots=dots, dot_counts=counts)[0, :, :, :3].contiguous().cpu().numpy()
         raise NotImplementedError("rendering is out of scope of the accelerated path (use the reference env to visualise)")
 
     def close(self):

@@ -184,6 +184,102 @@ class HipEnvBatch:
             A.check(A.lib().cn_env_get_human_actions(self._h, A.ptr(out), A.stream_ptr()), "cn_env_get_human_actions")
         return out
 
+    def get_visibility(self):
+        """The robot-side detect_visible decision on the current state (uint8 [E,H], 0 beyond the env's crowd size): what the next
+        observation of this state would call visible (cn_env_get_visibility)."""
+        out = torch.zeros(self.E, self.H, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_env_get_visibility(self._h, A.ptr(out), A.stream_ptr()), "cn_env_get_visibility")
+        return out
+
+    def render(self, size=128, env_ids=None, half_width=None, dots=None, dot_counts=None, out=None):
+        """The current state of the envs (all, or those `env_ids` -- an int tensor or list -- selects) as uint8 [n,size,size,4] RGBA images
+        on the device: get_state, get_human_counts, get_visibility and the robot's heading (its velocity when holonomic, (cos theta, sin theta)
+        for a unicycle) go to render_scenes.  No host synchronisation.  dots [n,max_dots,2] float32 absolute positions with dot_counts [n]
+        int32 (e.g. predicted human positions) are drawn as green discs; half_width defaults to arena_size + 1."""
+        cfg = self.cfg
+        humans, robot = self.get_state()
+        counts, visible = self.get_human_counts(), self.get_visibility()
+        if env_ids is not None:
+            idx = torch.as_tensor(env_ids, dtype=torch.int64, device=self.device).reshape(-1)
+            humans, robot = humans.index_select(0, idx), robot.index_select(0, idx)
+            counts, visible = counts.index_select(0, idx), visible.index_select(0, idx)
+        if cfg.kinematics == 0:
+            heading = robot[:, 2:4].to(torch.float32)
+        else:
+            heading = torch.stack((torch.cos(robot[:, 6]), torch.sin(robot[:, 6])), dim=1).to(torch.float32)
+        return render_scenes(humans, robot, counts=counts, visible=visible, robot_heading=heading.contiguous(), dots=dots, dot_counts=dot_counts,
+                             robot_radius=cfg.robot_radius, ring_radius=cfg.sensor_range + cfg.robot_radius + cfg.human_radius, size=size,
+                             half_width=cfg.arena_size + 1.0 if half_width is None else half_width, out=out)
+
+
+def render_scenes(humans, robot, counts=None, visible=None, robot_heading=None, dots=None, dot_counts=None, robot_radius=0.3,
+                  ring_radius=0.0, size=128, half_width=7.0, out=None):
+    """cn_render_scenes: n scenes -> uint8 [n,size,size,4] RGBA images on the device, one launch, by the exact fp32 rule of
+    include/crowdnav_hip.h.  humans float64 [n,H,8] / robot float64 [n,8] in the layout of HipEnvBatch.get_state(); counts int32 [n], visible
+    uint8 [n,H], robot_heading float32 [n,2], dots float32 [n,max_dots,2] + dot_counts int32 [n] are optional (None: every slot holds a human,
+    all visible, heading = robot velocity, no dots).  out: optional uint8 [n,size,size,4] tensor to draw into."""
+    for name, t, dt in (("humans", humans, torch.float64), ("robot", robot, torch.float64), ("counts", counts, torch.int32),
+                        ("visible", visible, torch.uint8), ("robot_heading", robot_heading, torch.float32), ("dots", dots, torch.float32),
+                        ("dot_counts", dot_counts, torch.int32), ("out", out, torch.uint8)):
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise A.CnError("render_scenes: %s must live on the GPU (no CPU fallback)" % name)
+        if t.dtype != dt or not t.is_contiguous():
+            raise A.CnError("render_scenes: %s must be a contiguous %s tensor" % (name, dt))
+    _need_cuda()
+    if humans.dim() != 3 or humans.shape[2] != 8 or robot.shape != (humans.shape[0], 8):
+        raise A.CnError("render_scenes: humans must be [n,H,8] and robot [n,8]")
+    n, H, size = int(humans.shape[0]), int(humans.shape[1]), int(size)
+    max_dots = 0
+    if dots is not None:
+        if dots.dim() != 3 or dots.shape[0] != n or dots.shape[2] != 2:
+            raise A.CnError("render_scenes: dots must be [n,max_dots,2]")
+        max_dots = int(dots.shape[1])
+        if max_dots == 0:
+            dots = dot_counts = None
+    elif dot_counts is not None:
+        raise A.CnError("render_scenes: dot_counts given without dots")
+    for name, t, shape in (("counts", counts, (n,)), ("visible", visible, (n, H)), ("robot_heading", robot_heading, (n, 2)),
+                           ("dot_counts", dot_counts, (n,)), ("out", out, (n, size, size, 4))):
+        if t is not None and tuple(t.shape) != shape:
+            raise A.CnError("render_scenes: %s must have shape %s" % (name, list(shape)))
+    if out is None:
+        out = torch.empty(n, size, size, 4, dtype=torch.uint8, device=humans.device)
+    with torch.cuda.device(humans.device):
+        A.check(A.lib().cn_render_scenes(n, H, A.ptr(humans), A.ptr(robot), A.ptr(counts), A.ptr(visible), A.ptr(robot_heading), A.ptr(dots),
+                                         A.ptr(dot_counts), max_dots, float(robot_radius), float(ring_radius), size, float(half_width),
+                                         A.ptr(out), A.stream_ptr()), "cn_render_scenes")
+    return out
+
+
+def prediction_dots(obs, env_ids=None):
+    """The predicted human positions an observation with predictions carries (spatial_edges wider than 2: CrowdSimPred-v0, or
+    CrowdSimPredRealGST-v0 behind the prediction wrapper) as the (dots [n,H*P,2] float32, dot_counts [n] int32) pair of render_scenes: rows
+    0..detected_human_num-1, columns 2.. as (P,2) robot-relative offsets, plus the robot position.  Device tensors in, device tensors out."""
+    se, rn, det = obs["spatial_edges"], obs["robot_node"], obs["detected_human_num"]
+    if env_ids is not None:
+        idx = torch.as_tensor(env_ids, dtype=torch.int64, device=se.device).reshape(-1)
+        se, rn, det = se.index_select(0, idx), rn.index_select(0, idx), det.index_select(0, idx)
+    n, H, P = se.shape[0], se.shape[1], (se.shape[2] - 2) // 2
+    dots = se[:, :, 2:].to(torch.float32).reshape(n, H * P, 2) + rn.reshape(n, 1, -1)[:, :, 0:2].to(torch.float32)
+    counts = (det.reshape(n).to(torch.int32) * P).contiguous()
+    return dots.contiguous(), counts
+
+
+def tile_images(images):
+    """[N,h,w,c] -> one [rows*h, cols*w, c] mosaic with rows = ceil(sqrt(N)), cols = ceil(N / rows), filled row by row; missing tiles are
+    black (the layout of the vec-env API's tile_images)."""
+    import numpy as np
+    images = np.asarray(images)
+    N, h, w, c = images.shape
+    rows = int(np.ceil(np.sqrt(N)))
+    cols = int(np.ceil(float(N) / rows))
+    grid = np.zeros((rows * cols, h, w, c), dtype=images.dtype)
+    grid[:N] = images
+    return grid.reshape(rows, cols, h, w, c).transpose(0, 2, 1, 3, 4).reshape(rows * h, cols * w, c)
+
 
 def orca_solve(self_state, others, neighbor_dist=10.0, max_neighbors=None, time_horizon=5.0, time_step=0.25):
     """Batched stand-alone ORCA (rvo2 replacement).  self_state [B,8], others [B,n,5] float32 device tensors -> [B,2]."""

@@ -15,7 +15,7 @@ import torch
 from . import _abi as A
 from . import info as I
 from .config import Config, to_env_config
-from .hip import HipEnvBatch
+from .hip import HipEnvBatch, prediction_dots, tile_images
 from .policy import make_spaces
 
 _OBS_KEYS = ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num", "visible_masks")
@@ -51,6 +51,7 @@ class BatchedCrowdSim(object):
         self._keys = [k for k in _OBS_KEYS if k in self.observation_space.spaces]
         self._t0 = time.time()
         self._closed = False
+        self._last_obs = None         # the newest device observation (a reference, no copy): get_images draws its predictions
         # VecPretextNormalize (GST predictions written into spatial_edges[:, :, 2:], social penalty, distance sort)
         self._pretext = None
         if pretext_wrapper:
@@ -75,6 +76,7 @@ class BatchedCrowdSim(object):
         if self._pretext is not None:
             self._pretext.reset_buffers()
             obs, _ = self._apply_pretext(obs, torch.zeros(self.num_envs, device=self.device))
+        self._last_obs = obs
         return obs
 
     def step_device(self, actions):
@@ -83,6 +85,7 @@ class BatchedCrowdSim(object):
         obs, reward, done, info, ep_ret, ep_len = self._env.step(actions)
         if self._pretext is not None:
             obs, reward = self._apply_pretext(obs, reward)
+        self._last_obs = obs
         return obs, reward, done, info, ep_ret, ep_len
 
     # ---- reference-compatible API ----
@@ -123,7 +126,21 @@ class BatchedCrowdSim(object):
     def talk2Env(self, data):
         return [True] * self.num_envs       # render aid only in the reference (crowd_sim_pred_real_gst.py:64-74)
 
-    def render(self, mode="human"):
+    def get_images(self, size=128, env_ids=None, predictions=True):
+        """The current state of every env (or of `env_ids`) as numpy uint8 [n,size,size,3], drawn on the device in one launch
+        (HipEnvBatch.render).  When the observation carries predictions (edge_width > 2) and `predictions` is set, the predicted positions
+        of the last observation this object returned are drawn as dots."""
+        dots = counts = None
+        if predictions and self.edge_width > 2 and self._last_obs is not None:
+            dots, counts = prediction_dots(self._last_obs, env_ids)
+        img = self._env.render(size=size, env_ids=env_ids, dots=dots, dot_counts=counts)
+        return img[..., :3].contiguous().cpu().numpy()
+
+    def render(self, mode="human", size=128, max_envs=16):
+        """mode='rgb_array': the tile_images mosaic of the first min(num_envs, max_envs) envs, numpy uint8 [rows*size, cols*size, 3].  There
+        is no viewer window: mode='human' raises."""
+        if mode == "rgb_array":
+            return tile_images(self.get_images(size=size, env_ids=list(range(min(self.num_envs, int(max_envs))))))
         raise NotImplementedError("rendering is out of scope of the accelerated path (use the reference env to visualise)")
 
     # ---- checkpointing (a bit-exact --resume needs the simulator state, not only the policy: train.py:105-108 restores weights only) ----

@@ -147,7 +147,7 @@ typedef struct cn_policy cn_policy;
 
 /* Bumped whenever a struct layout, a signature or the snapshot format changes (round 4: cn_obs.row_plan, cn_env_config.robot_fov /
  * human_fov, the profiling entry points, snapshot layout CNENV004); the ctypes binding refuses a library that reports another number. */
-#define CN_ABI_VERSION 406
+#define CN_ABI_VERSION 407
 const char *cn_last_error(void);
 int cn_version(void);
 int cn_device_count(void);
@@ -201,6 +201,11 @@ int cn_env_get_danger_min_dist(cn_env_batch *env, double *out, void *stream);
 /* len(self.humans) of every env: out [E] int32 (device).  Constant human_num unless sim.human_num_range > 0; the slots beyond it in
  * cn_env_get_state / cn_env_get_human_actions hold no human. */
 int cn_env_get_human_counts(cn_env_batch *env, int32_t *out, void *stream);
+/* The robot-side detect_visible(robot, human, robot1=True) decision (crowd_sim.py:513-552) on the CURRENT state, by the device function the
+ * observation decides with: configured sensor range and robot_fov, heading from the velocity or from theta by kinematics.  It is what the
+ * reference's render colours its humans by (crowd_sim_pred.py:236-370, crowd_sim_var_num.py render: `self.human_visibility`).
+ * out [E,H] uint8 (device), 0 in the slots beyond the env's crowd size.  Ordered like cn_env_get_state. */
+int cn_env_get_visibility(cn_env_batch *env, uint8_t *out, void *stream);
 /* Overwrite the per-env case counters (crowd_sim_var_num.py:316-318 `case_counter[phase] = test_case`, :337
  * rand_seed = offset[phase] + case_counter + thisSeed): the NEXT reset of env e generates the scenario of that case.
  * counters [E] uint64 (device).  Lets a batch replay chosen test cases (one per env) instead of consecutive ones. */
@@ -213,6 +218,32 @@ int cn_env_set_case_counters(cn_env_batch *env, const uint64_t *counters, void *
 int64_t cn_env_snapshot_bytes(const cn_env_batch *env);
 int cn_env_save(cn_env_batch *env, void *dst, void *stream);
 int cn_env_load(cn_env_batch *env, const void *src, void *stream);
+
+/* ---- rendering: n scenes -> n RGBA8 images in one launch ----
+ * Replaces the drawing of the reference's render() (crowd_sim_pred.py:236-370, crowd_sim_var_num.py render) for the vec-env slot
+ * render(mode='rgb_array') / get_images() (rl/vec_env/vec_env.py:121).  No matplotlib look: the image is DEFINED by the rule below, in fp32
+ * with every operation rounded once and only + - *, comparisons and int -> float conversions per pixel, so a float32 restatement
+ * reproduces every pixel.  All inputs are caller-owned device buffers, converted f64 -> f32 by round-to-nearest first:
+ *   humans [n,H,8] and robot [n,8] in the layout of cn_env_get_state; counts [n] int32 humans present (the first counts[i] slots; NULL = H
+ *   everywhere; slots at or beyond it are never read); visible [n,H] uint8, 1 = drawn as seen by the robot (NULL = all); robot_heading [n,2]
+ *   float32 direction of the robot's heading mark, any length, 0,0 = none (NULL = the robot's velocity); dots [n,max_dots,2] float32 absolute
+ *   positions with dot_counts [n] int32 (dots NULL = none; dot_counts NULL = max_dots everywhere), max_dots <= 1024; ring_radius <= 0 = no
+ *   sensor ring; 16 <= size <= 1024, size % 4 == 0; out [n,size,size] RGBA8 words R | G<<8 | B<<16 | 255<<24, 16-byte aligned.
+ * With S = size, L = half_width: pitch q = (2*L)/S; pixel (row i, col j) has centre x = (j + 0.5f)*q - L, y = L - (i + 0.5f)*q (row 0 is the
+ * top).  For a shape centred at c: dx = x - cx, dy = y - cy, d2 = dx*dx + dy*dy.  w = 0.5f*q, hw = 0.75f*q, t = 1.5f*q.  Layers, later over
+ * earlier:
+ *   0 background white (255,255,255)
+ *   1 sensor ring around the robot: lo = R - w, hi = R + w, d2 >= lo*lo && d2 <= hi*hi, grey (160,160,160)
+ *   2 the robot's goal: |dx| + |dy| <= 0.3f, red (220,0,0)
+ *   3 dots 0..dot_counts[i]-1: d2 <= 0.12f*0.12f, green (0,160,0)
+ *   4 humans 0..counts[i]-1: outline d2 <= r*r && (r - t <= 0 || d2 >= (r-t)*(r-t)), blue (0,0,255) if visible else red (255,0,0); then the
+ *     heading mark along the velocity v: s2 = vx*vx + vy*vy, none if s2 <= 1e-12f, dot = dx*vx + dy*vy, cr = dx*vy - dy*vx,
+ *     dot >= 0 && dot*dot <= (r*r)*s2 && cr*cr <= (hw*hw)*s2, dark red (160,0,0)
+ *   5 the robot: d2 <= rr*rr gold (255,215,0), then its heading mark by the same rule along robot_heading.
+ * One launch, no atomics, no host synchronisation. */
+int cn_render_scenes(int n, int H, const double *humans, const double *robot, const int32_t *counts, const uint8_t *visible,
+                     const float *robot_heading, const float *dots, const int32_t *dot_counts, int max_dots, float robot_radius,
+                     float ring_radius, int size, float half_width, uint32_t *out, void *stream);
 
 /* Stand-alone batched ORCA solve (the rvo2 replacement): B independent agents, each with n_other neighbours.
  * self [B,8] = px,py,vx,vy,radius,max_speed,pref_vx,pref_vy ; others [B,n_other,5] = px,py,vx,vy,radius (float32);
