@@ -15,6 +15,8 @@ ABI_VERSION = 407          # CN_ABI_VERSION of include/crowdnav_hip.h this bindi
 PROF_KERNELS, PROF_SLOT_WORDS = 8, 2048
 PROF_KERNEL_IDS = {"env_step": 0, "orca_lane": 1, "hh_fused": 2, "rn_fused": 3, "orca_lp3": 4, "env_pregen": 5, "row_plan": 6, "other": 7}
 ENV_KINDS = {"CrowdSimVarNum-v0": 0, "CrowdSimPred-v0": 1, "CrowdSimPredRealGST-v0": 2, "CrowdSimVarNumCollect-v0": 3}
+GSTD_MODES = {None: 0, "train": 1, "val": 2, "test": 2}        # CN_GSTD_ALL / TRAIN / VAL
+GSTD_FRAME_ORDER, GSTD_DUPLICATE_ID, GSTD_TOO_MANY_PEDS = 1, 2, 4
 INFO_NOTHING, INFO_TIMEOUT, INFO_COLLISION, INFO_REACHGOAL, INFO_DANGER = range(5)
 
 
@@ -144,6 +146,7 @@ ABI_SYMBOLS = [
     "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
     "cn_env_get_visibility", "cn_render_scenes",
+    "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
 ]
 
 _lib = None
@@ -268,6 +271,10 @@ def lib():
         L.cn_gst_eval_workspace_bytes.restype = C.c_int64
         L.cn_gst_eval_workspace_bytes.argtypes = [i32, i32, i32]
         L.cn_gst_eval_step.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(GstWeights), vp, vp, i64, vp, vp, vp, vp]
+        L.cn_gst_data_frames.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]
+        L.cn_gst_data_count.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_gst_data_fill.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_gst_gather_batch.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_ppo_minibatch_workspace_bytes.restype = C.c_int64
         L.cn_ppo_minibatch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
         L.cn_ppo_row_totals.argtypes = [i32, i32, i32, vp, vp, vp]

@@ -11,8 +11,10 @@ Two execution paths of the training step (train.py:121-146: forward, negative lo
 Evaluation (eval.py's `inference`: the per-epoch validation pass and the sampled test protocol) has the same two paths: HipGstEvaluator --
 cn_gst_eval_step (csrc/gst_eval.hip), batches of sequences per boundary call, one read-back per pass -- behind evaluate(backend='hip') / test(), and
 the torch-op graph (evaluate's default, the CPU tests' path and the cross-check of the kernel).
-The dataset, the rotation augmentation, the learning-rate schedule and the checkpoint format are host code either way, and the
-producer of the data is the batched simulator (collect.py: thousands of simulated crowds per GPU).
+The learning-rate schedule and the checkpoint format are host code either way, and the producer of the data is the batched simulator
+(collect.py: thousands of simulated crowds per GPU).  The dataset and the rotation augmentation have the same two paths: TrajectoriesDataset over the
+text files with the per-item loop (train(data_dir, ...)), or DeviceTrajectories -- the sequences cut out of collect_log's observations on the device
+(csrc/gst_data.hip), minibatches assembled and rotated there (cn_gst_gather_batch), one read-back per epoch (train(dataset=..., batch_size=...)).
 
 Scope note: the reference trains on `<dataset>_dset_<split>_batch_trajectories.pt` files produced by scripts/data/create_*datasets*.py,
 which are NOT part of the reference checkout (only the shell wrappers that call them are).  This module therefore feeds the loop with
@@ -328,15 +330,16 @@ class HipGstTrainer:
                                               C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()), A.ptr(out), A.ptr(gauss), A.stream_ptr()), "cn_gst_train_step")
         return out, gauss[:, :, :N]
 
-    def optimizer_step(self):
-        """clip_grad_norm_(parameters, clip_grad) + Adam.step() (train.py:143-146) over the flat bucket."""
+    def optimizer_step(self, grad_scale=1.0):
+        """clip_grad_norm_(parameters, clip_grad) + Adam.step() (train.py:143-146) over the flat bucket.  grad_scale multiplies the gradient before
+        the norm is taken (train.py:134: loss / args.batch_size ahead of backward and clip_grad_norm_)."""
         from . import hip
         self.step_no += 1
         if self.optimizer is not None:
             for st in self.optimizer.state.values():
                 st["step"] = torch.tensor(float(self.step_no))
         hip.adam_clip_step(self.flat["p"], self.flat["g"], self.flat["m"], self.flat["v"], self.step_no, self.lr, self.betas, self.eps, self.clip_grad,
-                           workspace=self.adam_ws)
+                           grad_scale=grad_scale, workspace=self.adam_ws)
 
 
 def temperature(epoch, total_epochs, base_temp, temp_min=0.03):
@@ -417,6 +420,201 @@ class HipGstEvaluator:
                 t = torch.cat((t, torch.zeros(shape, dtype=t.dtype, device=t.device)), dim=ax)
             out.append(t)
         return torch.stack(out, 0)
+
+
+class DeviceTrajectories(Dataset):
+    """TrajectoriesDataset's content as device tensors: the six ragged arrays (obs_traj, pred_traj, obs_traj_rel, pred_traj_rel [P,2,5],
+    loss_mask, loss_mask_rel [P,10]), seq_start_end, frame_id_seq and the env of every sequence (seq_env).  from_log builds it on the device
+    from collect.collect_log's observations (csrc/gst_data.hip: cn_gst_data_frames / _count / _fill, no files, one read-back); from_dataset
+    uploads a TrajectoriesDataset.  __getitem__ returns the host class's 12 entries as device tensors (the graph tensors are made on demand),
+    so evaluate / test / the torch backend take it through a DataLoader unchanged; gather() assembles a minibatch for cn_gst_train_step /
+    cn_gst_eval_step on the device (cn_gst_gather_batch)."""
+
+    FIELDS = ("obs_traj", "pred_traj", "obs_traj_rel", "pred_traj_rel", "loss_mask", "loss_mask_rel")
+
+    def __init__(self, arrays, counts, frame_id_seq, seq_env, obs_seq_len=5, pred_seq_len=5):
+        super().__init__()
+        from . import _abi as A
+        self.A = A
+        self.obs_seq_len, self.pred_seq_len, self.skip, self.seq_len = obs_seq_len, pred_seq_len, 1, obs_seq_len + pred_seq_len
+        for k, t in zip(self.FIELDS, arrays):
+            setattr(self, k, t)
+        self.device = self.obs_traj.device
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.num_seq = len(self.counts)
+        if self.num_seq == 0:
+            raise RuntimeError("no sequence of %d frames with a pedestrian present throughout" % self.seq_len)
+        cum = [0] + np.cumsum(self.counts).tolist()
+        self.seq_start_end = list(zip(cum[:-1], cum[1:]))
+        self.total_peds = int(cum[-1])
+        self.frame_id_seq = [np.float64(v) for v in frame_id_seq]
+        self.seq_env = np.asarray(seq_env, dtype=np.int64)
+        self._seq_start = torch.as_tensor(np.asarray(cum[:-1], dtype=np.int32)).to(self.device)
+        self._seq_count = torch.as_tensor(self.counts.astype(np.int32)).to(self.device)
+
+    @classmethod
+    def from_dataset(cls, ds, device):
+        """Upload of a TrajectoriesDataset (the sequences' envs are not known to it: seq_env is -1)."""
+        dev = torch.device(device)
+        arrays = [getattr(ds, k).to(dev, torch.float32).contiguous() for k in cls.FIELDS]
+        return cls(arrays, [e - s for s, e in ds.seq_start_end], ds.frame_id_seq, [-1] * len(ds.seq_start_end), ds.obs_seq_len, ds.pred_seq_len)
+
+    @classmethod
+    def from_log(cls, log, mode=None, env_ids=None):
+        """log [F,E,H,4] float32 on the device (collect.collect_log) -> what TrajectoriesDataset(dir, mode=mode) holds for the files
+        collect_lines writes from it, files in env order.  env_ids: only these envs, in this order.  Raises on a log the rule does not cover:
+        frame ids that do not strictly increase within an env (an episode boundary), a sample with the same prediction id twice, a sequence
+        of more than 64 pedestrians."""
+        from . import _abi as A
+        if mode not in A.GSTD_MODES:
+            raise RuntimeError("Wrong mode for TrajectoriesDataset.")
+        if not (torch.is_tensor(log) and log.is_cuda and log.dtype == torch.float32 and log.dim() == 4 and log.shape[3] == 4):
+            raise A.CnError("DeviceTrajectories.from_log: log must be a float32 [F,E,H,4] tensor on the GPU (there is no CPU fallback of the HIP path)")
+        envs = None if env_ids is None else [int(e) for e in env_ids]
+        if envs is not None:
+            log = log[:, torch.as_tensor(envs, dtype=torch.int64, device=log.device)]
+        log = log.contiguous()
+        F_, E, H, _ = log.shape
+        if H > A.CN_MAX_HUMANS:
+            raise A.CnError("DeviceTrajectories.from_log: %d rows per observation, the kernels stop at %d" % (H, A.CN_MAX_HUMANS))
+        if F_ < 10 or E < 1:
+            raise RuntimeError("no sequence of 10 frames with a pedestrian present throughout in a log of %d samples of %d envs" % (F_, E))
+        dev, L, md, W = log.device, A.lib(), A.GSTD_MODES[mode], F_ - 9
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)   # noqa: E731
+        visible, frame_id, status = i32(F_, E), torch.empty(F_, E, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
+        frame_list, ped_count, first_frame = i32(E, F_), i32(E * W), torch.empty(E * W, device=dev)
+        with torch.cuda.device(dev):
+            A.check(L.cn_gst_data_frames(F_, E, H, A.ptr(log), A.ptr(visible), A.ptr(frame_id), A.ptr(status), A.stream_ptr()), "cn_gst_data_frames")
+            listed_before = (torch.cumsum(visible, 0).to(torch.int32) - visible).contiguous()
+            A.check(L.cn_gst_data_count(F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
+                                        A.ptr(first_frame), A.ptr(status), A.stream_ptr()), "cn_gst_data_count")
+            ped_offset = (torch.cumsum(ped_count, 0).to(torch.int32) - ped_count).contiguous()
+            host = torch.cat((status, ped_count, first_frame.view(torch.int32))).cpu().numpy()       # the one read-back of the build
+            st, counts, first = int(host[0]), host[1:1 + E * W].astype(np.int64), host[1 + E * W:].view(np.float32)
+            if st & A.GSTD_FRAME_ORDER:
+                raise RuntimeError("DeviceTrajectories.from_log: the frame ids of an env do not strictly increase (the log spans an episode boundary)")
+            if st & A.GSTD_DUPLICATE_ID:
+                raise RuntimeError("The same pedestrian has multiple locations in the same frame.")
+            if st & A.GSTD_TOO_MANY_PEDS:
+                raise RuntimeError("DeviceTrajectories.from_log: a window holds more than %d pedestrians, the training kernels' bound" % A.CN_MAX_HUMANS)
+            is_seq = counts > 0
+            total = int(counts.sum())
+            if total == 0:
+                raise RuntimeError("no sequence of 10 frames with a pedestrian present throughout in the log (mode %r)" % (mode,))
+            if total >= 2 ** 31 // 10:
+                raise A.CnError("DeviceTrajectories.from_log: %d pedestrian rows exceed the 32-bit offsets of the build" % total)
+            arrays = [torch.empty(total, 2, 5, device=dev) for _ in range(4)] + [torch.empty(total, 10, device=dev) for _ in range(2)]
+            A.check(L.cn_gst_data_fill(F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
+                                       A.ptr(ped_offset), total, *([A.ptr(t) for t in arrays] + [A.stream_ptr()])), "cn_gst_data_fill")
+        env_of = np.nonzero(is_seq)[0] // W
+        return cls(arrays, counts[is_seq], first[is_seq], env_of if envs is None else np.asarray(envs, dtype=np.int64)[env_of])
+
+    def __len__(self):
+        return self.num_seq
+
+    def __getitem__(self, index):
+        s, e = self.seq_start_end[index]
+        T = self.obs_seq_len
+        v_obs, A_obs = seq_to_graph(self.obs_traj[s:e], self.obs_traj_rel[s:e])
+        v_pred, A_pred = seq_to_graph(self.pred_traj[s:e], self.pred_traj_rel[s:e])
+        lm = self.loss_mask_rel[s:e]
+        am = (lm.t().unsqueeze(2) * lm.t().unsqueeze(1)).float()
+        return [self.obs_traj[s:e], self.pred_traj[s:e], self.obs_traj_rel[s:e], self.pred_traj_rel[s:e], lm, self.loss_mask[s:e],
+                v_obs, A_obs, v_pred, A_pred, am[:T], am[T:]]
+
+    def gather(self, index, num_peds, cos_sin=None):
+        """index [B] int32 on the device, num_peds = max(4, the largest crowd among them), cos_sin None or [B,2] float32 on the device ->
+        v_obs, v_pred [B,5,num_peds,2] (seq_to_graph's vertices, rotated as rotate_graph does), loss_mask_rel [B,num_peds,10]; rows at or beyond a
+        sequence's crowd are zeros."""
+        A = self.A
+        B = int(index.shape[0])
+        if index.dtype != torch.int32 or (cos_sin is not None and (cos_sin.dtype != torch.float32 or tuple(cos_sin.shape) != (B, 2))):
+            raise A.CnError("DeviceTrajectories.gather: index must be int32 [B] and cos_sin float32 [B,2]")
+        v_obs, v_pred = torch.empty(B, 5, num_peds, 2, device=self.device), torch.empty(B, 5, num_peds, 2, device=self.device)
+        lm = torch.empty(B, num_peds, 10, device=self.device)
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_gather_batch(B, int(num_peds), self.num_seq, self.total_peds, A.ptr(index), A.ptr(cos_sin), A.ptr(self._seq_start),
+                                                A.ptr(self._seq_count), A.ptr(self.obs_traj_rel), A.ptr(self.pred_traj_rel), A.ptr(self.loss_mask_rel),
+                                                A.ptr(v_obs), A.ptr(v_pred), A.ptr(lm), A.stream_ptr()), "cn_gst_gather_batch")
+        return v_obs, v_pred, lm
+
+    def num_peds(self, order):
+        """The gather's pedestrian axis for the sequences `order` (host indices): max(4, the largest crowd among them)."""
+        return max(4, int(self.counts[order].max()))
+
+
+def _draw_theta(rotation_pattern):
+    """train.py:115-117: the rotation angle of one training item, drawn from torch's global generator."""
+    return (torch.randint(0, 4, ()).float() / 2. * np.pi).item() if rotation_pattern == "right_angle" else (torch.rand(()) * 2. * np.pi).item()
+
+
+def epoch_plan(n, rotation_pattern):
+    """The order and the rotation angles of one training epoch over n sequences, drawn up front by the calls the per-item loop makes, in its
+    sequence: iterating DataLoader(dataset, batch_size=1, shuffle=True) and drawing theta after every item.  -> (order [n] int64,
+    thetas [n] float64 or None); torch's global generator is left where that loop leaves it."""
+    order, thetas = [], []
+    for idx in DataLoader(range(int(n)), batch_size=1, shuffle=True):
+        order.append(int(idx))
+        if rotation_pattern is not None:
+            thetas.append(_draw_theta(rotation_pattern))
+    return np.asarray(order, dtype=np.int64), (np.asarray(thetas, dtype=np.float64) if rotation_pattern is not None else None)
+
+
+def _offset_errors_batched(x_pred, x_target, loss_mask):
+    """average_offset_error / final_offset_error (mgnn/utils.py:8-28) of every sequence of a batch: [B,P,N,2], [B,P,N,2], [B,N] -> [B,N] each."""
+    err = torch.sqrt(((torch.cumsum(x_pred, 1) - torch.cumsum(x_target, 1)) ** 2.).sum(3))
+    return err.mean(1) * loss_mask, err[:, -1] * loss_mask
+
+
+def _train_epoch_device(hip_tr, ds, order, thetas, batch_size, optimizer, obs_len):
+    """One training epoch with the data on the device: per step a gather, the training step, the fused clip + Adam step; the step's loss and
+    its aoe / foe terms go into per-epoch device buffers and come back in ONE read-back.  -> (losses [steps] float64, aoe, foe, m: float32
+    arrays of the per-pedestrian terms in step order)."""
+    dev, n, B = ds.device, len(order), int(batch_size)
+    index = torch.as_tensor(order.astype(np.int32)).to(dev)
+    cos_sin = None if thetas is None else torch.as_tensor(np.stack((np.cos(thetas), np.sin(thetas)), 1).astype(np.float32)).to(dev)
+    chunks = [(lo, min(lo + B, n)) for lo in range(0, n, B)]
+    widths = [int(ds.counts[order[lo]]) if B == 1 else (hi - lo) * ds.num_peds(order[lo:hi]) for lo, hi in chunks]
+    off = np.concatenate(([0], np.cumsum(widths))).astype(np.int64)
+    loss_buf, terms = torch.empty(len(chunks), device=dev), torch.empty(3, int(off[-1]), device=dev)
+    for k, (lo, hi) in enumerate(chunks):
+        vo, vp, lm_rel = ds.gather(index[lo:hi], ds.num_peds(order[lo:hi]), None if cos_sin is None else cos_sin[lo:hi])
+        hip_tr.lr = optimizer.param_groups[0]["lr"]                           # the StepLR schedule drives the fused step too
+        out, gauss = hip_tr.loss_and_grads(vo, vp, lm_rel, p_drop=0.1)
+        hip_tr.optimizer_step(grad_scale=1.0 / B)
+        loss_buf[k].copy_(out[0])
+        seg = terms[:, off[k]:off[k + 1]]
+        if B == 1:                                                            # the per-item loop's own expressions on its own shapes
+            c = widths[k]
+            gauss, lm_rel, vp = gauss[:, :, :c], lm_rel[:, :c], vp[:, :, :c].contiguous()
+            xs = gauss[..., :2] * lm_rel[:, :, obs_len - 1].unsqueeze(1).unsqueeze(-1)
+            lm = (lm_rel.sum(2) == lm_rel.shape[2]).float()
+            seg[0].copy_(average_offset_error(xs, vp, lm)); seg[1].copy_(final_offset_error(xs, vp, lm)); seg[2].copy_(lm[0])
+        else:
+            xs = gauss[..., :2] * lm_rel[:, :, obs_len - 1].unsqueeze(1).unsqueeze(-1)
+            lm = (lm_rel.sum(2) == lm_rel.shape[2]).float()
+            aoe, foe = _offset_errors_batched(xs, vp, lm)
+            seg[0].copy_(aoe.reshape(-1)); seg[1].copy_(foe.reshape(-1)); seg[2].copy_(lm.reshape(-1))
+    host = torch.cat((loss_buf, terms.reshape(-1))).cpu().numpy()              # the epoch's one read-back
+    t = host[len(chunks):].reshape(3, -1)
+    return host[:len(chunks)].astype(np.float64), t[0], t[1], t[2]
+
+
+def _evaluate_device(model, ds, batch_size=32):
+    """evaluate(backend='hip') with the data on the device: the gather in its no-rotation form feeds cn_gst_eval_step, batches of consecutive
+    sequences, one read-back per pass."""
+    model.eval()
+    ev = HipGstEvaluator(model)
+    index = torch.arange(len(ds), dtype=torch.int32, device=ds.device)
+    rows = []
+    with torch.no_grad():
+        for lo in range(0, len(ds), batch_size):
+            hi = min(lo + batch_size, len(ds))
+            seq, ped, _ = ev.evaluate_batch(*ds.gather(index[lo:hi], ds.num_peds(np.arange(lo, hi))))
+            rows.append(torch.stack((seq[:, 0, 0] / seq[:, 0, 1], seq[:, 0, 2], seq[:, 0, 3], ped[:, 0, :, 2].sum(1)), 1))
+    r = torch.cat(rows, 0).double().cpu().numpy()
+    m = max(float(r[:, 3].sum()), 1.0)
+    return float(r[:, 0].mean()), float(r[:, 1].sum() / m), float(r[:, 2].sum() / m)
 
 
 def _eval_backend(model, backend):
@@ -536,17 +734,36 @@ def test(model, loader, device, num_samples=20, seed=1000, backend=None, batch_s
             float(r[:, 3].sum() / m), float(r[:, 6].sum() / m))
 
 
-def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad=10.0, rotation_pattern="random", save_epochs=10, init_temp=0.5,
-          random_seed=1000, device=None, num_workers=0, log=print, backend=None, val_backend=None):
+def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad=10.0, rotation_pattern="random", save_epochs=10, init_temp=0.5,
+          random_seed=1000, device=None, num_workers=0, log=print, backend=None, val_backend=None, dataset=None, batch_size=1):
     """gst_updated/scripts/experiments/train.py:49-195 for the shipped configuration.  data_dir holds the text files of collect.py /
     collect_data.py; the first 80 % of every file's windows train, the rest validate (TrajectoriesDataset modes).  Writes
     <out_dir>/checkpoint/{epoch_<n>.pt, args.pickle, train_hist.pickle} in the reference's format (+ args.json / train_hist.json): the
-    directory is a valid config.pred.model_dir for load_predictor here and for the reference's CrowdNavPredInterfaceMultiEnv."""
+    directory is a valid config.pred.model_dir for load_predictor here and for the reference's CrowdNavPredInterfaceMultiEnv.
+    dataset = (train, val) of DeviceTrajectories replaces data_dir.  With backend 'hip' the epoch then runs with the data on the device: the
+    order and the angles are drawn up front (epoch_plan: the draws of the per-item loop), minibatches are consecutive chunks of batch_size of that
+    order (train.py's args.batch_size; the last may be short), each assembled by cn_gst_gather_batch, and the losses come back once per epoch.
+    batch_size > 1 needs that path (a data_dir is uploaded for it)."""
+    if out_dir is None or (data_dir is None) == (dataset is None):
+        raise ValueError("train() needs an out_dir and either a data_dir or dataset=(train, val)")
+    batch_size = int(batch_size)
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1 (got %d)" % batch_size)
     torch.manual_seed(random_seed)
     np.random.seed(random_seed)
     device = torch.device(device if device is not None else ("cuda:0" if torch.cuda.is_available() else "cpu"))
-    ds_train = TrajectoriesDataset(data_dir, mode="train")
-    ds_val = TrajectoriesDataset(data_dir, mode="val")
+    if backend is None:
+        backend = "hip" if device.type == "cuda" else "torch"
+    if batch_size > 1 and backend != "hip":
+        raise ValueError("batch_size > 1 needs backend='hip': the op graph trains one sequence per step")
+    if dataset is not None:
+        ds_train, ds_val = dataset
+    else:
+        ds_train = TrajectoriesDataset(data_dir, mode="train")
+        ds_val = TrajectoriesDataset(data_dir, mode="val")
+        if batch_size > 1:
+            ds_train, ds_val = DeviceTrajectories.from_dataset(ds_train, device), DeviceTrajectories.from_dataset(ds_val, device)
+    on_device = backend == "hip" and isinstance(ds_train, DeviceTrajectories)
     loader_train = DataLoader(ds_train, batch_size=1, shuffle=True, num_workers=num_workers)
     loader_val = DataLoader(ds_val, batch_size=1, shuffle=False, num_workers=num_workers)
     model = GSTPredictor().to(device)
@@ -554,8 +771,6 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=max(int(temp_epochs / 4), 1), gamma=0.3)
     # backend: 'hip' = the training step as hand-written kernels through the C ABI (HipGstTrainer; the default on a GPU), 'torch' = the op graph
     # above under autograd (CPU tests, and the cross-check of the kernels)
-    if backend is None:
-        backend = "hip" if device.type == "cuda" else "torch"
     if backend == "hip" and clip_grad is None:
         raise ValueError("backend='hip' clips the gradient norm in its fused Adam step: pass a clip_grad (the reference's default is 10)")
     # the per-epoch validation follows the training step's backend (cn_gst_eval_step with 'hip'); val_backend forces one ('torch': the op graph)
@@ -566,7 +781,7 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
     os.makedirs(ckpt_dir, exist_ok=True)
     run_args = dict(spatial="gumbel_social_transformer", temporal="faster_lstm", output_dim=5, embedding_size=64, spatial_num_heads=8,
                     spatial_num_heads_edges=0, spatial_num_layers=1, ghost=False, lstm_hidden_size=64, lstm_num_layers=1, decode_style="recursive",
-                    detach_sample=False, motion_dim=2, only_observe_full_period=False, dataset="sj", obs_seq_len=5, pred_seq_len=5, batch_size=1,
+                    detach_sample=False, motion_dim=2, only_observe_full_period=False, dataset="sj", obs_seq_len=5, pred_seq_len=5, batch_size=batch_size,
                     lr=lr, clip_grad=clip_grad, rotation_pattern=rotation_pattern, num_epochs=num_epochs, temp_epochs=temp_epochs,
                     save_epochs=save_epochs, init_temp=init_temp, random_seed=random_seed, deterministic=False, resume_training=False,
                     resume_epoch=None)
@@ -582,11 +797,15 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
         t0 = time.time()
         tau = temperature(epoch, temp_epochs, init_temp)
         losses, aoes, foes, ms = [], [], [], []
-        for item in loader_train:
+        if on_device:
+            order, thetas = epoch_plan(len(ds_train), rotation_pattern)
+            ep = _train_epoch_device(hip_tr, ds_train, order, thetas, batch_size, optimizer, model.obs_len)
+            losses, aoes, foes, ms = list(ep[0]), [ep[1]], [ep[2]], [ep[3]]
+        for item in (() if on_device else loader_train):
             if item[6].shape[2] > 128:            # train.py:118-119
                 continue
             if rotation_pattern is not None:
-                theta = (torch.randint(0, 4, ()).float() / 2. * np.pi).item() if rotation_pattern == "right_angle" else (torch.rand(()) * 2. * np.pi).item()
+                theta = _draw_theta(rotation_pattern)
                 item = list(item)
                 item[6], item[8] = rotate_graph(item[6], theta), rotate_graph(item[8], theta)
             if hip_tr is not None:
@@ -616,7 +835,11 @@ def train(data_dir, out_dir, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad
         scheduler.step()
         m = max(float(np.concatenate(ms).sum()), 1.0)
         tr = (float(np.mean(losses)), float(np.concatenate(aoes).sum() / m), float(np.concatenate(foes).sum() / m))
-        va = evaluate(model, loader_val, device, backend=val_backend)
+        if on_device and val_backend == "hip" and isinstance(ds_val, DeviceTrajectories):
+            iter(DataLoader(range(len(ds_val)), batch_size=1, shuffle=False))   # every DataLoader iterator draws its base seed from the global generator
+            va = _evaluate_device(model, ds_val)
+        else:
+            va = evaluate(model, loader_val, device, backend=val_backend)
         for k, a, b in (("loss", tr[0], va[0]), ("aoe", tr[1], va[1]), ("foe", tr[2], va[2])):
             hist["train_%s_task" % k].append(a); hist["val_%s_task" % k].append(b)
         hist["epoch"] = epoch

@@ -2,7 +2,9 @@
 """End to end, the way the reference's pipeline goes (collect_data.py -> gst_updated train.py -> config.pred.model_dir):
 simulate crowds on the GPU, write the GST dataset files, train the predictor on them, load the checkpoint back.
 
-    python examples/collect_and_train_gst.py [--envs 256] [--steps 400] [--epochs 5] [--out /tmp/gst_run]
+    python examples/collect_and_train_gst.py [--envs 256] [--steps 400] [--epochs 5] [--out /tmp/gst_run] [--device-data --batch-size 32]
+
+--device-data skips the files: the observations stay on the GPU, the sequences are cut out of them there and ALL envs train, in minibatches.
 """
 import argparse
 import os
@@ -14,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from crowdnav_prediction_attngraph_amd import config as C  # noqa: E402
 from crowdnav_prediction_attngraph_amd import gst_train  # noqa: E402
-from crowdnav_prediction_attngraph_amd.collect import CollectVecEnv, collect_lines  # noqa: E402
+from crowdnav_prediction_attngraph_amd.collect import CollectVecEnv, collect_lines, collect_log  # noqa: E402
 from crowdnav_prediction_attngraph_amd.gst import GSTPredictor  # noqa: E402
 
 
@@ -24,6 +26,8 @@ def main():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--train-files", type=int, default=4, help="how many of the env files the (per-sequence, host-driven) training loop reads")
+    ap.add_argument("--device-data", action="store_true", help="cut the sequences out of the observations on the GPU and train on all envs (no files)")
+    ap.add_argument("--batch-size", type=int, default=1, help="sequences per optimiser step (train.py's args.batch_size)")
     ap.add_argument("--out", default="/tmp/gst_run")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -31,6 +35,17 @@ def main():
     envs = CollectVecEnv(425, a.envs, dev, config=cfg)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    if a.device_data:
+        log = collect_log(envs, a.steps)
+        sets = tuple(gst_train.DeviceTrajectories.from_log(log, mode) for mode in ("train", "val"))
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        envs.close()
+        print("collected %d envs x %d steps = %d env-steps and cut %d + %d sequences out of them on the device in %.2f s (%.0f env-steps/s)"
+              % (a.envs, a.steps, a.envs * a.steps, len(sets[0]), len(sets[1]), t1 - t0, a.envs * a.steps / (t1 - t0)))
+        model, hist = gst_train.train(out_dir=os.path.join(a.out, "run"), dataset=sets, batch_size=a.batch_size, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4),
+                                      save_epochs=a.epochs, device=dev)
+        return report(a, dev, hist)
     lines = collect_lines(envs, a.steps)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
@@ -44,7 +59,12 @@ def main():
     rows = sum(len(x) for x in lines)
     print("collected %d envs x %d steps = %d env-steps, %d (frame, id, x, y) rows in %.2f s (%.0f env-steps/s incl. the text formatting on the host)"
           % (a.envs, a.steps, a.envs * a.steps, rows, t1 - t0, a.envs * a.steps / (t1 - t0)))
-    model, hist = gst_train.train(data_dir, os.path.join(a.out, "run"), num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev)
+    model, hist = gst_train.train(data_dir, os.path.join(a.out, "run"), num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev,
+                                  batch_size=a.batch_size)
+    report(a, dev, hist)
+
+
+def report(a, dev, hist):
     ck = os.path.join(a.out, "run", "checkpoint", "epoch_%d.pt" % a.epochs)
     GSTPredictor.from_checkpoint(ck, dev)
     print("val aoe %.4f -> %.4f, val foe %.4f -> %.4f; checkpoint %s" % (hist["val_aoe_task"][0], hist["val_aoe_task"][-1], hist["val_foe_task"][0],

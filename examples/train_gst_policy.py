@@ -4,6 +4,9 @@ on them (or load one from --model-dir) -> PPO on CrowdSimPredRealGST-v0 with tha
 evaluating on the seeded test cases every --eval-interval updates -> the final 500-case line.
 
     python examples/train_gst_policy.py [--model-dir DIR] [--envs 512] [--updates 400] [--lr 4e-5] [--eval-interval 100] [--out /tmp/gst_policy]
+                                        [--device-data --batch-size 32]
+
+--device-data keeps the collected observations on the GPU and trains the predictor on ALL collect envs in minibatches (no files).
 """
 import argparse
 import logging
@@ -16,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from crowdnav_prediction_attngraph_amd import config as C  # noqa: E402
 from crowdnav_prediction_attngraph_amd import gst_train  # noqa: E402
-from crowdnav_prediction_attngraph_amd.collect import CollectVecEnv, collect_lines  # noqa: E402
+from crowdnav_prediction_attngraph_amd.collect import CollectVecEnv, collect_lines, collect_log  # noqa: E402
 from crowdnav_prediction_attngraph_amd.gst import GSTPredictor, find_checkpoint  # noqa: E402
 from crowdnav_prediction_attngraph_amd.trainer import train  # noqa: E402
 
@@ -26,6 +29,15 @@ ENV = "CrowdSimPredRealGST-v0"
 def fresh_predictor(a, dev):
     """collect_data.py -> gst_updated train.py, as examples/collect_and_train_gst.py does it."""
     envs = CollectVecEnv(a.seed, a.collect_envs, dev, config=C.non_randomized(**{"sim.human_num": 20, "robot.policy": "orca"}))
+    run = os.path.join(a.out, "predictor")
+    if a.device_data:
+        log = collect_log(envs, a.collect_steps)
+        envs.close()
+        sets = tuple(gst_train.DeviceTrajectories.from_log(log, mode) for mode in ("train", "val"))
+        _, hist = gst_train.train(out_dir=run, dataset=sets, batch_size=a.batch_size, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev)
+        print("predictor (%d + %d sequences of %d envs, batches of %d): val aoe %.4f -> %.4f, val foe %.4f -> %.4f" % (
+            len(sets[0]), len(sets[1]), a.collect_envs, a.batch_size, hist["val_aoe_task"][0], hist["val_aoe_task"][-1], hist["val_foe_task"][0], hist["val_foe_task"][-1]), flush=True)
+        return run
     lines = collect_lines(envs, a.collect_steps)
     envs.close()
     data_dir = os.path.join(a.out, "data")
@@ -33,8 +45,7 @@ def fresh_predictor(a, dev):
     for i in range(min(a.train_files, a.collect_envs)):
         with open(os.path.join(data_dir, "%d.txt" % i), "w") as f:
             f.write("\n".join(lines[i]) + "\n")
-    run = os.path.join(a.out, "predictor")
-    _, hist = gst_train.train(data_dir, run, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev)
+    _, hist = gst_train.train(data_dir, run, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev, batch_size=a.batch_size)
     print("predictor: val aoe %.4f -> %.4f, val foe %.4f -> %.4f" % (hist["val_aoe_task"][0], hist["val_aoe_task"][-1], hist["val_foe_task"][0],
                                                                    hist["val_foe_task"][-1]), flush=True)
     return run
@@ -46,6 +57,8 @@ def main():
     ap.add_argument("--collect-envs", type=int, default=256)
     ap.add_argument("--collect-steps", type=int, default=400)
     ap.add_argument("--train-files", type=int, default=4)
+    ap.add_argument("--device-data", action="store_true", help="cut the sequences out of the observations on the GPU and train on all collect envs (no files)")
+    ap.add_argument("--batch-size", type=int, default=1, help="sequences per optimiser step (train.py's args.batch_size)")
     ap.add_argument("--epochs", type=int, default=5)
     ap.add_argument("--envs", type=int, default=512)
     ap.add_argument("--updates", type=int, default=400)

@@ -575,6 +575,48 @@ int64_t cn_gst_eval_workspace_bytes(int B, int N, int S);
 int cn_gst_eval_step(int B, int N, int S, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const float *noise,
                      void *workspace, int64_t workspace_bytes, float *seq_out, float *ped_out, float *gauss_out, void *stream);
 
+/* ---- GST predictor training DATA on the device: sequences from the collect batch's observation log, and minibatches of them ----
+ * Replaces gst_updated/src/mgnn/trajectories.py:9-160 (TrajectoriesDataset: obs 5, pred 5, skip 1, frame_diff 1, invalid -999) over the text
+ * files of collect_data.py, without the files: the output is what that class holds for the files written from the same log, envs in order.
+ *   log [F,E,H,4] float32, 16-byte aligned: the pred_info rows of F sampled observations of E CrowdSimVarNumCollect-v0 envs -- frame id,
+ *   prediction id, px, py; a row is visible (a line of the file) iff py is not infinite.  F >= 10, 1 <= H <= 64, F * E < 2^24.
+ * The rule.  Per env the samples with a visible row are its frames, in order, with the frame id of their visible rows.  Candidate window i is
+ * frames i .. i+9 of that list; with W = frames - 9 candidates, i belongs to mode TRAIN iff i < (int)((W + 1) * 0.8) in float64, to VAL
+ * otherwise, to ALL always.  A candidate becomes a sequence iff consecutive frame ids differ by exactly 1 and some prediction id has a row in
+ * all ten frames.  Its pedestrians are the window's distinct prediction ids in ascending order; positions are the float32 values, -999 where
+ * the pedestrian has no row; a displacement is (float)((double)x[t] - (double)x[t-1]) where both exist and 0 at t = 0 where x[0] exists, else
+ * -999; loss_mask = 1 where a row exists, loss_mask_rel = 1 where the displacement does.  Sequences are ordered by (env, i).
+ * Status word (int32 on the device, zeroed by the caller, OR-ed into): the log is refused if it is not zero after cn_gst_data_count --
+ *   CN_GSTD_FRAME_ORDER     the frame ids of an env's list do not strictly increase (an episode boundary), or the visible rows of one sample
+ *                           carry different frame ids
+ *   CN_GSTD_DUPLICATE_ID    two visible rows of one sample carry the same prediction id
+ *   CN_GSTD_TOO_MANY_PEDS   a sequence has more than 64 pedestrians (the bound of cn_gst_train_step / cn_gst_eval_step)
+ * Three calls around two exclusive sums the caller runs on the device (so the ragged output needs no atomics and no launch-order dependence):
+ *   cn_gst_data_frames  -> visible [F,E] int32 0/1, frame_id [F,E] float32
+ *   (listed_before [F,E] int32 = exclusive sum of visible along F)
+ *   cn_gst_data_count   -> frame_list [E,F] int32 scratch, ped_count [E*(F-9)] int32 pedestrians of candidate e*(F-9)+i (0: not a sequence of
+ *                          this mode), first_frame [E*(F-9)] float32 its first frame id
+ *   (ped_offset [E*(F-9)] int32 = exclusive sum of ped_count; total_peds = its total)
+ *   cn_gst_data_fill    -> obs_traj, pred_traj, obs_traj_rel, pred_traj_rel [total_peds,2,5], loss_mask, loss_mask_rel [total_peds,10]; the same
+ *                          mode and buffers as the count call. */
+enum { CN_GSTD_ALL = 0, CN_GSTD_TRAIN = 1, CN_GSTD_VAL = 2 };
+enum { CN_GSTD_FRAME_ORDER = 1, CN_GSTD_DUPLICATE_ID = 2, CN_GSTD_TOO_MANY_PEDS = 4 };
+int cn_gst_data_frames(int F, int E, int H, const float *log, int32_t *visible, float *frame_id, int32_t *status, void *stream);
+int cn_gst_data_count(int F, int E, int H, int mode, const float *log, const int32_t *visible, const int32_t *listed_before,
+                      const float *frame_id, int32_t *frame_list, int32_t *ped_count, float *first_frame, int32_t *status, void *stream);
+int cn_gst_data_fill(int F, int E, int H, int mode, const float *log, const int32_t *visible, const int32_t *listed_before,
+                     const float *frame_id, const int32_t *frame_list, const int32_t *ped_count, const int32_t *ped_offset,
+                     int64_t total_peds, float *obs_traj, float *pred_traj, float *obs_traj_rel, float *pred_traj_rel, float *loss_mask,
+                     float *loss_mask_rel, void *stream);
+/* One minibatch for cn_gst_train_step / cn_gst_eval_step: v_obs, v_pred [B,5,Np,2] and loss_mask_rel_out [B,Np,10] of the sequences
+ * index [B] (int32, device) of a dataset of num_seq sequences (seq_start / seq_count [num_seq] int32: first pedestrian row and crowd).
+ * v[b,t,n,c] = traj_rel[seq_start + n, c, t] (mgnn/utils.py:44-77 seq_to_graph), rotated by (c, s) = cos_sin[b] (float32 [B,2]) as
+ * mgnn/utils.py:80-90 rotate_graph does: x*c - y*s, x*s + y*c, every product and sum rounded once, the -999 entries included; cos_sin NULL
+ * copies instead (zeros keep their sign).  Rows n >= seq_count are zeros, values and mask; 4 <= Np <= 64, crowds above Np are cut. */
+int cn_gst_gather_batch(int B, int Np, int num_seq, int64_t total_peds, const int32_t *index, const float *cos_sin, const int32_t *seq_start,
+                        const int32_t *seq_count, const float *obs_traj_rel, const float *pred_traj_rel, const float *loss_mask_rel,
+                        float *v_obs, float *v_pred, float *loss_mask_rel_out, void *stream);
+
 /* ---- rollout math ---- */
 /* rewards [T,N], values [T+1,N], masks [T+1,N] -> returns[t][n] for t < T (row T untouched).  fp32, torch op order. */
 int cn_gae(int T, int N, const float *rewards, const float *values, const float *masks, double gamma, double lam,
