@@ -78,6 +78,22 @@ struct CnStampScope {
 #define CN_WAVE 64
 
 // ---- wave-level primitives (64 lanes) ----
+// A value that was loaded ahead of its use: what is computed from it stays below this point (the compiler otherwise hoists the first
+// operation on it -- a conversion, a readfirstlane -- up to the load and waits for the load there).
+template <class T> __device__ __forceinline__ T held(T v) { asm volatile("" : "+v"(v)); return v; }
+// ... of a wave-uniform value: from here on it lives in scalar registers
+template <class T> __device__ __forceinline__ T held_uniform(T v)
+{
+    static_assert(sizeof(T) == 4 || sizeof(T) == 8, "held_uniform: one or two words");
+    v = held(v);
+    int w[sizeof(T) / 4];
+    __builtin_memcpy(w, &v, sizeof(T));
+#pragma unroll
+    for (int k = 0; k < (int)(sizeof(T) / 4); ++k) w[k] = __builtin_amdgcn_readfirstlane(w[k]);
+    __builtin_memcpy(&v, w, sizeof(T));
+    return v;
+}
+
 __device__ __forceinline__ float wv_readlane(float x, int lane_uniform)
 {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane_uniform));

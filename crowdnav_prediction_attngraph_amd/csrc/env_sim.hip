@@ -61,7 +61,9 @@ __global__ __launch_bounds__(64) void env_reset_kernel(EnvDev s, cn_obs ob, int 
     double shared_nd = s.cfg.orca_neighbor_dist;
     int n = s.H;
     if (e == 0 && lane == 0) *s.lp3_cnt = 0; // the ORCA pass that follows starts with an empty linearProgram3 list
-    do_reset(s, R, e, lane, rb, h, shared_nd, n, ob, with_obs != 0);
+    const bool nx_ready = s.nx_ready[e] != 0;
+    const uint64_t case_counter = s.case_counter[e];
+    do_reset(s, R, e, lane, nx_ready, case_counter, rb, h, shared_nd, n, ob, with_obs != 0);
     if (!with_obs && lane == 0) s.pend[e] = 1;
     store_env(s, e, lane, rb, h);
     if (lane == 0) { s.shared_nd[e] = shared_nd; if (s.nh) s.nh[e] = n; }
@@ -159,6 +161,11 @@ __global__ __launch_bounds__(64) void env_obs_kernel(EnvDev s, cn_obs ob)
 // SPLIT = true: first half only (everything up to the kinematics and the reset bookkeeping); env_obs_kernel finishes the step after
 // the roll-out kernels.
 // W = 4: three helper wavefronts per env for the long placement loops of dense crowds (see CoopLds); W = 1: one wavefront per env
+// Memory: the kernel is the latency chain of its slowest wavefront, so its reads are issued in two batches instead of one dependent trip
+// after the other.  The GATHER at the top issues every load whose address depends only on (e, lane) and whose value no store of this launch
+// produces, with no store in front of it; what the kernel changes later (step / case counter, crowd size) is used from those registers and
+// never read again.  The SECOND batch goes out as soon as the outcome of the step is known: the staged episode of an env that resets, the
+// env's MT19937 state where the step will draw from it (rng_prefetch).
 // DEFER = true (dense crowds without a lane kernel): the observation is written, the post-observation updates -- which nothing in the
 // observation depends on -- are left to env_post_kernel on the side stream, in front of the ORCA pass that needs the new goals: the
 // long placement loops of the few envs that change goals then run beside the policy forward instead of in front of it.
@@ -174,18 +181,51 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
     }
     const cn_env_config &c = s.cfg;
     const int H = s.H;
+    // ---- gather (indices of the per-slot arrays are clamped to the H slots, not to the crowd size: that is one of the loads)
+    const int lj = lane < H ? lane : 0;
     int n = crowd_size(s, e);  // humans present during this step's reward / kinematics
-    const bool isH = lane < n;
     Rng R{MT_N, false};
     Robot rb;
     Lane h;
     load_env(s, e, lane, rb, h);
     double shared_nd = s.shared_nd[e];
     int step_counter = s.step_counter[e];
+    float ax = actions[2 * e], ay = actions[2 * e + 1];
+    // this step's ORCA velocity of human `lane` (social-force humans compute theirs below and do not use these)
+    const float hax = s.hact[(size_t)e * 2 * H + lj], hay = s.hact[(size_t)e * 2 * H + H + lj];
+    double ep_ret_in = s.ep_ret[e];
+    int ep_cnt_in = s.ep_cnt[e];
+    int nx_ready_in = s.nx_ready[e];
+    uint64_t case_counter = s.case_counter[e];
+    double desired_v = 0.0, wheel_in[4] = {0.0, 0.0, 0.0, 0.0};
+    if (c.kinematics == CN_KIN_UNICYCLE && c.robot_policy == CN_ROBOT_NETWORK) {
+        desired_v = s.desired_v[e];
+        if (s.wheel) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) wheel_in[k] = s.wheel[(size_t)e * 4 + k];
+            rng_prefetch(R, s, e, lane); // smooth_action's dead band draws on every step
+        }
+    }
+    int obs_cnt = 0, obs_max = -1;
+    if (c.human_num_range > 0) { obs_cnt = s.obs_cnt[e]; obs_max = s.obs_max[e]; }
+    int rob_sim_valid = 0, rob_sim_n = 0;
+    float rob_nd = 0.0f, rob_seen = 0.0f;
+    if (c.robot_policy == CN_ROBOT_ORCA) {
+        rob_sim_valid = s.rob_sim_valid[e];
+        if (s.rob_sim_n) rob_sim_n = s.rob_sim_n[e];
+        rob_nd = s.rob_nd[e];
+        rob_seen = s.rob_seen[(size_t)e * H + lj];
+    }
+    int seen_before = 0; // human_visibility of the last observation
+    if (c.phase == CN_PHASE_TEST) seen_before = s.vis[(size_t)e * H + lj];
+    // the one wait of the gather (the wave-uniform words would otherwise each be waited for where they are loaded: see held())
+    n = held_uniform(n); step_counter = held_uniform(step_counter); shared_nd = held_uniform(shared_nd); ax = held_uniform(ax); ay = held_uniform(ay);
+    ep_ret_in = held_uniform(ep_ret_in); ep_cnt_in = held_uniform(ep_cnt_in); case_counter = held_uniform(case_counter);
+    const bool nx_ready = held_uniform(nx_ready_in) != 0;
+    const bool isH = lane < n;
     if (e == 0 && lane == 0) *s.lp3_cnt = 0; // the ORCA pass that follows starts with an empty linearProgram3 list
 
     // srnn.clip_action (crowd_nav/policy/srnn.py:17-34), float32 like the numpy action array
-    float ax = actions[2 * e], ay = actions[2 * e + 1];
     double uni_v = 0.0, uni_r = 0.0; // ActionRot(v, r) of the unicycle robot
     double axd = 0.0, ayd = 0.0;     // float64 action of the social-force robot
     if (c.robot_policy == CN_ROBOT_SOCIAL_FORCE) {
@@ -209,14 +249,15 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
         // crowd_sim_var_num.py:371-375: action = robot.act(copy of last_human_states) -> ORCA.predict (orca.py:64-117) on the
         // robot's BELIEFS about all H humans (never-seen ones sit at the (15,15) dummy); no clip_action on this path
         float nd, seen_r;
-        if (!s.rob_sim_valid[e] || (s.rob_sim_n && s.rob_sim_n[e] != n + 1)) { // orca.py:80-82: new simulator when the crowd size changed
+        if (!held(rob_sim_valid) || (s.rob_sim_n && held(rob_sim_n) != n + 1)) { // orca.py:80-82: new simulator when the crowd size changed
             nd = (float)shared_nd;
             seen_r = (float)(h.l4 + 0.01 + c.orca_safety_space);
             if (isH) s.rob_seen[(size_t)e * H + lane] = seen_r;
             if (lane == 0) { s.rob_nd[e] = nd; s.rob_sim_valid[e] = 1; if (s.rob_sim_n) s.rob_sim_n[e] = (uint8_t)(n + 1); }
         } else {
-            nd = s.rob_nd[e];
-            seen_r = s.rob_seen[(size_t)e * H + (isH ? lane : 0)];
+            nd = held(rob_nd);
+            rob_seen = held(rob_seen);
+            seen_r = isH ? rob_seen : __shfl(rob_seen, 0, 64); // (lanes past the crowd carry slot 0's value, as they always did)
         }
         double gvx = rb.gx - rb.px, gvy = rb.gy - rb.py;
         const double speed = sqrt(gvx * gvx + gvy * gvy);
@@ -229,7 +270,7 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
         // running sum self.desiredVelocity[0], clipped to +-v_pref (float64 from there on, as with the numpy the reference pins)
         const float dv = fminf(fmaxf(ax, (float)-0.1), (float)0.087);
         ay = fminf(fmaxf(ay, (float)-0.06), (float)0.06);
-        uni_v = fmin(fmax(s.desired_v[e] + (double)dv, -c.robot_v_pref), c.robot_v_pref);
+        uni_v = fmin(fmax(held(desired_v) + (double)dv, -c.robot_v_pref), c.robot_v_pref);
         uni_r = (double)ay;
         if (lane == 0) s.desired_v[e] = uni_v;
         if (s.wheel) {
@@ -237,9 +278,9 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
             // a Turtlebot2i (wheel radius 0.035 m, track 0.23 m) clipped to +-17.5 rad/s, low-pass filtered in the test phase, then
             // reduced towards zero by a noisy dead band N(1.8, 0.15) per wheel.  Wave-uniform; these are the first draws of the step.
             double *wh = s.wheel + (size_t)e * 4;
-            const double last_left = wh[0], last_right = wh[1];
-            double gauss = wh[2];
-            bool has_gauss = wh[3] != 0.0;
+            const double last_left = held(wheel_in[0]), last_right = held(wheel_in[1]);
+            double gauss = held(wheel_in[2]);
+            bool has_gauss = held(wheel_in[3]) != 0.0;
             rng_load(R, s, e, lane);
             const double w = uni_r / c.time_step;
             double left = (2.0 * uni_v - 0.23 * w) / (2.0 * 0.035), right = (2.0 * uni_v + 0.23 * w) / (2.0 * 0.035);
@@ -307,7 +348,7 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
     double min_danger = 0.0, rf_truth = 0.0;
     if (test_phase) {
         const double *tre = s.tr + (size_t)e * (s.R + 1) * 4 * H;
-        const bool seen = isH && s.vis[(size_t)e * H + lane];
+        const bool seen = isH && held(seen_before) != 0;
         double best = INFINITY;
         for (int k = 1; k <= s.P; ++k) {
             if (isH) {
@@ -432,33 +473,41 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
         h.vx = sfx; h.vy = sfy;
         s.hact[(size_t)e * 2 * H + lane] = (float)sfx; s.hact[(size_t)e * 2 * H + H + lane] = (float)sfy; // for cn_env_get_human_actions
     } else if (isH) {
-        const float hax = s.hact[(size_t)e * 2 * H + lane], hay = s.hact[(size_t)e * 2 * H + H + lane];
         h.px = h.px + (double)hax * c.time_step;
         h.py = h.py + (double)hay * c.time_step;
         h.vx = (double)hax; h.vy = (double)hay;
     }
     step_counter += 1;
-    const double ep_ret = s.ep_ret[e] + reward;
-    const int ep_cnt = s.ep_cnt[e] + 1;
+    const double ep_ret = ep_ret_in + reward;
+    const int ep_cnt = ep_cnt_in + 1;
+    const bool resetting = done && c.auto_reset;
+    const int period = (int)(5.0 / c.time_step + 0.5);
     if (lane == 0) {
         reward_out[e] = (float)reward; done_out[e] = (uint8_t)done; info_out[e] = (uint8_t)info;
         ep_ret_out[e] = ep_ret; ep_len_out[e] = ep_cnt;
         if (not_done_out) not_done_out[e] = done ? 0.0f : 1.0f; // the `masks` tensor of train.py:185-186
     }
-    if (done && c.auto_reset) {
+    // ---- second batch: the outcome is known, and with it what the slow paths of this env will read
+    if (resetting) {
         // vec-env auto-reset: the terminal observation is replaced by the first observation of the next episode.
         // (The terminal step's own crowd-size / goal-change / respawn draws happen before np.random.seed and cannot be observed.)
-        do_reset(s, R, e, lane, rb, h, shared_nd, n, ob, !SPLIT);
+        do_reset(s, R, e, lane, nx_ready, case_counter, rb, h, shared_nd, n, ob, !SPLIT);
         if (SPLIT && lane == 0) s.pend[e] = 1;
     } else {
         // (auto_reset == 0, the single-env gym object: a terminal step is an ordinary step -- terminal observation, goal
         // changes and respawns included, crowd_sim_var_num.py:430-458 -- and the caller resets explicitly)
-        if (c.human_num_range > 0 && (step_counter % (int)(5.0 / c.time_step + 0.5)) == 0) {
+        // the draws of an ordinary step: the crowd-size change and the goal changes every 5 s, and a human at its goal (the periodic updates
+        // may move goals, so on those steps the stream is fetched whatever the ballot says; on all others the ballot is the one
+        // post_obs_updates takes, on the same values).  The stream arrives while the observation is written.
+        bool draws = (c.human_num_range > 0 || (!SPLIT && !DEFER && c.random_goal_changing)) && (step_counter % period) == 0;
+        if (!SPLIT && !DEFER && c.end_goal_changing) draws = draws || __ballot(isH && norm2(h.gx - h.px, h.gy - h.py) < h.rad) != 0;
+        if (draws) rng_prefetch(R, s, e, lane);
+        if (c.human_num_range > 0 && (step_counter % period) == 0) {
             // crowd_sim_var_num.py:404-437 / crowd_sim_pred.py:165-190: every 5 s humans leave from the END of the list (only ones the
             // robot was not looking at) or new ones are appended, before the observation is generated
             rng_load(R, s, e, lane);
             if (rng_double(R, lane) < 0.5) {
-                const int oc = s.obs_cnt[e], om = s.obs_max[e];
+                const int oc = held(obs_cnt), om = held(obs_max);
                 int max_remove;
                 if (c.env_kind == CN_ENV_VARNUM) {
                     max_remove = n - (c.human_num - c.human_num_range);
@@ -482,7 +531,7 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
             write_obs(s, e, lane, n, false, rb, h, ob, step_counter);
             if constexpr (DEFER) {
                 // (a superset of the envs post_obs_updates does anything for: it evaluates `reached` after the periodic goal changes)
-                bool need = c.random_goal_changing && (step_counter % (int)(5.0 / c.time_step + 0.5)) == 0;
+                bool need = c.random_goal_changing && (step_counter % period) == 0;
                 if (c.end_goal_changing) need = need || __ballot(lane < n && norm2(h.gx - h.px, h.gy - h.py) < h.rad) != 0;
                 if (need && lane == 0) s.post_list[atomicAdd(s.post_cnt, 1)] = e;
             } else {

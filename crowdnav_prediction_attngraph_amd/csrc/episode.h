@@ -701,11 +701,12 @@ __device__ __forceinline__ void write_obs(const EnvDev &s, int e, int lane, int 
 
 // crowd_sim_var_num.py:303-363 reset (seed, robot, humans, potential, first observation)
 // the RNG-consuming part of reset(): seed, robot, humans (crowd_sim_var_num.py:333-340, :64-146)
-__device__ __forceinline__ void gen_episode_head(const EnvDev &s, Rng &R, int e, int lane, Robot &rb, int &n)
+// (case_counter: the caller's copy of s.case_counter[e])
+__device__ __forceinline__ void gen_episode_head(const EnvDev &s, Rng &R, int e, int lane, uint64_t case_counter, Robot &rb, int &n)
 {
     const cn_env_config &c = s.cfg;
     const uint64_t offset = c.phase == CN_PHASE_TRAIN ? 2000ull : (c.phase == CN_PHASE_VAL ? 0ull : 1000ull);
-    const uint64_t seed = offset + s.case_counter[e] + (uint64_t)(s.seed_base + e);
+    const uint64_t seed = offset + case_counter + (uint64_t)(s.seed_base + e);
     rng_seed(R, (uint32_t)seed, lane);
     double px, py, gx, gy;
     if (c.kinematics == CN_KIN_UNICYCLE) {
@@ -736,21 +737,21 @@ __device__ __forceinline__ void gen_episode_head(const EnvDev &s, Rng &R, int e,
     }
     rb.px = px; rb.py = py; rb.gx = gx; rb.gy = gy; rb.vx = 0.0; rb.vy = 0.0;
 }
-__device__ __forceinline__ void gen_episode(const EnvDev &s, Rng &R, int e, int lane, Robot &rb, Lane &h, double &shared_nd, int &n)
+__device__ __forceinline__ void gen_episode(const EnvDev &s, Rng &R, int e, int lane, uint64_t case_counter, Robot &rb, Lane &h, double &shared_nd, int &n)
 {
-    gen_episode_head(s, R, e, lane, rb, n);
+    gen_episode_head(s, R, e, lane, case_counter, rb, n);
     for (int i = 0; i < n; ++i) gen_human(s, R, lane, i, i, rb, h, shared_nd);
     rb.pot = -fabs(norm2(rb.gx - rb.px, rb.gy - rb.py));
 }
 
 // the rest of reset(): belief cleared (:108), case counter advanced (:348), episode statistics, first observation
-__device__ __forceinline__ void finish_reset(const EnvDev &s, int e, int lane, int n, Robot &rb, Lane &h, const cn_obs &ob, bool with_obs = true)
+__device__ __forceinline__ void finish_reset(const EnvDev &s, int e, int lane, int n, uint64_t case_counter, Robot &rb, Lane &h, const cn_obs &ob, bool with_obs = true)
 {
     const cn_env_config &c = s.cfg;
     h.l0 = h.l1 = h.l2 = h.l3 = h.l4 = 0.0;
     const uint64_t case_size = c.phase == CN_PHASE_TRAIN ? (4294967295ull - 2000ull) : (c.phase == CN_PHASE_VAL ? c.val_size : c.test_size);
     if (lane == 0) {
-        s.case_counter[e] = (s.case_counter[e] + (uint64_t)c.nenv) % case_size;
+        s.case_counter[e] = (case_counter + (uint64_t)c.nenv) % case_size;
         s.step_counter[e] = 0; s.ep_ret[e] = 0.0; s.ep_cnt[e] = 0;
         if (s.nh) { s.obs_cnt[e] = 0; s.obs_max[e] = -1; } // :327 observed_human_ids = []
         if (s.max_pid) s.max_pid[e] = n; // crowd_sim_var_num_collect.py:79-81
@@ -760,11 +761,16 @@ __device__ __forceinline__ void finish_reset(const EnvDev &s, int e, int lane, i
     if (with_obs) write_obs(s, e, lane, n, true, rb, h, ob, 0);
 }
 
-// crowd_sim_var_num.py:303-363 reset.  Uses the pre-generated episode when the side stream has one ready.
-__device__ __forceinline__ void do_reset(const EnvDev &s, Rng &R, int e, int lane, Robot &rb, Lane &h, double &shared_nd, int &n, const cn_obs &ob,
-                                         bool with_obs = true)
+// crowd_sim_var_num.py:303-363 reset.  Uses the pre-generated episode when the side stream has one ready (nx_ready and case_counter: the
+// caller's copies of s.nx_ready[e] and s.case_counter[e]).  The staged episode is read in ONE batch: its MT19937 state goes straight into
+// R.mt (whatever that held is dead) while the records are loaded into the registers of the episode that just ended.
+__device__ __forceinline__ void do_reset(const EnvDev &s, Rng &R, int e, int lane, bool nx_ready, uint64_t case_counter, Robot &rb, Lane &h,
+                                         double &shared_nd, int &n, const cn_obs &ob, bool with_obs = true)
 {
-    if (s.nx_ready[e]) {
+    if (nx_ready) {
+        rng_sync();
+        mt_dma(R.mt, s.nx_mt + (size_t)e * MT_N, lane);
+        const int pos = s.nx_mt_pos[e];
         n = s.nx_nh ? s.nx_nh[e] : s.H;
         const int H = s.H;
         const int lj = lane < H ? lane : 0;
@@ -775,16 +781,15 @@ __device__ __forceinline__ void do_reset(const EnvDev &s, Rng &R, int e, int lan
         const double *r = s.nx_rob + (size_t)e * 8;
         rb.px = r[R_PX]; rb.py = r[R_PY]; rb.vx = 0.0; rb.vy = 0.0; rb.gx = r[R_GX]; rb.gy = r[R_GY]; rb.theta = r[R_THETA]; rb.pot = r[R_POT];
         shared_nd = s.nx_shared_nd[e];
-        rng_sync();
-        for (int k = lane; k < MT_N; k += 64) R.mt[k] = s.nx_mt[(size_t)e * MT_N + k];
-        R.pos = s.nx_mt_pos[e];
+        mt_dma_wait();
+        R.pos = pos;
         R.loaded = true;
         rng_sync();
         if (lane == 0) s.nx_ready[e] = 0;
     } else {
-        gen_episode(s, R, e, lane, rb, h, shared_nd, n);
+        gen_episode(s, R, e, lane, case_counter, rb, h, shared_nd, n);
     }
-    finish_reset(s, e, lane, n, rb, h, ob, with_obs);
+    finish_reset(s, e, lane, n, case_counter, rb, h, ob, with_obs);
 }
 
 __device__ __forceinline__ void load_env(const EnvDev &s, int e, int lane, Robot &rb, Lane &h)
@@ -832,8 +837,9 @@ __device__ __forceinline__ void pregen_env(const EnvDev &s, int e, int lane, lon
     double shared_nd = s.shared_nd[e]; // overwritten by the first Human() when randomised, unused otherwise
     int n = H;
     if (prog == 0) {
-        gen_episode_head(s, R, e, lane, rb, n);
-        if (lane == 0) s.nx_case[e] = s.case_counter[e];
+        const uint64_t case_counter = s.case_counter[e];
+        gen_episode_head(s, R, e, lane, case_counter, rb, n);
+        if (lane == 0) s.nx_case[e] = case_counter;
         prog = 1;
     } else {
         const int lj = lane < H ? lane : 0;

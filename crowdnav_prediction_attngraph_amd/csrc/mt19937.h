@@ -17,6 +17,8 @@ struct Rng {
     int pos;
     bool loaded;
     uint32_t *mt = g_mt_lds;
+    bool pre_ok = false; // rng_prefetch: the state is on its way into mt, its position into pre_pos
+    int pre_pos = 0;
 };
 __device__ __forceinline__ void rng_sync()
 {
@@ -25,11 +27,37 @@ __device__ __forceinline__ void rng_sync()
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
 }
 
+// The 624 words of one stream, global -> LDS without passing through registers (global_load_lds_dword: lane l of chunk t lands at
+// dst[64 t + l], the stream's own order).  Nothing waits here: the copy runs beside whatever follows until mt_dma_wait().
+__device__ __forceinline__ void mt_dma(uint32_t *dst, const uint32_t *src, int lane)
+{
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    typedef __attribute__((address_space(1))) const uint32_t glb_u32;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the wavefront's earlier LDS traffic on dst has landed
+#pragma unroll
+    for (int t = 0; t < (MT_N + 63) / 64; ++t)
+        if (lane + 64 * t < MT_N) __builtin_amdgcn_global_load_lds((glb_u32 *)(src + lane + 64 * t), (lds_u32 *)(dst + 64 * t), 4, 0, 0);
+}
+__device__ __forceinline__ void mt_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// a wavefront that knows it will draw fetches its stream early; the rng_load at the first draw then only waits for it
+__device__ __forceinline__ void rng_prefetch(Rng &R, const EnvDev &s, int e, int lane)
+{
+    if (R.loaded || R.pre_ok) return;
+    mt_dma(R.mt, s.mt + (size_t)e * MT_N, lane);
+    R.pre_pos = s.mt_pos[e];
+    R.pre_ok = true;
+}
 __device__ __forceinline__ void rng_load(Rng &R, const EnvDev &s, int e, int lane)
 {
     if (R.loaded) return;
-    for (int k = lane; k < MT_N; k += 64) R.mt[k] = s.mt[(size_t)e * MT_N + k];
-    R.pos = s.mt_pos[e];
+    if (R.pre_ok) {
+        mt_dma_wait();
+        R.pos = held(R.pre_pos);
+    } else {
+        for (int k = lane; k < MT_N; k += 64) R.mt[k] = s.mt[(size_t)e * MT_N + k];
+        R.pos = s.mt_pos[e];
+    }
     R.loaded = true;
     rng_sync();
 }

@@ -254,8 +254,11 @@ __global__ __launch_bounds__(256) void orca_lp3_kernel(EnvDev s)
     for (int p = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6)); p < pairs; p += gridDim.x * 4) {
         const bool act = 2 * p + half < total;
         const int k = act ? 2 * p + half : 2 * p; // (an odd list: the upper half of the last wavefront idles on a copy of the lower one's data)
+        // (header and line in one round trip: all 32 line slots of a listed agent are allocated, the ones past nn hold stale lines)
         const Lp3Hdr hd = s.lp3_hdr[k];
-        const float4 ln = hl < hd.nn ? s.lp3_lines[(size_t)k * 32 + hl] : make_float4(0.0f, 0.0f, 1.0f, 0.0f);
+        float4 raw = s.lp3_lines[(size_t)k * 32 + hl];
+        raw.x = held(raw.x); raw.y = held(raw.y); raw.z = held(raw.z); raw.w = held(raw.w); // (or the load sinks behind the test of nn again)
+        const float4 ln = hl < hd.nn ? raw : make_float4(0.0f, 0.0f, 1.0f, 0.0f);
         LpLine L;
         L.px = ln.x; L.py = ln.y; L.dx = ln.z; L.dy = ln.w;
         float rx = hd.rx, ry = hd.ry;
@@ -468,15 +471,37 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
     // (the kernel for NB slots serves crowds of more than NB' agents, NB' the next smaller network: at most 63 / (NB' - 1) + 2 envs per wavefront)
     constexpr int NENV = NB == 8 ? 65 : (NB == 20 ? 10 : 5);
     __shared__ double s_px[128], s_py[128], s_vx[128], s_vy[128], s_rad[128], s_rob[NENV][4];
+    // this lane's own words go out in the same batch as the staging loads, not behind the barrier and behind each other: its goal and
+    // preferred speed, and its private simulator -- read whether it is still valid or not (a rebuild below overwrites what was read)
+    const double *hum = s.hum + (size_t)e * 8 * H;
+    const size_t ei = (size_t)e * H + i;
+    double sgx, sgy, svpref, shared_nd_in;
+    int sim_valid_in, sim_n_in = 0;
+    float sim_nd_in, sim_r_in, sim_ms_in;
     {
         const int a0 = blk * 64;
         const int e0 = a0 / H, e1 = (min(a0 + 63, s.E * H - 1)) / H;
-        const int nrows = (e1 - e0 + 1) * H; // <= 63 + 2 H <= 127 (H <= 32)
-        for (int r = threadIdx.x; r < nrows; r += 64) {
-            const int ee = e0 + r / H, j = r - (r / H) * H;
-            const double *hm = s.hum + (size_t)ee * 8 * H;
-            s_px[r] = hm[F_PX * H + j]; s_py[r] = hm[F_PY * H + j]; s_vx[r] = hm[F_VX * H + j]; s_vy[r] = hm[F_VY * H + j];
-            s_rad[r] = hm[F_RAD * H + j];
+        const int nrows = (e1 - e0 + 1) * H; // <= 63 + 2 H <= 127 (H <= 32): two rows per lane at most
+        double st[2][5];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int r = threadIdx.x + 64 * it;
+            if (r < nrows) {
+                const int ee = e0 + r / H, j = r - (r / H) * H;
+                const double *hm = s.hum + (size_t)ee * 8 * H;
+                st[it][0] = hm[F_PX * H + j]; st[it][1] = hm[F_PY * H + j]; st[it][2] = hm[F_VX * H + j]; st[it][3] = hm[F_VY * H + j];
+                st[it][4] = hm[F_RAD * H + j];
+            }
+        }
+        sgx = hum[F_GX * H + i]; sgy = hum[F_GY * H + i]; svpref = hum[F_VPREF * H + i];
+        sim_valid_in = s.sim_valid[ei];
+        if (s.sim_n) sim_n_in = s.sim_n[ei];
+        sim_nd_in = s.sim_nd[ei]; sim_r_in = s.sim_self_radius[ei]; sim_ms_in = s.sim_self_maxspeed[ei];
+        shared_nd_in = s.shared_nd[e];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {
+            const int r = threadIdx.x + 64 * it;
+            if (r < nrows) { s_px[r] = st[it][0]; s_py[r] = st[it][1]; s_vx[r] = st[it][2]; s_vy[r] = st[it][3]; s_rad[r] = st[it][4]; }
         }
         if (c.robot_visible)
             for (int q = threadIdx.x; q <= e1 - e0; q += 64) {
@@ -486,19 +511,16 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
         __syncthreads();
     }
     const int eq = e - (blk * 64) / H, eb = eq * H; // this lane's env inside the staged block
-    const double *hum = s.hum + (size_t)e * 8 * H;
     const double spx = s_px[eb + i], spy = s_py[eb + i], svx = s_vx[eb + i], svy = s_vy[eb + i], srad = s_rad[eb + i];
-    const double sgx = hum[F_GX * H + i], sgy = hum[F_GY * H + i], svpref = hum[F_VPREF * H + i];
     const double safety = c.orca_safety_space;
     const bool rv = c.robot_visible != 0;
     const int n_agents = n + (rv ? 1 : 0);
-    const size_t ei = (size_t)e * H + i;
     // lazily (re)build human i's private simulator: orca.py:80-89
     float nd = 0.0f, self_r = 0.0f, self_ms = 0.0f;
     if (active) {
-        const bool rebuild = !s.sim_valid[ei] || (s.sim_n && s.sim_n[ei] != n_agents);
+        const bool rebuild = !sim_valid_in || (s.sim_n && sim_n_in != n_agents);
         if (rebuild) {
-            nd = (float)s.shared_nd[e];
+            nd = (float)shared_nd_in;
             self_r = (float)(srad + 0.01 + safety);
             self_ms = (float)svpref;
             if (s.sim_seen)
@@ -506,7 +528,7 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
             s.sim_nd[ei] = nd; s.sim_self_radius[ei] = self_r; s.sim_self_maxspeed[ei] = self_ms; s.sim_valid[ei] = 1;
             if (s.sim_n) s.sim_n[ei] = (uint8_t)n_agents;
         } else {
-            nd = s.sim_nd[ei]; self_r = s.sim_self_radius[ei]; self_ms = s.sim_self_maxspeed[ei];
+            nd = sim_nd_in; self_r = sim_r_in; self_ms = sim_ms_in;
         }
     }
     const float fpx = (float)spx, fpy = (float)spy, fvx = (float)svx, fvy = (float)svy;

@@ -127,6 +127,14 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
     float *R0 = smem + O_R0, *R1 = smem + O_R1, *R2 = smem + O_R2, *R3 = smem + O_R3, *R4 = smem + O_R4, *R5 = smem + O_R5;
     // ---- robot_linear.0: relu(W [256,9] . [temporal_edges(2) | robot_node(7)] + b); thread = feature; h_in -> LDS ----
     const int w4 = wave & 3, hi = wave >> 2; // two groups of four wavefronts run independent products side by side
+    // the row offsets of this wavefront's two envs (written by the human-human kernel in front of this one: the plan's offsets or its own
+    // scan) are final when the kernel starts: their round trip runs beside the first stage instead of in front of the attention's row fetch
+    int r0q[2], r1q[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const int e = e0 + 2 * wave + q < E ? e0 + 2 * wave + q : E - 1;
+        r0q[q] = a.row_off[e]; r1q[q] = a.row_off[e + 1];
+    }
     {
         const int n = tid & 255; // feature; the two thread halves split the envs
         float w[9];
@@ -150,6 +158,8 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
             R4[i * S128 + c] = a.hxs_in[(size_t)e * 128 + c];
         }
     }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) { r0q[q] = held_uniform(r0q[q]); r1q[q] = held_uniform(r1q[q]); } // (arrived with the first stage's loads: scalar from here)
     __syncthreads();
     // ---- z = [u (256) | relu(enc) (64)] = te_w [320,256] . robot_states + te_b ;  gh = W_hh [384,128] . h_in (unmasked, no bias) ----
     if (hi == 0) { // (five feature blocks do not fit 128 registers: three and two)
@@ -166,15 +176,10 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
     // so the first 8 rows of BOTH envs are fetched up front into registers; envs with more rows walk the rest in chunks of 8.
     {
         constexpr int CH = 8;
-        int r0q[2], ndq[2];
+        int ndq[2];
         float x[2][CH][4];
-        const int *row_off = a.row_off; // written by the human-human kernel in front of this one: the plan's offsets or its own scan
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = 2 * wave + q;
-            const int e = e0 + i < E ? e0 + i : E - 1;
-            r0q[q] = row_off[e]; ndq[q] = row_off[e + 1] - r0q[q];
-        }
+        for (int q = 0; q < 2; ++q) ndq[q] = r1q[q] - r0q[q];
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
