@@ -143,7 +143,7 @@ ABI_SYMBOLS = [
     "cn_split_bf16", "cn_split_bf16_padded", "cn_linear_fwd", "cn_linear_fwd_act", "cn_linear_wgrad_splits", "cn_linear_wgrad", "cn_small_mm", "cn_gst_create", "cn_gst_destroy", "cn_gst_set_weights", "cn_gst_predict",
     "cn_gst_wrapper_reset", "cn_gst_wrapper_step", "cn_gst_wrapper_set_interval", "cn_gst_wrapper_history_len", "cn_gst_wrapper_save", "cn_gst_wrapper_load", "cn_gae", "cn_adv_stats", "cn_adv_normalize", "cn_episode_stats_update", "cn_eval_state_words", "cn_eval_accumulate",
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
-    "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
+    "cn_ppo_minibatch_max_rows", "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
     "cn_env_get_visibility", "cn_render_scenes",
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
@@ -275,6 +275,8 @@ def lib():
         L.cn_gst_data_count.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gst_data_fill.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gst_gather_batch.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_ppo_minibatch_max_rows.restype = C.c_int64
+        L.cn_ppo_minibatch_max_rows.argtypes = []
         L.cn_ppo_minibatch_workspace_bytes.restype = C.c_int64
         L.cn_ppo_minibatch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
         L.cn_ppo_row_totals.argtypes = [i32, i32, i32, vp, vp, vp]

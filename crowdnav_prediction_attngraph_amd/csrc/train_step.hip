@@ -330,11 +330,20 @@ int layer_dw(int M, int N, int K, const float *dy, const float *gate, const floa
     return cn_linear_wgrad(M, N, K, dy, N, gate, inp, K, splits, reinterpret_cast<float *>(base + L.part), reinterpret_cast<float *>(base + L.dbp), dW, db, (void *)st);
 }
 
+// Rows one call may take.  The per-row buffers of the human-human block are [rows, <= 1536] fp32 matrices; the widest, qkv / d_qkv, is the A
+// operand of the bf16x3 product dX = d_qkv Wc (layer_dx), whose kernel addresses A by 32-bit ELEMENT offsets row * 1536 + column
+// (gemm3p.h: `ao`, and the launcher's M * lda < 2^31).  Every other index of the step is either 64-bit, relative to a tile / split, or of a
+// narrower matrix with <= rows rows (T * N <= rows), so rows * 1536 < 2^31 is the one bound -- whatever T * N * H, the padded size, is.
+// The workspace query, the step and the host-side query below all read this constant.
+constexpr int64_t TR_MAX_ROWS = ((1LL << 31) - 1) / 1536; // 1 398 101
+
 } // namespace
+
+extern "C" int64_t cn_ppo_minibatch_max_rows(void) { return TR_MAX_ROWS; }
 
 extern "C" int64_t cn_ppo_minibatch_workspace_bytes(int T, int N, int H, int D, int64_t rows)
 {
-    if (T < 1 || N < 1 || H < 1 || H > 48 || D < 1 || D > 16 || rows < 0) return 0;
+    if (T < 1 || N < 1 || H < 1 || H > 48 || D < 1 || D > 16 || rows < 0 || rows > TR_MAX_ROWS) return 0;
     return (int64_t)carve(T, N, H, D, rows).total;
 }
 
@@ -359,7 +368,8 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
                b.returns && b.old_logp && b.adv, "cn_ppo_minibatch_step: null storage tensor");
     const int64_t Bs = (int64_t)b.T * b.N;
     CN_REQUIRE(rows >= Bs && rows <= Bs * b.H, "cn_ppo_minibatch_step: rows=%lld outside [B, B * H] = [%lld, %lld]", (long long)rows, (long long)Bs, (long long)(Bs * b.H));
-    CN_REQUIRE(Bs * b.H < (1LL << 31) / 1536, "cn_ppo_minibatch_step: minibatch too large for 32-bit element offsets");
+    CN_REQUIRE(rows <= TR_MAX_ROWS, "cn_ppo_minibatch_step: rows=%lld above cn_ppo_minibatch_max_rows() = %lld (32-bit element offsets into [rows, 1536])",
+               (long long)rows, (long long)TR_MAX_ROWS);
     {
         const void *const *pp = reinterpret_cast<const void *const *>(P), *const *gp = reinterpret_cast<const void *const *>(G);
         for (size_t i = 0; i < sizeof(cn_policy_weights) / sizeof(void *); ++i)

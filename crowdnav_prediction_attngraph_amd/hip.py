@@ -1104,6 +1104,19 @@ class MinibatchStepper:
         self.policy = policy
         self._ws = None
         self._ptrs = None
+        # Parameters the call does not write: only the ones the loss never reaches (the reference leaves their .grad None).  Their slices of
+        # the flat bucket still enter the all-reduce, the clip norm and Adam, so the caller keeps them zero (ppo.PPO._update_fast); any
+        # OTHER parameter outside cn_policy_weights would silently train on a stale gradient, hence the refusal here.
+        covered = {k for _, k in A.POLICY_WEIGHT_KEYS}
+        self.uncovered = [name for name, p in policy.named_parameters() if p.requires_grad and name not in covered]
+        stray = [name for name in self.uncovered if not name.startswith("base.human_node_final_linear.")]
+        if stray:
+            raise A.CnError("MinibatchStepper: cn_ppo_minibatch_step writes no gradient for %s" % ", ".join(stray))
+
+    @staticmethod
+    def max_rows():
+        """The most compacted rows one call takes (cn_ppo_minibatch_max_rows: host-only, the bound the C call itself enforces)."""
+        return int(A.lib().cn_ppo_minibatch_max_rows())
 
     @staticmethod
     def supported(policy, rollouts):

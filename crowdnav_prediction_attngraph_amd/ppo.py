@@ -154,20 +154,52 @@ class PPO():
             return False
         return hip.MinibatchStepper.supported(self.actor_critic, rollouts)
 
-    def _update_fast(self, rollouts, advantages, d):
-        flat = self._flat
+    def _fast_plan(self, rollouts):
+        """(stepper, per-env row totals) when every minibatch this update() can draw fits one cn_ppo_minibatch_step, else None: the update then
+        takes the autograd-joined path.  Decided on the host from the one readback update() makes anyway, before the first permutation is
+        drawn and before any launch of the step: the npb envs with the most rows together bound every minibatch of every epoch."""
         if getattr(self, "_stepper", None) is None or self._stepper.policy is not self.actor_critic:
             self._stepper = hip.MinibatchStepper(self.actor_critic)
-        stepper = self._stepper
+        E = rollouts.rewards.shape[1]
+        assert E >= self.num_mini_batch, (
+            "PPO requires the number of processes ({}) to be greater than or equal to the number of PPO mini batches ({}).".format(E, self.num_mini_batch))
+        totals = self._stepper.row_totals(rollouts)              # the ONE readback of update(): rows per env -> rows per minibatch on the host
+        cap = self._stepper.max_rows()
+        if int(totals.sum()) > cap and int(torch.sort(totals, descending=True).values[:E // self.num_mini_batch].sum()) > cap:
+            return None
+        return self._stepper, totals
+
+    def _unwritten_spans(self, stepper):
+        """[start, end) ranges of the flat bucket that belong to parameters cn_ppo_minibatch_step does not write (adjacent ones merged: the two
+        tensors of human_node_final_linear are one range).  Cached with the bucket: _bind_flat makes a new one when anything moved."""
+        flat = self._flat
+        if flat.get("unwritten") is None or flat["unwritten"][0] is not stepper:
+            off, spans = 0, []
+            for name, p in self.actor_critic.named_parameters():
+                if not p.requires_grad:
+                    continue
+                end = off + (p.numel() + 3) // 4 * 4
+                if name in stepper.uncovered:
+                    if spans and spans[-1][1] == off:
+                        spans[-1][1] = end
+                    else:
+                        spans.append([off, end])
+                off = end
+            flat["unwritten"] = (stepper, spans)
+        return flat["unwritten"][1]
+
+    def _update_fast(self, rollouts, advantages, d, stepper, totals):
+        flat = self._flat
         for p, (_, gv, _, _) in zip(self._params(), flat["views"]):     # the bucket views must still be the gradients (checked once per update())
             if p.grad is not gv and (p.grad is None or p.grad.data_ptr() != gv.data_ptr()):
                 p.grad = gv
+        # The slices the step never writes still enter the all-reduce, the clip norm and Adam: exact zeros once per update(), like the
+        # bucket-wide zero_() of the autograd-joined path, whatever was left there before.
+        for a, b in self._unwritten_spans(stepper):
+            flat["g"][a:b].zero_()
         E = rollouts.rewards.shape[1]
         dev = rollouts.rewards.device
-        assert E >= self.num_mini_batch, (
-            "PPO requires the number of processes ({}) to be greater than or equal to the number of PPO mini batches ({}).".format(E, self.num_mini_batch))
         npb = E // self.num_mini_batch
-        totals = stepper.row_totals(rollouts)                    # the ONE readback of update(): rows per env -> rows per minibatch on the host
         starts = list(range(0, E, npb))
         losses = torch.zeros(self.ppo_epoch * len(starts), 3, device=dev)
         hyper = (self.clip_param, self.value_loss_coef, self.entropy_coef, self.use_clipped_value_loss)
@@ -217,7 +249,9 @@ class PPO():
         ar_events = []
         self.last_allreduce_ms = None
         if on_gpu and self._fast_path(rollouts):
-            return self._update_fast(rollouts, advantages, d)
+            plan = self._fast_plan(rollouts)
+            if plan is not None:
+                return self._update_fast(rollouts, advantages, d, *plan)
         for e in range(self.ppo_epoch):
             if not self.actor_critic.is_recurrent:
                 raise NotImplementedError("feed-forward policies are out of scope")

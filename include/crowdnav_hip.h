@@ -704,7 +704,11 @@ typedef struct {
     float clip_param, value_loss_coef, entropy_coef;
     int use_clipped_value_loss;
 } cn_ppo_hyper;
-int64_t cn_ppo_minibatch_workspace_bytes(int T, int N, int H, int D, int64_t rows);
+/* The most rows one call takes (host-only, no device needed): rows * 1536 < 2^31, the 32-bit element offsets into the [rows, 1536] q|k|v
+ * gradient -- a bound on the LIVE rows, not on T * N * H.  Past it cn_ppo_minibatch_workspace_bytes returns 0 and cn_ppo_minibatch_step fails
+ * with CN_ERR_INVALID before any launch; the caller takes another route for that minibatch. */
+int64_t cn_ppo_minibatch_max_rows(void);
+int64_t cn_ppo_minibatch_workspace_bytes(int T, int N, int H, int D, int64_t rows); /* 0 = shape outside the box above, or rows past the bound */
 /* totals [E] int32 (device) = sum_t clamp(detected_human_num[t, e], 1, H) over t < T: the compacted rows env e contributes to a minibatch */
 int cn_ppo_row_totals(int T, int E, int H, const float *detected_human_num, int32_t *totals, void *stream);
 int cn_ppo_minibatch_step(const cn_ppo_batch *batch, int64_t rows, const cn_policy_weights *params, const cn_policy_weights *grads,

@@ -44,6 +44,22 @@ def test_struct_layouts_match_the_header():
     assert (A.PROF_KERNELS, A.PROF_SLOT_WORDS) == (int(re.search(r"CN_PROF_KERNELS = (\d+)", hdr).group(1)), int(re.search(r"CN_PROF_SLOT_WORDS = (\d+)", hdr).group(1)))
 
 
+def test_minibatch_row_bound_is_one_host_side_number():
+    """cn_ppo_minibatch_max_rows() needs no device and is the bound cn_ppo_minibatch_workspace_bytes applies: rows * 1536 < 2^31 (32-bit element
+    offsets into the [rows, 1536] q|k|v gradient), on the live rows whatever T * N * H is.  (The C call's refusal on both sides of it:
+    tests/test_gpu_minibatch_edges.py.)"""
+    lib = A.lib()
+    top = lib.cn_ppo_minibatch_max_rows()
+    assert top * 1536 < 2 ** 31 <= (top + 1) * 1536
+    T, N, H, D = 30, 2048, 48, 2                                   # T * N * H = 2.9 M: the padded size is past the bound, the rows decide
+    assert T * N * H > top
+    assert lib.cn_ppo_minibatch_workspace_bytes(T, N, H, D, T * N) > 0
+    assert lib.cn_ppo_minibatch_workspace_bytes(T, N, H, D, top) > 0
+    assert lib.cn_ppo_minibatch_workspace_bytes(T, N, H, D, top + 1) == 0
+    from crowdnav_prediction_attngraph_amd import hip
+    assert hip.MinibatchStepper.max_rows() == top
+
+
 def test_no_cpu_fallback_without_gpu():
     import torch
     if torch.cuda.is_available():

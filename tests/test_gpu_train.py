@@ -163,14 +163,30 @@ def test_hip_attention_forward_backward_matches_torch_autograd(mode):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("H,B", [(20, 96), (64, 48), (5, 120)])   # the fp64 reference is a Python loop over samples: keep B small
+@pytest.mark.parametrize("H,B", [(20, 96), (64, 48), (5, 120),   # the fp64 reference is a Python loop over samples: keep B small
+                                  (1, 10), (33, 40), (48, 40)])     # a softmax over one element; the first and the widest training H of the 64-wide class
 def test_hh_attention_size_classes_match_fp64_autograd(H, B):
     """cn_hh_attention_fwd/bwd through their size-class lists (<= 8 / 16 / 32 / 64 live humans, one launch per class walking only
-    its own units) vs an fp64 torch graph of softmax(scale q k^T) v per (sample, head): every class is populated."""
+    its own units) vs an fp64 torch graph of softmax(scale q k^T) v per (sample, head): every class H admits is populated."""
+    _check_hh_attention(H, B, None)
+
+
+@pytest.mark.gpu
+def test_hh_attention_with_three_empty_class_lists_matches_fp64_autograd():
+    """The same at H = 20 with every count <= 8: the lists of the 16-, 32- and 64-wide classes are empty, their launches find no unit."""
+    _check_hh_attention(20, 24, 8)
+
+
+def _check_hh_attention(H, B, cap):
+    """cap = None: counts 1..H with 1, 8, 9, H planted; cap = c: counts 1..c with 1 and c planted."""
     from crowdnav_prediction_attngraph_amd import hip
     g = torch.Generator().manual_seed(H * 1000 + B)
-    nd = torch.randint(1, H + 1, (B,), generator=g)
-    nd[:4] = torch.tensor([1, min(H, 8), min(H, 9), H])
+    nd = torch.randint(1, (cap or H) + 1, (B,), generator=g)
+    if cap is None:
+        nd[:4] = torch.tensor([1, min(H, 8), min(H, 9), H])
+    else:
+        nd[:2] = torch.tensor([1, cap])
+    assert int(nd.max()) == (cap or H)
     row_off = torch.zeros(B + 1, dtype=torch.int32)
     row_off[1:] = torch.cumsum(nd, 0)
     R = int(row_off[-1])
@@ -287,13 +303,14 @@ def test_linear_act_epilogues_match_fp64(M, N, K, act, relu_from, pad_to):
 
 
 @pytest.mark.gpu
-def test_hr_attention_forward_backward_matches_dense_torch():
+@pytest.mark.parametrize("B,H", [(5, 1), (37, 20), (19, 33), (11, 48), (7, 64)])
+def test_hr_attention_forward_backward_matches_dense_torch(B, H):
     """cn_hr_attention_fwd/bwd on compacted rows, in the u = Ws^T t form, vs the reference's dense masked formulation
     (att_func, selfAttn_srnn_temp_node.py:145-177: t . (Ws o + bs) * H/8, masked_fill(-1e9), softmax, bmm) under torch
-    autograd in fp64: same output and same gradients for t, Ws and o (bs gets zero: the softmax cannot see it)."""
+    autograd in fp64: same output and same gradients for t, Ws and o (bs gets zero: the softmax cannot see it).  H = 1 (a softmax over one
+    element), 20, and 33 / 48 / 64: more than one 32-row pass per sample."""
     from crowdnav_prediction_attngraph_amd import hip
     g = torch.Generator().manual_seed(11)
-    B, H = 37, 20
     nd = torch.randint(1, H + 1, (B,), generator=g)
     nd[0], nd[1] = 1, H
     row_off = torch.cat([torch.zeros(1, dtype=torch.int64), nd.cumsum(0)]).to(torch.int32)
@@ -320,6 +337,46 @@ def test_hr_attention_forward_backward_matches_dense_torch():
     for got, want, what in ((hr.detach(), ref.detach(), "hr"), (tg.grad, tr.grad, "d_t"), (wg.grad, wr.grad, "d_Ws"), (og.grad, orr.grad, "d_o")):
         err = float((got.cpu().double() - want).abs().max())
         assert err <= 2e-5 * max(float(want.abs().max()), 1.0), (what, err)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [1, 2, 5, 12, 16])
+@pytest.mark.parametrize("R", [1, 7, 4097])
+def test_embed0_forward_and_gradients_match_fp64(R, D):
+    """cn_embed0_fwd / cn_embed0_bwd behind hip.Embed0 (the D -> 128 input layer of the human-human block, 1 <= D <= 16) against
+    relu(x W^T + b) in fp64: the output, dW and db within 2e-5 of the largest reference magnitude (the bar of the GRU and robot-human attention
+    tests; fp32 products and sums).  R = 1 and 7: fewer rows than a block walks per trip; 4097: one more row than the 4096 partial blocks of the
+    backward.  Some rows carry the simulator's padding value 15.0 in every column, as the rows past the detected count do."""
+    from crowdnav_prediction_attngraph_amd import hip
+    g = torch.Generator().manual_seed(100 * R + D)
+    x = 3.0 * torch.randn(R, D, generator=g)
+    x[torch.rand(R, generator=g) < 0.2] = 15.0
+    x[R // 2] = 15.0
+    w = torch.randn(128, D, generator=g) / D ** 0.5
+    b = torch.randn(128, generator=g) * 0.5
+    dy = torch.randn(R, 128, generator=g)
+    wg, bg = w.cuda().requires_grad_(), b.cuda().requires_grad_()
+    y = hip.Embed0.apply(x.cuda(), wg, bg)
+    y.backward(dy.cuda())
+    torch.cuda.synchronize()
+    wr, br = w.double().requires_grad_(), b.double().requires_grad_()
+    pre = torch.nn.functional.linear(x.double(), wr, br)
+    # the ReLU's gradient is discontinuous: the reference takes the kernel's own active set, which may differ from the fp64 one only where the
+    # pre-activation is at rounding level (tests/test_gpu_train.py::test_hip_linear_forward_and_gradients_match_fp64 does the same)
+    act = y.detach().cpu() > 0
+    bar_y = 2e-5 * max(float(pre.detach().clamp(min=0).abs().max()), 1.0)
+    flipped = pre.detach()[act != (pre.detach() > 0)].abs()
+    assert flipped.numel() == 0 or float(flipped.max()) <= bar_y
+    yr = pre * act.double()
+    yr.backward(dy.double())
+    for got, want, what in ((y.detach(), pre.detach().clamp(min=0), "y"), (wg.grad, wr.grad, "dW"), (bg.grad, br.grad, "db")):
+        assert got.shape == want.shape, what
+        err = float((got.cpu().double() - want).abs().max())
+        assert err <= 2e-5 * max(float(want.abs().max()), 1.0), (what, err, float(want.abs().max()))
+    wg2, bg2 = w.cuda().requires_grad_(), b.cuda().requires_grad_()     # fixed summation order: a second run gives identical bits
+    y2 = hip.Embed0.apply(x.cuda(), wg2, bg2)
+    y2.backward(dy.cuda())
+    assert torch.equal(y, y2) and torch.equal(wg.grad, wg2.grad) and torch.equal(bg.grad, bg2.grad)
 
 
 @pytest.mark.gpu
