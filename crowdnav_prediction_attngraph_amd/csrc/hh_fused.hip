@@ -135,7 +135,9 @@ __device__ long long *g_hh_tim = nullptr; // [block][16] phase cycle sums of wav
 struct TileCtx {
     int e_lo, n_env, r0, nrows; // envs [e_lo, e_lo + n_env), first compacted row, rows (e_lo / r0: contiguous tiles only)
     int my_env, my_start;       // lane l <-> row l of the tile: env index inside the tile (-1 beyond nrows), its first row
-    int my_src, my_out;         // ... its row of the [E*H, D] input and its compacted output row (two-team kernel: tiles need not be contiguous)
+    int my_src;                 // ... its row of the [E*H, D] input (two-team kernel: tiles need not be contiguous)
+    int out0, it;               // two-team kernel: lane k <-> env k of the tile: its first output row (contiguous tiles; it = 0) or its item
+                                // of the plan, whose output row tile_body requests behind the e0 loads; the lane's own output row follows there
     int tile_ord;
 };
 
@@ -622,28 +624,25 @@ __device__ __forceinline__ TileCtx next_tile(const int *row_off, int e, int e_en
     for (int k = 0; k < n_env; ++k) cnt += lane >= __builtin_amdgcn_readlane(st, k) ? 1 : 0;
     t.my_env = lane < t.nrows ? cnt - 1 : -1;
     t.my_start = __shfl(st, cnt - 1 >= 0 ? cnt - 1 : 0, 64);
-    t.my_src = 0; t.my_out = t.r0 + lane; // my_src: set by the caller that needs it (it knows H)
+    t.my_src = 0; // set by the caller that needs it (it knows H)
+    t.out0 = t.r0 + (lane < n_env ? st : 0); t.it = 0;
     return t;
 }
 
-// A tile of the row plan (row_plan.h): the envs listed for it, in the order listed.  The two loads (item k of the list on lane k, then the
-// first output row of that env) are issued a tile ahead (PlanPre) -- two memory round trips that would otherwise open every tile.
-struct PlanPre { int it, out0; };
-__device__ __forceinline__ PlanPre plan_prefetch(const int32_t *plan, int E, int tile, int lane)
-{
-    PlanPre p;
-    p.it = (plan + rp_off_items(E))[(size_t)tile * 64 + lane];
-    p.out0 = (plan + rp_off_rowoff())[p.it & 0xffff]; // slots behind the end of the list hold stale items: any 16-bit index stays inside the plan
-    return p;
-}
-__device__ __forceinline__ TileCtx plan_tile(const PlanPre &pre, int H, int tile_ord, int lane)
+// A tile of the row plan (row_plan.h): the envs listed for it, in the order listed.  Two dependent loads (item k of the list on lane k, then
+// the first output row of that env), and neither is waited for where it is issued: the items of tile n + 1 and the output rows of tile
+// n are requested inside tile n behind its e0 loads (tile_body; loads return in order, so whatever is requested IN FRONT of the e0
+// batch is waited for with it), and looked at when the X product is through.
+// (tile_body's plan_next: the word offset of the item list of the workgroup's next tile inside the plan, PLAN_LAST when the tile in hand is
+// its last one, PLAN_NONE when there is no plan.  An offset, not a pointer: a pointer pair is carried across the tile in VGPRs and spilled.)
+constexpr int PLAN_NONE = -2, PLAN_LAST = -1;
+__device__ __forceinline__ TileCtx plan_tile(int item, int H, int tile_ord, int lane)
 {
     TileCtx t;
-    const unsigned long long zero = __ballot((pre.it >> 16) == 0); // the list ends at its first zero item
+    const unsigned long long zero = __ballot((item >> 16) == 0); // the list ends at its first zero item
     const int cnt = zero ? __ffsll((long long)zero) - 1 : 64;
-    const int it = lane < cnt ? pre.it : 0;
+    const int it = lane < cnt ? item : 0;
     const int rows = it >> 16, id = it & 0xffff;
-    const int out0 = pre.out0;
     int incl = rows;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(incl, o, 64); if (lane >= o) incl += y; }
@@ -657,7 +656,7 @@ __device__ __forceinline__ TileCtx plan_tile(const PlanPre &pre, int H, int tile
     t.my_start = __shfl(st, me, 64);
     const int off = lane - t.my_start;
     t.my_src = __shfl(id, me, 64) * H + off;
-    t.my_out = __shfl(out0, me, 64) + off;
+    t.out0 = 0; t.it = item;
     return t;
 }
 
@@ -806,7 +805,7 @@ __device__ __forceinline__ void finish_turn(char *lds, int ctr_off, int lane)
 
 // out_sp rows of feature blocks 4*wave + J0, 4*wave + J0 + 1: own partial sum + the other team's (from LDS) + bias, ReLU, streamed to HBM
 template <int NRB, int J0, int RB>
-__device__ __forceinline__ void finish_rows(const TileCtx &t, const f32x4 (&acc)[4][NRB], const char *xch, const HhFusedWeights &W,
+__device__ __forceinline__ void finish_rows(const TileCtx &t, int my_out, const f32x4 (&acc)[4][NRB], const char *xch, const HhFusedWeights &W,
                                             float *__restrict__ out_sp, int lane, int wave, const f32x4 *bpre = nullptr)
 {
     const int i = lane & 15, g = lane >> 4, loff = lane * 16;
@@ -818,7 +817,7 @@ __device__ __forceinline__ void finish_rows(const TileCtx &t, const f32x4 (&acc)
         for (int rb = 0; rb < NRB; ++rb) {
             const f32x4 other = *reinterpret_cast<const f32x4 *>(xch + ((wave * 2 + jj) * RB + rb) * 1024 + loff);
             const int row = rb * 16 + i;
-            const int orow = __shfl(t.my_out, row, 64); // every lane takes part in the shuffle: rows 0..63 = lanes 0..63
+            const int orow = __shfl(my_out, row, 64); // every lane takes part in the shuffle: rows 0..63 = lanes 0..63
             if (row < t.nrows) {
                 f32x4 v = acc[J0 + jj][rb] + other + b;
 #pragma unroll
@@ -837,7 +836,7 @@ constexpr int PF = 2;
 
 template <int NRB, bool TRAIN>
 __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const float *__restrict__ se, const HhFusedWeights &W, const WeightBuf &WB,
-                                          float *__restrict__ out_sp, char *lds, int lane_in, int wave, int tm)
+                                          float *__restrict__ out_sp, char *lds, int lane_in, int wave, int tm, const int32_t *__restrict__ plan, int plan_next, int &it_next)
 {
     // Everything derived from the lane index is recomputed per tile: visible as loop invariant, the compiler hoists a few dozen
     // per-lane addresses out of the tile loop and keeps them alive (spilled) across the whole kernel.
@@ -866,13 +865,67 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
     // when it gets here, and nobody touches them before the second __syncthreads below)
     if (w8 == 0 && lane < 4) *reinterpret_cast<unsigned *>(lds + LDS_CTR + 4 * lane) = 0u;
     unsigned bar_target = 0;
-    // The embedding_layer.2 weights of this wavefront (4 k-steps x 8 fragments, 32 KB) are requested before anything else: in the
-    // X phase below all eight wavefronts are in the same phase, nothing hides its 256 KB weight stream (6 k cycles at the L2 rate,
-    // the longest item of the tile prologue) -- here it runs under the latency-bound e0 phase.
+    // ---------------- e0: relu(x W0^T + b0) for feature k-step `wave` (natural k order); team tm takes the row blocks of its parity ----------------
+    // The inputs were written a moment ago by another launch on other XCDs: a load of them is a trip to the fabric, and a wait between
+    // two of them is a trip more.  So everything the first (up to) four input features need -- the rows' x, the 8 x 4 weights of the
+    // lane's feature group, the bias -- is requested in ONE batch, IN FRONT of the embedding_layer.2 stream below (loads return in
+    // order: behind that stream the batch would wait for its 32 KB too), and waited for once; wider inputs go on in chunks of four
+    // features (32 weight registers), one wait each, an odd width ends on a single feature.  Per output element the products are still added onto the bias in the order
+    // d = 0, 1, ..., D - 1.
+    constexpr int NRR = (NRB + 1) / 2; // row blocks of a team (the last one may lie behind the tile: it repeats the last row and stores nothing)
+    const int c0 = 32 * wave + 8 * g;
+    const float *xp[NRR];
+    float v[NRR][8];
+    float xv[NRR][4], wv[8][4], bv0[8];
+    auto e0_load = [&](const int d0, const int q0, const int q1) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = q0; q < q1; ++q) {
+#pragma unroll
+            for (int rr = 0; rr < NRR; ++rr) xv[rr][q] = xp[rr][d0 + q];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) wv[u][q] = W.emb0_w[(c0 + u) * D + d0 + q];
+        }
+    };
+    auto e0_fma = [&](const int q0, const int q1) __attribute__((always_inline)) {
+#pragma unroll
+        for (int q = q0; q < q1; ++q)
+#pragma unroll
+            for (int rr = 0; rr < NRR; ++rr)
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[rr][u] += xv[rr][q] * wv[u][q];
+    };
+#pragma unroll
+    for (int rr = 0; rr < NRR; ++rr) {
+        int row = (2 * rr + tm) * 16 + i;
+        row = row < t.nrows ? row : t.nrows - 1; // padded rows repeat the last live row: finite values, masked later
+        // my_src < E * H: the row of an env of a verified plan (hh_fused_kernel) or of the workgroup's own chunk
+        xp[rr] = se + (size_t)__shfl(t.my_src, row, 64) * D;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+#pragma unroll
+        for (int rr = 0; rr < NRR; ++rr) xv[rr][q] = 0.0f;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) wv[u][q] = 0.0f;
+    }
+    {   // (the widths of the envs are even: pairs.  D = 1 requests feature 0 twice -- no branch among the loads -- and uses it once)
+        const int q1 = D >= 2 ? 1 : 0;
+#pragma unroll
+        for (int rr = 0; rr < NRR; ++rr) { xv[rr][0] = xp[rr][0]; xv[rr][1] = xp[rr][q1]; }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) { wv[u][0] = W.emb0_w[(c0 + u) * D]; wv[u][1] = W.emb0_w[(c0 + u) * D + q1]; }
+    }
+    if (D >= 4) e0_load(0, 2, 4);
+#pragma unroll
+    for (int u = 0; u < 8; ++u) bv0[u] = W.emb0_b[c0 + u];
+    __builtin_amdgcn_sched_barrier(0);
+    // The embedding_layer.2 weights of this wavefront (4 k-steps x 8 fragments, 32 KB) come next: in the X phase below all eight
+    // wavefronts are in the same phase, nothing hides its 256 KB weight stream (6 k cycles at the L2 rate, the longest item of the
+    // tile prologue) -- here it runs under the latency-bound e0 phase.
     bf16x8 wq[4][8]; // [k-step][j*2 + plane]
     {
-        const int wv = w8 >> 1, half = w8 & 1; // position in the baked image: [wave 4][ks 4][j 8 = half 2 x 4][plane 2]
-        const unsigned wp = WB.emb2 + (unsigned)wv * 4 * 16 * 1024;
+        const int wv_ = w8 >> 1, half = w8 & 1; // position in the baked image: [wave 4][ks 4][j 8 = half 2 x 4][plane 2]
+        const unsigned wp = WB.emb2 + (unsigned)wv_ * 4 * 16 * 1024;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
@@ -881,30 +934,51 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 wq[ks][2 * j + 1] = ldb(WB, wp + ((ks * 8 + half * 4 + j) * 2 + 1) * 1024, uoff);
             }
     }
-    // ---------------- e0: relu(x W0^T + b0) for feature k-step `wave` (natural k order); team tm takes the row blocks of its parity ----------------
+    // Behind them, the two loads of the plan that nobody waits for before the X product is through: the first output row of this tile's
+    // envs and the item list of the workgroup's next tile.  (Without a plan both read one word of the input instead: no branch among
+    // the loads, whose join would cost a wait.)
+    int out0_ld, it_ld;
+    const int pnext = TRAIN ? PLAN_NONE : __builtin_amdgcn_readfirstlane(plan_next);
+    const bool has_plan = pnext != PLAN_NONE, has_next = pnext >= 0;
     {
-        const int c0 = 32 * wave + 8 * g;
+        const int32_t *dummy = reinterpret_cast<const int32_t *>(se);
+        // slots behind the end of the list hold stale items: any 16-bit index stays inside the plan (8 + 65 535 < rp_words(E) for every E)
+        out0_ld = *(has_plan ? plan + rp_off_rowoff() + (t.it & 0xffff) : dummy);
+        it_ld = *(has_next ? plan + pnext + lane : dummy);
+    }
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int rr = 0; rr < (NRB + 1) / 2; ++rr) {
+    for (int rr = 0; rr < NRR; ++rr)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) xv[rr][q] = held(xv[rr][q]); // (the products, and the register moves that pair them up, stay behind the loads above)
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        bv0[u] = held(bv0[u]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wv[u][q] = held(wv[u][q]);
+    }
+    {
+#pragma unroll
+        for (int rr = 0; rr < NRR; ++rr)
+#pragma unroll
+            for (int u = 0; u < 8; ++u) v[rr][u] = bv0[u];
+        e0_fma(0, 1);
+        if (D >= 2) e0_fma(1, 2);
+        if (D >= 4) e0_fma(2, 4);
+        int d0 = 4;
+        for (; d0 + 4 <= D; d0 += 4) { e0_load(d0, 0, 4); e0_fma(0, 4); }
+        if (d0 + 2 <= D) { e0_load(d0, 0, 2); e0_fma(0, 2); }
+        if ((D & 1) && D > 1) { e0_load(D - 1, 0, 1); e0_fma(0, 1); } // an odd width ends on a single feature, in a trip of its own
+#pragma unroll
+        for (int rr = 0; rr < NRR; ++rr) {
             const int rb = 2 * rr + tm;
             if (rb < NRB) {
-                int row = rb * 16 + i;
-                row = row < t.nrows ? row : t.nrows - 1; // padded rows repeat the last live row: finite values, masked later
-                const float *xp = se + (size_t)__shfl(t.my_src, row, 64) * D;
-                float v[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = W.emb0_b[c0 + u];
-                for (int d = 0; d < D; ++d) {
-                    const float xd = xp[d];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] += xd * W.emb0_w[(c0 + u) * D + d];
-                }
                 bf16x8 hi, lo;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) { v[u] = fmaxf(v[u], 0.0f); __bf16 h, l; split1(v[u], h, l); hi[u] = h; lo[u] = l; }
+                for (int u = 0; u < 8; ++u) { v[rr][u] = fmaxf(v[rr][u], 0.0f); __bf16 h, l; split1(v[rr][u], h, l); hi[u] = h; lo[u] = l; }
                 if (TRAIN) {
-                    st4(o_e0, (rb * 16 + i) * 128 + c0, f32x4{v[0], v[1], v[2], v[3]});
-                    st4(o_e0, (rb * 16 + i) * 128 + c0 + 4, f32x4{v[4], v[5], v[6], v[7]});
+                    st4(o_e0, (rb * 16 + i) * 128 + c0, f32x4{v[rr][0], v[rr][1], v[rr][2], v[rr][3]});
+                    st4(o_e0, (rb * 16 + i) * 128 + c0 + 4, f32x4{v[rr][4], v[rr][5], v[rr][6], v[rr][7]});
                 }
                 *reinterpret_cast<bf16x8 *>(lds + LDS_S + (wave * RB + rb) * 1024 + loff) = hi;
                 *reinterpret_cast<bf16x8 *>(lds + LDS_S + E0_PLANE + (wave * RB + rb) * 1024 + loff) = lo;
@@ -913,6 +987,7 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
     }
     __syncthreads();
     HH_T(0);
+    int my_out; // the tile's output rows
     // ---------------- X = relu(e0 W2^T + b2): wavefront w8 of the 8 produces feature blocks 4*w8..4*w8+3 (X k-steps 2*w8, 2*w8+1) ----------------
     {
         f32x4 acc[4][NRB];
@@ -944,6 +1019,10 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 for (int rb = 0; rb < NRB; ++rb) acc[j][rb] = mfma(w[2 * j], xh[rb], acc[j][rb]);
             __builtin_amdgcn_sched_barrier(0);
         }
+        // (the embedding_layer.2 stream is through, and with it the two loads of the plan behind it)
+        out0_ld = held(out0_ld); it_ld = held(it_ld);
+        it_next = has_next ? it_ld : 0;
+        my_out = __shfl(has_plan ? out0_ld : t.out0, t.my_env >= 0 ? t.my_env : 0, 64) + (lane - t.my_start);
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
             const int fb0 = 4 * w8 + 2 * p;
@@ -1292,8 +1371,8 @@ __device__ __forceinline__ void tile_body(const TileCtx &t, int H, int D, const 
                 for (int rb = 0; rb < NRB; ++rb) *reinterpret_cast<f32x4 *>(xch + XCH_TEAM + ((wave * 2 + jj) * RB + rb) * 1024 + loff) = acc_os[jj][rb];
         }
         __syncthreads();
-        if (tm == 0) finish_rows<NRB, 0, RB>(t, acc_os, xch + XCH_TEAM, W, out_sp, lane, wave, bfin);
-        else finish_rows<NRB, 2, RB>(t, acc_os, xch, W, out_sp, lane, wave, bfin);
+        if (tm == 0) finish_rows<NRB, 0, RB>(t, my_out, acc_os, xch + XCH_TEAM, W, out_sp, lane, wave, bfin);
+        else finish_rows<NRB, 2, RB>(t, my_out, acc_os, xch, W, out_sp, lane, wave, bfin);
     }
     HH_T(12);
 #ifdef HH_TIMING
@@ -1320,78 +1399,131 @@ __global__ __launch_bounds__(512, 2) void hh_fused_kernel(int E, int H, int D, c
 #ifdef HH_TIMING
     const long long k_c0 = clock64(), k_r0 = wall_clock64(); // shader-clock cycles and the constant 100 MHz counter: their ratio is the clock
 #endif
-    // a row plan made with the observation (row_plan.h) replaces the row-offset scan and the contiguous tile splitter below
-    bool planned = !TRAIN && det && rp_usable(plan, E, H) && plan[1] == (int)gridDim.x;
-    if (planned) {
+    const int tid = (int)threadIdx.x, lane = tid & 63, w8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wave = w8 & 3, tm = w8 >> 2;
+    // A row plan made with the observation (row_plan.h) replaces the row-offset scan and the contiguous tile splitter below.  It was written
+    // a moment ago by another launch on other XCDs, and so was detected_human_num: every dependent load of them is a trip to the fabric
+    // in front of the first MFMA of all 256 workgroups.  So everything whose address follows from the kernel arguments, blockIdx and the
+    // lane goes out in ONE batch in front of the first wait -- the 8-word header (one scalar load), the item list of the first tile,
+    // this thread's share of the verification (below) and of the plan -> row_off copy -- and only the output rows of the first tile's
+    // envs and its input rows (tile_body) make a second trip.
+    // The batch is issued before anything is known about the buffer's contents (the tests fill it with 0xFF, and with plans of other
+    // observations), so its addresses must not depend on them: the builder completes no plan beyond RP_EMAX envs or RP_HMAX rows per
+    // env, and inside that box every index below is at most rp_off_items(RP_EMAX) + 255 * 64 + 63 = 21 515 words (the grid has at most
+    // 256 workgroups, rp_workgroups), inside the rp_words(E') >= 66 568 words of a plan buffer for ANY batch size E'.
+    bool planned = false;
+    int n_plan = 0;
+    int it_cur = 0; // the item list of the workgroup's tile in hand: item k on lane k
+    if (!TRAIN && det && plan && E >= 1 && E <= RP_EMAX && H <= RP_HMAX) {
+        struct alignas(16) Hdr { int32_t w[RP_HDR]; };
+        const int32_t *pro = plan + rp_off_rowoff();
+        const Hdr hdr = *reinterpret_cast<const Hdr *>(plan);
+        it_cur = (plan + rp_off_items(E))[(size_t)blockIdx.x * 64 + lane];
         // ... and it must be the plan of THIS observation: a caller that stepped / reset the batch in between, or changed
         // detected_human_num (the worst-case leg of bench.py), still holds a complete plan of the right shape.  Every workgroup
-        // compares every env's row count in the plan with clamp(det) -- 3 coalesced loads per env, 8 envs per thread at 4096 envs --
-        // and all of them come to the same verdict; a stale plan means the scan path below, exactly as without a plan.
-        const int32_t *pro = plan + rp_off_rowoff();
-        int bad = 0;
-        for (int i = (int)threadIdx.x; i < E; i += (int)blockDim.x) {
-            int nd = (int)det[i]; nd = nd < 1 ? 1 : (nd > H ? H : nd);
-            bad |= (pro[i + 1] - pro[i]) ^ nd;
+        // compares every env's row count in the plan with clamp(det) -- 3 coalesced loads per env, at most VU = 8 envs per thread, all
+        // in flight together (indices behind the batch repeat env E - 1; E <= RP_EMAX leaves no remainder) -- and all of them come to
+        // the same verdict; a stale plan means the scan path below, exactly as without a plan.
+        constexpr int VU = RP_EMAX / 512;
+        float dv[VU];
+        int pa[VU], pb[VU];
+#pragma unroll
+        for (int k = 0; k < VU; ++k) { // (no test of E in here: a branch between the loads costs a wait at its join)
+            const int i = tid + 512 * k, ic = i < E ? i : E - 1;
+            dv[k] = det[ic]; pa[k] = pro[ic]; pb[k] = pro[ic + 1];
         }
-        // (the verdict is combined through the dynamic LDS: __syncthreads_or would add a static __shared__ word, and this kernel's
-        // dynamic allocation is the whole 160 KB -- the launch attribute is refused when static + dynamic exceed it)
-        volatile int *flag = reinterpret_cast<volatile int *>(lds);
-        if (threadIdx.x == 0) *flag = 0;
-        __syncthreads();
-        if (__ballot(bad != 0) != 0ull && (threadIdx.x & 63) == 0) *flag = 1;
-        __syncthreads();
-        planned = __builtin_amdgcn_readfirstlane(*flag) == 0;
-        __syncthreads(); // everybody has read the verdict before the LDS is reused
+        const int ci = (int)blockIdx.x * 512 + tid; // the caller's row_off array gets the plan's offsets: one word per thread, see below
+        int cpy = pro[ci <= E ? ci : 0];
+        // ---- the one wait of the prologue (held: left alone, the compiler sinks the verification loads behind the test of the header) ----
+#pragma unroll
+        for (int k = 0; k < VU; ++k) { dv[k] = held(dv[k]); pa[k] = held(pa[k]); pb[k] = held(pb[k]); }
+        cpy = held(cpy); it_cur = held(it_cur);
+        const bool shaped = hdr.w[0] == RP_MAGIC && hdr.w[4] == E && hdr.w[5] == H && hdr.w[1] == (int)gridDim.x;
+        if (shaped) {
+            int bad = 0;
+#pragma unroll
+            for (int k = 0; k < VU; ++k) {
+                int nd = (int)dv[k]; nd = nd < 1 ? 1 : (nd > H ? H : nd);
+                bad |= (pb[k] - pa[k]) ^ nd;
+            }
+            // The verdict is combined through the dynamic LDS (__syncthreads_or would add a static __shared__ word, and this kernel's
+            // dynamic allocation is the whole 160 KB -- the launch attribute is refused when static + dynamic exceed it): every
+            // wavefront writes its own word, one barrier, everybody reads the eight.  The words lie in the X region, which a planned
+            // launch writes next behind the first __syncthreads() of its first tile; the scan path reuses them at once and puts a
+            // barrier in front (below).
+            team::lds_u32 *vw = (team::lds_u32 *)lds;
+            const unsigned wbad = __ballot(bad != 0) != 0ull ? 1u : 0u; // (every lane active)
+            if (lane == 0) vw[w8] = wbad;
+            __syncthreads();
+            unsigned any = 0;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) any |= vw[k];
+            planned = __builtin_amdgcn_readfirstlane(any) == 0;
+            if (!planned) __syncthreads(); // everybody has read the verdict before row_offsets_prologue reuses the LDS
+        }
+        if (planned) {
+            n_plan = hdr.w[2];
+            // Nobody inside this launch waits for these: the caller's row_off array (what the kernels behind this one and the debug taps
+            // index by), the live-row count of the stamps and of the profiled launches.  Their loads travelled with the batch above;
+            // the stores leave here, fire and forget.  (The grid covers E + 1 words in one pass for every E it is sized for; the loop is for
+            // a grid that is not.)
+            if (ci <= E) row_off[ci] = cpy;
+            for (int i = ci + (int)gridDim.x * 512; i <= E; i += (int)gridDim.x * 512) row_off[i] = pro[i];
+            if (blockIdx.x == 0 && tid == 0) {
+                if (stamp) stamp[1] = (unsigned long long)hdr.w[3];
+                if (live_total) atomicAdd(live_total, (unsigned long long)hdr.w[3]);
+            }
+            // (the second trip -- the input rows of the first tile, the output rows of its envs -- starts in tile_body)
+        }
     }
     if (det && !planned) row_offsets_prologue<512>(E, H, det, row_off, live_total, lds);
-    if (!TRAIN && stamp && blockIdx.x == 0 && threadIdx.x == 0) stamp[1] = (unsigned long long)(planned ? plan[3] : row_off[E]);
+    if (!TRAIN && !planned && stamp && blockIdx.x == 0 && tid == 0) stamp[1] = (unsigned long long)row_off[E];
 #ifdef HH_TIMING
     const long long k_c1 = clock64();
 #endif
     __builtin_amdgcn_s_setprio(1); // above the simulator's side-stream wavefronts; the attention chains go to 3 (tile_body)
-    const int lane = threadIdx.x & 63, w8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wave = w8 & 3, tm = w8 >> 2;
     // tiles of this workgroup: the plan's tiles c, c + NW, ... -- or, without a plan, the chunk of consecutive envs [boundary(c), boundary(c + 1))
     // cut by next_tile
-    int e = 0, e_end = 0, chunk_end_row = 0, n_plan = 0;
-    PlanPre pre{0, 0};
-    if (planned) {
-        if (live_total && blockIdx.x == 0 && threadIdx.x == 0) *live_total += (unsigned long long)plan[3];
-        n_plan = plan[2];
-        pre = plan_prefetch(plan, E, (int)blockIdx.x, lane);
-        // the caller's row_off array gets the plan's offsets (it is what the kernels behind this one and the debug taps index by)
-        for (int i = (int)(blockIdx.x * blockDim.x + threadIdx.x); i <= E; i += (int)(gridDim.x * blockDim.x)) row_off[i] = plan[rp_off_rowoff() + i];
-    } else {
+    int e = 0, e_end = 0, chunk_end_row = 0;
+    if (!planned) {
         const int total = ld_ro(row_off + E);
         e = chunk_boundary(row_off, E, total, (int)blockIdx.x, (int)gridDim.x, lane);
         e_end = chunk_boundary(row_off, E, total, (int)blockIdx.x + 1, (int)gridDim.x, lane);
         if (e >= e_end) return;
-        chunk_end_row = ld_ro(row_off + e_end);
+        chunk_end_row = __builtin_amdgcn_readfirstlane(ld_ro(row_off + e_end));
     }
     int tile_ord = 0;
     const team::WeightBuf WB = team::make_weight_buf(W);
     for (;;) {
         TileCtx t;
+        int it_next = 0;
+        int plan_next = PLAN_NONE;
+        int ln = lane; // (what follows from the lane index is recomputed per tile, as in tile_body: hoisted, it is spilled)
+        asm volatile("" : "+v"(ln));
         if (planned) {
             if (tile_ord >= n_plan) break;
-            const PlanPre cur = pre;
             ++tile_ord;
-            if (tile_ord < n_plan) pre = plan_prefetch(plan, E, (int)blockIdx.x + tile_ord * (int)gridDim.x, lane);
-            t = plan_tile(cur, H, tile_ord - 1, lane);
-            if (t.nrows == 0) continue; // fewer envs than tiles
+            // the items of the next tile: an index of the verified plan (tile < n_plan * NW <= RP_TMAX)
+            plan_next = tile_ord < n_plan ? rp_off_items(E) + ((int)blockIdx.x + tile_ord * (int)gridDim.x) * 64 : PLAN_LAST;
+            t = plan_tile(it_cur, H, tile_ord - 1, ln);
+            if (t.nrows == 0) { // fewer envs than tiles
+                it_cur = plan_next >= 0 ? plan[plan_next + ln] : 0;
+                continue;
+            }
         } else {
             if (e >= e_end) break;
-            t = next_tile<team::FR>(row_off, e, e_end, chunk_end_row, tile_ord++, lane);
-            t.my_src = (t.e_lo + t.my_env) * H + (lane - t.my_start);
+            t = next_tile<team::FR>(row_off, e, e_end, chunk_end_row, tile_ord++, ln);
+            t.my_src = (t.e_lo + t.my_env) * H + (ln - t.my_start);
             e += t.n_env;
         }
         const int nrb = (t.nrows + 15) >> 4;
         switch (nrb) {
-        case 1: team::tile_body<1, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
-        case 2: team::tile_body<2, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
-        case 3: team::tile_body<3, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
-        default: team::tile_body<4, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm); break;
+        case 1: team::tile_body<1, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm, plan, plan_next, it_next); break;
+        case 2: team::tile_body<2, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm, plan, plan_next, it_next); break;
+        case 3: team::tile_body<3, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm, plan, plan_next, it_next); break;
+        default: team::tile_body<4, TRAIN>(t, H, D, se, W, WB, out_sp, lds, lane, wave, tm, plan, plan_next, it_next); break;
         }
+        it_cur = it_next;
     }
 #ifdef HH_TIMING
     if (g_hh_tim && (threadIdx.x & 255) == 0) { // whole-kernel span of wavefront 0 of each team: [13] cycles, [14] 10 ns ticks, [15] prologue cycles
