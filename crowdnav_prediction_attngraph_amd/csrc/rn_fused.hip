@@ -13,6 +13,11 @@
 // Products run "transposed" (A operand = weight fragment, B operand = activations): the C layout then holds 4 consecutive output
 // features of one env per lane, which is a float4 store into the next layer's [env][feature] LDS image; the B operand of the
 // next product is two float4 reads of that image (k = 32 ks + 8*(lane>>4) + 0..7), split to bf16 hi / lo once per stage.
+//
+// The kernel is a latency chain, so what it waits for is counted (profiles/HISTORY.md section 14): one batch of loads at kernel entry brings
+// every small operand (observation, hidden state, masks, noise, biases, head weights) into registers and a 12 KB LDS table; behind it a
+// wavefront waits for weight fragments and out_sp rows only, and no stage call is longer than 8 k-steps (32 in sequence on the longest path:
+// te 8, edge 8, W_ih 4, ac0 4, a2 / c2 8).  Two instantiations: with the four test taps and without.
 #include "rn_fused.h"
 #include "row_plan.h"
 
@@ -30,7 +35,16 @@ constexpr int O_R2 = O_R1 + TE * S512;      // 384: gh
 constexpr int O_R3 = O_R2 + TE * S384;      // 384: gi
 constexpr int O_R4 = O_R3 + TE * S384;      // 128: h_in
 constexpr int O_R5 = O_R4 + TE * S128;      // 128: h_new
-constexpr int LDS_FLOATS = O_R5 + TE * S128;
+// the table: every small operand of the chain (biases, head weights, the 16 envs' masks and noise), fetched in the ONE batch at kernel entry
+constexpr int O_T = O_R5 + TE * S128;
+constexpr int T_TEB = 0, T_EDGEB = T_TEB + 320, T_BIH = T_EDGEB + 64, T_BHH = T_BIH + 384, T_AC0B = T_BHH + 384, T_A2B = T_AC0B + 512;
+constexpr int T_C2B = T_A2B + 256, T_CLW = T_C2B + 256, T_FMW = T_CLW + 256;
+constexpr int T_VEC4 = (T_FMW + 512) / 4;   // 736 float4
+constexpr int T_SM = T_FMW + 512;           // 64 words: masks (16) | eps (32) | cl_b | fm_b (2) | logstd (2)
+constexpr int SM_MASK = 0, SM_EPS = 16, SM_CLB = 48, SM_FMB = 49, SM_LS = 51, SM_WORDS = 53;
+constexpr int T_FLOATS = T_SM + 64;         // 3008 floats, 12 032 B
+constexpr int LDS_FLOATS = O_T + T_FLOATS;  // 144 640 B of the 160 KB: one workgroup per CU, as before
+static_assert(LDS_FLOATS * sizeof(float) <= 160 * 1024, "rn_fused: LDS");
 
 __device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
@@ -44,10 +58,11 @@ __device__ __forceinline__ float fast_tanh(float x)
 }
 __device__ __forceinline__ float fast_sigmoid(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }
 
-// out[env][out_off + 16*fb + ..] = act(W[fb] . in[env][in_off ..] + bias) for the feature blocks fb = fb0 + wave, fb0 + wave + 4, ...
-// Wfrag: baked fragments [fb][K/32][plane hi,lo][64 lanes][8 bf16]; NFB = feature blocks of this wavefront
-template <int K, int NFB, int ACT>
-__device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_first, int fb_step, const float *__restrict__ bias, const float *in, int in_stride,
+// out[env][out_off + 16*fb + ..] = act(W[fb] . in[env][in_off ..] + bias) for the feature blocks fb = fb_first, fb_first + fb_step, ...
+// Wfrag: baked fragments [fb][K/32][plane hi,lo][64 lanes][8 bf16]; NFB = feature blocks of this wavefront; bias: the LDS copy (table, below),
+// only looked at with BIAS: a run-time test of the pointer put every block's bias load into a basic block of its own
+template <int K, int NFB, int ACT, bool BIAS>
+__device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_first, int fb_step, const float *bias, const float *in, int in_stride,
                                       float *out, int out_stride, int out_off, int relu_from, int lane)
 {
     const bf16x8 *__restrict__ Wfrag = reinterpret_cast<const bf16x8 *>(Wfrag_);
@@ -101,7 +116,7 @@ __device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_f
     for (int j = 0; j < NFB; ++j) {
         const int f0 = (fb_first + j * fb_step) * 16 + 4 * g;
         f32x4 v = acc[j];
-        if (bias) v += *reinterpret_cast<const f32x4 *>(bias + f0);
+        if (BIAS) v += *reinterpret_cast<const f32x4 *>(bias + f0);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             if (ACT == A_RELU) { if (f0 + q >= relu_from) v[q] = fmaxf(v[q], 0.0f); }
@@ -111,12 +126,20 @@ __device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_f
     }
 }
 
-// The chain runs in 128 registers per lane (activations split per k-step, two k-steps of weight fragments in flight, the wide stages in chunks
-// of <= 3 feature blocks, nothing held across the barriers).  On its own that is a few us slower than the 255-register form it replaced in
+// The chain runs in 128 registers per lane (activations split per k-step, two k-steps of weight fragments in flight, at most four feature blocks
+// per call, nothing held across the barriers).  On its own that is a few us slower than the 255-register form it replaced in
 // round 6 (see git history); but a workgroup then takes HALF of its CU's registers, and the ORCA tail's wavefronts (orca_lp3_kernel on the
 // simulator's side stream: 32 registers, no LDS, 37 us of VALU work for the whole chip) run on the same CUs beside this latency chain instead
 // of making it wait for CUs of its own: hh_fused -> rn_fused gap 17.7 -> 9.9 us, step 0.2806 -> 0.2705 ms at 4096 envs x 20 humans (same box),
 // configs[4] 2.07 -> 2.05 ms beside the cooperative ORCA kernel.
+//
+// Loads.  Apart from the weight fragments and the out_sp rows, everything the chain reads -- the 16 envs' observation, hidden state, masks and
+// noise, robot_linear's weights, every bias, the head's weights, the row offsets -- has an address that follows from the arguments, blockIdx and
+// the lane.  It all leaves in ONE batch in front of the first wait (indices clamped, never guarded: a branch among the loads costs a wait at
+// its join) and is read from LDS (the table) or from pinned registers afterwards; the chain behind it waits for weight fragments and out_sp
+// rows only.  TAPS is a template parameter for the same reason: the tap stores sit behind the arithmetic of their phase, with no test of a
+// pointer between two loads.
+template <bool TAPS>
 __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedArgs a)
 {
     const CnStampScope stamp_scope(a.stamp);
@@ -124,50 +147,118 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
     __builtin_amdgcn_s_setprio(3); // critical path of the step: win the issue arbitration against the side stream's simulator wavefronts
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int e0 = blockIdx.x * TE;
-    float *R0 = smem + O_R0, *R1 = smem + O_R1, *R2 = smem + O_R2, *R3 = smem + O_R3, *R4 = smem + O_R4, *R5 = smem + O_R5;
-    // ---- robot_linear.0: relu(W [256,9] . [temporal_edges(2) | robot_node(7)] + b); thread = feature; h_in -> LDS ----
+    float *R0 = smem + O_R0, *R1 = smem + O_R1, *R2 = smem + O_R2, *R3 = smem + O_R3, *R4 = smem + O_R4, *R5 = smem + O_R5, *T = smem + O_T;
     const int w4 = wave & 3, hi = wave >> 2; // two groups of four wavefronts run independent products side by side
-    // the row offsets of this wavefront's two envs (written by the human-human kernel in front of this one: the plan's offsets or its own
-    // scan) are final when the kernel starts: their round trip runs beside the first stage instead of in front of the attention's row fetch
+    // ---- the batch ----
+    // the row offsets of this wavefront's two envs (written by the human-human kernel in front of this one: the plan's offsets or its own scan)
     int r0q[2], r1q[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int e = e0 + 2 * wave + q < E ? e0 + 2 * wave + q : E - 1;
         r0q[q] = a.row_off[e]; r1q[q] = a.row_off[e + 1];
     }
+    // robot_linear.0 (thread = feature n, the two thread halves split the envs): its weights, and the observation of the half's 8 envs spread
+    // over the lanes: lane l < 16 temporal word l, lane l < 56 robot_node word l (env l / 7).  The tail workgroup repeats env E - 1.
+    const int n = tid & 255;
+    float w[9];
+#pragma unroll
+    for (int d = 0; d < 9; ++d) w[d] = a.rl_w[n * 9 + d];
+    float bn = a.rl_b[n];
+    float obs_t, obs_r;
     {
-        const int n = tid & 255; // feature; the two thread halves split the envs
-        float w[9];
+        const int lt = lane < 16 ? lane : 15, lr = lane < 56 ? lane : 55;
+        const int it = e0 + 8 * hi + (lt >> 1), ir = e0 + 8 * hi + lr / 7;
+        obs_t = a.temporal[(size_t)(it < E ? it : E - 1) * 2 + (lt & 1)];
+        obs_r = a.robot_node[(size_t)(ir < E ? ir : E - 1) * 7 + lr % 7];
+    }
+    // h_in: 4 words per thread
+    float hx[4];
 #pragma unroll
-        for (int d = 0; d < 9; ++d) w[d] = a.rl_w[n * 9 + d];
-        const float bn = a.rl_b[n];
-        for (int i = (tid >> 8) * (TE / 2); i < (tid >> 8) * (TE / 2) + TE / 2; ++i) {
-            const int e = e0 + i < E ? e0 + i : E - 1; // the tail workgroup repeats the last env (results discarded)
-            float acc = bn;
-            acc += a.temporal[e * 2] * w[0];
-            acc += a.temporal[e * 2 + 1] * w[1];
+    for (int k = 0; k < 4; ++k) {
+        const int i = (tid >> 7) + 4 * k;
+        hx[k] = a.hxs_in[(size_t)(e0 + i < E ? e0 + i : E - 1) * 128 + (tid & 127)];
+    }
+    // the table's vectors: the table is the concatenation of nine arrays, 736 float4, two per thread.  Array and offset are selected per lane
+    // from local copies of the pointers: ?: over locals compiles to selects, over the argument's members to a tree of branches
+    f32x4 tv[2];
+    {
+        const float *const p_teb = a.te_b, *const p_edgeb = a.edge_b, *const p_bih = a.bih, *const p_bhh = a.bhh, *const p_ac0b = a.ac0_b;
+        const float *const p_a2b = a.a2_b, *const p_c2b = a.c2_b, *const p_clw = a.cl_w, *const p_fmw = a.fm_w;
 #pragma unroll
-            for (int d = 0; d < 7; ++d) acc += a.robot_node[e * 7 + d] * w[2 + d];
-            acc = fmaxf(acc, 0.0f);
-            R0[i * S512 + n] = acc;
-            if (a.tap_robot && e0 + i < E) a.tap_robot[(size_t)(e0 + i) * 256 + n] = acc;
-        }
-        for (int idx = tid; idx < TE * 128; idx += 512) {
-            const int i = idx >> 7, c = idx & 127;
-            const int e = e0 + i < E ? e0 + i : E - 1;
-            R4[i * S128 + c] = a.hxs_in[(size_t)e * 128 + c];
+        for (int r = 0; r < 2; ++r) {
+            const int j = 512 * r + tid < T_VEC4 ? 512 * r + tid : T_VEC4 - 1, f = 4 * j;
+            const float *src = p_teb; int first = T_TEB;
+            src = f >= T_EDGEB ? p_edgeb : src; first = f >= T_EDGEB ? T_EDGEB : first;
+            src = f >= T_BIH ? p_bih : src; first = f >= T_BIH ? T_BIH : first;
+            src = f >= T_BHH ? p_bhh : src; first = f >= T_BHH ? T_BHH : first;
+            src = f >= T_AC0B ? p_ac0b : src; first = f >= T_AC0B ? T_AC0B : first;
+            src = f >= T_A2B ? p_a2b : src; first = f >= T_A2B ? T_A2B : first;
+            src = f >= T_C2B ? p_c2b : src; first = f >= T_C2B ? T_C2B : first;
+            src = f >= T_CLW ? p_clw : src; first = f >= T_CLW ? T_CLW : first;
+            src = f >= T_FMW ? p_fmw : src; first = f >= T_FMW ? T_FMW : first;
+            tv[r] = *reinterpret_cast<const f32x4 *>(src + (f - first));
         }
     }
+    // the small words: one per lane (without eps its lanes re-read the mask)
+    float smw;
+    {
+        const float *const p_masks = a.masks, *const p_eps = a.eps, *const p_clb = a.cl_b, *const p_fmb = a.fm_b, *const p_ls = a.logstd;
+        const bool has_eps = p_eps != nullptr;
+        const int sl = lane < SM_WORDS ? lane : SM_WORDS - 1;
+        const int i = sl < SM_EPS ? sl : (sl - SM_EPS) >> 1;
+        const int e = e0 + i < E ? e0 + i : E - 1;
+        const bool is_eps = sl >= SM_EPS && has_eps;
+        const float *src = is_eps ? p_eps : p_masks; int off = is_eps ? 2 * e + (sl & 1) : e; // (lanes >= SM_CLB: i = 16 .. 18, clamped like any env)
+        src = sl >= SM_CLB ? p_clb : src; off = sl >= SM_CLB ? 0 : off;
+        src = sl >= SM_FMB ? p_fmb : src; off = sl >= SM_FMB ? sl - SM_FMB : off;
+        src = sl >= SM_LS ? p_ls : src; off = sl >= SM_LS ? sl - SM_LS : off;
+        smw = src[off];
+    }
+    // ---- the one wait ----
 #pragma unroll
-    for (int q = 0; q < 2; ++q) { r0q[q] = held_uniform(r0q[q]); r1q[q] = held_uniform(r1q[q]); } // (arrived with the first stage's loads: scalar from here)
+    for (int d = 0; d < 9; ++d) w[d] = held(w[d]);
+    bn = held(bn); obs_t = held(obs_t); obs_r = held(obs_r); smw = held(smw);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) hx[k] = held(hx[k]);
+#pragma unroll
+    for (int r = 0; r < 2; ++r) tv[r] = held(tv[r]);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) { r0q[q] = held_uniform(r0q[q]); r1q[q] = held_uniform(r1q[q]); } // scalar from here
+    *reinterpret_cast<f32x4 *>(T + 4 * tid) = tv[0];
+    if (512 + tid < T_VEC4) *reinterpret_cast<f32x4 *>(T + 4 * (512 + tid)) = tv[1];
+    if (wave == 0) T[T_SM + lane] = smw;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) R4[((tid >> 7) + 4 * k) * S128 + (tid & 127)] = hx[k];
+    // ---- robot_linear.0: relu(W [256,9] . [temporal_edges(2) | robot_node(7)] + b) ----
+    {
+        float rs[TE / 2];
+#pragma unroll
+        for (int ii = 0; ii < TE / 2; ++ii) {
+            float acc = bn;
+            acc += wv_readlane(obs_t, 2 * ii) * w[0];
+            acc += wv_readlane(obs_t, 2 * ii + 1) * w[1];
+#pragma unroll
+            for (int d = 0; d < 7; ++d) acc += wv_readlane(obs_r, 7 * ii + d) * w[2 + d];
+            rs[ii] = fmaxf(acc, 0.0f);
+            R0[(8 * hi + ii) * S512 + n] = rs[ii];
+        }
+        if (TAPS) {
+#pragma unroll
+            for (int ii = 0; ii < TE / 2; ++ii) {
+                const int i = 8 * hi + ii;
+                if (e0 + i < E) a.tap_robot[(size_t)(e0 + i) * 256 + n] = rs[ii];
+            }
+        }
+    }
     __syncthreads();
     // ---- z = [u (256) | relu(enc) (64)] = te_w [320,256] . robot_states + te_b ;  gh = W_hh [384,128] . h_in (unmasked, no bias) ----
-    if (hi == 0) { // (five feature blocks do not fit 128 registers: three and two)
-        stage<256, 3, A_RELU>(a.f_te, w4, 4, a.te_b, R0, S512, R1, S512, 0, 256, lane);
-        stage<256, 2, A_RELU>(a.f_te, w4 + 12, 4, a.te_b, R0, S512, R1, S512, 0, 256, lane);
-    } else { // (six feature blocks of weight fragments, two k-steps deep, do not fit 128 registers: three and three)
-        stage<128, 3, A_NONE>(a.f_whh, w4, 4, nullptr, R4, S128, R2, S384, 0, 0, lane);
-        stage<128, 3, A_NONE>(a.f_whh, w4 + 12, 4, nullptr, R4, S128, R2, S384, 0, 0, lane);
+    // 20 feature blocks of 8 k-steps and 24 of 4, dealt so that every wavefront runs 8 k-steps: five wavefronts take four te blocks each,
+    // three take eight W_hh blocks each in two calls
+    if (wave < 5) {
+        stage<256, 4, A_RELU, true>(a.f_te, wave, 5, T + T_TEB, R0, S512, R1, S512, 0, 256, lane);
+    } else {
+        stage<128, 4, A_NONE, false>(a.f_whh, wave - 5, 3, nullptr, R4, S128, R2, S384, 0, 0, lane);
+        stage<128, 4, A_NONE, false>(a.f_whh, wave - 5 + 12, 3, nullptr, R4, S128, R2, S384, 0, 0, lane);
     }
     __syncthreads();
     // ---- robot-human attention (u-form, see hr_attention_kernel in attention.h): wavefront w owns envs 2w, 2w+1 ----
@@ -216,7 +307,6 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
             const float p = lane < nd ? expf(s - mx) : 0.0f;
             const float denom = wv_sum(p);
             const float at = p / denom;
-            if (a.tap_attn && lane < H && e0 + i < E) a.tap_attn[(size_t)(e0 + i) * H + lane] = at;
             float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
@@ -238,7 +328,8 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
             }
             float *o = R0 + i * S512; // robot_states are dead: hr takes their place
             o[lane] = o0; o[64 + lane] = o1; o[128 + lane] = o2; o[192 + lane] = o3;
-            if (a.tap_hr && e0 + i < E) {
+            if (TAPS && e0 + i < E) { // (behind the env's last out_sp row, not between the two passes)
+                if (lane < H) a.tap_attn[(size_t)(e0 + i) * H + lane] = at;
                 float *t = a.tap_hr + (size_t)(e0 + i) * 256;
                 t[lane] = o0; t[64 + lane] = o1; t[128 + lane] = o2; t[192 + lane] = o3;
             }
@@ -246,66 +337,68 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
     }
     __syncthreads();
     // ---- edge = relu(edge_attention_embed [64,256] . hr + b) -> z[320:384] ----
-    if (hi == 0) stage<256, 1, A_RELU>(a.f_edge, w4, 4, a.edge_b, R0, S512, R1, S512, 320, 0, lane);
+    if (hi == 0) stage<256, 1, A_RELU, true>(a.f_edge, w4, 4, T + T_EDGEB, R0, S512, R1, S512, 320, 0, lane);
     __syncthreads();
     // ---- gi = W_ih [384,128] . [enc | edge] + b_ih ----
-    stage<128, 3, A_NONE>(a.f_wih, wave, 8, a.bih, R1 + 256, S512, R3, S384, 0, 0, lane);
+    stage<128, 3, A_NONE, true>(a.f_wih, wave, 8, T + T_BIH, R1 + 256, S512, R3, S384, 0, 0, lane);
     __syncthreads();
     // ---- GRU cell, pointwise part (gate order r,z,n; h and gh masked by the done mask: srnn_model.py:43-46) ----
-    for (int idx = tid; idx < TE * 128; idx += 512) {
-        const int i = idx >> 7, c = idx & 127;
-        const int e = e0 + i < E ? e0 + i : E - 1;
-        const float m = a.masks[e];
-        const float *gie = R3 + i * S384, *ghe = R2 + i * S384;
-        const float hr = m * ghe[c] + a.bhh[c], hz = m * ghe[128 + c] + a.bhh[128 + c], hn = m * ghe[256 + c] + a.bhh[256 + c];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = (tid >> 7) + 4 * k, c = tid & 127;
+        const float m = T[T_SM + SM_MASK + i];
+        const float *gie = R3 + i * S384, *ghe = R2 + i * S384, *bhh = T + T_BHH;
+        const float hr = m * ghe[c] + bhh[c], hz = m * ghe[128 + c] + bhh[128 + c], hn = m * ghe[256 + c] + bhh[256 + c];
         const float r = fast_sigmoid(gie[c] + hr);
         const float z = fast_sigmoid(gie[128 + c] + hz);
-        const float n = fast_tanh(gie[256 + c] + r * hn);
+        const float nn = fast_tanh(gie[256 + c] + r * hn);
         const float h = m * R4[i * S128 + c];
-        const float hnew = (1.0f - z) * n + z * h;
+        const float hnew = (1.0f - z) * nn + z * h;
         R5[i * S128 + c] = hnew;
         if (e0 + i < E) a.hxs_out[(size_t)(e0 + i) * 128 + c] = hnew;
     }
     __syncthreads();
     // ---- actor / critic trunks: tanh((W0 Wo) h + ..) [512,128], then the two [256,256] second layers ----
-    stage<128, 4, A_TANH>(a.f_ac0, wave, 8, a.ac0_b, R5, S128, R0, S512, 0, 0, lane);
+    stage<128, 4, A_TANH, true>(a.f_ac0, wave, 8, T + T_AC0B, R5, S128, R0, S512, 0, 0, lane);
     __syncthreads();
     {
-        const float *fw = hi == 0 ? a.f_a2 : a.f_c2, *fb = hi == 0 ? a.a2_b : a.c2_b;
+        const float *fw = hi == 0 ? a.f_a2 : a.f_c2, *fb = hi == 0 ? T + T_A2B : T + T_C2B;
         const float *src = hi == 0 ? R0 : R0 + 256;
-        stage<256, 2, A_TANH>(fw, w4, 4, fb, src, S512, R1, S512, hi * 256, 0, lane);
-        stage<256, 2, A_TANH>(fw, w4 + 8, 4, fb, src, S512, R1, S512, hi * 256, 0, lane);
+        stage<256, 4, A_TANH, true>(fw, w4, 4, fb, src, S512, R1, S512, hi * 256, 0, lane);
     }
     __syncthreads();
-    // ---- critic_linear + DiagGaussian head (model.py:64-72): wavefront w owns envs 2w, 2w+1 ----
+    // ---- critic_linear + DiagGaussian head (model.py:64-72): wavefront w owns envs 2w, 2w+1; every operand is in LDS ----
     for (int q = 0; q < 2; ++q) {
         const int i = 2 * wave + q;
         if (e0 + i >= E) break;
         const int e = e0 + i;
-        const float *av = R1 + i * S512, *cv = av + 256;
+        const float *av = R1 + i * S512, *cv = av + 256, *cl_w = T + T_CLW, *fm_w = T + T_FMW, *sm = T + T_SM;
         float sv = 0.f, s0 = 0.f, s1 = 0.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const int d = lane + 64 * k;
-            sv += cv[d] * a.cl_w[d];
-            s0 += av[d] * a.fm_w[d];
-            s1 += av[d] * a.fm_w[256 + d];
-            if (a.tap_actor) a.tap_actor[(size_t)e * 256 + d] = av[d];
+            sv += cv[d] * cl_w[d];
+            s0 += av[d] * fm_w[d];
+            s1 += av[d] * fm_w[256 + d];
         }
         sv = wv_sum(sv); s0 = wv_sum(s0); s1 = wv_sum(s1);
         if (lane == 0) {
-            a.value[e] = sv + a.cl_b[0];
+            a.value[e] = sv + sm[SM_CLB];
             if (a.action) {
-                const float mean0 = s0 + a.fm_b[0], mean1 = s1 + a.fm_b[1];
-                const float ls0 = a.logstd[0], ls1 = a.logstd[1];
+                const float mean0 = s0 + sm[SM_FMB], mean1 = s1 + sm[SM_FMB + 1];
+                const float ls0 = sm[SM_LS], ls1 = sm[SM_LS + 1];
                 const float sd0 = expf(ls0), sd1 = expf(ls1);
-                const float a0 = a.eps ? mean0 + sd0 * a.eps[2 * e] : mean0;
-                const float a1 = a.eps ? mean1 + sd1 * a.eps[2 * e + 1] : mean1;
+                const float a0 = a.eps ? mean0 + sd0 * sm[SM_EPS + 2 * i] : mean0;
+                const float a1 = a.eps ? mean1 + sd1 * sm[SM_EPS + 2 * i + 1] : mean1;
                 a.action[2 * e] = a0; a.action[2 * e + 1] = a1;
                 const float HALF_LOG_2PI = 0.91893853320467274178f;
                 const float d0 = a0 - mean0, d1 = a1 - mean1;
                 a.logp[e] = (-(d0 * d0) / (2.0f * sd0 * sd0) - ls0 - HALF_LOG_2PI) + (-(d1 * d1) / (2.0f * sd1 * sd1) - ls1 - HALF_LOG_2PI);
             }
+        }
+        if (TAPS) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a.tap_actor[(size_t)e * 256 + lane + 64 * k] = av[lane + 64 * k];
         }
     }
 }
@@ -337,19 +430,31 @@ int rn_fused_bake(int N, int K, const float *w, float *out, hipStream_t st)
     return CN_OK;
 }
 
-int rn_fused_forward(int E, int H, const RnFusedArgs &args, hipStream_t st)
+template <bool TAPS>
+static int rn_fused_launch(int E, int H, const RnFusedArgs &a, hipStream_t st)
 {
     constexpr size_t lds = (size_t)LDS_FLOATS * sizeof(float);
     static thread_local int attr_dev = -1;
     int dev = 0;
     CN_HIP(hipGetDevice(&dev));
     if (dev != attr_dev) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rn_fused_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rn_fused_kernel<TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         attr_dev = dev;
     }
-    RnFusedArgs a = args;
-    a.stamp = cn_stamp_slot(CN_K_RN_FUSED);
-    hipLaunchKernelGGL(rn_fused_kernel, dim3((E + TE - 1) / TE), dim3(512), lds, st, E, H, a);
+    hipLaunchKernelGGL(rn_fused_kernel<TAPS>, dim3((E + TE - 1) / TE), dim3(512), lds, st, E, H, a);
     CN_CHECK_LAUNCH();
     return CN_OK;
+}
+
+int rn_fused_forward(int E, int H, const RnFusedArgs &args, hipStream_t st)
+{
+    CN_REQUIRE(E >= 1, "rn_fused_forward: E must be positive");
+    const bool taps = args.tap_robot || args.tap_attn || args.tap_hr || args.tap_actor;
+    CN_REQUIRE(!taps || (args.tap_robot && args.tap_attn && args.tap_hr && args.tap_actor), "rn_fused_forward: the four taps come together");
+    // the table's vectors are fetched as float4
+    for (const float *p : {args.te_b, args.edge_b, args.bih, args.bhh, args.ac0_b, args.a2_b, args.c2_b, args.cl_w, args.fm_w})
+        CN_REQUIRE(p && ((uintptr_t)p & 15) == 0, "rn_fused_forward: biases and head weights must be 16-byte aligned");
+    RnFusedArgs a = args;
+    a.stamp = cn_stamp_slot(CN_K_RN_FUSED);
+    return taps ? rn_fused_launch<true>(E, H, a, st) : rn_fused_launch<false>(E, H, a, st);
 }
