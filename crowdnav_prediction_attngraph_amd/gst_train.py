@@ -5,7 +5,7 @@ embedding 64, 8 heads, 1 layer, spatial_num_heads_edges = 0, no ghost, faster_ls
 
 Two execution paths of the training step (train.py:121-146: forward, negative log-likelihood, backward, clip, Adam):
   * on a GPU (backend 'hip', the default there): HipGstTrainer -- cn_gst_train_step (csrc/gst_train.hip: forward + loss + hand-derived
-    reverse pass, one workgroup per sequence, the reference's four dropout sites) and cn_adam_clip_step, through the C ABI;
+    reverse pass, one workgroup per sequence, the reference's four dropout sites) and flat_adam.FlatAdam (cn_adam_clip_step), through the C ABI;
   * the torch-op graph below under autograd (backend 'torch'): what CPU tensors use (unit tests, pinned to the reference's numbers) and the
     independent cross-check of the kernels (tests/test_gpu_gst_train.py holds the two against each other).
 Evaluation (eval.py's `inference`: the per-epoch validation pass and the sampled test protocol) has the same two paths: HipGstEvaluator --
@@ -270,39 +270,29 @@ def sequence_loss(model, item, device, p_drop=0.1, noise=None):
 class HipGstTrainer:
     """The training step of the predictor on the MI355X through the C ABI: forward + negative log-likelihood + backward as ONE boundary call
     (cn_gst_train_step, csrc/gst_train.hip: one workgroup per sequence, hand-derived reverse pass, the reference's four dropout sites with the
-    library's own counter-based masks) and gradient-norm clip + Adam as another (cn_adam_clip_step over one flat bucket).  Replaces, per
+    library's own counter-based masks) and gradient-norm clip + Adam as another (flat_adam.FlatAdam: cn_adam_clip_step over one flat bucket).  Replaces, per
     optimiser step, train.py:121-146: model(...) -> negative_log_likelihood_full_partial -> loss.backward() -> clip_grad_norm_ -> optimizer.step().
     The model's parameters become views of the flat bucket, so state_dict() / checkpoints are those of the torch path."""
 
     def __init__(self, model, lr=1e-3, clip_grad=10.0, betas=(0.9, 0.999), eps=1e-8, seed=1000, optimizer=None):
         from . import _abi as A
-        self.A = A
-        self.model = model
-        params = [dict(model.named_parameters())[k] for _, k in A.GST_WEIGHT_KEYS]
-        if not all(p.is_cuda and p.dtype == torch.float32 for p in params):
+        from .flat_adam import FlatAdam
+        self.A, self.model = A, model
+        named = dict(model.named_parameters())
+        named = [(k, named[k]) for _, k in A.GST_WEIGHT_KEYS]
+        if not all(p.is_cuda and p.dtype == torch.float32 for _, p in named):
             raise A.CnError("HipGstTrainer: the predictor must live on the GPU in float32 (there is no CPU fallback of the HIP path)")
-        dev = params[0].device
-        n = sum((p.numel() + 3) // 4 * 4 for p in params)         # every tensor 16-byte aligned inside the bucket
-        self.flat = {k: torch.zeros(n, dtype=torch.float32, device=dev) for k in ("p", "g", "m", "v")}
+        self.flat = FlatAdam(named, optimizer)   # the torch optimiser object stays the owner of the moments (its state_dict() goes into the checkpoints)
         self.w, self.g = A.GstWeights(), A.GstWeights()
-        off = 0
-        for (field, _), p in zip(A.GST_WEIGHT_KEYS, params):
-            k = p.numel()
-            pv, gv = self.flat["p"][off:off + k].view_as(p), self.flat["g"][off:off + k].view_as(p)
-            pv.copy_(p.data)
-            p.data = pv
-            p.grad = gv
+        for (field, _), (pv, gv, _, _) in zip(A.GST_WEIGHT_KEYS, self.flat.views):
             setattr(self.w, field, pv.data_ptr())
             setattr(self.g, field, gv.data_ptr())
-            if optimizer is not None:      # the torch optimiser object stays the owner of the moments (its state_dict() goes into the checkpoints)
-                optimizer.state[p] = {"step": torch.tensor(0.0), "exp_avg": self.flat["m"][off:off + k].view_as(p), "exp_avg_sq": self.flat["v"][off:off + k].view_as(p)}
-            off += (k + 3) // 4 * 4
-        self.optimizer = optimizer
-        self.lr, self.clip_grad, self.betas, self.eps = float(lr), clip_grad, betas, float(eps)
-        self.step_no, self.seed = 0, int(seed)
-        self.adam_ws = torch.empty(A.lib().cn_adam_workspace_doubles(), dtype=torch.float64, device=dev)
-        self.ws = None
-        self.dev = dev
+        self.lr, self.clip_grad, self.betas, self.eps, self.seed = float(lr), clip_grad, betas, float(eps), int(seed)
+        self.ws, self.dev = None, self.flat.p.device
+
+    @property
+    def step_no(self):
+        return self.flat.step_no
 
     def loss_and_grads(self, v_obs, v_pred, loss_mask_rel, p_drop=0.1, seed=None):
         """v_obs [B,5,N,2], v_pred [B,5,N,2], loss_mask_rel [B,N,10] (any device) -> (loss_and_count [2] on the device, gauss [B,5,N,5]: mu_x, mu_y,
@@ -333,13 +323,8 @@ class HipGstTrainer:
     def optimizer_step(self, grad_scale=1.0):
         """clip_grad_norm_(parameters, clip_grad) + Adam.step() (train.py:143-146) over the flat bucket.  grad_scale multiplies the gradient before
         the norm is taken (train.py:134: loss / args.batch_size ahead of backward and clip_grad_norm_)."""
-        from . import hip
-        self.step_no += 1
-        if self.optimizer is not None:
-            for st in self.optimizer.state.values():
-                st["step"] = torch.tensor(float(self.step_no))
-        hip.adam_clip_step(self.flat["p"], self.flat["g"], self.flat["m"], self.flat["v"], self.step_no, self.lr, self.betas, self.eps, self.clip_grad,
-                           grad_scale=grad_scale, workspace=self.adam_ws)
+        self.flat.step(self.lr, self.betas, self.eps, self.clip_grad, grad_scale=grad_scale)
+        self.flat.sync_optimizer_state()
 
 
 def temperature(epoch, total_epochs, base_temp, temp_min=0.03):
@@ -566,9 +551,15 @@ def _offset_errors_batched(x_pred, x_target, loss_mask):
     return err.mean(1) * loss_mask, err[:, -1] * loss_mask
 
 
+def _step_sample_and_mask(gauss, lm_rel, obs_len):
+    """forward_train's x_sample_pred [B,P,N,2] and loss_mask_per_pedestrian [B,N] from cn_gst_train_step's gauss [B,P,N,5] and loss_mask_rel [B,N,T+P]."""
+    xs = gauss[..., :2] * lm_rel[:, :, obs_len - 1].unsqueeze(1).unsqueeze(-1)
+    return xs, (lm_rel.sum(2) == lm_rel.shape[2]).float()
+
+
 def _train_epoch_device(hip_tr, ds, order, thetas, batch_size, optimizer, obs_len):
     """One training epoch with the data on the device: per step a gather, the training step, the fused clip + Adam step; the step's loss and
-    its aoe / foe terms go into per-epoch device buffers and come back in ONE read-back.  -> (losses [steps] float64, aoe, foe, m: float32
+    its aoe / foe terms go into per-epoch device buffers and come back in ONE read-back.  -> (losses [steps] float64, [aoe], [foe], [m]: float32
     arrays of the per-pedestrian terms in step order)."""
     dev, n, B = ds.device, len(order), int(batch_size)
     index = torch.as_tensor(order.astype(np.int32)).to(dev)
@@ -587,17 +578,56 @@ def _train_epoch_device(hip_tr, ds, order, thetas, batch_size, optimizer, obs_le
         if B == 1:                                                            # the per-item loop's own expressions on its own shapes
             c = widths[k]
             gauss, lm_rel, vp = gauss[:, :, :c], lm_rel[:, :c], vp[:, :, :c].contiguous()
-            xs = gauss[..., :2] * lm_rel[:, :, obs_len - 1].unsqueeze(1).unsqueeze(-1)
-            lm = (lm_rel.sum(2) == lm_rel.shape[2]).float()
-            seg[0].copy_(average_offset_error(xs, vp, lm)); seg[1].copy_(final_offset_error(xs, vp, lm)); seg[2].copy_(lm[0])
-        else:
-            xs = gauss[..., :2] * lm_rel[:, :, obs_len - 1].unsqueeze(1).unsqueeze(-1)
-            lm = (lm_rel.sum(2) == lm_rel.shape[2]).float()
-            aoe, foe = _offset_errors_batched(xs, vp, lm)
-            seg[0].copy_(aoe.reshape(-1)); seg[1].copy_(foe.reshape(-1)); seg[2].copy_(lm.reshape(-1))
+        xs, lm = _step_sample_and_mask(gauss, lm_rel, obs_len)
+        aoe, foe = (average_offset_error(xs, vp, lm), final_offset_error(xs, vp, lm)) if B == 1 else _offset_errors_batched(xs, vp, lm)
+        seg[0].copy_(aoe.reshape(-1)); seg[1].copy_(foe.reshape(-1)); seg[2].copy_(lm.reshape(-1))
     host = torch.cat((loss_buf, terms.reshape(-1))).cpu().numpy()              # the epoch's one read-back
     t = host[len(chunks):].reshape(3, -1)
-    return host[:len(chunks)].astype(np.float64), t[0], t[1], t[2]
+    return host[:len(chunks)].astype(np.float64), [t[0]], [t[1]], [t[2]]
+
+
+def _train_items(loader, rotation_pattern):
+    """The per-item epochs' items (train.py:115-119): those of more than 128 pedestrians skipped, every kept one rotated by an angle drawn after it."""
+    for item in loader:
+        if item[6].shape[2] > 128:
+            continue
+        if rotation_pattern is not None:
+            theta = _draw_theta(rotation_pattern)
+            item = list(item)
+            item[6], item[8] = rotate_graph(item[6], theta), rotate_graph(item[8], theta)
+        yield item
+
+
+def _item_terms(loss, xs, lm, v_pred_gt):
+    """One per-item step's entries of (losses, aoes, foes, ms), read back."""
+    return loss.item(), average_offset_error(xs, v_pred_gt, lm).cpu().numpy(), final_offset_error(xs, v_pred_gt, lm).cpu().numpy(), lm[0].cpu().numpy()
+
+
+def _train_epoch_items_hip(hip_tr, loader, rotation_pattern, optimizer, device, obs_len):
+    """One epoch of one loader item per optimiser step through the kernels: forward, loss, backward (dropout 0.1 like model.train()) as one boundary
+    call, then the fused clip + Adam step.  -> (losses, aoes, foes, ms), one entry per step."""
+    rows = []
+    for item in _train_items(loader, rotation_pattern):
+        lm_rel = item[4].to(device)
+        hip_tr.lr = optimizer.param_groups[0]["lr"]                           # the StepLR schedule drives the fused step too
+        out, gauss = hip_tr.loss_and_grads(item[6], item[8], lm_rel, p_drop=0.1)
+        hip_tr.optimizer_step()
+        rows.append(_item_terms(out[0], *_step_sample_and_mask(gauss, lm_rel, obs_len), item[8].to(device)))
+    return tuple(zip(*rows))
+
+
+def _train_epoch_items_torch(model, loader, rotation_pattern, optimizer, clip_grad, device):
+    """The same epoch on the op graph under autograd (train.py:121-146)."""
+    rows = []
+    for item in _train_items(loader, rotation_pattern):
+        loss, gp, xs, info, v_pred_gt = sequence_loss(model, item, device)
+        loss.backward()
+        rows.append(_item_terms(loss.detach(), xs.detach(), info["loss_mask_per_pedestrian"], v_pred_gt))
+        if clip_grad is not None:
+            torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad)
+        optimizer.step()
+        optimizer.zero_grad()
+    return tuple(zip(*rows))
 
 
 def _evaluate_device(model, ds, batch_size=32):
@@ -792,46 +822,17 @@ def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3,
     with open(os.path.join(ckpt_dir, "args.pickle"), "wb") as f:
         pickle.dump(argparse.Namespace(**run_args), f)
     hist = {"epoch": 0, "train_loss_task": [], "val_loss_task": [], "train_aoe_task": [], "val_aoe_task": [], "train_foe_task": [], "val_foe_task": []}
+    if on_device:            # the order and the angles drawn up front by the per-item loop's own calls
+        run_epoch = lambda: _train_epoch_device(hip_tr, ds_train, *epoch_plan(len(ds_train), rotation_pattern), batch_size, optimizer, model.obs_len)   # noqa: E731
+    elif hip_tr is not None:
+        run_epoch = lambda: _train_epoch_items_hip(hip_tr, loader_train, rotation_pattern, optimizer, device, model.obs_len)   # noqa: E731
+    else:
+        run_epoch = lambda: _train_epoch_items_torch(model, loader_train, rotation_pattern, optimizer, clip_grad, device)   # noqa: E731
     for epoch in range(1, num_epochs + 1):
         model.train()
         t0 = time.time()
         tau = temperature(epoch, temp_epochs, init_temp)
-        losses, aoes, foes, ms = [], [], [], []
-        if on_device:
-            order, thetas = epoch_plan(len(ds_train), rotation_pattern)
-            ep = _train_epoch_device(hip_tr, ds_train, order, thetas, batch_size, optimizer, model.obs_len)
-            losses, aoes, foes, ms = list(ep[0]), [ep[1]], [ep[2]], [ep[3]]
-        for item in (() if on_device else loader_train):
-            if item[6].shape[2] > 128:            # train.py:118-119
-                continue
-            if rotation_pattern is not None:
-                theta = _draw_theta(rotation_pattern)
-                item = list(item)
-                item[6], item[8] = rotate_graph(item[6], theta), rotate_graph(item[8], theta)
-            if hip_tr is not None:
-                # one boundary call: forward, loss, backward (dropout 0.1 like model.train()); then the fused clip + Adam step
-                lm_rel = item[4].to(device)
-                hip_tr.lr = optimizer.param_groups[0]["lr"]                       # the StepLR schedule below drives the fused step too
-                out, gauss = hip_tr.loss_and_grads(item[6], item[8], lm_rel, p_drop=0.1)
-                hip_tr.optimizer_step()
-                losses.append(out[0].item())
-                lm_fp = lm_rel[:, :, model.obs_len - 1]
-                xs = gauss[..., :2] * lm_fp.unsqueeze(1).unsqueeze(-1)
-                lm = (lm_rel.sum(2) == lm_rel.shape[2]).float()
-                v_pred_gt = item[8].to(device)
-                aoes.append(average_offset_error(xs, v_pred_gt, lm).cpu().numpy()); foes.append(final_offset_error(xs, v_pred_gt, lm).cpu().numpy())
-                ms.append(lm[0].cpu().numpy())
-                continue
-            loss, gp, xs, info, v_pred_gt = sequence_loss(model, item, device)
-            losses.append(loss.item())
-            loss.backward()
-            lm = info["loss_mask_per_pedestrian"]
-            aoes.append(average_offset_error(xs.detach(), v_pred_gt, lm).cpu().numpy()); foes.append(final_offset_error(xs.detach(), v_pred_gt, lm).cpu().numpy())
-            ms.append(lm[0].cpu().numpy())
-            if clip_grad is not None:
-                torch.nn.utils.clip_grad_norm_(model.parameters(), clip_grad)
-            optimizer.step()
-            optimizer.zero_grad()
+        losses, aoes, foes, ms = run_epoch()
         scheduler.step()
         m = max(float(np.concatenate(ms).sum()), 1.0)
         tr = (float(np.mean(losses)), float(np.concatenate(aoes).sum() / m), float(np.concatenate(foes).sum() / m))

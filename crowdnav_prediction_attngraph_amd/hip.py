@@ -1105,7 +1105,7 @@ class MinibatchStepper:
         self._ws = None
         self._ptrs = None
         # Parameters the call does not write: only the ones the loss never reaches (the reference leaves their .grad None).  Their slices of
-        # the flat bucket still enter the all-reduce, the clip norm and Adam, so the caller keeps them zero (ppo.PPO._update_fast); any
+        # the flat bucket still enter the all-reduce, the clip norm and Adam, so the caller keeps them zero (ppo.PPO._minibatch_step_producer); any
         # OTHER parameter outside cn_policy_weights would silently train on a stale gradient, hence the refusal here.
         covered = {k for _, k in A.POLICY_WEIGHT_KEYS}
         self.uncovered = [name for name, p in policy.named_parameters() if p.requires_grad and name not in covered]

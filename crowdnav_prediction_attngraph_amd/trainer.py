@@ -134,7 +134,7 @@ def save_checkpoint(save_dir, update, actor_critic, agent, envs, rollouts, stats
     stem = os.path.join(d, "%.5i" % update)
     if rank == 0:
         torch.save(actor_critic.state_dict(), stem + ".pt")
-    agent._sync_optimizer_state()
+    agent.sync_optimizer_state()
     ck = {"format": 1, "update": update, "optimizer": agent.optimizer.state_dict(), "rng_cpu": torch.get_rng_state(),
           "rng_cuda": torch.cuda.get_rng_state(device), "env": envs.state_dict(),
           "rollout0": {"obs": {k: v[0].clone() for k, v in rollouts.obs.items()},
