@@ -6,7 +6,7 @@ visible humans' (frame id, prediction id, px, py) rows of every `pred_interval`-
 tab-separated text file per env.  Here the E envs are one device batch (cn_env_batch with env_kind CN_ENV_COLLECT): the `pred_info`
 observations of a block of steps stay on the GPU and cross PCIe once per block; the files are byte-for-byte what the reference
 writes for the same seeds (tests/test_gpu_collect.py replays the reference's own traces).  collect_log keeps the observations on the device
-altogether: gst_train.DeviceTrajectories.from_log cuts the training sequences out of them there, without files.
+altogether: gst_data.DeviceTrajectories.from_log cuts the training sequences out of them there, without files.
 """
 import os
 
@@ -135,7 +135,7 @@ def collect_lines(envs, tot_steps, pred_interval=1, block=256):
 def collect_log(envs, tot_steps, pred_interval=1):
     """collect_lines' stepping without the host formatting: the observations it would format, as ONE device tensor [F, E, H, 4] float32
     (F = ceil(tot_steps / pred_interval) samples; row = frame id, prediction id, px, py, +inf where the human is not visible) -- the input of
-    gst_train.DeviceTrajectories.from_log.  Nothing crosses PCIe."""
+    gst_data.DeviceTrajectories.from_log.  Nothing crosses PCIe."""
     tot_steps, pred_interval = int(tot_steps), int(pred_interval)
     F = (tot_steps + pred_interval - 1) // pred_interval
     log = torch.empty(F, envs.num_envs, envs.human_num, 4, device=envs.device)

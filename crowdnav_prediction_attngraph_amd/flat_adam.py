@@ -1,4 +1,4 @@
-"""FlatAdam -- the flat-bucket optimiser of both training paths (ppo.PPO.update, gst_train.HipGstTrainer) and the only place that knows the
+"""FlatAdam -- the flat-bucket optimiser of both training paths (ppo.PPO.update, gst_hip.HipGstTrainer) and the only place that knows the
 bucket layout.  ONE fp32 buffer each for the parameters, their gradients and the two Adam moments; every p.data / p.grad /
 optimizer.state[p]['exp_avg'|'exp_avg_sq'] is a view into them, so a gradient all-reduce needs no packing and grad-norm clip + Adam is one
 boundary call (cn_adam_clip_step).  Binding is plain tensor work on the parameters' device; only step() reaches the library."""

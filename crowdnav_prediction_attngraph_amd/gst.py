@@ -2,8 +2,11 @@
 over all envs on the device with no host synchronisation and no per-env Python loop.
 
 On a GPU the predictor and the wrapper processing run as hand-written HIP kernels (csrc/gst.hip through cn_gst_predict /
-cn_gst_wrapper_step); the torch-op expression of the same math below is what CPU tensors use (unit tests) and doubles
-as an independent cross-check of the kernels.  Same state-dict keys as the shipped checkpoints (`epoch_100.pt` loads unchanged):
+cn_gst_wrapper_step, gst_hip.HipGST); the torch-op expression of the same math below is what CPU tensors use (unit tests) and doubles
+as an independent cross-check of the kernels.  GSTPredictor holds the package's ONE op graph of the predictor: the encoder layer
+(_transformer, with the reference's four dropout sites) and the recursion over observed and decoded steps serve inference (forward), the
+training step under autograd and the sampled test decode (gst_train.forward_train is the adapter from the dataset's layout).
+Same state-dict keys as the shipped checkpoints (`epoch_100.pt` loads unchanged):
   gst_updated/src/gumbel_social_transformer/st_model.py:271-455 (faster_lstm, recursive decode, fully connected edges)
   gst_updated/scripts/wrapper/crowd_nav_interface_parallel.py:45-114
   rl/vec_env/vec_pretext_normalize.py:85-191
@@ -49,8 +52,8 @@ class _GST(nn.Module):
 
 
 class GSTPredictor(nn.Module):
-    """Inference-only Gumbel Social Transformer with the shipped hyper-parameters (embedding 64, 8 heads, 1 layer,
-    spatial_num_heads_edges = 0, ghost = False, LSTM 64, obs 5 / pred 5, output_dim 5)."""
+    """Gumbel Social Transformer with the shipped hyper-parameters (embedding 64, 8 heads, 1 layer, spatial_num_heads_edges = 0,
+    ghost = False, LSTM 64, obs 5 / pred 5, output_dim 5).  Built in eval mode; forward is inference only."""
 
     def __init__(self, obs_len=5, pred_len=5):
         super().__init__()
@@ -68,11 +71,13 @@ class GSTPredictor(nn.Module):
         m.load_state_dict(ck["model_state_dict"] if "model_state_dict" in ck else ck)
         return m
 
-    def _transformer(self, x, attn_mask):
-        """x [B,H,2], attn_mask [B,H,H] float (target, neighbor) -> [B,H,64]."""
+    def _transformer(self, x, attn_mask, p_drop=0.0):
+        """x [B,H,2], attn_mask [B,H,H] float (target, neighbor) -> [B,H,64].  p_drop: the reference's four dropout sites (mha.py:243,
+        node_encoder_layer_no_ghost.py:57,61,62), active in training mode only; they draw from torch's generator in this order."""
         g = self.gumbel_social_transformer
         L = g.node_encoder_layers[0]
         B, H, _ = x.shape
+        tr = self.training and p_drop > 0
         x = g.node_embedding(x)
         ped = (attn_mask.sum(-1) > 0).to(x.dtype).unsqueeze(-1)
         x = L.norm_node(x) * ped
@@ -80,9 +85,11 @@ class GSTPredictor(nn.Module):
         p = torch.softmax((q * 8 ** -0.5) @ k.transpose(-1, -2), dim=-1)
         p = p * attn_mask.unsqueeze(1)                      # float mask: multiply after the softmax, then renormalise (mha.py:236-242)
         p = p / (p.sum(-1, keepdim=True) + 1e-10)
+        p = F.dropout(p, p_drop, tr)
         o = (p @ v).transpose(1, 2).reshape(B, H, 64)
-        x = x + L.self_attn.out_proj(o)
-        return x + L.linear2(F.relu(L.linear1(L.norm1_node(x))))
+        x = x + F.dropout(L.self_attn.out_proj(o), p_drop, tr)
+        x2 = F.dropout(F.relu(L.linear1(L.norm1_node(x))), p_drop, tr)
+        return x + F.dropout(L.linear2(x2), p_drop, tr)
 
     def _lstm_cell(self, x, h, c):
         g = F.linear(x, self.lstm.weight_ih_l0, self.lstm.bias_ih_l0) + F.linear(h, self.lstm.weight_hh_l0, self.lstm.bias_hh_l0)
@@ -90,41 +97,54 @@ class GSTPredictor(nn.Module):
         c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(gg)
         return torch.sigmoid(o) * torch.tanh(c), c
 
+    def recursion(self, v_obs, attn_obs, m_rel, p_drop=0.0, noise=None):
+        """st_model.py:271-455 (faster_lstm, recursive decode, only_observe_full_period = False), the one graph of inference, training and test.
+        v_obs [B,T,N,2] displacements, attn_obs [B,T,N,N] (target, neighbour), m_rel [B,N,>=T] displacement mask (its column T-1 is
+        loss_mask_rel_full_partial) -> (mu [B,P,N,2], sx, sy, corr [B,P,N,1]), x_sample [B,P,N,2]: what is fed back, masked.
+        noise None: the mean is fed back.  noise [B,P,N,2] (standard-normal draws): sample_gaussian's arithmetic (st_model.py:235-240) on the
+        caller's draws instead of torch.empty(...).normal_()."""
+        B, T, N, _ = v_obs.shape
+        xs = self._transformer(v_obs.reshape(B * T, N, 2), attn_obs.reshape(B * T, N, N), p_drop).view(B, T, N, 64)
+        xs = xs * m_rel[:, :, :T].permute(0, 2, 1).unsqueeze(-1)
+        h = torch.zeros(B * N, 64, device=v_obs.device, dtype=xs.dtype)
+        c = torch.zeros_like(h)
+        for t in range(T):
+            h, c = self._lstm_cell(xs[:, t].reshape(B * N, 64), h, c)
+        lm_fp = m_rel[:, :, T - 1]                                                        # [B, N]
+        mk = lm_fp.reshape(B * N, 1)
+        h, c = h * mk, c * mk
+        attn_pred = (lm_fp.unsqueeze(2) * lm_fp.unsqueeze(1)).permute(0, 2, 1)
+        mus, sxs, sys_, cors, samples = [], [], [], [], []
+        x_sample = None
+        for tt in range(self.pred_len):
+            if tt > 0:
+                xt = self._transformer(x_sample.reshape(B, N, 2), attn_pred, p_drop).reshape(B * N, 64) * mk
+                hp, cp = self._lstm_cell(xt, h, c)
+                h = hp * mk + h * (1 - mk)
+                c = cp * mk + c * (1 - mk)
+            raw = self.hidden2pos(h).view(B, N, 5).unsqueeze(1)
+            mu = raw[..., :2]
+            mus.append(mu); sxs.append(raw[..., 2:3].exp()); sys_.append(raw[..., 3:4].exp()); cors.append(raw[..., 4:5].tanh())
+            if noise is not None:
+                sx, sy, corr, ex, ey = sxs[-1], sys_[-1], cors[-1], noise[:, tt:tt + 1, :, 0:1], noise[:, tt:tt + 1, :, 1:2]
+                mu = torch.cat((sx * ex, corr * sy * ex + ((1. - corr ** 2.) ** 0.5) * sy * ey), dim=3) + mu
+            x_sample = mu * lm_fp.unsqueeze(1).unsqueeze(-1)
+            samples.append(x_sample)
+        return (torch.cat(mus, 1), torch.cat(sxs, 1), torch.cat(sys_, 1), torch.cat(cors, 1)), torch.cat(samples, 1)
+
     @torch.no_grad()
     def forward(self, in_traj, in_mask):
         """in_traj [E,H,T,2] world positions (-999 where unseen), in_mask [E,H,T,1] 0/1 float ->
         out_traj [E,H,P,5] (cumulative mu_x, mu_y, sigma_x, sigma_y, corr; positions -999 where not predicted), out_mask [E,H,1]."""
         E, H, T, _ = in_traj.shape
-        P = self.pred_len
         m = in_mask[..., 0]
         m_rel = torch.cat([m[:, :, :1], m[:, :, :-1] * m[:, :, -1:]], dim=2)       # crowd_nav_interface_parallel.py:76-78
         lm_fp = m_rel[:, :, -1]
         rel = torch.cat([torch.zeros(E, H, 1, 2, device=in_traj.device), in_traj[:, :, 1:] - in_traj[:, :, :-1]], dim=2)
         rel = INVALID * (1 - m_rel.unsqueeze(-1)) + rel * m_rel.unsqueeze(-1)
-        mt = m_rel.permute(0, 2, 1).reshape(E * T, H)
-        xs = self._transformer(rel.permute(0, 2, 1, 3).reshape(E * T, H, 2), mt.unsqueeze(2) * mt.unsqueeze(1)).view(E, T, H, 64)
-        xs = xs * m_rel.permute(0, 2, 1).unsqueeze(-1)
-        h = torch.zeros(E * H, 64, device=in_traj.device)
-        c = torch.zeros_like(h)
-        for t in range(T):
-            h, c = self._lstm_cell(xs[:, t].reshape(E * H, 64), h, c)
-        mk = lm_fp.reshape(E * H, 1)
-        h, c = h * mk, c * mk
-        attn_pred = lm_fp.unsqueeze(2) * lm_fp.unsqueeze(1)
-        mus, sxs, sys_, cors = [], [], [], []
-        x_sample = None
-        for tt in range(P):
-            if tt > 0:
-                xt = self._transformer(x_sample, attn_pred).reshape(E * H, 64) * mk
-                hp, cp = self._lstm_cell(xt, h, c)
-                h = hp * mk + h * (1 - mk)
-                c = cp * mk + c * (1 - mk)
-            raw = self.hidden2pos(h).view(E, H, 5)
-            mu = raw[..., :2]
-            mus.append(mu); sxs.append(raw[..., 2:3].exp()); sys_.append(raw[..., 3:4].exp()); cors.append(raw[..., 4:5].tanh())
-            x_sample = mu * lm_fp.unsqueeze(-1)
-        mu = torch.stack(mus, 1).cumsum(1)
-        sx, sy, corr = torch.stack(sxs, 1), torch.stack(sys_, 1), torch.stack(cors, 1)
+        mt = m_rel.permute(0, 2, 1)                                                 # [E,T,H]
+        (mu, sx, sy, corr), _ = self.recursion(rel.permute(0, 2, 1, 3), mt.unsqueeze(3) * mt.unsqueeze(2), m_rel)
+        mu = mu.cumsum(1)
         sxc, syc = (sx ** 2).cumsum(1).sqrt(), (sy ** 2).cumsum(1).sqrt()
         corrc = (corr * sx * sy).cumsum(1) / (sxc * syc)
         lm_pred = lm_fp[:, None, :, None]
@@ -151,7 +171,7 @@ class PretextProcessor:
         if use_hip if use_hip is not None else self.device.type == "cuda":
             if predict_steps != 5:
                 raise NotImplementedError("the GST kernels are specialised to the shipped predictor (5 observed / 5 predicted steps)")
-            from .hip import HipGST
+            from .gst_hip import HipGST
             self.hip = HipGST(human_num, num_envs, device=self.device)     # raises if the extension is missing: no fallback on a GPU
             self.hip.set_weights(predictor.state_dict())
             self.hip.wrapper_set_interval(self.interval)

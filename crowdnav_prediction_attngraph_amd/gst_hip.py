@@ -1,0 +1,238 @@
+"""The GST predictor's boundary calls: thin object wrappers over the C ABI of csrc/gst.hip (HipGST: cn_gst_predict and the
+VecPretextNormalize processing, cn_gst_wrapper_*), csrc/gst_train.hip (HipGstTrainer: cn_gst_train_step + the flat Adam bucket) and
+csrc/gst_eval.hip (HipGstEvaluator: cn_gst_eval_step), and the three things they share: the cn_gst_weights struct over a list of tensors, a
+batch of sequences brought to the call's device and layout, the grow-only workspace."""
+import ctypes as C
+
+import torch
+
+from . import _abi as A
+from .flat_adam import FlatAdam
+
+
+def gst_weights(tensors, who):
+    """The cn_gst_weights struct over `tensors` (in _abi.GST_WEIGHT_KEYS order), read by the kernels where they are: nothing is copied."""
+    tensors = list(tensors)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() for t in tensors):
+        raise A.CnError("%s: the predictor must live on the GPU in float32 (there is no CPU fallback of the HIP path)" % who)
+    w = A.GstWeights()
+    for (field, _), t in zip(A.GST_WEIGHT_KEYS, tensors):
+        setattr(w, field, t.data_ptr())
+    return w
+
+
+def predictor_params(model):
+    """The predictor's parameters in _abi.GST_WEIGHT_KEYS order."""
+    named = dict(model.named_parameters())
+    return [(k, named[k]) for _, k in A.GST_WEIGHT_KEYS]
+
+
+def gst_batch(who, dev, v_obs, v_pred, loss_mask_rel, noise=None, max_samples=64):
+    """v_obs, v_pred [B,5,N,2], loss_mask_rel [B,N,10], noise None or [B,S,5,N,2] (any device) -> N and the four as contiguous float32 on
+    `dev`, padded along the pedestrian axis to max(N, 4) with absent pedestrians (zeros)."""
+    B, T, N, _ = v_obs.shape
+    if T != 5 or v_pred.shape[1] != 5 or N > A.CN_MAX_HUMANS:
+        raise A.CnError("%s: 5 observed + 5 predicted steps and at most 64 pedestrians per sequence (got %d + %d steps, %d pedestrians)" % (who, T, v_pred.shape[1], N))
+    if noise is not None and (not 1 <= noise.shape[1] <= max_samples or tuple(noise.shape) != (B, noise.shape[1], 5, N, 2)):
+        raise A.CnError("%s: noise must be [B,S,5,N,2] with 1 <= S <= %d (got %s for B=%d, N=%d)" % (who, max_samples, tuple(noise.shape), B, N))
+    out = []
+    for t in (v_obs, v_pred, loss_mask_rel, noise):
+        if t is not None:
+            if N < 4:
+                t = torch.nn.functional.pad(t, (0, 0, 0, 4 - N))
+            t = t.to(dev, torch.float32, non_blocking=True).contiguous()
+        out.append(t)
+    return [N] + out
+
+
+def workspace(ws, need, dev):
+    """The grow-only scratch buffer of a boundary call: `ws` if it holds `need` bytes, a larger one otherwise."""
+    return ws if ws is not None and ws.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
+
+
+def _need_cuda():
+    if not torch.cuda.is_available():
+        raise A.CnError("no GPU visible: the GST predictor's hot path only runs on MI355X (no CPU fallback)")
+
+
+class HipGST:
+    """cn_gst handle: GST predictor (cn_gst_predict) and the VecPretextNormalize processing (cn_gst_wrapper_*)."""
+
+    def __init__(self, human_num, max_envs, device=None):
+        _need_cuda()
+        self.H, self.maxE = int(human_num), int(max_envs)
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_create(self.H, self.maxE, C.byref(h)), "cn_gst_create")
+        self._h = h
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            A.lib().cn_gst_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, state_dict):
+        keep = [state_dict[key].detach().to(device=self.device, dtype=torch.float32).contiguous() for _, key in A.GST_WEIGHT_KEYS]
+        w = gst_weights(keep, "HipGST")
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_set_weights(self._h, C.byref(w), A.stream_ptr()), "cn_gst_set_weights")
+        self._keep = keep
+
+    def predict(self, in_traj, in_mask):
+        """in_traj [E,H,5,2], in_mask [E,H,5] or [E,H,5,1] float -> (out_traj [E,H,5,5], out_mask [E,H,1])."""
+        E = in_traj.shape[0]
+        out = torch.empty(E, self.H, 5, 5, device=self.device)
+        om = torch.empty(E, self.H, device=self.device)
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_predict(self._h, E, A.ptr(in_traj.float().contiguous()), A.ptr(in_mask.float().reshape(E, self.H, 5).contiguous()),
+                                           A.ptr(out), A.ptr(om), A.stream_ptr()), "cn_gst_predict")
+        return out, om.unsqueeze(-1)
+
+    def wrapper_reset(self, E):
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_wrapper_reset(self._h, int(E), A.stream_ptr()), "cn_gst_wrapper_reset")
+        self._wrap_E = int(E)
+
+    def wrapper_set_interval(self, pred_interval):
+        """int(data.pred_timestep // env.time_step): the history keeps 4 * pred_interval + 1 observations, every pred_interval-th is fed."""
+        A.check(A.lib().cn_gst_wrapper_set_interval(self._h, int(pred_interval)), "cn_gst_wrapper_set_interval")
+
+    def wrapper_state(self):
+        """(traj [len,E,H,2] float32, mask [len,E,H] uint8) = the observation history in time order, oldest first (cn_gst_wrapper_save)."""
+        L, E = int(A.lib().cn_gst_wrapper_history_len(self._h)), self._wrap_E
+        traj = torch.empty(L, E, self.H, 2, device=self.device)
+        mask = torch.empty(L, E, self.H, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_wrapper_save(self._h, A.ptr(traj), A.ptr(mask), A.stream_ptr()), "cn_gst_wrapper_save")
+        return traj, mask
+
+    def wrapper_load_state(self, traj, mask):
+        L = int(A.lib().cn_gst_wrapper_history_len(self._h))
+        if traj.shape[0] != L or tuple(traj.shape[2:]) != (self.H, 2) or tuple(mask.shape) != tuple(traj.shape[:3]):
+            raise A.CnError("history of shape %s / %s does not fit this wrapper (length %d, %d humans)" % (tuple(traj.shape), tuple(mask.shape), L, self.H))
+        E = int(traj.shape[1])
+        traj = traj.to(device=self.device, dtype=torch.float32).contiguous()
+        mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_wrapper_load(self._h, E, A.ptr(traj), A.ptr(mask), A.stream_ptr()), "cn_gst_wrapper_load")
+        torch.cuda.current_stream(self.device).synchronize()   # the sources are temporaries
+        self._wrap_E = E
+
+    def wrapper_step(self, obs, rewards, dist, collision_penalty, out=None):
+        """obs: raw env observation (spatial_edges [E,H,12] by human id, visible_masks u8/bool); rewards [E] float32 updated in place."""
+        E = obs["robot_node"].shape[0]
+        if out is None:
+            out = torch.empty(E, self.H, 12, device=self.device)
+        o = A.Obs()
+        o.robot_node = A.ptr(obs["robot_node"])
+        o.spatial_edges = A.ptr(obs["spatial_edges"])
+        vm = obs["visible_masks"]
+        vm = vm.view(torch.uint8) if vm.dtype == torch.bool else vm
+        o.visible_masks = A.ptr(vm.contiguous())
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_gst_wrapper_step(self._h, E, C.byref(o), float(dist), float(collision_penalty), A.ptr(rewards), A.ptr(out), A.stream_ptr()),
+                    "cn_gst_wrapper_step")
+        return out
+
+
+class HipGstTrainer:
+    """The training step of the predictor on the MI355X through the C ABI: forward + negative log-likelihood + backward as ONE boundary call
+    (cn_gst_train_step, csrc/gst_train.hip: one workgroup per sequence, hand-derived reverse pass, the reference's four dropout sites with the
+    library's own counter-based masks) and gradient-norm clip + Adam as another (flat_adam.FlatAdam: cn_adam_clip_step over one flat bucket).  Replaces, per
+    optimiser step, train.py:121-146: model(...) -> negative_log_likelihood_full_partial -> loss.backward() -> clip_grad_norm_ -> optimizer.step().
+    The model's parameters become views of the flat bucket, so state_dict() / checkpoints are those of the torch path."""
+
+    def __init__(self, model, lr=1e-3, clip_grad=10.0, betas=(0.9, 0.999), eps=1e-8, seed=1000, optimizer=None):
+        named = predictor_params(model)
+        gst_weights([p for _, p in named], "HipGstTrainer")   # refuses a CPU model before anything is rebound
+        self.model = model
+        self.flat = FlatAdam(named, optimizer)   # the torch optimiser object stays the owner of the moments (its state_dict() goes into the checkpoints)
+        self.w, self.g = (gst_weights([v[i] for v in self.flat.views], "HipGstTrainer") for i in (0, 1))
+        self.lr, self.clip_grad, self.betas, self.eps, self.seed = float(lr), clip_grad, betas, float(eps), int(seed)
+        self.ws, self.dev = None, self.flat.p.device
+
+    @property
+    def step_no(self):
+        return self.flat.step_no
+
+    def loss_and_grads(self, v_obs, v_pred, loss_mask_rel, p_drop=0.1, seed=None):
+        """v_obs [B,5,N,2], v_pred [B,5,N,2], loss_mask_rel [B,N,10] (any device) -> (loss_and_count [2] on the device, gauss [B,5,N,5]: mu_x, mu_y,
+        sigma_x, sigma_y, corr); the gradients land in the flat bucket (every parameter's .grad).  Crowds of fewer than 4 pedestrians are padded
+        with absent ones."""
+        N, vo, vp, lm, _ = gst_batch("HipGstTrainer", self.dev, v_obs, v_pred, loss_mask_rel)
+        B, Np = vo.shape[0], vo.shape[2]
+        self.ws = workspace(self.ws, int(A.lib().cn_gst_train_workspace_bytes(B, Np)), self.dev)
+        out = torch.empty(2, device=self.dev)
+        gauss = torch.empty(B, 5, Np, 5, device=self.dev)
+        sd = self.seed + 7919 * self.step_no if seed is None else int(seed)
+        with torch.cuda.device(self.dev):
+            A.check(A.lib().cn_gst_train_step(B, Np, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(self.w), C.byref(self.g), float(p_drop), C.c_uint64(sd & (2 ** 64 - 1)),
+                                              C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()), A.ptr(out), A.ptr(gauss), A.stream_ptr()), "cn_gst_train_step")
+        return out, gauss[:, :, :N]
+
+    def optimizer_step(self, grad_scale=1.0):
+        """clip_grad_norm_(parameters, clip_grad) + Adam.step() (train.py:143-146) over the flat bucket.  grad_scale multiplies the gradient before
+        the norm is taken (train.py:134: loss / args.batch_size ahead of backward and clip_grad_norm_)."""
+        self.flat.step(self.lr, self.betas, self.eps, self.clip_grad, grad_scale=grad_scale)
+        self.flat.sync_optimizer_state()
+
+
+class HipGstEvaluator:
+    """Evaluation of the predictor on the MI355X through the C ABI: cn_gst_eval_step (csrc/gst_eval.hip) runs, for a batch of sequences in one
+    boundary call, what eval.py:63-117 does per sequence -- the forward with dropout off, the masked negative log-likelihood and the
+    average / final offset errors; validation (the mean fed back) or the test protocol (S sampled decodes per sequence on the caller's draws).
+    The kernels read the model's parameters where they are (also when they are views of a HipGstTrainer's flat bucket): nothing is copied."""
+
+    MAX_PEDS, MAX_SAMPLES = 64, 64
+
+    def __init__(self, model):
+        self.model = model
+        params = self._params()
+        gst_weights(params, "HipGstEvaluator")                # refuses a CPU model
+        self.dev, self.ws = params[0].device, None
+
+    def _params(self):
+        return [p for _, p in predictor_params(self.model)]
+
+    def evaluate_batch(self, v_obs, v_pred, loss_mask_rel, noise=None):
+        """v_obs, v_pred [B,5,N,2], loss_mask_rel [B,N,10] (any device), or lists of B per-sequence tensors ([5,N_b,2] / [N_b,10], a leading
+        axis of one allowed) of different crowd sizes; noise None (validation) or [B,S,5,N,2] / a list of [S,5,N_b,2] (test: S decodes per
+        sequence on these standard-normal draws).  Crowds are padded to the batch's largest (at least four) with absent pedestrians.
+        -> seq [B,R,4] (NLL sum, valid pairs, sum of masked aoe, sum of masked foe), ped [B,R,N,3] (aoe, foe, loss_mask_per_pedestrian),
+        gauss [B,R,5,N,5] (mu_x, mu_y, sigma_x, sigma_y, corr), R = max(S, 1), all on the device (nothing is read back here)."""
+        N, vo, vp, lm, nz = gst_batch("HipGstEvaluator", self.dev, self._stack(v_obs, 3, 1), self._stack(v_pred, 3, 1), self._stack(loss_mask_rel, 2, 0),
+                                      None if noise is None else self._stack(noise, 4, 2), self.MAX_SAMPLES)
+        B, Np, S = vo.shape[0], vo.shape[2], 0 if nz is None else int(nz.shape[1])
+        w = gst_weights(self._params(), "HipGstEvaluator")    # on every call: the parameters may be views of a trainer's bucket rebound since
+        self.ws = workspace(self.ws, int(A.lib().cn_gst_eval_workspace_bytes(B, Np, S)), self.dev)
+        R = max(S, 1)
+        seq, ped, gauss = torch.empty(B, R, 4, device=self.dev), torch.empty(B, R, Np, 3, device=self.dev), torch.empty(B, R, 5, Np, 5, device=self.dev)
+        with torch.cuda.device(self.dev):
+            A.check(A.lib().cn_gst_eval_step(B, Np, S, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(w), A.ptr(nz), C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()),
+                                             A.ptr(seq), A.ptr(ped), A.ptr(gauss), A.stream_ptr()), "cn_gst_eval_step")
+        return seq, ped[:, :, :N], gauss[:, :, :, :N]
+
+    @staticmethod
+    def _stack(x, rank, ax):
+        """A tensor as it is; a list of per-sequence tensors of `rank` axes (a leading axis of one allowed) padded along the pedestrian axis `ax`
+        with zeros (absent pedestrians) and stacked."""
+        if torch.is_tensor(x):
+            return x
+        xs = [t[0] if t.dim() == rank + 1 else t for t in x]
+        n = max(t.shape[ax] for t in xs)
+        out = []
+        for t in xs:
+            if t.shape[ax] != n:
+                shape = list(t.shape)
+                shape[ax] = n - t.shape[ax]
+                t = torch.cat((t, torch.zeros(shape, dtype=t.dtype, device=t.device)), dim=ax)
+            out.append(t)
+        return torch.stack(out, 0)

@@ -6,7 +6,7 @@ every rank owns a disjoint shard of envs and
     global (ppo.py:38-39 semantics over all T x E_total samples);
   * per optimiser step ONE all-reduce of a single flat fp32 gradient bucket (all parameters, ~10 MB) over RCCL/xGMI,
     averaged, then the grad-norm clip and Adam run identically on every rank.
-The bucket and its optimiser step are flat_adam.FlatAdam, shared with gst_train.HipGstTrainer.  update() is one epoch / minibatch loop: a
+The bucket and its optimiser step are flat_adam.FlatAdam, shared with gst_hip.HipGstTrainer.  update() is one epoch / minibatch loop: a
 gradient producer (cn_ppo_minibatch_step, or the autograd-joined graph), then _optimizer_step.
 """
 import functools

@@ -11,7 +11,7 @@ call = t for the observed slice t = 0..4 and 5 + tt - 1 for decode step tt = 1..
 (h * Np + i) * Np + j (i = target row, j = neighbour), site 1 = out_proj output [Np, 64], site 2 = FFN hidden [Np, 128], site 3 = FFN output
 [Np, 64], all row-major; Np = max(N, 4) is the padded pedestrian count the kernel sees.
 
-The graph is the op graph of gst_train._transformer_train / forward_train / negative_log_likelihood_full_partial, one sequence at a time,
+The graph is the op graph of gst.GSTPredictor._transformer / gst_train.forward_train / negative_log_likelihood_full_partial, one sequence at a time,
 with the four F.dropout calls replaced by a multiplication with those arrays; the loss is pooled over the batch like the kernel's (sum of
 masked NLL / valid pairs of the whole batch)."""
 import copy
@@ -69,7 +69,7 @@ def masks(seed, b, call, Np, p):
 
 
 def _layer(model, x, attn_mask, mks, records=None):
-    """gst_train._transformer_train on x [S,H,2] (S slices of one sequence), the F.dropout calls replaced by the arrays mks[s] (the four site
+    """gst.GSTPredictor._transformer on x [S,H,2] (S slices of one sequence), the F.dropout calls replaced by the arrays mks[s] (the four site
     arrays of slice s, sliced to the unpadded crowd)."""
     g = model.gumbel_social_transformer
     L = g.node_encoder_layers[0]

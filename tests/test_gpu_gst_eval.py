@@ -285,6 +285,41 @@ def test_evaluate_test_and_train_through_the_interface(gold, gold_eval, data_dir
         assert runs[0][1]["train_%s_task" % col] == runs[1][1]["train_%s_task" % col]
 
 
+def test_a_sequence_of_more_than_64_pedestrians_takes_the_op_graph_inside_a_batch():
+    """Three sequences of 5, 65 and 4 pedestrians (ragged presence) at batch_size = 2: the second takes the op-graph detour while the first is
+    pending, the third sits at the padding floor of four pedestrians.  The pass returns one row per sequence, the detour's ahead of the batch that was
+    pending (every row against the op graph's row of the same sequence, whose losses lie far apart); the detour's row has the op graph's own bits; validation and test(2 samples, recorded
+    draws) agree with the torch backend at the ragged-batch bars (loss 2e-5, offset errors 1.5e-4)."""
+    from crowdnav_prediction_attngraph_amd import gst_train as T
+    sizes, items, model = (5, 65, 4), [], None
+    for i, n in enumerate(sizes):
+        mdl, lm, v_obs, v_pred, g = _ragged(1, n, 20 + i)
+        model = model or mdl
+        am = (lm[0].t().unsqueeze(2) * lm[0].t().unsqueeze(1)).unsqueeze(0)
+        item = [None] * 12
+        item[4], item[6], item[8], item[10], item[11] = lm, v_obs, v_pred, am[:, :5], am[:, 5:]
+        items.append(item)
+    draws = [torch.randn(2, 5, n, 2, generator=g) for n in sizes]
+    seqs = lambda: ((it[6].shape[2], it) for it in items)     # noqa: E731
+    for what, row, draw in (("validation", T._val_row, None), ("test", T._test_row, lambda n, d=iter(draws): next(d))):
+        hip = T._eval_pass(model, seqs(), "cuda", row, T.HipGstEvaluator(model), 2, draw)
+        assert hip.shape[0] == 3, what
+        hip = hip[[1, 0, 2]]                                  # entry order: the detour, then the batch of the first and the third sequence
+        ref = T._eval_pass(model, seqs(), "cuda", row, None, 2, None if draw is None else (lambda n, d=iter(draws): next(d)))
+        assert hip.shape == ref.shape == (3, 4 if draw is None else 8), what
+        m = [float((it[4].sum(2) == 10).sum()) for it in items]
+        assert list(hip[:, -1]) == m and list(ref[:, -1]) == m and abs(hip[0, 0] - hip[2, 0]) > 100 * BAR, (what, m, hip)
+        assert np.array_equal(hip[1], ref[1]), what + ": the detour is the op graph"
+        _close(torch.from_numpy(hip[:, 0]), torch.from_numpy(ref[:, 0]), BAR, what + " rows: loss")
+        _close(torch.from_numpy(hip[:, 1:-1]), torch.from_numpy(ref[:, 1:-1]), BAR_OE, what + " rows: sums of aoe / foe")
+    a, b = T.evaluate(model, items, "cuda", backend="hip", batch_size=2), T.evaluate(model, items, "cuda", backend="torch")
+    for x, y, bar in zip(a, b, (BAR, BAR_OE, BAR_OE)):
+        assert abs(x - y) <= bar, (a, b)
+    a, b = (T.test(model, items, "cuda", num_samples=2, backend=be, batch_size=2, draws=draws) for be in ("hip", "torch"))
+    for x, y, bar in zip(a, b, (BAR,) + (BAR_OE,) * 6):
+        assert abs(x - y) <= bar, (a, b)
+
+
 def test_bad_arguments_are_refused_with_a_message_and_launch_nothing(gold):
     from crowdnav_prediction_attngraph_amd import _abi as A
     from crowdnav_prediction_attngraph_amd import gst_train as T
