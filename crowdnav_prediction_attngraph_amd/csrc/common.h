@@ -139,6 +139,36 @@ __device__ __forceinline__ float wv_sum(float v)
     v += wv_dpp<0x143, 0xc>(v, 0.0f);
     return wv_readlane(v, 63);
 }
+__device__ __forceinline__ double wv_readlane_d(double v, int lane_uniform)
+{
+    const long long b = __double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), lane_uniform);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), lane_uniform);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// the same DPP steps on the two halves of a double (both halves move with one control word, so a lane always sees a whole operand)
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double wv_dpp(double v, double identity)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v), id = (unsigned long long)__double_as_longlong(identity);
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)id, (int)(unsigned)b, CTRL, ROW_MASK, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp((int)(unsigned)(id >> 32), (int)(unsigned)(b >> 32), CTRL, ROW_MASK, 0xf, false);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+// min is order-independent (no NaN operands here), so the fp64 minimum may take the DPP tree of the fp32 one: 12 DPP moves, 6 v_min_f64
+// and two v_readlane instead of 12 ds_bpermute round trips.  Every lane of the wavefront must be active.  The result is wave-uniform.
+// (Sums keep the xor butterfly below: their association is part of the bits.)
+__device__ __forceinline__ double wv_min_dpp(double v)
+{
+    const double I = __builtin_inf();
+    v = fmin(v, wv_dpp<0x111, 0xf>(v, I));
+    v = fmin(v, wv_dpp<0x112, 0xf>(v, I));
+    v = fmin(v, wv_dpp<0x114, 0xf>(v, I));
+    v = fmin(v, wv_dpp<0x118, 0xf>(v, I));
+    v = fmin(v, wv_dpp<0x142, 0xa>(v, I));
+    v = fmin(v, wv_dpp<0x143, 0xc>(v, I));
+    return wv_readlane_d(v, 63);
+}
 __device__ __forceinline__ double wv_min(double v)
 {
 #pragma unroll

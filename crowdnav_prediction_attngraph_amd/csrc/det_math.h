@@ -106,7 +106,8 @@ __device__ __forceinline__ double det_log(double x)
 // heading -- the direction of its velocity when the robot is holonomic (at rest: +x, or -x for vx = -0.0, as np.arctan2 has it), its theta
 // otherwise.  Decision-equivalent form of arccos(clip(v_fov . v_12)) <= fov / 2 (see the oracle's in_fov for why); coincident agents
 // give NaN and are not visible.
-__device__ __forceinline__ bool in_fov(const cn_env_config &c, double fov, double px1, double py1, double vx1, double vy1, double theta1,
+template <class C>
+__device__ __forceinline__ bool in_fov(const C &c, double fov, double px1, double py1, double vx1, double vy1, double theta1,
                                        double px2, double py2)
 {
     double fx, fy;

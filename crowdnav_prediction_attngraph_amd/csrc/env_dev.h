@@ -79,7 +79,8 @@ struct EnvDev {
 // the by-value kernel argument of one launch, with the stamp slot of `kernel_id` for the current step (measurement aid)
 static EnvDev stamped(const EnvDev &d, int kernel_id) { EnvDev c = d; c.stamp = cn_stamp_slot(kernel_id); return c; }
 
-__device__ __forceinline__ int crowd_size(const EnvDev &s, int e) { return s.nh ? s.nh[e] : s.H; }
+template <class S>
+__device__ __forceinline__ int crowd_size(const S &s, int e) { return s.nh ? s.nh[e] : s.H; }
 
 // The reference's rejection sampling of human positions / goals is unbounded; after this many attempts the last candidate is
 // accepted (same constant and rule in the oracle: oracle/crowdsim_oracle.h ORC_MAX_PLACEMENT_ATTEMPTS).

@@ -7,6 +7,7 @@
 //
 // Files:
 //   env_dev.h    EnvDev (the per-env arrays a launch receives by value), Lp3Hdr, the F_* / R_* field enums
+//   env_profile.h  compile-time config profiles: the view of EnvDev the device code reads (generic = EnvDev; ProfileTrain pins the default training class)
 //   det_math.h   deterministic sin/cos, exp and log (+,-,*,/ only), the field-of-view test
 //   orca.h       RVO2's linear programs and every ORCA kernel listed below (it also brings in row_plan.h, for the lane kernel)
 //   mt19937.h    numpy's legacy RandomState stream (Rng), staged in LDS
@@ -37,6 +38,7 @@
 // Reference semantics (file:line under the reference repo) are cited at each block.
 #include "common.h"
 #include "env_dev.h"
+#include "env_profile.h"
 #include "det_math.h"
 #include "orca.h"
 #include "mt19937.h"
@@ -47,6 +49,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 
 namespace {
 
@@ -169,17 +172,20 @@ __global__ __launch_bounds__(64) void env_obs_kernel(EnvDev s, cn_obs ob)
 // DEFER = true (dense crowds without a lane kernel): the observation is written, the post-observation updates -- which nothing in the
 // observation depends on -- are left to env_post_kernel on the side stream, in front of the ORCA pass that needs the new goals: the
 // long placement loops of the few envs that change goals then run beside the policy forward instead of in front of it.
-template <bool SPLIT, int W = 1, bool DEFER = false>
-__global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev s, const float *actions, cn_obs ob, float *reward_out,
+// PF: the config profile (env_profile.h).  Everything below reads the view `s`; ProfileTrain is instantiated for <false, 1, false> only.
+template <bool SPLIT, int W = 1, bool DEFER = false, class PF = ProfileGeneric>
+__global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev s_arg, const float *actions, cn_obs ob, float *reward_out,
                                                       uint8_t *done_out, uint8_t *info_out, double *ep_ret_out, int32_t *ep_len_out, float *not_done_out)
 {
+    typename EnvViewOf<PF>::type s(s_arg); // generic: a reference to the argument itself
+    typedef typename std::decay<decltype(s)>::type View;
     const CnStampScope stamp_scope(s.stamp);
     const int lane = threadIdx.x & 63;
     const int e = blockIdx.x;
     if constexpr (W > 1) {
         if (threadIdx.x >= 64) { coop_helper_loop<W>(lane, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))); return; }
     }
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     const int H = s.H;
     // ---- gather (indices of the per-slot arrays are clamped to the H slots, not to the crowd size: that is one of the loads)
     const int lj = lane < H ? lane : 0;
@@ -335,7 +341,9 @@ __global__ __launch_bounds__(64 * W, W > 1 ? 2 : 4) void env_step_kernel(EnvDev 
     const double cdx = h.px - rb.px, cdy = h.py - rb.py;
     const double closest = isH ? sqrt(cdx * cdx + cdy * cdy) - h.rad - c.robot_radius : INFINITY;
     const bool collision = wv_any(closest < 0.0);
-    const double dmin = wv_min(closest);
+    double dmin;
+    if constexpr (view_pinned<View>) dmin = wv_min_dpp(closest);
+    else dmin = wv_min(closest);
     const double goal_dist = norm2(rb.px - rb.gx, rb.py - rb.gy);
     const bool reaching_goal = goal_dist < (c.kinematics == CN_KIN_UNICYCLE ? 0.6 : c.robot_radius); // :487-492
     const double global_time = (double)step_counter * c.time_step;
@@ -649,6 +657,11 @@ static bool lane_path_of(const cn_env_batch *env)
     // (a narrowed human field of view goes through the cooperative kernel: the lane kernel has no visibility test in its inner loops)
     return env->d.cfg.humans_policy == CN_HUMANS_ORCA && slots <= 32 && env->d.cfg.human_fov >= 2.0;
 }
+
+// the batch belongs to the default training class: its step launch takes the instantiation compiled for ProfileTrain (env_profile.h);
+// every other batch takes the generic one.  (orca_lane_kernel has no pinned instantiation: the profile removes three of its 49 argument
+// loads and none of its 69 spilled scalars, and measured beside the generic one it was 0.2-0.8 us slower: profiles/HISTORY.md section 17)
+static bool train_profile(const cn_env_batch *env) { return train_profile_of(env->d); }
 
 // refill the next-episode staging of the envs that just consumed theirs (rare: ~1.5 % of envs per step; a 60 us chain of serial fp64
 // work per such env).  It only depends on the step that just ran; nothing needs it before those envs finish their NEXT episode.
@@ -1024,6 +1037,7 @@ extern "C" int cn_env_step(cn_env_batch *env, const float *actions, const cn_obs
             env->post_deferred = true;
         }
         else if (coop) hipLaunchKernelGGL((env_step_kernel<false, 4>), dim3(env->d.E), dim3(256), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
+        else if (train_profile(env)) hipLaunchKernelGGL((env_step_kernel<false, 1, false, ProfileTrain>), dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
         else hipLaunchKernelGGL(env_step_kernel<false>, dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
         CN_CHECK_LAUNCH();
     }

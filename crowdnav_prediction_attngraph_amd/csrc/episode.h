@@ -3,6 +3,7 @@
 // goal changes / respawns.  The kernels that run them are in env_sim.hip, whose translation unit this is part of.
 #pragma once
 #include "env_dev.h"
+#include "env_profile.h"
 #include "det_math.h"
 #include "mt19937.h"
 
@@ -28,14 +29,6 @@ __device__ __forceinline__ bool closer_than(double x, double y, double d)
     if (q < dd * (1.0 - 0x1p-48)) return true;
     if (q > dd * (1.0 + 0x1p-48)) return false;
     return sqrt(q) < d;
-}
-
-__device__ __forceinline__ double wv_readlane_d(double v, int lane_uniform)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b & 0xffffffffll), lane_uniform);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), lane_uniform);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 // ---- a long rejection loop over the W wavefronts of a workgroup (dense crowds, BASELINE configs[4]) ----
@@ -181,11 +174,11 @@ __device__ __forceinline__ void coop_screen_pass(CoopLds<W> &Q, const uint32_t *
 // A candidate whose six words straddle the end of the block rides as lane 0 of the first pass over the regenerated block.  In crowds of ~50 randomised humans these loops run for 10^2 .. 10^5 candidates (BASELINE configs[4]).
 //   kind 0: position of a new human (noise = u * 2),  kind 1: new goal (noise = (u - 0.5) * vp)
 //   humans 0 .. n_list - 1 except `skip` are tested with md = radius + rad_j + discomfort_dist against their position and their goal
-template <int W = 1>
-__device__ __forceinline__ void place_by_rejection(const EnvDev &s, Rng &R, int lane, int kind, double radius, double vp, double md_r, int n_list, int skip,
+template <int W = 1, class S>
+__device__ __forceinline__ void place_by_rejection(const S &s, Rng &R, int lane, int kind, double radius, double vp, double md_r, int n_list, int skip,
                                                    const Robot &rb, const Lane &h, double &out_x, double &out_y)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     const int max_att = c.max_placement_attempts > 0 ? c.max_placement_attempts : CN_MAX_PLACEMENT_ATTEMPTS;
     auto make = [&](double u0, double u1, double u2, double &x, double &y) {
         const double angle = u0 * M_PI * 2.0;
@@ -547,10 +540,10 @@ __device__ __forceinline__ void coop_helper_loop(int lane, int wave)
 // crowd_sim_var_num.py:116-146 generate_circle_crossing_human (+ Agent.__init__/sample_random_attributes draws).
 // All lanes compute the candidate position identically; the min-distance test against the existing agents is
 // lane-parallel.  n_existing = number of humans currently in self.humans (slot itself included on respawn, :455).
-template <int W = 1>
-__device__ __forceinline__ void gen_human(const EnvDev &s, Rng &R, int lane, int slot, int n_existing, const Robot &rb, Lane &h, double &shared_nd)
+template <int W = 1, class S>
+__device__ __forceinline__ void gen_human(const S &s, Rng &R, int lane, int slot, int n_existing, const Robot &rb, Lane &h, double &shared_nd)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     double radius = c.human_radius, vpref = c.human_v_pref;
     if (c.randomize_attributes) {
         shared_nd = rng_uniform(R, lane, 5.0, 10.0); // agent.py:21-22
@@ -570,10 +563,10 @@ __device__ __forceinline__ void gen_human(const EnvDev &s, Rng &R, int lane, int
 
 // crowd_sim.py:415-450 update_human_goals_randomly (every human, goal_change_chance) and :453-485 update_human_goal (one human,
 // end_goal_change_chance: `only` >= 0 selects it)
-template <int W = 1>
-__device__ __forceinline__ void change_goals(const EnvDev &s, Rng &R, int lane, int n, const Robot &rb, Lane &h, int only = -1)
+template <int W = 1, class S>
+__device__ __forceinline__ void change_goals(const S &s, Rng &R, int lane, int n, const Robot &rb, Lane &h, int only = -1)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     const int H = n; // the humans present
     for (int i = only >= 0 ? only : 0; i < (only >= 0 ? only + 1 : H); ++i) {
         double vp_i = __shfl(h.vpref, i, 64);
@@ -590,7 +583,8 @@ __device__ __forceinline__ void change_goals(const EnvDev &s, Rng &R, int lane, 
 
 // detect_visible(robot, human, robot1=True), crowd_sim.py:513-552: inside the robot's field of view (FOV = 2*pi: iff not coincident) and
 // within sensor range; `present`: the slot holds a human.  The observation (write_obs) and cn_env_get_visibility both decide with this function.
-__device__ __forceinline__ bool robot_sees(const cn_env_config &c, const Robot &rb, bool present, double hpx, double hpy, double hrad)
+template <class C>
+__device__ __forceinline__ bool robot_sees(const C &c, const Robot &rb, bool present, double hpx, double hpy, double hrad)
 {
     const double dx = rb.px - hpx, dy = rb.py - hpy;
     bool vis = present && !(dx == 0.0 && dy == 0.0) && (norm2(dx, dy) - c.robot_radius - hrad <= c.sensor_range);
@@ -600,9 +594,10 @@ __device__ __forceinline__ bool robot_sees(const cn_env_config &c, const Robot &
 
 // crowd_sim_var_num.py:233-279 generate_ob / crowd_sim_pred.py:62-97 / crowd_sim_pred_real_gst.py:76-93,
 // crowd_sim.py:558-572 get_num_human_in_fov, :243-273 update_last_human_states.
-__device__ __forceinline__ void write_obs(const EnvDev &s, int e, int lane, int n, bool reset, const Robot &rb, Lane &h, const cn_obs &ob, int step_counter)
+template <class S>
+__device__ __forceinline__ void write_obs(const S &s, int e, int lane, int n, bool reset, const Robot &rb, Lane &h, const cn_obs &ob, int step_counter)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     const int H = s.H, D = s.D, P = s.P; // H observation rows (crowd_sim_var_num.py:249, crowd_sim_pred.py:78), n humans present
     const bool isH = lane < n, isRow = lane < H;
     const bool vis = robot_sees(c, rb, isH, h.px, h.py, h.rad);
@@ -656,7 +651,10 @@ __device__ __forceinline__ void write_obs(const EnvDev &s, int e, int lane, int 
         const double key = vis ? sqrt(ex * ex + ey * ey) : INFINITY;
         int rank = 0;
         for (int m = 0; m < H; ++m) {
-            const double km = __shfl(key, m, 64);
+            // (m is wave-uniform: a pinned view reads lane m with two v_readlane instead of two ds_bpermute round trips -- the same word)
+            double km;
+            if constexpr (view_pinned<S>) km = wv_readlane_d(key, m);
+            else km = __shfl(key, m, 64);
             rank += (km < key || (km == key && m < lane)) ? 1 : 0;
         }
         row = rank;
@@ -702,9 +700,10 @@ __device__ __forceinline__ void write_obs(const EnvDev &s, int e, int lane, int 
 // crowd_sim_var_num.py:303-363 reset (seed, robot, humans, potential, first observation)
 // the RNG-consuming part of reset(): seed, robot, humans (crowd_sim_var_num.py:333-340, :64-146)
 // (case_counter: the caller's copy of s.case_counter[e])
-__device__ __forceinline__ void gen_episode_head(const EnvDev &s, Rng &R, int e, int lane, uint64_t case_counter, Robot &rb, int &n)
+template <class S>
+__device__ __forceinline__ void gen_episode_head(const S &s, Rng &R, int e, int lane, uint64_t case_counter, Robot &rb, int &n)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     const uint64_t offset = c.phase == CN_PHASE_TRAIN ? 2000ull : (c.phase == CN_PHASE_VAL ? 0ull : 1000ull);
     const uint64_t seed = offset + case_counter + (uint64_t)(s.seed_base + e);
     rng_seed(R, (uint32_t)seed, lane);
@@ -737,7 +736,8 @@ __device__ __forceinline__ void gen_episode_head(const EnvDev &s, Rng &R, int e,
     }
     rb.px = px; rb.py = py; rb.gx = gx; rb.gy = gy; rb.vx = 0.0; rb.vy = 0.0;
 }
-__device__ __forceinline__ void gen_episode(const EnvDev &s, Rng &R, int e, int lane, uint64_t case_counter, Robot &rb, Lane &h, double &shared_nd, int &n)
+template <class S>
+__device__ __forceinline__ void gen_episode(const S &s, Rng &R, int e, int lane, uint64_t case_counter, Robot &rb, Lane &h, double &shared_nd, int &n)
 {
     gen_episode_head(s, R, e, lane, case_counter, rb, n);
     for (int i = 0; i < n; ++i) gen_human(s, R, lane, i, i, rb, h, shared_nd);
@@ -745,9 +745,10 @@ __device__ __forceinline__ void gen_episode(const EnvDev &s, Rng &R, int e, int 
 }
 
 // the rest of reset(): belief cleared (:108), case counter advanced (:348), episode statistics, first observation
-__device__ __forceinline__ void finish_reset(const EnvDev &s, int e, int lane, int n, uint64_t case_counter, Robot &rb, Lane &h, const cn_obs &ob, bool with_obs = true)
+template <class S>
+__device__ __forceinline__ void finish_reset(const S &s, int e, int lane, int n, uint64_t case_counter, Robot &rb, Lane &h, const cn_obs &ob, bool with_obs = true)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     h.l0 = h.l1 = h.l2 = h.l3 = h.l4 = 0.0;
     const uint64_t case_size = c.phase == CN_PHASE_TRAIN ? (4294967295ull - 2000ull) : (c.phase == CN_PHASE_VAL ? c.val_size : c.test_size);
     if (lane == 0) {
@@ -764,7 +765,8 @@ __device__ __forceinline__ void finish_reset(const EnvDev &s, int e, int lane, i
 // crowd_sim_var_num.py:303-363 reset.  Uses the pre-generated episode when the side stream has one ready (nx_ready and case_counter: the
 // caller's copies of s.nx_ready[e] and s.case_counter[e]).  The staged episode is read in ONE batch: its MT19937 state goes straight into
 // R.mt (whatever that held is dead) while the records are loaded into the registers of the episode that just ended.
-__device__ __forceinline__ void do_reset(const EnvDev &s, Rng &R, int e, int lane, bool nx_ready, uint64_t case_counter, Robot &rb, Lane &h,
+template <class S>
+__device__ __forceinline__ void do_reset(const S &s, Rng &R, int e, int lane, bool nx_ready, uint64_t case_counter, Robot &rb, Lane &h,
                                          double &shared_nd, int &n, const cn_obs &ob, bool with_obs = true)
 {
     if (nx_ready) {
@@ -792,7 +794,8 @@ __device__ __forceinline__ void do_reset(const EnvDev &s, Rng &R, int e, int lan
     finish_reset(s, e, lane, n, case_counter, rb, h, ob, with_obs);
 }
 
-__device__ __forceinline__ void load_env(const EnvDev &s, int e, int lane, Robot &rb, Lane &h)
+template <class S>
+__device__ __forceinline__ void load_env(const S &s, int e, int lane, Robot &rb, Lane &h)
 {
     const int H = s.H;
     const int lj = lane < H ? lane : 0;
@@ -805,7 +808,8 @@ __device__ __forceinline__ void load_env(const EnvDev &s, int e, int lane, Robot
     const double *r = s.rob + (size_t)e * 8;
     rb.px = r[R_PX]; rb.py = r[R_PY]; rb.vx = r[R_VX]; rb.vy = r[R_VY]; rb.gx = r[R_GX]; rb.gy = r[R_GY]; rb.theta = r[R_THETA]; rb.pot = r[R_POT];
 }
-__device__ __forceinline__ void store_env(const EnvDev &s, int e, int lane, const Robot &rb, const Lane &h)
+template <class S>
+__device__ __forceinline__ void store_env(const S &s, int e, int lane, const Robot &rb, const Lane &h)
 {
     const int H = s.H;
     if (lane < H) {
@@ -823,8 +827,8 @@ __device__ __forceinline__ void store_env(const EnvDev &s, int e, int lane, cons
 }
 
 // the body of env_pregen_kernel (env_sim.hip): one wavefront, one env; R.mt = that wavefront's 624-word LDS slice
-template <int W = 1>
-__device__ __forceinline__ void pregen_env(const EnvDev &s, int e, int lane, long long budget, Rng &R)
+template <int W = 1, class S>
+__device__ __forceinline__ void pregen_env(const S &s, int e, int lane, long long budget, Rng &R)
 {
     if (s.nx_ready[e]) return;
     const long long t0 = wall_clock64();
@@ -882,10 +886,10 @@ __device__ __forceinline__ void pregen_env(const EnvDev &s, int e, int lane, lon
 }
 
 // goal changes every 5 s and respawns of the humans that reached their goal (crowd_sim_var_num.py:446-456): after the observation
-template <int W = 1>
-__device__ __forceinline__ void post_obs_updates(const EnvDev &s, Rng &R, int e, int lane, int n, int step_counter, const Robot &rb, Lane &h, double &shared_nd)
+template <int W = 1, class S>
+__device__ __forceinline__ void post_obs_updates(const S &s, Rng &R, int e, int lane, int n, int step_counter, const Robot &rb, Lane &h, double &shared_nd)
 {
-    const cn_env_config &c = s.cfg;
+    const auto &c = s.cfg;
     const int H = n; // the humans present
     const bool isH = lane < H;
     const int period = (int)(5.0 / c.time_step + 0.5);

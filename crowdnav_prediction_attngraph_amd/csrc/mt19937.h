@@ -41,14 +41,16 @@ __device__ __forceinline__ void mt_dma(uint32_t *dst, const uint32_t *src, int l
 __device__ __forceinline__ void mt_dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // a wavefront that knows it will draw fetches its stream early; the rng_load at the first draw then only waits for it
-__device__ __forceinline__ void rng_prefetch(Rng &R, const EnvDev &s, int e, int lane)
+template <class S>
+__device__ __forceinline__ void rng_prefetch(Rng &R, const S &s, int e, int lane)
 {
     if (R.loaded || R.pre_ok) return;
     mt_dma(R.mt, s.mt + (size_t)e * MT_N, lane);
     R.pre_pos = s.mt_pos[e];
     R.pre_ok = true;
 }
-__device__ __forceinline__ void rng_load(Rng &R, const EnvDev &s, int e, int lane)
+template <class S>
+__device__ __forceinline__ void rng_load(Rng &R, const S &s, int e, int lane)
 {
     if (R.loaded) return;
     if (R.pre_ok) {
@@ -61,7 +63,8 @@ __device__ __forceinline__ void rng_load(Rng &R, const EnvDev &s, int e, int lan
     R.loaded = true;
     rng_sync();
 }
-__device__ __forceinline__ void rng_store(Rng &R, const EnvDev &s, int e, int lane)
+template <class S>
+__device__ __forceinline__ void rng_store(Rng &R, const S &s, int e, int lane)
 {
     if (!R.loaded) return;
     rng_sync();
