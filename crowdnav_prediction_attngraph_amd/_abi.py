@@ -80,6 +80,31 @@ POLICY_WEIGHT_KEYS = [
 ]
 
 
+# order == field order of cn_srnn_weights (DS-RNN baseline, base='srnn'); values == reference state_dict keys.  The three modules no gradient
+# reaches (base.humanNodeRNN.edge_embed, base.human_node_final_linear, base.spatial_linear) are not part of the forward
+SRNN_WEIGHT_KEYS = [
+    ("enc_s_w", "base.humanhumanEdgeRNN_spatial.encoder_linear.weight"), ("enc_s_b", "base.humanhumanEdgeRNN_spatial.encoder_linear.bias"),
+    ("gru_s_w_ih", "base.humanhumanEdgeRNN_spatial.gru.weight_ih_l0"), ("gru_s_w_hh", "base.humanhumanEdgeRNN_spatial.gru.weight_hh_l0"),
+    ("gru_s_b_ih", "base.humanhumanEdgeRNN_spatial.gru.bias_ih_l0"), ("gru_s_b_hh", "base.humanhumanEdgeRNN_spatial.gru.bias_hh_l0"),
+    ("enc_t_w", "base.humanhumanEdgeRNN_temporal.encoder_linear.weight"), ("enc_t_b", "base.humanhumanEdgeRNN_temporal.encoder_linear.bias"),
+    ("gru_t_w_ih", "base.humanhumanEdgeRNN_temporal.gru.weight_ih_l0"), ("gru_t_w_hh", "base.humanhumanEdgeRNN_temporal.gru.weight_hh_l0"),
+    ("gru_t_b_ih", "base.humanhumanEdgeRNN_temporal.gru.bias_ih_l0"), ("gru_t_b_hh", "base.humanhumanEdgeRNN_temporal.gru.bias_hh_l0"),
+    ("attn_temporal_w", "base.attn.temporal_edge_layer.0.weight"), ("attn_temporal_b", "base.attn.temporal_edge_layer.0.bias"),
+    ("attn_spatial_w", "base.attn.spatial_edge_layer.0.weight"), ("attn_spatial_b", "base.attn.spatial_edge_layer.0.bias"),
+    ("node_enc_w", "base.humanNodeRNN.encoder_linear.weight"), ("node_enc_b", "base.humanNodeRNN.encoder_linear.bias"),
+    ("edge_embed_w", "base.humanNodeRNN.edge_attention_embed.weight"), ("edge_embed_b", "base.humanNodeRNN.edge_attention_embed.bias"),
+    ("node_gru_w_ih", "base.humanNodeRNN.gru.weight_ih_l0"), ("node_gru_w_hh", "base.humanNodeRNN.gru.weight_hh_l0"),
+    ("node_gru_b_ih", "base.humanNodeRNN.gru.bias_ih_l0"), ("node_gru_b_hh", "base.humanNodeRNN.gru.bias_hh_l0"),
+    ("out_w", "base.humanNodeRNN.output_linear.weight"), ("out_b", "base.humanNodeRNN.output_linear.bias"),
+    ("actor0_w", "base.actor.0.weight"), ("actor0_b", "base.actor.0.bias"), ("actor2_w", "base.actor.2.weight"), ("actor2_b", "base.actor.2.bias"),
+    ("critic0_w", "base.critic.0.weight"), ("critic0_b", "base.critic.0.bias"), ("critic2_w", "base.critic.2.weight"), ("critic2_b", "base.critic.2.bias"),
+    ("critic_linear_w", "base.critic_linear.weight"), ("critic_linear_b", "base.critic_linear.bias"),
+    ("robot_linear_w", "base.robot_linear.weight"), ("robot_linear_b", "base.robot_linear.bias"),
+    ("fc_mean_w", "dist.fc_mean.weight"), ("fc_mean_b", "dist.fc_mean.bias"),
+    ("logstd", "dist.logstd._bias"),
+]
+
+
 # order == field order of cn_gst_weights; values == keys of the reference's GST checkpoint
 GST_WEIGHT_KEYS = [
     ("node_embedding_w", "gumbel_social_transformer.node_embedding.weight"), ("node_embedding_b", "gumbel_social_transformer.node_embedding.bias"),
@@ -121,6 +146,10 @@ class PolicyWeights(C.Structure):
     _fields_ = [(name, C.c_void_p) for name, _ in POLICY_WEIGHT_KEYS]
 
 
+class SrnnWeights(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _ in SRNN_WEIGHT_KEYS]
+
+
 PPO_BATCH_TENSORS = ["env_idx", "robot_node", "temporal_edges", "spatial_edges", "detected_human_num", "h0", "masks", "actions", "value_preds", "returns",
                      "old_logp", "adv"]     # pointer fields of cn_ppo_batch, in field order
 
@@ -147,6 +176,7 @@ ABI_SYMBOLS = [
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
     "cn_env_get_visibility", "cn_render_scenes",
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
+    "cn_srnn_create", "cn_srnn_destroy", "cn_srnn_set_weights", "cn_srnn_act", "cn_srnn_get_value", "cn_srnn_get_taps", "cn_srnn_set_gemm_mode",
 ]
 
 _lib = None
@@ -205,6 +235,13 @@ def lib():
         L.cn_policy_act.argtypes = [vp, i32, C.POINTER(Obs), vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_policy_get_value.argtypes = [vp, i32, C.POINTER(Obs), vp, vp, vp, vp]
         L.cn_policy_get_taps.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.cn_srnn_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+        L.cn_srnn_destroy.argtypes = [vp]
+        L.cn_srnn_set_weights.argtypes = [vp, C.POINTER(SrnnWeights), vp]
+        L.cn_srnn_act.argtypes = [vp, i32, C.POINTER(Obs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_srnn_get_value.argtypes = [vp, i32, C.POINTER(Obs), vp, vp, vp, vp, vp]
+        L.cn_srnn_get_taps.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.cn_srnn_set_gemm_mode.argtypes = [vp, i32]
         L.cn_policy_set_profiling.argtypes = [vp, i32]
         L.cn_policy_set_gemm_mode.argtypes = [vp, i32]
         L.cn_policy_set_self_attention.argtypes = [vp, i32]

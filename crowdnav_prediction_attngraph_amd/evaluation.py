@@ -203,7 +203,7 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     """test_size: the episode count of the sequential protocol (episode k runs case 2 k mod the config's test_size), or a sequence of case
     numbers to run instead (render_episodes).  poll_every: the count of running episodes is read back (the loop's only host synchronisation)
     every that many steps; steps taken after the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
-    hip_policy: a HipPolicy handle to run instead of actor_critic's own (train() evaluates through a second handle so that the training
+    hip_policy: a HipPolicy (DS-RNN baseline: HipSrnn) handle to run instead of actor_critic's own (train() evaluates through a second handle so that the training
     rollout finds its handle as it left it); use_kernel=False: the torch-op bookkeeping; per_env: a dict that receives the per-env results;
     frame_fn(t, env, obs): called once after the reset (t = 0) and once after every step (t = steps taken) with the HipEnvBatch and the
     observation it returned, e.g. to draw the state (render_episodes); it must leave both as they are."""
@@ -241,10 +241,13 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     if frame_fn is not None:
         frame_fn(0, env, obs)
     pol = None
+    srnn = actor_critic is not None and getattr(actor_critic, "is_srnn_baseline", False)     # DS-RNN: the edge state is carried as well
     if act_fn is None and not scripted:
-        pol = hip_policy if hip_policy is not None else actor_critic._hip_policy(E, device)
+        pol = hip_policy if hip_policy is not None else (actor_critic._hip_srnn(E, device) if srnn else actor_critic._hip_policy(E, device))
     zero_action = torch.zeros(E, 2, device=device)
     hx = [torch.zeros(E, 1, 128, device=device), torch.zeros(E, 1, 128, device=device)]
+    if srnn:
+        ex = [torch.zeros(E, env.H + 1, 256, device=device), torch.zeros(E, env.H + 1, 256, device=device)]
     acc = EvalAccumulator(E, device, use_kernel=use_kernel)
     acc.start(obs["robot_node"])
     masks = acc.masks
@@ -262,6 +265,12 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
                 pobs["spatial_edges"], _ = pretext.process(obs, zero_reward if t == 0 else rew)
             if act_fn is not None:
                 action = act_fn(t, pobs)
+            elif srnn:
+                # both states ping-pong between two buffers; the masks zero them at episode ends inside the kernels
+                out = dict(value=torch.empty(E, 1, device=device), action=torch.empty(E, 2, device=device), logp=torch.empty(E, 1, device=device),
+                           hxs=hx[(t + 1) & 1], edge_hxs=ex[(t + 1) & 1])
+                pol.act(pobs, hx[t & 1], ex[t & 1], masks, eps=None, out=out)
+                action = out["action"]
             else:
                 out = pol.act(pobs, hx[t & 1], masks, eps=None)      # deterministic: dist.mode() (model.py:66-67)
                 hx[(t + 1) & 1] = out["hxs"].view(E, 1, 128)

@@ -432,6 +432,94 @@ class HipPolicy:
         A.check(A.lib().cn_policy_reset_profile(self._h), "cn_policy_reset_profile")
 
 
+class HipSrnn:
+    """cn_srnn handle: rollout-time forward (act / get_value) of the DS-RNN baseline (Policy(base='srnn')).  Two launches per forward."""
+
+    def __init__(self, human_num, edge_width, max_envs, device=None):
+        _need_cuda()
+        self.H, self.D, self.maxE = int(human_num), int(edge_width), int(max_envs)
+        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
+        h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_srnn_create(self.H, self.D, self.maxE, C.byref(h)), "cn_srnn_create")
+        self._h = h
+        self._keep = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h:
+            A.lib().cn_srnn_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_weights(self, state_dict):
+        """state_dict: reference key -> float32 device tensor (the library snapshots them and splits the edge-GRU matrices)."""
+        w = A.SrnnWeights()
+        keep = []
+        for field, key in A.SRNN_WEIGHT_KEYS:
+            t = state_dict[key].detach()
+            if t.dtype != torch.float32 or t.device != self.device:
+                t = t.to(device=self.device, dtype=torch.float32)
+            t = t.contiguous()
+            keep.append(t)
+            setattr(w, field, t.data_ptr())
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_srnn_set_weights(self._h, C.byref(w), A.stream_ptr()), "cn_srnn_set_weights")
+        self._keep = keep  # keep sources alive until the async copies are ordered behind later work on the stream
+
+    @staticmethod
+    def _obs(obs):
+        o = A.Obs()
+        o.robot_node, o.temporal_edges, o.spatial_edges = A.ptr(obs["robot_node"]), A.ptr(obs["temporal_edges"]), A.ptr(obs["spatial_edges"])
+        return o
+
+    def act(self, obs, hxs, edge_hxs, masks, eps=None, out=None):
+        """hxs [E,128] (or [E,1,128]), edge_hxs [E,H+1,256], masks [E,1].  out: dict(value, action, logp, hxs, edge_hxs) written in place (the
+        rollout passes storage rows); out["edge_hxs"] may be edge_hxs itself."""
+        E = obs["robot_node"].shape[0]
+        dev = self.device
+        if out is None:
+            out = dict(value=torch.empty(E, 1, device=dev), action=torch.empty(E, 2, device=dev), logp=torch.empty(E, 1, device=dev),
+                       hxs=torch.empty(E, 1, 128, device=dev), edge_hxs=torch.empty(E, self.H + 1, 256, device=dev))
+        if tuple(out["edge_hxs"].shape) != (E, self.H + 1, 256) or tuple(edge_hxs.shape) != (E, self.H + 1, 256) or hxs.numel() != E * 128:
+            raise A.CnError("HipSrnn.act: hidden state shapes must be [E,128] and [E,H+1,256]")
+        o = self._obs(obs)
+        with torch.cuda.device(dev):
+            A.check(A.lib().cn_srnn_act(self._h, E, C.byref(o), A.ptr(hxs.contiguous()), A.ptr(edge_hxs.contiguous()), A.ptr(masks.contiguous()),
+                                        A.ptr(None if eps is None else eps.contiguous()), A.ptr(out["value"]), A.ptr(out["action"]),
+                                        A.ptr(out["logp"]), A.ptr(out["hxs"]), A.ptr(out["edge_hxs"]), A.stream_ptr()), "cn_srnn_act")
+        return out
+
+    def get_value(self, obs, hxs, edge_hxs, masks, out=None):
+        E = obs["robot_node"].shape[0]
+        if out is None:
+            out = torch.empty(E, 1, device=self.device)
+        if tuple(edge_hxs.shape) != (E, self.H + 1, 256) or hxs.numel() != E * 128:
+            raise A.CnError("HipSrnn.get_value: hidden state shapes must be [E,128] and [E,H+1,256]")
+        o = self._obs(obs)
+        with torch.cuda.device(self.device):
+            A.check(A.lib().cn_srnn_get_value(self._h, E, C.byref(o), A.ptr(hxs.contiguous()), A.ptr(edge_hxs.contiguous()), A.ptr(masks.contiguous()),
+                                              A.ptr(out), A.stream_ptr()), "cn_srnn_get_value")
+        return out
+
+    def taps(self, E):
+        dev, H = self.device, self.H
+        t = dict(edge_out=torch.empty(E, H + 1, 256, device=dev), attn=torch.empty(E, H, device=dev), weighted=torch.empty(E, 256, device=dev),
+                 node_out=torch.empty(E, 256, device=dev), actor_feat=torch.empty(E, 256, device=dev))
+        with torch.cuda.device(dev):
+            A.check(A.lib().cn_srnn_get_taps(self._h, E, A.ptr(t["edge_out"]), A.ptr(t["attn"]), A.ptr(t["weighted"]), A.ptr(t["node_out"]),
+                                             A.ptr(t["actor_feat"]), A.stream_ptr()), "cn_srnn_get_taps")
+        return t
+
+    def set_gemm_mode(self, mode):
+        """'bf16x3' (default: the two edge-GRU products as split-precision MFMA) or 'fp32' (exact fp32 MFMA)."""
+        A.check(A.lib().cn_srnn_set_gemm_mode(self._h, {"fp32": 0, "bf16x3": 1}[mode]), "cn_srnn_set_gemm_mode")
+
+
 def compact_visible(spatial_edges, visible_masks):
     """args.sort_humans = False: (spatial_edges [B,H,D] with the visible humans moved to the front, detected [B,1] = max(1, visible)) --
     cn_obs_compact_visible; see include/crowdnav_hip.h for why this equals the reference's mask-based attention."""
@@ -1030,6 +1118,8 @@ class MinibatchStepper:
     @staticmethod
     def supported(policy, rollouts):
         base = policy.base
+        if getattr(policy, "is_srnn_baseline", False):      # DS-RNN: cn_ppo_minibatch_step knows the attention-graph network only
+            return False
         if not (base.use_self_attn and base.sort_humans and base.train_gemm_mode == "bf16x3" and base.train_fused_hh and base.train_fused_rn
                 and base.fused_rn_shapes_ok() and base.human_num <= 48 and base.edge_width <= 16):
             return False

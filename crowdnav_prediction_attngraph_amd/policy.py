@@ -1,4 +1,5 @@
-"""Policy -- host-side mirror of the reference's `rl.networks.model.Policy` (selfAttn_merge_srnn base + DiagGaussian).
+"""Policy -- host-side mirror of the reference's `rl.networks.model.Policy` (selfAttn_merge_srnn base, or the DS-RNN baseline 'srnn', +
+DiagGaussian).
 
 Same constructor signature, `act` / `get_value` / `evaluate_actions` contracts and state-dict keys as
 /root/reference/rl/networks/model.py:14-90 and rl/networks/selfAttn_srnn_temp_node.py:287-449, so reference
@@ -397,16 +398,163 @@ class AttnGraphBase(nn.Module):
         return value, self._mlp2(self.actor, out), h
 
 
+class _SrnnRNN(nn.Module):
+    """RNNBase of rl/networks/srnn_model.py:10-30: the GRU is created, and orthogonally initialised, before the Linear layers of the subclass.
+    The parameters live in nn.GRU for checkpoint-key parity; the forward below never calls the module (explicit cells: no vendor RNN library)."""
+
+    def __init__(self, input_size, rnn_size):
+        super().__init__()
+        self.gru = nn.GRU(input_size, rnn_size)
+        for name, param in self.gru.named_parameters():
+            if "bias" in name:
+                nn.init.constant_(param, 0)
+            elif "weight" in name:
+                nn.init.orthogonal_(param)
+
+
+class _SrnnNodeRNN(_SrnnRNN):
+    """HumanNodeRNN (srnn_model.py:108-146).  edge_embed is constructed and never used (a dead module: no gradient, in the state dict)."""
+
+    def __init__(self, rnn_size, embedding_size, input_size, edge_rnn_size, output_size):
+        super().__init__(embedding_size * 2, rnn_size)
+        self.encoder_linear = nn.Linear(input_size, embedding_size)
+        self.edge_embed = nn.Linear(edge_rnn_size, embedding_size)
+        self.edge_attention_embed = nn.Linear(edge_rnn_size * 2, embedding_size)
+        self.output_linear = nn.Linear(rnn_size, output_size)
+
+
+class _SrnnEdgeRNN(_SrnnRNN):
+    """HumanHumanEdgeRNN (srnn_model.py:177-199)."""
+
+    def __init__(self, input_size, embedding_size, rnn_size):
+        super().__init__(embedding_size, rnn_size)
+        self.encoder_linear = nn.Linear(input_size, embedding_size)
+
+
+def _gru_cell(gi, h, w_hh, b_hh):
+    """torch's GRU cell (gate order r, z, n) on a precomputed input side gi = W_i x + b_i."""
+    gh = F.linear(h, w_hh, b_hh)
+    i_r, i_z, i_n = gi.chunk(3, -1)
+    h_r, h_z, h_n = gh.chunk(3, -1)
+    r = torch.sigmoid(i_r + h_r)
+    z = torch.sigmoid(i_z + h_z)
+    n = torch.tanh(i_n + r * h_n)
+    return (1.0 - z) * n + z * h
+
+
+class SRNNBase(nn.Module):
+    """The DS-RNN baseline body (`base='srnn'`: rl/networks/srnn_model.py:326-468, the `args.env_type == 'crowd_sim'` branch, i.e. a 7-wide robot
+    node).  Two edge GRUs (one temporal edge, H spatial edges, hidden 256) whose state is LIVE -- `human_human_edge_rnn` [N,H+1,256], slot 0 the
+    temporal edge --, dot-product attention over ALL H slots (no mask: detected_human_num / visible_masks are not read), a node GRU (128) and the
+    actor / critic trunks.  Module names and construction order are the reference's: seeded inits are bit-identical and reference checkpoints load.
+    Three modules never reach the output and never get a gradient (humanNodeRNN.edge_embed, human_node_final_linear, spatial_linear)."""
+
+    DEAD_MODULES = ("humanNodeRNN.edge_embed", "human_node_final_linear", "spatial_linear")
+
+    def __init__(self, obs_space_dict, args):
+        super().__init__()
+        self.is_recurrent = True
+        self.args = args
+        self.human_num = obs_space_dict["spatial_edges"].shape[0]
+        self.edge_width = obs_space_dict["spatial_edges"].shape[1]
+        self.seq_length = _arg(args, "seq_length", 30)
+        self.nenv = _arg(args, "num_processes", 16)
+        self.nminibatch = _arg(args, "num_mini_batch", 2)
+        self.human_node_rnn_size = _arg(args, "human_node_rnn_size", 128)
+        self.human_human_edge_rnn_size = _arg(args, "human_human_edge_rnn_size", 256)
+        self.output_size = _arg(args, "human_node_output_size", 256)
+        emb = _arg(args, "human_node_embedding_size", 64)
+        edge_emb = _arg(args, "human_human_edge_embedding_size", 64)
+        attention_size = _arg(args, "attention_size", 64)
+        node_in = _arg(args, "human_node_input_size", 3)
+        temporal_in = _arg(args, "human_human_edge_input_size", 2)
+        if (self.human_node_rnn_size, self.human_human_edge_rnn_size, self.output_size, emb, attention_size) != (128, 256, 256, 64, 64) \
+                or (edge_emb, node_in, temporal_in) != (64, 3, 2):
+            raise NotImplementedError("the HIP kernels are specialised to the reference's network sizes (128/256/256/64/64)")
+        if _arg(args, "env_type", "crowd_sim") != "crowd_sim":
+            raise NotImplementedError("only the env_type == 'crowd_sim' branch of srnn_model.py:378 (robot node width 7) is implemented")
+        if not 1 <= self.human_num <= 64:
+            raise NotImplementedError("crowds of 1..64 humans (CN_MAX_HUMANS)")
+        # the flags of the attention-graph network that the rest of the package reads off a base; DS-RNN reads neither the count nor the masks
+        self.use_self_attn, self.sort_humans = False, True
+        gain = math.sqrt(2)
+        # construction order == srnn_model.py:354-386
+        self.humanNodeRNN = _SrnnNodeRNN(self.human_node_rnn_size, emb, node_in, self.human_human_edge_rnn_size, self.output_size)
+        self.humanhumanEdgeRNN_spatial = _SrnnEdgeRNN(self.edge_width, edge_emb, self.human_human_edge_rnn_size)
+        self.humanhumanEdgeRNN_temporal = _SrnnEdgeRNN(temporal_in, edge_emb, self.human_human_edge_rnn_size)
+        self.attn = _EdgeAttention(self.human_human_edge_rnn_size, attention_size)
+        h = self.output_size
+        self.actor = nn.Sequential(_ortho(nn.Linear(h, h), gain), nn.Tanh(), _ortho(nn.Linear(h, h), gain), nn.Tanh())
+        self.critic = nn.Sequential(_ortho(nn.Linear(h, h), gain), nn.Tanh(), _ortho(nn.Linear(h, h), gain), nn.Tanh())
+        self.critic_linear = _ortho(nn.Linear(h, 1), gain)
+        self.robot_linear = _ortho(nn.Linear(7, 3), gain)
+        self.human_node_final_linear = _ortho(nn.Linear(self.output_size, 2), gain)
+        self.spatial_linear = _ortho(nn.Linear(self.edge_width, 2), gain)
+
+    def counted_inputs(self, inputs):
+        return inputs
+
+    @staticmethod
+    def _edge_gi(rnn, x):
+        """ReLU(encoder_linear(x)) and the input side of the GRU for all time steps at once."""
+        e = F.relu(F.linear(x, rnn.encoder_linear.weight, rnn.encoder_linear.bias))
+        return F.linear(e, rnn.gru.weight_ih_l0, rnn.gru.bias_ih_l0)
+
+    def attention(self, h_t, h_s):
+        """EdgeAttention (srnn_model.py:256-323) on [..., 256] and [..., H, 256]: the temperature H / sqrt(64) MULTIPLIES, softmax over all H
+        slots without a mask.  Returns (weighted [..., 256], attention weights [..., H])."""
+        H = h_s.shape[-2]
+        te = F.linear(h_t, self.attn.temporal_edge_layer[0].weight, self.attn.temporal_edge_layer[0].bias)
+        se = F.linear(h_s, self.attn.spatial_edge_layer[0].weight, self.attn.spatial_edge_layer[0].bias)
+        a = torch.softmax((te.unsqueeze(-2) * se).sum(-1) * (H / math.sqrt(64.0)), dim=-1)
+        return (a.unsqueeze(-1) * h_s).sum(-2), a
+
+    def forward_sequence(self, inputs, node_h0, edge_h0, masks, T, N, taps=None):
+        """inputs: dict of [T*N, ...] (T-major), node_h0 [N,1,128] or [N,128], edge_h0 [N,H+1,256], masks [T*N,1].
+        Returns value [T*N,1], actor features [T*N,256], node h_T [N,128], edge h_T [N,H+1,256].  The state is multiplied by masks[t] at EVERY
+        step, which equals the reference's split of the sequence at the steps where any env has a zero mask (srnn_model.py:52-104)."""
+        B, H = T * N, self.human_num
+        rn = inputs["robot_node"].reshape(B, 7)
+        m = masks.reshape(T, N, 1)
+        et, es, node = self.humanhumanEdgeRNN_temporal, self.humanhumanEdgeRNN_spatial, self.humanNodeRNN
+        gi_t = self._edge_gi(et, inputs["temporal_edges"].reshape(B, 2)).view(T, N, -1)
+        gi_s = self._edge_gi(es, inputs["spatial_edges"].reshape(B, H, self.edge_width)).view(T, N, H, -1)
+        edge_h0 = edge_h0.reshape(N, H + 1, -1)
+        h_t, h_s = edge_h0[:, 0], edge_h0[:, 1:]
+        hts, hss = [], []
+        for t in range(T):
+            h_t = _gru_cell(gi_t[t], h_t * m[t], et.gru.weight_hh_l0, et.gru.bias_hh_l0)
+            h_s = _gru_cell(gi_s[t], h_s * m[t].unsqueeze(1), es.gru.weight_hh_l0, es.gru.bias_hh_l0)
+            hts.append(h_t)
+            hss.append(h_s)
+        ht_all, hs_all = torch.stack(hts, 0), torch.stack(hss, 0)                   # [T,N,256], [T,N,H,256]
+        weighted, a = self.attention(ht_all, hs_all)
+        enc = F.relu(F.linear(F.linear(rn, self.robot_linear.weight, self.robot_linear.bias), node.encoder_linear.weight, node.encoder_linear.bias))
+        ee = F.relu(F.linear(torch.cat((ht_all, weighted), -1).view(B, -1), node.edge_attention_embed.weight, node.edge_attention_embed.bias))
+        gi_n = F.linear(torch.cat((enc, ee), -1), node.gru.weight_ih_l0, node.gru.bias_ih_l0).view(T, N, -1)
+        h_n = node_h0.reshape(N, -1)
+        hns = []
+        for t in range(T):
+            h_n = _gru_cell(gi_n[t], h_n * m[t], node.gru.weight_hh_l0, node.gru.bias_hh_l0)
+            hns.append(h_n)
+        out = F.linear(torch.stack(hns, 0).view(B, -1), node.output_linear.weight, node.output_linear.bias)
+        feat = self.actor(out)
+        value = _skinny_linear(self.critic(out), self.critic_linear.weight, self.critic_linear.bias)
+        if taps is not None:
+            taps.update(edge_out=torch.cat((h_t.unsqueeze(1), h_s), 1), attn=a.reshape(B, H), weighted=weighted.reshape(B, -1), node_out=out, actor_feat=feat)
+        return value, feat, h_n, torch.cat((h_t.unsqueeze(1), h_s), 1)
+
+
 class Policy(nn.Module):
     """Drop-in for rl.networks.model.Policy."""
 
     def __init__(self, obs_shape, action_space, base=None, base_kwargs=None):
         super().__init__()
-        if base not in ("selfAttn_merge_srnn", None):
-            raise NotImplementedError("only base='selfAttn_merge_srnn' is implemented (the DS-RNN baseline 'srnn' is out of scope)")
+        if base not in ("selfAttn_merge_srnn", "srnn", None):
+            raise NotImplementedError("only base='selfAttn_merge_srnn' and base='srnn' are implemented")
         if action_space.__class__.__name__ != "Box":
             raise NotImplementedError("only Box(2) action spaces (holonomic robot) are implemented")
-        self.base = AttnGraphBase(obs_shape, base_kwargs)
+        self.base = (SRNNBase if base == "srnn" else AttnGraphBase)(obs_shape, base_kwargs)
         self.srnn = True
         self.dist = _DiagGaussian(self.base.output_size, action_space.shape[0])
         self._hip = None
@@ -445,8 +593,72 @@ class Policy(nn.Module):
 
     def weights_changed(self):
         """Tell the rollout path that parameter storage was written through raw pointers (the fused Adam kernel): the next
-        act / get_value re-snapshots the weights (cn_policy_set_weights)."""
+        act / get_value re-snapshots the weights (cn_policy_set_weights / cn_srnn_set_weights)."""
         self._hip_version = None
+
+    # ---- DS-RNN baseline (base='srnn'): cn_srnn handle, managed like the cn_policy one above ----
+    # arithmetic of the two edge-GRU products (cn_srnn_set_gemm_mode): 'bf16x3' = split-precision MFMA (default), 'fp32' = exact fp32 MFMA
+    srnn_gemm_mode = "bf16x3"
+
+    @property
+    def is_srnn_baseline(self):
+        return isinstance(self.base, SRNNBase)
+
+    def _hip_srnn(self, E, device):
+        from .hip import HipSrnn
+        if self._hip is None or self._hip.maxE < E or self._hip.device != device:
+            self._hip = HipSrnn(self.base.human_num, self.base.edge_width, E, device=device)
+            self._hip_version = None
+            self._hip_mode = None
+        if getattr(self, "_hip_mode", None) != self.srnn_gemm_mode:
+            self._hip.set_gemm_mode(self.srnn_gemm_mode)
+            self._hip_mode = self.srnn_gemm_mode
+        ver = self._weights_version()
+        if ver != self._hip_version:
+            self._hip.set_weights(self.state_dict())
+            self._hip_version = ver
+        return self._hip
+
+    def _srnn_obs32(self, inputs):
+        return {k: (v if v.dtype == torch.float32 else v.float()).contiguous() for k, v in inputs.items() if k in ("robot_node", "temporal_edges", "spatial_edges")}
+
+    def _srnn_act(self, inputs, rnn_hxs, masks, deterministic):
+        E, H = inputs["robot_node"].shape[0], self.base.human_num
+        hx, ex = rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"]
+        if hx.is_cuda:
+            pol = self._hip_srnn(E, hx.device)
+            eps = None if deterministic else torch.randn(E, 2, device=hx.device)
+            out = pol.act(self._srnn_obs32(inputs), hx.reshape(E, 128).float(), ex.reshape(E, H + 1, 256).float(), masks.reshape(E, 1).float(), eps=eps)
+            return out["value"], out["action"], out["logp"], {"human_node_rnn": out["hxs"], "human_human_edge_rnn": out["edge_hxs"]}
+        with torch.no_grad():
+            value, feat, h, e = self.base.forward_sequence(inputs, hx, ex, masks, 1, E)
+            mean = self.dist.fc_mean(feat)
+            std = self.dist.logstd(torch.zeros_like(mean)).exp()
+            action = mean if deterministic else mean + std * torch.randn_like(mean)
+            logp = self._log_prob(mean, std, action)
+        return value, action, logp, {"human_node_rnn": h.view(E, 1, 128), "human_human_edge_rnn": e}
+
+    def _srnn_get_value(self, inputs, rnn_hxs, masks):
+        E, H = inputs["robot_node"].shape[0], self.base.human_num
+        hx, ex = rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"]
+        if hx.is_cuda:
+            return self._hip_srnn(E, hx.device).get_value(self._srnn_obs32(inputs), hx.reshape(E, 128).float(), ex.reshape(E, H + 1, 256).float(),
+                                                          masks.reshape(E, 1).float())
+        with torch.no_grad():
+            value, _, _, _ = self.base.forward_sequence(inputs, hx, ex, masks, 1, E)
+        return value
+
+    def _srnn_evaluate_actions(self, inputs, rnn_hxs, masks, action):
+        """The T-step sequence in torch ops under autograd, on either device (a hand-written training kernel for the edge-GRU sequence is the
+        next step)."""
+        B = inputs["robot_node"].shape[0]
+        N = rnn_hxs["human_node_rnn"].shape[0]
+        value, feat, h, e = self.base.forward_sequence(inputs, rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"], masks, B // N, N)
+        mean = _skinny_linear(feat, self.dist.fc_mean.weight, self.dist.fc_mean.bias)
+        logstd = self.dist.logstd(torch.zeros_like(mean))
+        logp = self._log_prob(mean, logstd.exp(), action)
+        entropy = (0.5 + 0.5 * math.log(2 * math.pi) + logstd).mean()
+        return value, logp, entropy, {"human_node_rnn": h.view(N, 1, -1), "human_human_edge_rnn": e}
 
     def _edge_zeros(self, E, device):
         key = (E, str(device))
@@ -459,6 +671,8 @@ class Policy(nn.Module):
         return {k: (v if v.dtype == torch.float32 else v.float()).contiguous() for k, v in inputs.items() if k != "visible_masks"}
 
     def act(self, inputs, rnn_hxs, masks, deterministic=False):
+        if self.is_srnn_baseline:
+            return self._srnn_act(inputs, rnn_hxs, masks, deterministic)
         E = inputs["robot_node"].shape[0]
         hx = rnn_hxs["human_node_rnn"]
         if hx.is_cuda:
@@ -477,6 +691,8 @@ class Policy(nn.Module):
         return value, action, logp, {"human_node_rnn": h, "human_human_edge_rnn": self._edge_zeros(E, hx.device)}
 
     def get_value(self, inputs, rnn_hxs, masks):
+        if self.is_srnn_baseline:
+            return self._srnn_get_value(inputs, rnn_hxs, masks)
         E = inputs["robot_node"].shape[0]
         hx = rnn_hxs["human_node_rnn"]
         if hx.is_cuda:
@@ -492,6 +708,8 @@ class Policy(nn.Module):
 
     def evaluate_actions(self, inputs, rnn_hxs, masks, action):
         """inputs [T*N,...] (T = seq_length, N = num_processes / num_mini_batch), rnn_hxs at t=0 ([N,...])."""
+        if self.is_srnn_baseline:
+            return self._srnn_evaluate_actions(inputs, rnn_hxs, masks, action)
         B = inputs["robot_node"].shape[0]
         N = rnn_hxs["human_node_rnn"].shape[0]
         T = B // N

@@ -4,7 +4,10 @@ Same constructor signature and attribute names (`obs`, `recurrent_hidden_states`
 `action_log_probs`, `actions`, `masks`, `bad_masks`, `step`) so `train.py` and `PPO.update` use it unchanged.
 Differences that are invisible to callers:
   * `recurrent_hidden_states['human_human_edge_rnn']` is always zero in the reference (selfAttn_srnn_temp_node.py:389-393)
-    but stored as [T+1,N,H+1,256] (2.7 GB at 4096 envs); here it is a stride-0 view of one zero.
+    but stored as [T+1,N,H+1,256] (2.7 GB at 4096 envs); here it is a stride-0 view of one zero.  The DS-RNN baseline (base='srnn') has a
+    LIVE edge state: `materialize_edge_rnn()` allocates the real tensor, and `insert` does so by itself the first time it is handed an
+    edge state that is not that zero view, so the reference-shaped constructor serves both networks.  Once live, the edge state is copied,
+    moved and gathered like the node state; until then every method does exactly what it did without it.
   * `compute_returns` runs the GAE scan as one HIP kernel (cn_gae) when the buffers live on the GPU.
   * `recurrent_generator` gathers each minibatch with one index_select per tensor instead of a Python loop over envs.
 """
@@ -38,12 +41,27 @@ class RolloutStorage(object):
         self.bad_masks = torch.ones(num_steps + 1, num_processes, 1)
         self.num_steps = num_steps
         self.step = 0
+        self.edge_rnn_live = False
+
+    def materialize_edge_rnn(self):
+        """Allocate the real [T+1,N,H+1,256] edge state (zeros) on the storage's device; a no-op once it is live."""
+        if not self.edge_rnn_live:
+            self.recurrent_hidden_states["human_human_edge_rnn"] = torch.zeros(*self._edge_shape, device=self.rewards.device)
+            self.edge_rnn_live = True
+        return self.recurrent_hidden_states["human_human_edge_rnn"]
+
+    @staticmethod
+    def _is_zero_view(t):
+        return t.numel() > 0 and all(st == 0 for st in t.stride())
 
     def to(self, device):
         for key in self.obs:
             self.obs[key] = self.obs[key].to(device)
         self.recurrent_hidden_states["human_node_rnn"] = self.recurrent_hidden_states["human_node_rnn"].to(device)
-        self.recurrent_hidden_states["human_human_edge_rnn"] = torch.zeros(1, 1, 1, 1, device=device).expand(*self._edge_shape)
+        if self.edge_rnn_live:
+            self.recurrent_hidden_states["human_human_edge_rnn"] = self.recurrent_hidden_states["human_human_edge_rnn"].to(device)
+        else:
+            self.recurrent_hidden_states["human_human_edge_rnn"] = torch.zeros(1, 1, 1, 1, device=device).expand(*self._edge_shape)
         for name in ("rewards", "value_preds", "returns", "action_log_probs", "actions", "masks", "bad_masks"):
             setattr(self, name, getattr(self, name).to(device))
 
@@ -53,6 +71,10 @@ class RolloutStorage(object):
                 self.obs[key][self.step + 1].copy_(obs[key].view_as(self.obs[key][self.step + 1]), non_blocking=True)
         self.recurrent_hidden_states["human_node_rnn"][self.step + 1].copy_(
             recurrent_hidden_states["human_node_rnn"].view_as(self.recurrent_hidden_states["human_node_rnn"][self.step + 1]))
+        edge = recurrent_hidden_states.get("human_human_edge_rnn")
+        if edge is not None and (self.edge_rnn_live or not self._is_zero_view(edge)):
+            dst = self.materialize_edge_rnn()[self.step + 1]
+            dst.copy_(edge.reshape(dst.shape))
         self.actions[self.step].copy_(actions)
         self.action_log_probs[self.step].copy_(action_log_probs)
         self.value_preds[self.step].copy_(value_preds)
@@ -65,6 +87,8 @@ class RolloutStorage(object):
         for key in self.obs:
             self.obs[key][0].copy_(self.obs[key][-1])
         self.recurrent_hidden_states["human_node_rnn"][0].copy_(self.recurrent_hidden_states["human_node_rnn"][-1])
+        if self.edge_rnn_live:
+            self.recurrent_hidden_states["human_human_edge_rnn"][0].copy_(self.recurrent_hidden_states["human_human_edge_rnn"][-1])
         self.masks[0].copy_(self.masks[-1])
         self.bad_masks[0].copy_(self.bad_masks[-1])
 
@@ -122,6 +146,7 @@ class RolloutStorage(object):
 
             obs_batch = {key: take(self.obs[key]) for key in self.obs}
             hxs = {"human_node_rnn": self.recurrent_hidden_states["human_node_rnn"][0].index_select(0, idx),
-                   "human_human_edge_rnn": torch.zeros(1, 1, 1, device=dev).expand(N, *self._edge_shape[2:])}
+                   "human_human_edge_rnn": self.recurrent_hidden_states["human_human_edge_rnn"][0].index_select(0, idx) if self.edge_rnn_live
+                   else torch.zeros(1, 1, 1, device=dev).expand(N, *self._edge_shape[2:])}
             yield (obs_batch, hxs, take(self.actions), take(self.value_preds), take(self.returns), take(self.masks),
                    take(self.action_log_probs), take(advantages))

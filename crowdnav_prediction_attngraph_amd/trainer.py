@@ -55,22 +55,27 @@ def collect_rollout(envs, actor_critic, rollouts, stats=None, generator=None):
     """Fill `rollouts` (row 0 must hold the current observation / hidden state / mask).  Zero host syncs."""
     env = envs._env
     E, dev = envs.num_envs, envs.device
-    pol = actor_critic._hip_policy(E, dev)
+    srnn = getattr(actor_critic, "is_srnn_baseline", False)
+    pol = actor_critic._hip_srnn(E, dev) if srnn else actor_critic._hip_policy(E, dev)
     T = rollouts.num_steps
     hx = rollouts.recurrent_hidden_states["human_node_rnn"]
+    ex = rollouts.materialize_edge_rnn() if srnn else None                # DS-RNN: the live edge state, written row by row like the node state
     eps = torch.empty(T, E, 2, device=dev).normal_(generator=generator)   # the action noise of the whole rollout in one launch
     # the simulator writes a row plan beside every observation (hip.HipEnvBatch.row_plan): row t of the storage IS the newest observation of
     # `env` at every t of this loop (row 0: the last one of the previous rollout, or the reset), so the plan in the buffer is the one made
     # for it.  Not through the GST wrapper, which post-processes the observation.
     base = actor_critic.base
-    plan = env.row_plan if (envs._pretext is None and base.use_self_attn and base.sort_humans) else None
+    plan = env.row_plan if (envs._pretext is None and base.use_self_attn and base.sort_humans and not srnn) else None
     for t in range(T):
         obs_t = {k: rollouts.obs[k][t] for k in ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num")}
         out = dict(value=rollouts.value_preds[t], action=rollouts.actions[t], logp=rollouts.action_log_probs[t], hxs=hx[t + 1])
         pol_obs = obs_t
         if not base.sort_humans:   # args.sort_humans = False: attention masked by visible_masks -> visible humans first + their count
             pol_obs = base.counted_inputs(dict(obs_t, visible_masks=rollouts.obs["visible_masks"][t]))
-        pol.act(pol_obs, hx[t], rollouts.masks[t], eps=eps[t], out=out, row_plan=plan)
+        if srnn:                   # no row plan: DS-RNN runs every slot of every env
+            pol.act(pol_obs, hx[t], ex[t], rollouts.masks[t], eps=eps[t], out=dict(out, edge_hxs=ex[t + 1]))
+        else:
+            pol.act(pol_obs, hx[t], rollouts.masks[t], eps=eps[t], out=out, row_plan=plan)
         obs_n = {k: rollouts.obs[k][t + 1] for k in obs_t}
         obs_n["visible_masks"] = None
         if "visible_masks" in rollouts.obs:
@@ -97,17 +102,21 @@ def evaluate_policy(actor_critic, env_name, config, seed, eval_cases=None, devic
     policy, and what the training rollout has set on it (weight snapshot, gemm mode, a post-hh hook) stays as it is.  No torch RNG draw."""
     from .config import Config
     from .evaluation import _evaluate_batched
-    from .hip import HipPolicy
+    from .hip import HipPolicy, HipSrnn
     config = config if config is not None else Config()
     if eval_cases is None:
         eval_cases = int(config.env.test_size)
     E = len(set((2 * k) % int(config.env.test_size) for k in range(eval_cases)))     # distinct cases = envs of the batch (evaluation.py)
     base = actor_critic.base
-    pol = HipPolicy(base.human_num, base.edge_width, E, device=device)
+    srnn = getattr(actor_critic, "is_srnn_baseline", False)
+    pol = (HipSrnn if srnn else HipPolicy)(base.human_num, base.edge_width, E, device=device)
     try:
-        pol.set_self_attention(base.use_self_attn)
-        pol.set_taps(False)
-        pol.set_gemm_mode(actor_critic.rollout_gemm_mode)
+        if srnn:
+            pol.set_gemm_mode(actor_critic.srnn_gemm_mode)
+        else:
+            pol.set_self_attention(base.use_self_attn)
+            pol.set_taps(False)
+            pol.set_gemm_mode(actor_critic.rollout_gemm_mode)
         pol.set_weights(actor_critic.state_dict())
         return _evaluate_batched(actor_critic, env_name, config, seed, eval_cases, device, logging, predictor=predictor, hip_policy=pol)
     finally:
@@ -117,6 +126,8 @@ def evaluate_policy(actor_critic, env_name, config, seed, eval_cases=None, devic
 def bootstrap_value(actor_critic, rollouts):
     obs = {k: rollouts.obs[k][-1] for k in ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num", "visible_masks") if k in rollouts.obs}
     hxs = {"human_node_rnn": rollouts.recurrent_hidden_states["human_node_rnn"][-1]}
+    if getattr(rollouts, "edge_rnn_live", False):          # DS-RNN: the value of the last row needs its edge state
+        hxs["human_human_edge_rnn"] = rollouts.recurrent_hidden_states["human_human_edge_rnn"][-1]
     return actor_critic.get_value(obs, hxs, rollouts.masks[-1])
 
 
@@ -144,6 +155,8 @@ def save_checkpoint(save_dir, update, actor_critic, agent, envs, rollouts, stats
                        # same tiles, i.e. sums in the same order, as the uninterrupted run
                        "row_plan": envs._env.row_plan.clone()},
           "stats": stats.acc.clone()}
+    if getattr(rollouts, "edge_rnn_live", False):          # DS-RNN: the live edge state of row 0
+        ck["rollout0"]["edge_hxs"] = rollouts.recurrent_hidden_states["human_human_edge_rnn"][0].clone()
     path = stem + (".resume.pt" if rank == 0 else ".resume.rank%d.pt" % rank)
     torch.save(ck, path)
     return stem + ".pt", path
@@ -159,6 +172,8 @@ def load_checkpoint(policy_path, resume_path, actor_critic, agent, envs, rollout
     for k in rollouts.obs:
         rollouts.obs[k][0].copy_(r0["obs"][k])
     rollouts.recurrent_hidden_states["human_node_rnn"][0].copy_(r0["hxs"])
+    if "edge_hxs" in r0:
+        rollouts.materialize_edge_rnn()[0].copy_(r0["edge_hxs"])
     rollouts.masks[0].copy_(r0["masks"]); rollouts.bad_masks[0].copy_(r0["bad_masks"])
     if "row_plan" in r0 and r0["row_plan"].numel() == envs._env.row_plan.numel():   # (load_state_dict above cleared it)
         envs._env.row_plan.copy_(r0["row_plan"])
@@ -183,7 +198,7 @@ def update_flops(live_rows, samples, ppo_epoch):
 def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_updates=10, seed=425, config=None, ppo_epoch=5,
           num_mini_batch=2, lr=4e-5, eps=1e-5, clip_param=0.2, value_loss_coef=0.5, entropy_coef=0.0, max_grad_norm=0.5, gamma=0.99,
           gae_lambda=0.95, log=print, device=None, save_dir=None, save_interval=0, resume=None, use_self_attn=True, sort_humans=None,
-          pretext_wrapper=None, predictor=None, eval_interval=0, eval_cases=None):
+          pretext_wrapper=None, predictor=None, eval_interval=0, eval_cases=None, base=None):
     """Returns a list of per-update dicts (losses, timings, episode stats).  Works single- or multi-GPU (one process per
     GPU, torch.distributed initialised by the caller).  save_dir / save_interval: write checkpoints like train.py:213-219 (every
     `save_interval` updates and after the last one); resume = path of a `NNNNN.pt` written by this function: continue that run
@@ -194,7 +209,9 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
     eval_interval: every that many updates and after the last one, run the batched test protocol (evaluation.evaluate_batched: eval_cases
     episodes, default config.env.test_size, phase 'test', same config / seed / predictor) on the current weights and put its metrics under
     rec["eval"].  The training run itself -- losses, statistics, checkpoints, weights -- is bit-identical with and without it: the evaluation
-    owns its simulator, wrapper and policy handle and draws from no torch RNG stream.  Under torch.distributed rank 0 evaluates."""
+    owns its simulator, wrapper and policy handle and draws from no torch RNG stream.  Under torch.distributed rank 0 evaluates.
+    base: the network, 'selfAttn_merge_srnn' or 'srnn' (the DS-RNN baseline).  None follows config.robot.policy when it names one of the two, as
+    the reference's train.py:94 does, and is 'selfAttn_merge_srnn' otherwise."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     if pretext_wrapper is None:
@@ -214,12 +231,18 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
         raise ValueError("sort_humans=False needs the `visible_masks` observation, which %s does not provide" % env_name)
     base_kwargs = dict(env_name=env_name, num_processes=num_processes, num_mini_batch=num_mini_batch, seq_length=num_steps, use_self_attn=use_self_attn,
                        sort_humans=sort_humans)
-    actor_critic = Policy(envs.observation_space.spaces, envs.action_space, base_kwargs=base_kwargs, base="selfAttn_merge_srnn").to(device)
+    if base is None:
+        base = getattr(getattr(config, "robot", None), "policy", None)
+        if base not in ("selfAttn_merge_srnn", "srnn"):
+            base = "selfAttn_merge_srnn"
+    actor_critic = Policy(envs.observation_space.spaces, envs.action_space, base_kwargs=base_kwargs, base=base).to(device)
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         # identical weights on every rank (seeded above), but each env shard explores with its own action noise
         torch.cuda.manual_seed(seed + 1000003 * torch.distributed.get_rank())
     rollouts = RolloutStorage(num_steps, num_processes, envs.observation_space.spaces, envs.action_space, 128, 256)
     rollouts.to(device)
+    if actor_critic.is_srnn_baseline:
+        rollouts.materialize_edge_rnn()
     agent = PPO(actor_critic, clip_param, ppo_epoch, num_mini_batch, value_loss_coef, entropy_coef, lr=lr, eps=eps, max_grad_norm=max_grad_norm)
     obs = envs.reset_device()
     for k in rollouts.obs:

@@ -16,6 +16,9 @@
  *   cn_policy_create/destroy/set_weights <- rl/networks/model.py:16-46 Policy.__init__ / load_state_dict
  *   cn_policy_act              <- rl/networks/model.py:56-74 Policy.act (-> selfAttn_srnn_temp_node.py:360-449)
  *   cn_policy_get_value        <- rl/networks/model.py:76-80 Policy.get_value
+ *   cn_srnn_create/destroy/set_weights <- rl/networks/model.py:16-46 Policy.__init__ with base='srnn' / load_state_dict
+ *   cn_srnn_act                <- rl/networks/model.py:56-74 Policy.act (-> srnn_model.py:389-468 SRNN.forward, infer=True)
+ *   cn_srnn_get_value          <- rl/networks/model.py:76-80 Policy.get_value on that base
  *   cn_gae                     <- rl/networks/storage.py:123-132 RolloutStorage.compute_returns (use_gae branch)
  *   cn_adv_stats / cn_adv_normalize <- rl/ppo/ppo.py:37-39 advantage normalisation (split so that N GPUs can
  *                                 all-reduce the three partial sums in between)
@@ -336,6 +339,63 @@ int cn_policy_get_profile(cn_policy *p, double *ms_out /*[8]*/, int64_t *launche
  * queue's profiling on, a one-off cost of some hundred microseconds that must not fall into a timed window). */
 int cn_policy_get_profile_samples(cn_policy *p, float *ms_out, int cap);
 int cn_policy_reset_profile(cn_policy *p);
+
+/* ---- DS-RNN baseline policy (base='srnn': rl/networks/srnn_model.py + DiagGaussian head) ----
+ * The network every table of the paper compares against (config.py robot.policy: "For baseline: srnn").  Unlike the attention-graph
+ * network its edge state is LIVE: two edge GRUs (one temporal edge, H spatial edges, hidden 256) carry `human_human_edge_rnn`
+ * [E,H+1,256], slot 0 the temporal edge, from step to step; the attention runs over ALL H slots, padded humans included
+ * (detected_human_num and visible_masks are not read).  Only the `args.env_type == 'crowd_sim'` branch of srnn_model.py:378 (robot node
+ * width 7) exists here.  A forward is two launches whatever E and H: the edge-GRU kernel and the node kernel.
+ * Device pointers to the fp32 parameters, named after the reference state_dict keys; the three modules that never reach the output
+ * (base.humanNodeRNN.edge_embed, base.human_node_final_linear, base.spatial_linear) are not in it. */
+typedef struct {
+    const float *enc_s_w, *enc_s_b;                               /* base.humanhumanEdgeRNN_spatial.encoder_linear [64,D] */
+    const float *gru_s_w_ih, *gru_s_w_hh, *gru_s_b_ih, *gru_s_b_hh; /* base.humanhumanEdgeRNN_spatial.gru.* [768,64],[768,256],[768],[768] */
+    const float *enc_t_w, *enc_t_b;                               /* base.humanhumanEdgeRNN_temporal.encoder_linear [64,2] */
+    const float *gru_t_w_ih, *gru_t_w_hh, *gru_t_b_ih, *gru_t_b_hh; /* base.humanhumanEdgeRNN_temporal.gru.* */
+    const float *attn_temporal_w, *attn_temporal_b;               /* base.attn.temporal_edge_layer.0 [64,256] */
+    const float *attn_spatial_w, *attn_spatial_b;                 /* base.attn.spatial_edge_layer.0 [64,256] */
+    const float *node_enc_w, *node_enc_b;                         /* base.humanNodeRNN.encoder_linear [64,3] */
+    const float *edge_embed_w, *edge_embed_b;                     /* base.humanNodeRNN.edge_attention_embed [64,512] */
+    const float *node_gru_w_ih, *node_gru_w_hh, *node_gru_b_ih, *node_gru_b_hh; /* base.humanNodeRNN.gru.* [384,128] x 2, [384] x 2 */
+    const float *out_w, *out_b;                                   /* base.humanNodeRNN.output_linear [256,128] */
+    const float *actor0_w, *actor0_b, *actor2_w, *actor2_b;       /* base.actor.{0,2} [256,256] */
+    const float *critic0_w, *critic0_b, *critic2_w, *critic2_b;   /* base.critic.{0,2} [256,256] */
+    const float *critic_linear_w, *critic_linear_b;               /* base.critic_linear [1,256] */
+    const float *robot_linear_w, *robot_linear_b;                 /* base.robot_linear [3,7] */
+    const float *fc_mean_w, *fc_mean_b;                           /* dist.fc_mean [2,256] */
+    const float *logstd;                                          /* dist.logstd._bias [2,1] */
+} cn_srnn_weights;
+typedef struct cn_srnn cn_srnn;
+
+/* 1 <= human_num <= CN_MAX_HUMANS; edge_width = whatever the env gives (2 for CrowdSimVarNum-v0, 12 for the Pred envs); max_envs = the
+ * largest batch any later call will pass.  No CPU fallback: CN_ERR_NO_DEVICE without a gfx950 device. */
+int cn_srnn_create(int human_num, int edge_width, int max_envs, cn_srnn **out);
+int cn_srnn_destroy(cn_srnn *p);
+/* Snapshot the weights (copies them, splits the two edge GRUs' W_hh into bf16 hi / lo planes).  Call again after every optimiser step. */
+int cn_srnn_set_weights(cn_srnn *p, const cn_srnn_weights *w, void *stream);
+/* One rollout-time forward for E envs (srnn_model.py:389-468 with infer=True, then model.py:64-71).  Reads obs->robot_node,
+ * obs->temporal_edges and obs->spatial_edges only.  node_hxs_in/out [E,128], edge_hxs_in/out [E,H+1,256], masks [E,1] (both states are
+ * multiplied by it first, as RNNBase._forward_gru does), eps [E,2] standard-normal noise or NULL for the deterministic mode() action.
+ * Outputs value [E,1], action [E,2], logp [E,1].  edge_hxs_out MAY be edge_hxs_in itself (exactly the same pointer, not a partial overlap)
+ * and node_hxs_out may be node_hxs_in: every workgroup reads its own rows before it writes them.  The rollout passes two storage rows. */
+int cn_srnn_act(cn_srnn *p, int E, const cn_obs *obs, const float *node_hxs_in, const float *edge_hxs_in, const float *masks, const float *eps,
+                float *value, float *action, float *logp, float *node_hxs_out, float *edge_hxs_out, void *stream);
+/* The bits of cn_srnn_act's `value` (the same two kernels; the new edge state goes to a buffer of the handle, allocated by the first call). */
+int cn_srnn_get_value(cn_srnn *p, int E, const cn_obs *obs, const float *node_hxs_in, const float *edge_hxs_in, const float *masks, float *value,
+                      void *stream);
+/* Test taps of the last act / get_value call (NULL skips one): edge_out [E,H+1,256] (copied from where that call wrote it: the caller's
+ * edge_hxs_out must still hold it), attn [E,H] (softmax over all H slots), weighted [E,256], node_out [E,256] (output_linear),
+ * actor_feat [E,256]. */
+int cn_srnn_get_taps(cn_srnn *p, int E, float *edge_out, float *attn, float *weighted, float *node_out, float *actor_feat, void *stream);
+/* Arithmetic of the edge GRUs' recurrent product ([rows, 256] x W_hh^T, 4/5 of the edge-GRU FLOPs):
+ *   1 (default) = split precision (each fp32 operand as bf16 hi + lo, lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x32_bf16, fp32 accumulation;
+ *                 outputs within 1e-4 of the reference, the project's bar);
+ *   0           = exact fp32 on v_mfma_f32_16x16x4_f32.
+ * The input-side product ([rows, 64] x W_ih^T) is exact fp32 MFMA in BOTH modes: its operand, the edge embedding, is not bounded (unseen
+ * humans are padded with 15 m, embeddings reach 10 .. 30) and as a split product it alone was 1.1e-4 off the reference.  Everything else
+ * (encoders, gates, attention, node GRU, trunks, heads) always runs in fp32. */
+int cn_srnn_set_gemm_mode(cn_srnn *p, int mode);
 
 /* ---- device-side launch stamps (measurement aid for bench.py / tools; not part of the reference's interface) ----
  * The kernels of the rollout step (CN_PROF_K_*) stamp the device's 100 MHz wall clock when their first workgroups start and when their
