@@ -44,6 +44,7 @@
 #include "mt19937.h"
 #include "episode.h"
 
+#include <hip/hip_ext.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -677,6 +678,25 @@ static bool dense_crowd(cn_env_batch *env)
     return coop_env >= 0 ? coop_env != 0 : zone > 0.9 * 2.0 * M_PI * cf.circle_radius;
 }
 
+// Launch with an optional stop event.  An event handed to the launch completes with the kernel itself: it rides on the kernel's own
+// dispatch packet, where hipEventRecord puts a marker packet behind the kernel and the stream's next kernel waits for that marker too
+// (tools/event_gap_probe.hip, two 20 us kernels on one stream: nothing between them 0.9 us, a record between them 5.7 us, the first one's
+// stop event instead 2.0-2.1 us; the waiting stream's kernel starts 8.4 us after the kernel's end instead of 12.5-12.9).
+// The caller checks the launch with CN_CHECK_LAUNCH() as after hipLaunchKernelGGL.
+template <typename... KArgs, typename... Args>
+static void launch_ev(void (*kernel)(KArgs...), dim3 grid, dim3 blk, hipStream_t st, hipEvent_t stop, Args &&...args)
+{
+    if (stop) hipExtLaunchKernelGGL(kernel, grid, blk, 0, st, nullptr, stop, 0, static_cast<KArgs>(args)...);
+    else hipLaunchKernelGGL(kernel, grid, blk, 0, st, static_cast<KArgs>(args)...);
+}
+
+// a stream that is being captured into a graph takes plain launches and event records (the nodes a capture knows), never a stop event
+static bool capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
 static int launch_post(cn_env_batch *env, hipStream_t on)
 {
     hipLaunchKernelGGL(env_post_kernel<4>, dim3(env->d.E), dim3(256), 0, on, stamped(env->d, CN_K_OTHER));
@@ -713,11 +733,13 @@ static int launch_pregen(cn_env_batch *env, hipStream_t on)
 // The side-stream tail of the ORCA pass for the state the caller's stream has reached at this point: whatever the lane kernel could not
 // finish (the infeasible programs -> linearProgram3), or the whole pass for configurations without a lane kernel; the 'truth' roll-outs of
 // the test phase; and, in deferred mode, the episode pre-generation.  Ends with ev_orca, which the next step / reader waits for.
-static int launch_tail(cn_env_batch *env, hipStream_t main)
+// state_bound: ev_state already is the stop event of the last launch on `main` (prefetch_orca's lane kernel, nothing enqueued since);
+// otherwise it is recorded here, behind whatever `main` holds.
+static int launch_tail(cn_env_batch *env, hipStream_t main, bool state_bound = false)
 {
     const int agents = env->d.E * env->d.H;
     const bool lane_path = lane_path_of(env);
-    CN_HIP(hipEventRecord(env->ev_state, main));
+    if (!state_bound) CN_HIP(hipEventRecord(env->ev_state, main));
     CN_HIP(hipStreamWaitEvent(env->side, env->ev_state, 0));
     if (env->defer_tail && lane_path) {
         // beside the ORCA tail and the caller's robot-node kernel, on a stream of its own (behind the tail on ONE stream the two chains add
@@ -731,6 +753,10 @@ static int launch_tail(cn_env_batch *env, hipStream_t main)
         if (int rc = launch_post(env, env->side)) return rc;
         env->post_deferred = false;
     }
+    // ev_orca is the stop event of the ORCA launch where that is the side stream's last one (not while capturing; not in the test phase: the
+    // roll-outs follow; not for social-force humans: no launch)
+    const bool orca_bound = env->d.cfg.humans_policy == CN_HUMANS_ORCA && env->d.cfg.phase != CN_PHASE_TEST && !capturing(main);
+    const hipEvent_t ev_last = orca_bound ? env->ev_orca : nullptr;
     if (env->d.cfg.humans_policy == CN_HUMANS_ORCA) { // social-force humans act inside env_step_kernel (one lane per human, no solver)
         if (lane_path) {
             // the infeasible programs are finished by the cooperative routine on the side stream, next to the policy forward.
@@ -738,16 +764,16 @@ static int launch_tail(cn_env_batch *env, hipStream_t main)
             // wavefronts exit at once, longer lists are walked with a stride) keeps enough wavefronts in flight to hide the latency
             // of the cooperative routine
             const int blocks = (agents + 15) / 16;
-            hipLaunchKernelGGL(orca_lp3_kernel, dim3(blocks), dim3(256), 0, env->side, stamped(env->d, CN_K_ORCA_LP3));
+            launch_ev(orca_lp3_kernel, dim3(blocks), dim3(256), env->side, ev_last, stamped(env->d, CN_K_ORCA_LP3));
             CN_CHECK_LAUNCH();
         } else {
-            hipLaunchKernelGGL(orca_kernel, dim3((agents + 3) / 4), dim3(256), 0, env->side, stamped(env->d, CN_K_ORCA_LP3));
+            launch_ev(orca_kernel, dim3((agents + 3) / 4), dim3(256), env->side, ev_last, stamped(env->d, CN_K_ORCA_LP3));
             CN_CHECK_LAUNCH();
         }
     }
     if (env->d.cfg.phase == CN_PHASE_TEST) // 'truth' roll-out for the next step's Danger decision
         if (int rc = truth_rollout(env, env->side)) return rc;
-    CN_HIP(hipEventRecord(env->ev_orca, env->side));
+    if (!orca_bound) CN_HIP(hipEventRecord(env->ev_orca, env->side));
     env->orca_ready = true;
     env->tail_pending = false;
     return CN_OK;
@@ -762,7 +788,8 @@ static int sync_side(cn_env_batch *env, hipStream_t st)
     return CN_OK;
 }
 
-static int prefetch_orca(cn_env_batch *env, hipStream_t main, const cn_obs *obs)
+// pre_bound: ev_pre already is the stop event of the last launch on `main` (cn_env_step's step kernel); otherwise it is recorded here
+static int prefetch_orca(cn_env_batch *env, hipStream_t main, const cn_obs *obs, bool pre_bound = false)
 {
     const float *plan_det = obs ? obs->detected_human_num : nullptr;
     int32_t *row_plan = obs ? obs->row_plan : nullptr;
@@ -771,6 +798,9 @@ static int prefetch_orca(cn_env_batch *env, hipStream_t main, const cn_obs *obs)
     const bool lane_path = lane_path_of(env);
     const bool defer = env->defer_tail && lane_path;
     if (!defer) {
+        // With ev_pre / ev_state bound to the launches (the front of hh_fused 6.7 us shorter, this kernel's start 3.7 us earlier), medians of
+        // three 200-step runs per budget in one call: 44 us 0.2535, 40 us 0.2519, 38 us 0.2522, 36 us 0.2545, 34 us 0.2592, 32 us 0.2617 ms per
+        // step; env_step on its own clock does not move: the budget stays at 40 us (profiles/HISTORY.md section 18).
         // Round 5: 40 us.  With the placement loops 64 candidates at a time an episode is generated in ~30 us, and the lane kernel in front of
         // the policy got shorter (42 us): same box, 200 steps each -- 55 us 0.2866 / 0.2860 ms per step (human-human kernel 153 us on its own
         // clock: a quarter of its workgroups wait for this kernel's CUs), 45 us 0.2825, 40 us 0.2799 (139 us), 35 us 0.2903, 30 us 0.3001 (the
@@ -782,7 +812,7 @@ static int prefetch_orca(cn_env_batch *env, hipStream_t main, const cn_obs *obs)
         // policy: unbounded 0.138-0.139 ms, 65 us 0.139, 55 us 0.133, 45 us 0.135, 30 us 0.161 -- shorter is NOT better in this mode: the
         // ORCA tail kernel is queued behind this one, and when it starts before the policy's kernel has its workgroups on the CUs, that
         // kernel waits for them (the deferred mode removes exactly this coupling)
-        CN_HIP(hipEventRecord(env->ev_pre, main));
+        if (!pre_bound) CN_HIP(hipEventRecord(env->ev_pre, main));
         if (env->post_deferred) {
             // the side stream starts with the deferred goal changes, which the ORCA pass and with it the next step wait for: the
             // pre-generation (whose workgroups mostly wait for the CUs the policy's kernel holds) goes beside them
@@ -795,24 +825,28 @@ static int prefetch_orca(cn_env_batch *env, hipStream_t main, const cn_obs *obs)
             if (int rc = launch_pregen(env, env->side)) return rc;
         }
     }
+    bool state_bound = false;
     if (lane_path) {
         // one lane per agent, on the CALLER's stream: the policy forward the caller enqueues next starts behind this kernel, not
-        // beside it (see orca_lane_kernel), and a same-stream hand-over costs ~3 us where an event across streams costs 10-20
+        // beside it (see orca_lane_kernel), and a same-stream hand-over costs 1-2 us where an event across streams costs 8-13
+        // (tools/event_gap_probe.hip; in the step 15 us from env_step's end to the pre-generation's start)
         int32_t *plan = (plan_det && env->plan_ok && ((uintptr_t)plan_det & 15u) == 0) ? row_plan : nullptr;
         if (plan) row_plan = nullptr; // built below
         const int pg = plan ? rp_groups(env->d.E) : 0;
         const dim3 grid((agents + 63) / 64 + pg), blk(64);
         const EnvDev dl = stamped(env->d, CN_K_ORCA_LANE);
         unsigned long long *pst = cn_stamp_slot(CN_K_ROW_PLAN);
-        if (slots <= 8) hipLaunchKernelGGL((orca_lane_kernel<8, 8>), grid, blk, 0, main, dl, plan_det, plan, pg, pst);
-        else if (slots <= 20) hipLaunchKernelGGL((orca_lane_kernel<20, 32>), grid, blk, 0, main, dl, plan_det, plan, pg, pst);
-        else hipLaunchKernelGGL((orca_lane_kernel<32, 32>), grid, blk, 0, main, dl, plan_det, plan, pg, pst);
+        // the tail below is released by this launch's own stop event when it is the last thing on `main` in front of launch_tail: no
+        // memset of an unfilled plan behind it, the tail not held back, no capture
+        state_bound = !row_plan && !defer && !capturing(main);
+        auto lane = slots <= 8 ? orca_lane_kernel<8, 8> : slots <= 20 ? orca_lane_kernel<20, 32> : orca_lane_kernel<32, 32>;
+        launch_ev(lane, grid, blk, main, state_bound ? env->ev_state : nullptr, dl, plan_det, plan, pg, pst);
         CN_CHECK_LAUNCH();
     }
     // a caller's plan buffer that this step does not fill must not keep the previous observation's plan
     if (row_plan) CN_HIP(hipMemsetAsync(row_plan, 0, 4, main));
     if (defer) { env->tail_pending = true; env->orca_ready = false; return CN_OK; } // cn_env_launch_tail, or the next call into this batch
-    return launch_tail(env, main);
+    return launch_tail(env, main, state_bound);
 }
 
 extern "C" void cn_env_config_default(cn_env_config *c)
@@ -1022,6 +1056,7 @@ extern "C" int cn_env_step(cn_env_batch *env, const float *actions, const cn_obs
     hipStream_t st = (hipStream_t)stream;
     if (!env->orca_ready && !env->tail_pending) { if (int rc = prefetch_orca(env, st, nullptr)) return rc; }
     if (int rc = sync_side(env, st)) return rc; // human velocities for the current state (computed on the side stream; a held-back tail goes out now)
+    bool pre_bound = false;
     if (env->d.cfg.predict_truth) {
         hipLaunchKernelGGL(env_step_kernel<true>, dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
         CN_CHECK_LAUNCH();
@@ -1031,17 +1066,22 @@ extern "C" int cn_env_step(cn_env_batch *env, const float *actions, const cn_obs
         // without a lane kernel the next consumer of the goals is the ORCA pass on the side stream: the updates go there, in front of it
         // (with one, that kernel follows on the caller's stream and the loops stay in the step kernel, on four wavefronts)
         const bool defer = coop && !lane_path_of(env) && env->d.cfg.humans_policy == CN_HUMANS_ORCA;
+        auto step = env_step_kernel<false>;
+        int threads = 64;
         if (defer) {
             CN_HIP(hipMemsetAsync(env->d.post_cnt, 0, 4, st));
-            hipLaunchKernelGGL((env_step_kernel<false, 1, true>), dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
+            step = env_step_kernel<false, 1, true>;
             env->post_deferred = true;
         }
-        else if (coop) hipLaunchKernelGGL((env_step_kernel<false, 4>), dim3(env->d.E), dim3(256), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
-        else if (train_profile(env)) hipLaunchKernelGGL((env_step_kernel<false, 1, false, ProfileTrain>), dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
-        else hipLaunchKernelGGL(env_step_kernel<false>, dim3(env->d.E), dim3(64), 0, st, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info, ep_return, ep_len, not_done);
+        else if (coop) { step = env_step_kernel<false, 4>; threads = 256; }
+        else if (train_profile(env)) step = env_step_kernel<false, 1, false, ProfileTrain>;
+        // prefetch_orca follows at once: where it releases the pre-generation (the tail not held back), this launch's stop event does
+        pre_bound = !(env->defer_tail && lane_path_of(env)) && !capturing(st);
+        launch_ev(step, dim3(env->d.E), dim3(threads), st, pre_bound ? env->ev_pre : nullptr, stamped(env->d, CN_K_ENV_STEP), actions, *obs, reward, done, info,
+                  ep_return, ep_len, not_done);
         CN_CHECK_LAUNCH();
     }
-    return prefetch_orca(env, st, obs); // next step's ORCA overlaps whatever the caller enqueues next (the policy forward)
+    return prefetch_orca(env, st, obs, pre_bound); // next step's ORCA overlaps whatever the caller enqueues next (the policy forward)
 }
 
 extern "C" int cn_env_join(cn_env_batch *env, void *stream)
