@@ -154,6 +154,15 @@ PPO_BATCH_TENSORS = ["env_idx", "robot_node", "temporal_edges", "spatial_edges",
                      "old_logp", "adv"]     # pointer fields of cn_ppo_batch, in field order
 
 
+# the twelve parameters of the two edge RNNs: the first twelve fields of cn_srnn_weights == the fields of cn_srnn_edge_grads (cn_srnn_seq_bwd)
+SRNN_EDGE_KEYS = SRNN_WEIGHT_KEYS[:12]
+SRNN_SEQ_PARTIALS_BYTES = 64 * (768 * 256 + 1024 * 80 + 64 * 80) * 4      # CN_SRNN_SEQ_PARTIALS_BYTES
+
+
+class SrnnEdgeGrads(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name, _ in SRNN_EDGE_KEYS]
+
+
 class PpoBatch(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("T", "N", "E", "H", "D")] + [(n, C.c_void_p) for n in PPO_BATCH_TENSORS]
 
@@ -177,6 +186,7 @@ ABI_SYMBOLS = [
     "cn_env_get_visibility", "cn_render_scenes",
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
     "cn_srnn_create", "cn_srnn_destroy", "cn_srnn_set_weights", "cn_srnn_act", "cn_srnn_get_value", "cn_srnn_get_taps", "cn_srnn_set_gemm_mode",
+    "cn_srnn_seq_workspace_bytes", "cn_srnn_seq_fwd", "cn_srnn_seq_bwd",
 ]
 
 _lib = None
@@ -242,6 +252,10 @@ def lib():
         L.cn_srnn_get_value.argtypes = [vp, i32, C.POINTER(Obs), vp, vp, vp, vp, vp]
         L.cn_srnn_get_taps.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
         L.cn_srnn_set_gemm_mode.argtypes = [vp, i32]
+        L.cn_srnn_seq_workspace_bytes.argtypes = [i32, i32, i32, i32]
+        L.cn_srnn_seq_workspace_bytes.restype = i64
+        L.cn_srnn_seq_fwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
+        L.cn_srnn_seq_bwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(SrnnEdgeGrads), vp, vp, vp]
         L.cn_policy_set_profiling.argtypes = [vp, i32]
         L.cn_policy_set_gemm_mode.argtypes = [vp, i32]
         L.cn_policy_set_self_attention.argtypes = [vp, i32]

@@ -7,19 +7,7 @@
 
 namespace {
 constexpr size_t sr_align(size_t x) { return (x + 255) & ~size_t(255); }
-constexpr int SR_NW = sizeof(cn_srnn_weights) / sizeof(const float *);
 } // namespace
-
-struct cn_srnn {
-    int H, D, maxE, mode, have_weights;
-    char *pool;                 // weight snapshot (fp32), split planes of the two W_hh, taps
-    const float *w[SR_NW];      // snapshot pointers, in cn_srnn_weights field order
-    __bf16 *planes[4];          // split planes of W_hh: spatial hi / lo, temporal hi / lo
-    float *tap_attn, *tap_weighted, *tap_node, *tap_feat;
-    float *edge_ws;             // [maxE,H+1,256], allocated by the first cn_srnn_get_value (which has no edge output of the caller's)
-    const float *last_edge;     // the edge state the last forward wrote (the caller's edge_hxs_out, or edge_ws)
-    int lastE;
-};
 
 namespace {
 
@@ -36,21 +24,11 @@ void srnn_counts(int D, size_t *n)
     for (int i = 0; i < SR_NW; ++i) n[i] = c[i];
 }
 
-enum { W_ENC_S = 0, W_GRU_S = 2, W_ENC_T = 6, W_GRU_T = 8, W_ATTN = 12, W_NODE = 16, W_TRUNK = 26, W_HEADS = 34 };
-
 int srnn_forward(cn_srnn *p, int E, const cn_obs *obs, const float *node_in, const float *edge_in, const float *masks, const float *eps, float *value,
                  float *action, float *logp, float *node_out, float *edge_out, hipStream_t st)
 {
     const int H = p->H;
-    auto edge_w = [&](int enc, int gru, int plane, int din) {
-        SrnnEdgeW w;
-        w.enc_w = p->w[enc]; w.enc_b = p->w[enc + 1];
-        w.w_ih = p->w[gru]; w.w_hh = p->w[gru + 1]; w.b_ih = p->w[gru + 2]; w.b_hh = p->w[gru + 3];
-        w.hh_hi = p->planes[plane]; w.hh_lo = p->planes[plane + 1];
-        w.din = din;
-        return w;
-    };
-    const SrnnEdgeW ws = edge_w(W_ENC_S, W_GRU_S, 0, p->D), wt = edge_w(W_ENC_T, W_GRU_T, 2, 2);
+    const SrnnEdgeW ws = srnn_edge_weights(p, 1), wt = srnn_edge_weights(p, 0);
     const int tiles_t = (E + SR_TILE - 1) / SR_TILE;
     const long long tiles_s = ((long long)E * H + SR_TILE - 1) / SR_TILE;
     CN_REQUIRE(tiles_t + tiles_s < (1ll << 31), "cn_srnn: too many edge rows");
@@ -114,8 +92,8 @@ extern "C" int cn_srnn_create(int human_num, int edge_width, int max_envs, cn_sr
     size_t n[SR_NW], off[SR_NW], total = 0;
     srnn_counts(edge_width, n);
     for (int i = 0; i < SR_NW; ++i) { off[i] = total; total += sr_align(n[i] * sizeof(float)); }
-    size_t plane_off[4];
-    for (int i = 0; i < 4; ++i) {
+    size_t plane_off[8];            // W_hh planes, then W_hh^T planes
+    for (int i = 0; i < 8; ++i) {
         plane_off[i] = total;
         total += sr_align((size_t)768 * 256 * sizeof(__bf16));
     }
@@ -132,6 +110,7 @@ extern "C" int cn_srnn_create(int human_num, int edge_width, int max_envs, cn_sr
     }
     for (int i = 0; i < SR_NW; ++i) p->w[i] = reinterpret_cast<const float *>(p->pool + off[i]);
     for (int i = 0; i < 4; ++i) p->planes[i] = reinterpret_cast<__bf16 *>(p->pool + plane_off[i]);
+    for (int i = 0; i < 4; ++i) p->planes_t[i] = reinterpret_cast<__bf16 *>(p->pool + plane_off[4 + i]);
     p->tap_attn = reinterpret_cast<float *>(p->pool + o_attn);
     p->tap_weighted = reinterpret_cast<float *>(p->pool + o_wgt);
     p->tap_node = reinterpret_cast<float *>(p->pool + o_node);
@@ -163,6 +142,8 @@ extern "C" int cn_srnn_set_weights(cn_srnn *p, const cn_srnn_weights *w, void *s
     for (int s = 0; s < 2; ++s) {          // W_hh of both edge GRUs as bf16 hi / lo planes
         const int cnt = 768 * 256;
         hipLaunchKernelGGL(srnn_split_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, cnt, p->w[gru[s] + 1], p->planes[s * 2], p->planes[s * 2 + 1]);
+        CN_CHECK_LAUNCH();
+        hipLaunchKernelGGL(srnn_split_t_kernel, dim3((cnt + 255) / 256), dim3(256), 0, st, p->w[gru[s] + 1], p->planes_t[s * 2], p->planes_t[s * 2 + 1]);
         CN_CHECK_LAUNCH();
     }
     p->have_weights = 1;

@@ -28,6 +28,13 @@ struct SrnnEdgeW {                      // one weight set (temporal or spatial e
     int din;
 };
 
+// What the training forward (srnn_train.hip) keeps of one step for the backward, per weight set and gathered row: the gates r, z, n and
+// hn = W_hn (mask * h) + b_hn as four planes of 256, and the 64-wide post-ReLU embedding.  The rollout passes an empty one (SAVE = 0).
+struct SrnnEdgeSave {
+    float *gates_t, *gates_s;           // [rows of the set, 4, 256]
+    float *emb_t, *emb_s;               // [rows of the set, 64]
+};
+
 __device__ __forceinline__ float sr_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // Rows are the E * (H + 1) edges, gathered per weight set: workgroups [0, tiles_t) take 64 temporal rows (env e, slot 0) each, the others 64
@@ -43,10 +50,11 @@ __device__ __forceinline__ float sr_sigmoid(float x) { return 1.0f / (1.0f + exp
 //                    k-columns); the kernel is bound by the weight stream, not by the MFMA pipe.
 // edge_out may be edge_in itself: a tile reads its own rows only, all of them before the barrier except the element each lane re-reads in
 // the epilogue right before it writes that same element.
-template <int SPLIT>
+// SAVE = 1 (the training forward): the same arithmetic, and every row also leaves its gates and its embedding in `sv`.
+template <int SPLIT, int SAVE = 0>
 __global__ __launch_bounds__(SR_EDGE_THREADS) void srnn_edge_gru_kernel(int E, int H, int tiles_t, SrnnEdgeW wt, SrnnEdgeW ws, const float *__restrict__ temporal,
                                                                         const float *__restrict__ spatial, const float *edge_in,
-                                                                        const float *__restrict__ masks, float *edge_out)
+                                                                        const float *__restrict__ masks, float *edge_out, SrnnEdgeSave sv = SrnnEdgeSave{})
 {
     extern __shared__ __attribute__((aligned(16))) char sr_smem[];
     __bf16 *xh = reinterpret_cast<__bf16 *>(sr_smem);                       // split mode: mask * h, hi and lo planes, then the embedding
@@ -81,6 +89,7 @@ __global__ __launch_bounds__(SR_EDGE_THREADS) void srnn_edge_gru_kernel(int E, i
             v = w.enc_b[c];
             for (int k = 0; k < din; ++k) v = fmaf(w.enc_w[c * din + k], x[k], v);
             v = fmaxf(v, 0.0f);
+            if (SAVE) (is_t ? sv.emb_t : sv.emb_s)[(size_t)(r0 + row) * SR_EMB + c] = v;
         }
         xe[row * lde + c] = v;
     }
@@ -176,11 +185,16 @@ __global__ __launch_bounds__(SR_EDGE_THREADS) void srnn_edge_gru_kernel(int E, i
                     const float rg = sr_sigmoid(ar[rb][i] + br), zg = sr_sigmoid(az[rb][i] + bz);
                     const float ng = tanhf(ai[rb][i] + bin + rg * (ah[rb][i] + bhn));
                     edge_out[o] = (1.0f - zg) * ng + zg * h;
+                    if (SAVE) {
+                        float *g = (is_t ? sv.gates_t : sv.gates_s) + (size_t)r * (4 * SR_HID) + col;
+                        g[0] = rg; g[SR_HID] = zg; g[2 * SR_HID] = ng; g[3 * SR_HID] = ah[rb][i] + bhn;
+                    }
                 }
             }
     }
 }
 
+#ifndef SRNN_EDGE_KERNEL_ONLY   // srnn_train.hip launches the edge kernel only
 // split a fp32 matrix into bf16 hi / lo planes (split_bf16.h)
 __global__ void srnn_split_kernel(int n, const float *__restrict__ w, __bf16 *__restrict__ hi, __bf16 *__restrict__ lo)
 {
@@ -189,6 +203,19 @@ __global__ void srnn_split_kernel(int n, const float *__restrict__ w, __bf16 *__
         const __bf16 h = (__bf16)w[i];
         hi[i] = h;
         lo[i] = (__bf16)(w[i] - (float)h);
+    }
+}
+
+// W_hh [768,256] transposed and split: planes [256,768] whose rows are the 768 k of one hidden unit (the B fragments of the backward's
+// carry product d_gh . W_hh, srnn_train_kernels.h)
+__global__ void srnn_split_t_kernel(const float *__restrict__ w, __bf16 *__restrict__ hi, __bf16 *__restrict__ lo)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;       // index into the [256,768] planes
+    if (i < 768 * SR_HID) {
+        const float v = w[(size_t)(i % 768) * SR_HID + i / 768];
+        const __bf16 h = (__bf16)v;
+        hi[i] = h;
+        lo[i] = (__bf16)(v - (float)h);
     }
 }
 
@@ -393,4 +420,33 @@ __global__ __launch_bounds__(SR_NODE_THREADS, 2) void srnn_node_kernel(int E, in
     }
 }
 
+#endif // SRNN_EDGE_KERNEL_ONLY
+
 } // namespace
+
+// The handle (srnn.hip creates it; srnn_train.hip reads its snapshot, planes and mode)
+constexpr int SR_NW = sizeof(cn_srnn_weights) / sizeof(const float *);
+enum { W_ENC_S = 0, W_GRU_S = 2, W_ENC_T = 6, W_GRU_T = 8, W_ATTN = 12, W_NODE = 16, W_TRUNK = 26, W_HEADS = 34 };   // first field of each group
+
+struct cn_srnn {
+    int H, D, maxE, mode, have_weights;
+    char *pool;                 // weight snapshot (fp32), split planes of the two W_hh, taps
+    const float *w[SR_NW];      // snapshot pointers, in cn_srnn_weights field order
+    __bf16 *planes[4];          // split planes of W_hh: spatial hi / lo, temporal hi / lo
+    __bf16 *planes_t[4];        // the same of W_hh^T ([256,768]), for the training backward
+    float *tap_attn, *tap_weighted, *tap_node, *tap_feat;
+    float *edge_ws;             // [maxE,H+1,256], allocated by the first cn_srnn_get_value (which has no edge output of the caller's)
+    const float *last_edge;     // the edge state the last forward wrote (the caller's edge_hxs_out, or edge_ws)
+    int lastE;
+};
+
+static inline SrnnEdgeW srnn_edge_weights(const cn_srnn *p, int spatial)
+{
+    const int enc = spatial ? W_ENC_S : W_ENC_T, gru = spatial ? W_GRU_S : W_GRU_T, plane = spatial ? 0 : 2;
+    SrnnEdgeW w;
+    w.enc_w = p->w[enc]; w.enc_b = p->w[enc + 1];
+    w.w_ih = p->w[gru]; w.w_hh = p->w[gru + 1]; w.b_ih = p->w[gru + 2]; w.b_hh = p->w[gru + 3];
+    w.hh_hi = p->planes[plane]; w.hh_lo = p->planes[plane + 1];
+    w.din = spatial ? p->D : 2;
+    return w;
+}

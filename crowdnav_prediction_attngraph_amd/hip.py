@@ -1,5 +1,6 @@
 """Thin object wrappers over the C ABI handles (cn_env_batch, cn_policy) and the rollout-math entry points."""
 import ctypes as C
+import math
 
 import torch
 
@@ -433,7 +434,8 @@ class HipPolicy:
 
 
 class HipSrnn:
-    """cn_srnn handle: rollout-time forward (act / get_value) of the DS-RNN baseline (Policy(base='srnn')).  Two launches per forward."""
+    """cn_srnn handle of the DS-RNN baseline (Policy(base='srnn')): the rollout-time forward (act / get_value), two launches per forward, and the
+    edge-GRU sequence of the update (seq_fwd / seq_bwd)."""
 
     def __init__(self, human_num, edge_width, max_envs, device=None):
         _need_cuda()
@@ -518,6 +520,86 @@ class HipSrnn:
     def set_gemm_mode(self, mode):
         """'bf16x3' (default: the two edge-GRU products as split-precision MFMA) or 'fp32' (exact fp32 MFMA)."""
         A.check(A.lib().cn_srnn_set_gemm_mode(self._h, {"fp32": 0, "bf16x3": 1}[mode]), "cn_srnn_set_gemm_mode")
+
+    # ---- the edge-GRU sequence of the update (cn_srnn_seq_fwd / cn_srnn_seq_bwd); SrnnEdgeSequence below is the autograd face ----
+    def seq_workspace_bytes(self, T, N):
+        """0 = a shape the sequence kernels refuse (the caller then runs the torch-op loop)."""
+        return int(A.lib().cn_srnn_seq_workspace_bytes(int(T), int(N), self.H, self.D))
+
+    def _seq_args(self, who, T, N, tensors):
+        for name, t, shape in tensors:
+            if t is None:
+                continue
+            if not t.is_cuda or t.device != self.device:
+                raise A.CnError("%s: %s must live on %s" % (who, name, self.device))
+            if t.dtype != torch.float32:
+                raise A.CnError("%s: %s must be float32, not %s" % (who, name, t.dtype))
+            if t.numel() != math.prod(shape) or not t.is_contiguous():
+                raise A.CnError("%s: %s must be a contiguous tensor of shape %s" % (who, name, list(shape)))
+
+    def seq_fwd(self, temporal_edges, spatial_edges, edge_h0, masks, T, N, workspace=None):
+        """temporal_edges [T*N,2], spatial_edges [T*N,H,D], edge_h0 [N,H+1,256], masks [T*N,1] -> (h_all [T,N,H+1,256], workspace)."""
+        H, D, dev = self.H, self.D, self.device
+        self._seq_args("cn_srnn_seq_fwd", T, N, (("temporal_edges", temporal_edges, (T, N, 2)), ("spatial_edges", spatial_edges, (T, N, H, D)),
+                                                  ("edge_h0", edge_h0, (N, H + 1, 256)), ("masks", masks, (T, N))))
+        if workspace is None:
+            workspace = torch.empty(self.seq_workspace_bytes(T, N) // 4, device=dev)
+        h_all = torch.empty(T, N, H + 1, 256, device=dev)
+        with torch.cuda.device(dev):
+            A.check(A.lib().cn_srnn_seq_fwd(self._h, T, N, A.ptr(temporal_edges), A.ptr(spatial_edges), A.ptr(edge_h0), A.ptr(masks), A.ptr(h_all),
+                                            A.ptr(workspace), workspace.numel() * workspace.element_size(), A.stream_ptr()), "cn_srnn_seq_fwd")
+        return h_all, workspace
+
+    def seq_bwd(self, temporal_edges, spatial_edges, edge_h0, masks, h_all, d_h_all, workspace, T, N, grads, d_edge_h0=None):
+        """grads: the twelve gradient tensors in A.SRNN_EDGE_KEYS order (overwritten); d_edge_h0 [N,H+1,256] or None.  The workspace is the one
+        seq_fwd filled for the same arguments; the call consumes it."""
+        H, D, dev = self.H, self.D, self.device
+        who = "cn_srnn_seq_bwd"
+        self._seq_args(who, T, N, (("temporal_edges", temporal_edges, (T, N, 2)), ("spatial_edges", spatial_edges, (T, N, H, D)),
+                                   ("edge_h0", edge_h0, (N, H + 1, 256)), ("masks", masks, (T, N)), ("h_all", h_all, (T, N, H + 1, 256)),
+                                   ("d_h_all", d_h_all, (T, N, H + 1, 256)), ("d_edge_h0", d_edge_h0, (N, H + 1, 256))))
+        g = A.SrnnEdgeGrads()
+        for (field, _), t in zip(A.SRNN_EDGE_KEYS, grads):
+            if t is not None:
+                self._seq_args(who, T, N, ((field, t, t.shape),))
+            setattr(g, field, None if t is None else t.data_ptr())
+        if getattr(self, "_seq_partials", None) is None:
+            self._seq_partials = torch.empty(A.SRNN_SEQ_PARTIALS_BYTES // 4, device=dev)
+        with torch.cuda.device(dev):
+            A.check(A.lib().cn_srnn_seq_bwd(self._h, T, N, A.ptr(temporal_edges), A.ptr(spatial_edges), A.ptr(edge_h0), A.ptr(masks), A.ptr(h_all),
+                                            A.ptr(d_h_all), A.ptr(workspace), workspace.numel() * workspace.element_size(), C.byref(g),
+                                            A.ptr(d_edge_h0), A.ptr(self._seq_partials), A.stream_ptr()), who)
+
+
+class SrnnEdgeSequence(torch.autograd.Function):
+    """Both edge GRUs of the DS-RNN baseline over a [T,N] rollout slice: h_t = GRU(ReLU(enc x_t), mask_t * h_{t-1}) for the temporal edge and
+    the H spatial edges, on the kernel and with the arithmetic of the rollout (cn_srnn_seq_fwd), and BPTT plus the weight gradients as
+    cn_srnn_seq_bwd.  (hip, temporal_edges [T*N,2], spatial_edges [T*N,H,D], edge_h0 [N,H+1,256], masks [T*N,1], *the twelve parameters in
+    A.SRNN_EDGE_KEYS order) -> h_all [T,N,H+1,256].  `hip` is a HipSrnn whose weight snapshot holds these parameters (Policy._hip_srnn sees
+    to that); the parameter arguments only give autograd somewhere to put the gradients."""
+
+    @staticmethod
+    def forward(ctx, hip, temporal_edges, spatial_edges, edge_h0, masks, *params):
+        N = edge_h0.shape[0]
+        T = masks.numel() // N
+        te, se, h0, m = (t.detach().contiguous() for t in (temporal_edges, spatial_edges, edge_h0, masks))
+        h_all, ws = hip.seq_fwd(te, se, h0, m, T, N)
+        ctx.hip, ctx.ws, ctx.TN = hip, ws, (T, N)
+        ctx.shapes = [p.shape for p in params]
+        ctx.save_for_backward(te, se, h0, m, h_all)
+        return h_all
+
+    @staticmethod
+    def backward(ctx, d_h_all):
+        te, se, h0, m, h_all = ctx.saved_tensors
+        T, N = ctx.TN
+        if ctx.ws is None:
+            raise RuntimeError("SrnnEdgeSequence: the backward consumes the saved gates; it cannot run twice")
+        grads = [torch.empty(s, device=h_all.device) for s in ctx.shapes]
+        d_h0 = torch.empty_like(h0) if ctx.needs_input_grad[3] else None
+        ctx.hip.seq_bwd(te, se, h0, m, h_all, d_h_all.contiguous(), ctx.ws, T, N, grads, d_h0)
+        ctx.ws = None
+        return (None, None, None, d_h0, None) + tuple(grads)
 
 
 def compact_visible(spatial_edges, visible_masks):

@@ -450,10 +450,14 @@ class SRNNBase(nn.Module):
     Three modules never reach the output and never get a gradient (humanNodeRNN.edge_embed, human_node_final_linear, spatial_linear)."""
 
     DEAD_MODULES = ("humanNodeRNN.edge_embed", "human_node_final_linear", "spatial_linear")
+    # forward_sequence on GPU tensors: both edge GRUs over all T steps as hip.SrnnEdgeSequence (cn_srnn_seq_fwd / cn_srnn_seq_bwd) instead of
+    # the torch-op loop, which stays the definition (False, CPU tensors, or a shape cn_srnn_seq_workspace_bytes refuses)
+    train_edge_kernels = True
 
     def __init__(self, obs_space_dict, args):
         super().__init__()
         self.is_recurrent = True
+        self.hip_provider = None            # Policy sets it: (N, device) -> the HipSrnn handle with the current weights
         self.args = args
         self.human_num = obs_space_dict["spatial_edges"].shape[0]
         self.edge_width = obs_space_dict["spatial_edges"].shape[1]
@@ -509,6 +513,25 @@ class SRNNBase(nn.Module):
         a = torch.softmax((te.unsqueeze(-2) * se).sum(-1) * (H / math.sqrt(64.0)), dim=-1)
         return (a.unsqueeze(-1) * h_s).sum(-2), a
 
+    def _edge_parameters(self):
+        """The twelve parameters of the two edge RNNs in cn_srnn_weights field order (_abi.SRNN_EDGE_KEYS)."""
+        out = []
+        for rnn in (self.humanhumanEdgeRNN_spatial, self.humanhumanEdgeRNN_temporal):
+            out += [rnn.encoder_linear.weight, rnn.encoder_linear.bias, rnn.gru.weight_ih_l0, rnn.gru.weight_hh_l0, rnn.gru.bias_ih_l0, rnn.gru.bias_hh_l0]
+        return out
+
+    def _edge_sequence_handle(self, inputs, edge_h0, masks, T, N):
+        """The HipSrnn handle for the kernel path of the edge-GRU sequence, or None where the torch-op loop runs: train_edge_kernels off, CPU or
+        non-fp32 tensors, no provider (a base outside a Policy), or a shape the kernels refuse."""
+        if not (self.train_edge_kernels and self.hip_provider is not None and edge_h0.is_cuda):
+            return None
+        if any(t.dtype != torch.float32 for t in (inputs["temporal_edges"], inputs["spatial_edges"], edge_h0, masks)):
+            return None
+        from . import _abi as A
+        if A.lib().cn_srnn_seq_workspace_bytes(T, N, self.human_num, self.edge_width) <= 0:
+            return None
+        return self.hip_provider(N, edge_h0.device)
+
     def forward_sequence(self, inputs, node_h0, edge_h0, masks, T, N, taps=None):
         """inputs: dict of [T*N, ...] (T-major), node_h0 [N,1,128] or [N,128], edge_h0 [N,H+1,256], masks [T*N,1].
         Returns value [T*N,1], actor features [T*N,256], node h_T [N,128], edge h_T [N,H+1,256].  The state is multiplied by masks[t] at EVERY
@@ -517,17 +540,25 @@ class SRNNBase(nn.Module):
         rn = inputs["robot_node"].reshape(B, 7)
         m = masks.reshape(T, N, 1)
         et, es, node = self.humanhumanEdgeRNN_temporal, self.humanhumanEdgeRNN_spatial, self.humanNodeRNN
-        gi_t = self._edge_gi(et, inputs["temporal_edges"].reshape(B, 2)).view(T, N, -1)
-        gi_s = self._edge_gi(es, inputs["spatial_edges"].reshape(B, H, self.edge_width)).view(T, N, H, -1)
         edge_h0 = edge_h0.reshape(N, H + 1, -1)
-        h_t, h_s = edge_h0[:, 0], edge_h0[:, 1:]
-        hts, hss = [], []
-        for t in range(T):
-            h_t = _gru_cell(gi_t[t], h_t * m[t], et.gru.weight_hh_l0, et.gru.bias_hh_l0)
-            h_s = _gru_cell(gi_s[t], h_s * m[t].unsqueeze(1), es.gru.weight_hh_l0, es.gru.bias_hh_l0)
-            hts.append(h_t)
-            hss.append(h_s)
-        ht_all, hs_all = torch.stack(hts, 0), torch.stack(hss, 0)                   # [T,N,256], [T,N,H,256]
+        hip = self._edge_sequence_handle(inputs, edge_h0, masks, T, N)
+        if hip is not None:
+            from .hip import SrnnEdgeSequence
+            h_all = SrnnEdgeSequence.apply(hip, inputs["temporal_edges"].reshape(B, 2), inputs["spatial_edges"].reshape(B, H, self.edge_width), edge_h0,
+                                           masks.reshape(B, 1), *self._edge_parameters())
+            ht_all, hs_all = h_all[:, :, 0], h_all[:, :, 1:]                            # views of [T,N,H+1,256]
+            h_t, h_s = ht_all[-1].detach(), hs_all[-1].detach()
+        else:
+            gi_t = self._edge_gi(et, inputs["temporal_edges"].reshape(B, 2)).view(T, N, -1)
+            gi_s = self._edge_gi(es, inputs["spatial_edges"].reshape(B, H, self.edge_width)).view(T, N, H, -1)
+            h_t, h_s = edge_h0[:, 0], edge_h0[:, 1:]
+            hts, hss = [], []
+            for t in range(T):
+                h_t = _gru_cell(gi_t[t], h_t * m[t], et.gru.weight_hh_l0, et.gru.bias_hh_l0)
+                h_s = _gru_cell(gi_s[t], h_s * m[t].unsqueeze(1), es.gru.weight_hh_l0, es.gru.bias_hh_l0)
+                hts.append(h_t)
+                hss.append(h_s)
+            ht_all, hs_all = torch.stack(hts, 0), torch.stack(hss, 0)                   # [T,N,256], [T,N,H,256]
         weighted, a = self.attention(ht_all, hs_all)
         enc = F.relu(F.linear(F.linear(rn, self.robot_linear.weight, self.robot_linear.bias), node.encoder_linear.weight, node.encoder_linear.bias))
         ee = F.relu(F.linear(torch.cat((ht_all, weighted), -1).view(B, -1), node.edge_attention_embed.weight, node.edge_attention_embed.bias))
@@ -555,6 +586,8 @@ class Policy(nn.Module):
         if action_space.__class__.__name__ != "Box":
             raise NotImplementedError("only Box(2) action spaces (holonomic robot) are implemented")
         self.base = (SRNNBase if base == "srnn" else AttnGraphBase)(obs_shape, base_kwargs)
+        if base == "srnn":
+            self.base.hip_provider = self._hip_srnn
         self.srnn = True
         self.dist = _DiagGaussian(self.base.output_size, action_space.shape[0])
         self._hip = None
@@ -649,8 +682,9 @@ class Policy(nn.Module):
         return value
 
     def _srnn_evaluate_actions(self, inputs, rnn_hxs, masks, action):
-        """The T-step sequence in torch ops under autograd, on either device (a hand-written training kernel for the edge-GRU sequence is the
-        next step)."""
+        """The T-step sequence under autograd.  On the GPU the two edge GRUs -- the recurrent core, N (H+1) rows of 256 per step -- run as
+        hip.SrnnEdgeSequence (SRNNBase.train_edge_kernels); attention, the node GRU, the trunks and the heads are torch ops over all T at
+        once.  On the CPU everything is torch ops: that graph is the definition."""
         B = inputs["robot_node"].shape[0]
         N = rnn_hxs["human_node_rnn"].shape[0]
         value, feat, h, e = self.base.forward_sequence(inputs, rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"], masks, B // N, N)

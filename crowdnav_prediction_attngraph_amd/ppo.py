@@ -195,6 +195,9 @@ class PPO():
             scale = 1.0 / d.get_world_size()
         g = self.optimizer.param_groups[0]
         flat.step(g["lr"], g["betas"], g["eps"], self.max_grad_norm, grad_scale=scale)
+        # after every step, not once per update(): it only clears a flag, and the DS-RNN baseline's evaluate_actions reads the snapshot (the
+        # edge-GRU sequence kernels take the cn_srnn handle's weights)
+        self._weights_changed()
 
     def update(self, rollouts):
         advantages = self._advantages(rollouts)
@@ -211,7 +214,6 @@ class PPO():
                 self._optimizer_step(flat, d, ar_events)
                 k += 1
         if flat is not None:
-            self._weights_changed()    # once, not per optimiser step: it only clears a flag, and nothing reads the rollout-side snapshot in update()
             flat.sync_optimizer_state()
         if ar_events:      # mean duration of the gradient all-reduce on this rank's stream
             torch.cuda.synchronize()

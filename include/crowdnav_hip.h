@@ -18,6 +18,7 @@
  *   cn_policy_get_value        <- rl/networks/model.py:76-80 Policy.get_value
  *   cn_srnn_create/destroy/set_weights <- rl/networks/model.py:16-46 Policy.__init__ with base='srnn' / load_state_dict
  *   cn_srnn_act                <- rl/networks/model.py:56-74 Policy.act (-> srnn_model.py:389-468 SRNN.forward, infer=True)
+ *   cn_srnn_seq_fwd / _bwd      <- rl/ppo/ppo.py evaluate_actions on that base: the edge-GRU sequence of srnn_model.py:418-433 and its backward
  *   cn_srnn_get_value          <- rl/networks/model.py:76-80 Policy.get_value on that base
  *   cn_gae                     <- rl/networks/storage.py:123-132 RolloutStorage.compute_returns (use_gae branch)
  *   cn_adv_stats / cn_adv_normalize <- rl/ppo/ppo.py:37-39 advantage normalisation (split so that N GPUs can
@@ -396,6 +397,35 @@ int cn_srnn_get_taps(cn_srnn *p, int E, float *edge_out, float *attn, float *wei
  * humans are padded with 15 m, embeddings reach 10 .. 30) and as a split product it alone was 1.1e-4 off the reference.  Everything else
  * (encoders, gates, attention, node GRU, trunks, heads) always runs in fp32. */
 int cn_srnn_set_gemm_mode(cn_srnn *p, int mode);
+
+/* ---- DS-RNN baseline: the edge-GRU sequence of PPO.update (srnn_model.py:418-433 over a T-step minibatch) and its backward ----
+ * For t = 0 .. T-1 both edge GRUs compute h_t = GRU(ReLU(enc x_t), mask_t * h_{t-1}) with the kernel and the arithmetic of cn_srnn_act
+ * (rows gathered per weight set, one launch per step, the handle's weight snapshot, split planes and gemm mode: call cn_srnn_set_weights
+ * after every optimiser step).  No atomics on data, fixed summation orders, equal arguments give equal bits, and a row's h does not depend
+ * on which rows share its tile.  temporal_edges [T,N,2], spatial_edges [T,N,H,D], edge_h0 [N,H+1,256], masks [T,N], h_all [T,N,H+1,256].
+ *
+ * workspace: cn_srnn_seq_workspace_bytes(T, N, H, D) bytes.  The forward leaves the gates r, z, n and W_hn (mask * h) + b_hn and the 64-wide
+ * post-ReLU embedding of every row and step there; the backward overwrites the gates IN PLACE with dr, dz, dn, dn * r (what the weight
+ * gradients are summed from) and adds d_e and one [N,H+1,256] carry.  The function runs on the host and needs no device; it returns 0 for a
+ * shape the kernels refuse: H outside [1,64], D outside [1,64], T < 1, N < 1, or T * N * (H+1) * 1024 saved floats past 32-bit element
+ * offsets.  workspace_bytes is what the caller allocated (checked against the shape).
+ *
+ * cn_srnn_seq_bwd: d_h_all [T,N,H+1,256] is the gradient of h_all (read only).  BPTT for t = T-1 .. 0, one launch per step, then the weight
+ * gradients of each set as sums over all its rows and steps: the rows are cut into at most CN_SRNN_SEQ_CHUNKS ranges whose partial products
+ * land in `partials` (CN_SRNN_SEQ_PARTIALS_BYTES bytes, whatever the shape) and are added in range order.  grads: the twelve gradients, in
+ * cn_srnn_weights field order for the two edge RNNs, each OVERWRITTEN.  d_edge_h0 [N,H+1,256] (the carry of step -1) may be NULL. */
+typedef struct {
+    float *enc_s_w, *enc_s_b, *gru_s_w_ih, *gru_s_w_hh, *gru_s_b_ih, *gru_s_b_hh;
+    float *enc_t_w, *enc_t_b, *gru_t_w_ih, *gru_t_w_hh, *gru_t_b_ih, *gru_t_b_hh;
+} cn_srnn_edge_grads;
+#define CN_SRNN_SEQ_CHUNKS 64
+#define CN_SRNN_SEQ_PARTIALS_BYTES ((int64_t)CN_SRNN_SEQ_CHUNKS * (768 * 256 + 1024 * 80 + 64 * 80) * 4)
+int64_t cn_srnn_seq_workspace_bytes(int T, int N, int H, int D);
+int cn_srnn_seq_fwd(cn_srnn *p, int T, int N, const float *temporal_edges, const float *spatial_edges, const float *edge_h0, const float *masks,
+                    float *h_all, void *workspace, int64_t workspace_bytes, void *stream);
+int cn_srnn_seq_bwd(cn_srnn *p, int T, int N, const float *temporal_edges, const float *spatial_edges, const float *edge_h0, const float *masks,
+                    const float *h_all, const float *d_h_all, void *workspace, int64_t workspace_bytes, const cn_srnn_edge_grads *grads,
+                    float *d_edge_h0, void *partials, void *stream);
 
 /* ---- device-side launch stamps (measurement aid for bench.py / tools; not part of the reference's interface) ----
  * The kernels of the rollout step (CN_PROF_K_*) stamp the device's 100 MHz wall clock when their first workgroups start and when their
