@@ -342,6 +342,17 @@ def check(rc, what=""):
         raise CnError("%s failed (status %d): %s" % (what or "libcrowdnav_hip call", rc, msg.decode() if msg else ""))
 
 
+def call(name, *args, device=None):
+    """Run the library function `name`, which returns a status, and raise CnError with the library's message when it is not 0.  device: run it
+    under torch.cuda.device(device), for the calls that launch on (or allocate for) the current device; None: no guard."""
+    fn = getattr(lib(), name)
+    if device is None:
+        return check(fn(*args), name)
+    import torch
+    with torch.cuda.device(device):
+        return check(fn(*args), name)
+
+
 def default_env_config(**over):
     cfg = EnvConfig()
     lib().cn_env_config_default(C.byref(cfg))

@@ -155,9 +155,8 @@ class EvalAccumulator(object):
                     or danger_dist.dtype != torch.float64 or done.numel() != E or info.numel() != E or ep_return.numel() != E
                     or robot_node.numel() != 7 * E or danger_dist.numel() != E):
                 raise A.CnError("EvalAccumulator.update: done / info u8 [E], ep_return / danger_dist f64 [E], robot_node f32 [E,1,7] expected (E = %d)" % E)
-            with torch.cuda.device(self.device):
-                A.check(A.lib().cn_eval_accumulate(E, A.ptr(done), A.ptr(info), A.ptr(ep_return), A.ptr(robot_node), A.ptr(danger_dist), A.ptr(self.state),
-                                                   A.ptr(self.masks), A.stream_ptr()), "cn_eval_accumulate")
+            A.call("cn_eval_accumulate", E, A.ptr(done), A.ptr(info), A.ptr(ep_return), A.ptr(robot_node), A.ptr(danger_dist), A.ptr(self.state),
+                   A.ptr(self.masks), A.stream_ptr(), device=self.device)
             return self.masks
         act = self.active != 0
         pos = robot_node.reshape(E, 7)[:, :2]
@@ -203,11 +202,11 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     """test_size: the episode count of the sequential protocol (episode k runs case 2 k mod the config's test_size), or a sequence of case
     numbers to run instead (render_episodes).  poll_every: the count of running episodes is read back (the loop's only host synchronisation)
     every that many steps; steps taken after the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
-    hip_policy: a HipPolicy (DS-RNN baseline: HipSrnn) handle to run instead of actor_critic's own (train() evaluates through a second handle so that the training
+    hip_policy: a policy handle (base.make_hip_handle) to run instead of actor_critic's own (train() evaluates through a second handle so that the training
     rollout finds its handle as it left it); use_kernel=False: the torch-op bookkeeping; per_env: a dict that receives the per-env results;
     frame_fn(t, env, obs): called once after the reset (t = 0) and once after every step (t = steps taken) with the HipEnvBatch and the
     observation it returned, e.g. to draw the state (render_episodes); it must leave both as they are."""
-    from .hip import HipEnvBatch
+    from .hip_env import HipEnvBatch
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = to_env_config(config, env_name, 1, "test")          # nenv = 1: case counters advance by one, as in the sequential run
     scripted = actor_critic is None and act_fn is None
@@ -241,13 +240,11 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     if frame_fn is not None:
         frame_fn(0, env, obs)
     pol = None
-    srnn = actor_critic is not None and getattr(actor_critic, "is_srnn_baseline", False)     # DS-RNN: the edge state is carried as well
     if act_fn is None and not scripted:
-        pol = hip_policy if hip_policy is not None else (actor_critic._hip_srnn(E, device) if srnn else actor_critic._hip_policy(E, device))
+        pol = hip_policy if hip_policy is not None else actor_critic._hip_handle(E, device)
+        # the state the handle carries ping-pongs between two buffers
+        hxs = [{k: torch.zeros(shape, device=device) for k, shape in pol.state_shapes(E).items()} for _ in (0, 1)]
     zero_action = torch.zeros(E, 2, device=device)
-    hx = [torch.zeros(E, 1, 128, device=device), torch.zeros(E, 1, 128, device=device)]
-    if srnn:
-        ex = [torch.zeros(E, env.H + 1, 256, device=device), torch.zeros(E, env.H + 1, 256, device=device)]
     acc = EvalAccumulator(E, device, use_kernel=use_kernel)
     acc.start(obs["robot_node"])
     masks = acc.masks
@@ -265,15 +262,9 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
                 pobs["spatial_edges"], _ = pretext.process(obs, zero_reward if t == 0 else rew)
             if act_fn is not None:
                 action = act_fn(t, pobs)
-            elif srnn:
-                # both states ping-pong between two buffers; the masks zero them at episode ends inside the kernels
-                out = dict(value=torch.empty(E, 1, device=device), action=torch.empty(E, 2, device=device), logp=torch.empty(E, 1, device=device),
-                           hxs=hx[(t + 1) & 1], edge_hxs=ex[(t + 1) & 1])
-                pol.act(pobs, hx[t & 1], ex[t & 1], masks, eps=None, out=out)
-                action = out["action"]
             else:
-                out = pol.act(pobs, hx[t & 1], masks, eps=None)      # deterministic: dist.mode() (model.py:66-67)
-                hx[(t + 1) & 1] = out["hxs"].view(E, 1, 128)
+                # deterministic: dist.mode() (model.py:66-67); the masks zero the state at episode ends inside the kernels
+                out, _ = pol.act_rnn(pobs, hxs[t & 1], masks, eps=None, rnn_hxs_out=hxs[(t + 1) & 1])
                 action = out["action"]
         obs, rew, done, info, ep_ret, _ = env.step(action)
         env.get_danger_min_dist(out=danger_dist)
@@ -308,7 +299,7 @@ def render_episodes(actor_critic, env_name, config, seed, cases, size=256, devic
     state, frame t the state after step t -- the last one therefore shows what the vec-env's auto-reset left.  The frames go into ONE
     preallocated device buffer [T,n,size,size] RGBA and are read back once at the end; a request whose buffer would exceed 4 GiB is
     refused."""
-    from .hip import prediction_dots
+    from .hip_env import prediction_dots
     cases = sorted(set(int(c) for c in cases))
     if not cases:
         raise ValueError("render_episodes: no cases given")

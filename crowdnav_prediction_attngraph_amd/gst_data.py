@@ -195,10 +195,10 @@ class DeviceTrajectories(Dataset):
         visible, frame_id, status = i32(F_, E), torch.empty(F_, E, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
         frame_list, ped_count, first_frame = i32(E, F_), i32(E * W), torch.empty(E * W, device=dev)
         with torch.cuda.device(dev):
-            A.check(L.cn_gst_data_frames(F_, E, H, A.ptr(log), A.ptr(visible), A.ptr(frame_id), A.ptr(status), A.stream_ptr()), "cn_gst_data_frames")
+            A.call("cn_gst_data_frames", F_, E, H, A.ptr(log), A.ptr(visible), A.ptr(frame_id), A.ptr(status), A.stream_ptr())
             listed_before = (torch.cumsum(visible, 0).to(torch.int32) - visible).contiguous()
-            A.check(L.cn_gst_data_count(F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
-                                        A.ptr(first_frame), A.ptr(status), A.stream_ptr()), "cn_gst_data_count")
+            A.call("cn_gst_data_count", F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
+                   A.ptr(first_frame), A.ptr(status), A.stream_ptr())
             ped_offset = (torch.cumsum(ped_count, 0).to(torch.int32) - ped_count).contiguous()
             host = torch.cat((status, ped_count, first_frame.view(torch.int32))).cpu().numpy()       # the one read-back of the build
             st, counts, first = int(host[0]), host[1:1 + E * W].astype(np.int64), host[1 + E * W:].view(np.float32)
@@ -215,8 +215,8 @@ class DeviceTrajectories(Dataset):
             if total >= 2 ** 31 // 10:
                 raise A.CnError("DeviceTrajectories.from_log: %d pedestrian rows exceed the 32-bit offsets of the build" % total)
             arrays = [torch.empty(total, 2, 5, device=dev) for _ in range(4)] + [torch.empty(total, 10, device=dev) for _ in range(2)]
-            A.check(L.cn_gst_data_fill(F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
-                                       A.ptr(ped_offset), total, *([A.ptr(t) for t in arrays] + [A.stream_ptr()])), "cn_gst_data_fill")
+            A.call("cn_gst_data_fill", F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
+                   A.ptr(ped_offset), total, *([A.ptr(t) for t in arrays] + [A.stream_ptr()]))
         env_of = np.nonzero(is_seq)[0] // W
         return cls(arrays, counts[is_seq], first[is_seq], env_of if envs is None else np.asarray(envs, dtype=np.int64)[env_of])
 
@@ -242,10 +242,9 @@ class DeviceTrajectories(Dataset):
             raise A.CnError("DeviceTrajectories.gather: index must be int32 [B] and cos_sin float32 [B,2]")
         v_obs, v_pred = torch.empty(B, 5, num_peds, 2, device=self.device), torch.empty(B, 5, num_peds, 2, device=self.device)
         lm = torch.empty(B, num_peds, 10, device=self.device)
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_gather_batch(B, int(num_peds), self.num_seq, self.total_peds, A.ptr(index), A.ptr(cos_sin), A.ptr(self._seq_start),
-                                                A.ptr(self._seq_count), A.ptr(self.obs_traj_rel), A.ptr(self.pred_traj_rel), A.ptr(self.loss_mask_rel),
-                                                A.ptr(v_obs), A.ptr(v_pred), A.ptr(lm), A.stream_ptr()), "cn_gst_gather_batch")
+        A.call("cn_gst_gather_batch", B, int(num_peds), self.num_seq, self.total_peds, A.ptr(index), A.ptr(cos_sin), A.ptr(self._seq_start),
+               A.ptr(self._seq_count), A.ptr(self.obs_traj_rel), A.ptr(self.pred_traj_rel), A.ptr(self.loss_mask_rel),
+               A.ptr(v_obs), A.ptr(v_pred), A.ptr(lm), A.stream_ptr(), device=self.device)
         return v_obs, v_pred, lm
 
     def num_peds(self, order):

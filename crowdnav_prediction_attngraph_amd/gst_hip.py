@@ -8,6 +8,7 @@ import torch
 
 from . import _abi as A
 from .flat_adam import FlatAdam
+from .hip_policy import HipHandle
 
 
 def gst_weights(tensors, who):
@@ -50,68 +51,40 @@ def workspace(ws, need, dev):
     return ws if ws is not None and ws.numel() >= need else torch.empty(need, dtype=torch.uint8, device=dev)
 
 
-def _need_cuda():
-    if not torch.cuda.is_available():
-        raise A.CnError("no GPU visible: the GST predictor's hot path only runs on MI355X (no CPU fallback)")
-
-
-class HipGST:
+class HipGST(HipHandle):
     """cn_gst handle: GST predictor (cn_gst_predict) and the VecPretextNormalize processing (cn_gst_wrapper_*)."""
+    _sym, _weights = "cn_gst", (A.GstWeights, A.GST_WEIGHT_KEYS)
 
     def __init__(self, human_num, max_envs, device=None):
-        _need_cuda()
         self.H, self.maxE = int(human_num), int(max_envs)
-        self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_create(self.H, self.maxE, C.byref(h)), "cn_gst_create")
-        self._h = h
-        self._keep = None
+        self._open(device, self.H, self.maxE)
 
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            A.lib().cn_gst_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_weights(self, state_dict):
-        keep = [state_dict[key].detach().to(device=self.device, dtype=torch.float32).contiguous() for _, key in A.GST_WEIGHT_KEYS]
-        w = gst_weights(keep, "HipGST")
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_set_weights(self._h, C.byref(w), A.stream_ptr()), "cn_gst_set_weights")
-        self._keep = keep
+    def _weights_struct(self, fields, tensors):
+        return gst_weights(tensors, "HipGST")
 
     def predict(self, in_traj, in_mask):
         """in_traj [E,H,5,2], in_mask [E,H,5] or [E,H,5,1] float -> (out_traj [E,H,5,5], out_mask [E,H,1])."""
         E = in_traj.shape[0]
         out = torch.empty(E, self.H, 5, 5, device=self.device)
         om = torch.empty(E, self.H, device=self.device)
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_predict(self._h, E, A.ptr(in_traj.float().contiguous()), A.ptr(in_mask.float().reshape(E, self.H, 5).contiguous()),
-                                           A.ptr(out), A.ptr(om), A.stream_ptr()), "cn_gst_predict")
+        A.call("cn_gst_predict", self._h, E, A.ptr(in_traj.float().contiguous()), A.ptr(in_mask.float().reshape(E, self.H, 5).contiguous()),
+               A.ptr(out), A.ptr(om), A.stream_ptr(), device=self.device)
         return out, om.unsqueeze(-1)
 
     def wrapper_reset(self, E):
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_wrapper_reset(self._h, int(E), A.stream_ptr()), "cn_gst_wrapper_reset")
+        A.call("cn_gst_wrapper_reset", self._h, int(E), A.stream_ptr(), device=self.device)
         self._wrap_E = int(E)
 
     def wrapper_set_interval(self, pred_interval):
         """int(data.pred_timestep // env.time_step): the history keeps 4 * pred_interval + 1 observations, every pred_interval-th is fed."""
-        A.check(A.lib().cn_gst_wrapper_set_interval(self._h, int(pred_interval)), "cn_gst_wrapper_set_interval")
+        A.call("cn_gst_wrapper_set_interval", self._h, int(pred_interval))
 
     def wrapper_state(self):
         """(traj [len,E,H,2] float32, mask [len,E,H] uint8) = the observation history in time order, oldest first (cn_gst_wrapper_save)."""
         L, E = int(A.lib().cn_gst_wrapper_history_len(self._h)), self._wrap_E
         traj = torch.empty(L, E, self.H, 2, device=self.device)
         mask = torch.empty(L, E, self.H, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_wrapper_save(self._h, A.ptr(traj), A.ptr(mask), A.stream_ptr()), "cn_gst_wrapper_save")
+        A.call("cn_gst_wrapper_save", self._h, A.ptr(traj), A.ptr(mask), A.stream_ptr(), device=self.device)
         return traj, mask
 
     def wrapper_load_state(self, traj, mask):
@@ -121,8 +94,7 @@ class HipGST:
         E = int(traj.shape[1])
         traj = traj.to(device=self.device, dtype=torch.float32).contiguous()
         mask = mask.to(device=self.device, dtype=torch.uint8).contiguous()
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_wrapper_load(self._h, E, A.ptr(traj), A.ptr(mask), A.stream_ptr()), "cn_gst_wrapper_load")
+        A.call("cn_gst_wrapper_load", self._h, E, A.ptr(traj), A.ptr(mask), A.stream_ptr(), device=self.device)
         torch.cuda.current_stream(self.device).synchronize()   # the sources are temporaries
         self._wrap_E = E
 
@@ -137,9 +109,7 @@ class HipGST:
         vm = obs["visible_masks"]
         vm = vm.view(torch.uint8) if vm.dtype == torch.bool else vm
         o.visible_masks = A.ptr(vm.contiguous())
-        with torch.cuda.device(self.device):
-            A.check(A.lib().cn_gst_wrapper_step(self._h, E, C.byref(o), float(dist), float(collision_penalty), A.ptr(rewards), A.ptr(out), A.stream_ptr()),
-                    "cn_gst_wrapper_step")
+        A.call("cn_gst_wrapper_step", self._h, E, C.byref(o), float(dist), float(collision_penalty), A.ptr(rewards), A.ptr(out), A.stream_ptr(), device=self.device)
         return out
 
 
@@ -173,9 +143,8 @@ class HipGstTrainer:
         out = torch.empty(2, device=self.dev)
         gauss = torch.empty(B, 5, Np, 5, device=self.dev)
         sd = self.seed + 7919 * self.step_no if seed is None else int(seed)
-        with torch.cuda.device(self.dev):
-            A.check(A.lib().cn_gst_train_step(B, Np, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(self.w), C.byref(self.g), float(p_drop), C.c_uint64(sd & (2 ** 64 - 1)),
-                                              C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()), A.ptr(out), A.ptr(gauss), A.stream_ptr()), "cn_gst_train_step")
+        A.call("cn_gst_train_step", B, Np, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(self.w), C.byref(self.g), float(p_drop), C.c_uint64(sd & (2 ** 64 - 1)),
+               C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()), A.ptr(out), A.ptr(gauss), A.stream_ptr(), device=self.dev)
         return out, gauss[:, :, :N]
 
     def optimizer_step(self, grad_scale=1.0):
@@ -215,9 +184,8 @@ class HipGstEvaluator:
         self.ws = workspace(self.ws, int(A.lib().cn_gst_eval_workspace_bytes(B, Np, S)), self.dev)
         R = max(S, 1)
         seq, ped, gauss = torch.empty(B, R, 4, device=self.dev), torch.empty(B, R, Np, 3, device=self.dev), torch.empty(B, R, 5, Np, 5, device=self.dev)
-        with torch.cuda.device(self.dev):
-            A.check(A.lib().cn_gst_eval_step(B, Np, S, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(w), A.ptr(nz), C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()),
-                                             A.ptr(seq), A.ptr(ped), A.ptr(gauss), A.stream_ptr()), "cn_gst_eval_step")
+        A.call("cn_gst_eval_step", B, Np, S, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(w), A.ptr(nz), C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()),
+               A.ptr(seq), A.ptr(ped), A.ptr(gauss), A.stream_ptr(), device=self.dev)
         return seq, ped[:, :, :N], gauss[:, :, :, :N]
 
     @staticmethod

@@ -7,9 +7,10 @@ checkpoints load and `train.py` runs unchanged.  Two execution paths:
 
   * rollout (`act`, `get_value`, no autograd) on a GPU -> hand-written HIP kernels through the C ABI
     (cn_policy_act / cn_policy_get_value).  There is no fallback: on CUDA tensors a missing extension raises.
-  * training (`evaluate_actions`, needs gradients) -> the same math expressed in torch ops so autograd provides the
-    backward (hand-written backward kernels are the next step).  CPU tensors also take this path; it
-    exists for the CPU unit tests and the reference's `--no-cuda` plumbing mode, never silently on a GPU box.
+  * training (`evaluate_actions`, needs gradients) -> on a GPU the forward and the backward of every heavy stage are hand-written HIP
+    kernels behind torch.autograd.Functions (hip_train: HHBlockFused, RnSequence, SrnnEdgeSequence, ...); autograd only joins them and
+    carries the folded weights' gradients back to their factors.  CPU tensors take the same graph in torch ops: it is the definition, and
+    it exists for the CPU unit tests and the reference's `--no-cuda` plumbing mode, never silently on a GPU box.
 
 Parameter construction order follows the reference so that `torch.manual_seed(s); Policy(...)` yields bit-identical
 initial weights (tests/test_host_policy.py checks this against checksums captured from the reference).
@@ -168,11 +169,26 @@ class AttnGraphBase(nn.Module):
     # arithmetic of the three large human-human Linear layers in the PPO update on the GPU: 'bf16x3' = split-precision MFMA
     # kernels (forward, dX, dW; same arithmetic as the rollout forward), 'fp32' = torch / rocBLAS fp32
     train_gemm_mode = "bf16x3"
-    # the human-human block of the update's forward as one fused launch (hip.HHBlockFused; crowds of <= 48 humans) instead of five
+    # the human-human block of the update's forward as one fused launch (hip_train.HHBlockFused; crowds of <= 48 humans) instead of five
     train_fused_hh = True
     # everything behind the human-human block (robot node, robot-human attention, GRU sequence, trunks, heads, log-prob) as ONE call forward and
-    # ONE backward (hip.RnSequence: cn_rn_seq_fwd / cn_rn_seq_bwd) instead of torch modules with HIP Functions spliced in
+    # ONE backward (hip_train.RnSequence: cn_rn_seq_fwd / cn_rn_seq_bwd) instead of torch modules with HIP Functions spliced in
     train_fused_rn = True
+
+    gemm_mode_attr = "rollout_gemm_mode"      # the Policy attribute that holds the gemm mode of this base's rollout handle
+
+    def make_hip_handle(self, E, device):
+        """The rollout handle of this network for up to E envs, configured but without weights."""
+        from .hip_policy import HipPolicy
+        hip = HipPolicy(self.human_num, self.edge_width, E, device=device)
+        hip.set_self_attention(self.use_self_attn)
+        hip.set_taps(False)          # rollout path: nobody reads the test taps
+        return hip
+
+    def forward_rnn(self, inputs, rnn_hxs, masks, T, N):
+        """forward_sequence under the contract both bases share: (value, actor features, rnn_hxs after step T of the state this base carries)."""
+        value, feat, h = self.forward_sequence(inputs, rnn_hxs["human_node_rnn"], masks, T, N)
+        return value, feat, {"human_node_rnn": h.view(N, 1, -1)}
 
     def counted_inputs(self, inputs):
         """sort_humans = True: the inputs as they are.  sort_humans = False (selfAttn_srnn_temp_node.py:378-383, :410-414): both attention modules
@@ -187,7 +203,7 @@ class AttnGraphBase(nn.Module):
         vm = inputs["visible_masks"].reshape(B, self.human_num)
         out = dict(inputs)
         if se.is_cuda:
-            from .hip import compact_visible
+            from .hip_policy import compact_visible
             out["spatial_edges"], out["detected_human_num"] = compact_visible(se, vm)
         else:
             m = vm.to(torch.bool).clone()
@@ -198,7 +214,7 @@ class AttnGraphBase(nn.Module):
         return out
 
     def fused_rn_shapes_ok(self):
-        """hip.RnSequence hard-codes every layer shape of the robot-node sequence (_abi.RN_WEIGHT_SHAPES) and computes its products as bf16x3
+        """hip_train.RnSequence hard-codes every layer shape of the robot-node sequence (_abi.RN_WEIGHT_SHAPES) and computes its products as bf16x3
         splits: evaluate_actions takes it only when the modules have exactly those shapes and train_gemm_mode asks for that arithmetic
         ('fp32' keeps the torch / exact-fp32 path of forward_sequence)."""
         rnn, g = self.humanNodeRNN, self.humanNodeRNN.gru
@@ -210,13 +226,13 @@ class AttnGraphBase(nn.Module):
                 and tuple(self.critic_linear.weight.shape) == (1, 256))
 
     def rn_sequence(self, inputs, out_sp, row_off, h0, masks, actions, T, N, dist):
-        """(value [B,1], logp [B,1], h_T [N,128]) through hip.RnSequence.  The two affine pairs without a nonlinearity in between are composed
+        """(value [B,1], logp [B,1], h_T [N,128]) through hip_train.RnSequence.  The two affine pairs without a nonlinearity in between are composed
         here in torch ops (tiny products, autograd carries the folded gradients back to both factors): u = Ws^T (Wt r + bt) -- the
         spatial_edge_layer projection moved to the robot side, its bias keeps an exactly-zero gradient -- and (actor.0 ; critic.0) o output_linear."""
-        from .hip import RnSequence
+        from .hip_train import RnSequence
         B = T * N
         sl, tl, rnn = self.attn.spatial_edge_layer[0], self.attn.temporal_edge_layer[0], self.humanNodeRNN
-        from .hip import weight_mm as mm     # weight-by-weight products: cn_small_mm forward and backward (no library GEMM / GEMV)
+        from .hip_train import weight_mm as mm     # weight-by-weight products: cn_small_mm forward and backward (no library GEMM / GEMV)
         te_w = torch.cat([mm(sl.weight.t(), tl.weight), rnn.encoder_linear.weight], 0)
         te_b = torch.cat([mm(sl.weight.t(), tl.bias) + 0.0 * sl.bias.sum(), rnn.encoder_linear.bias], 0)
         w0 = torch.cat([self.actor[0].weight, self.critic[0].weight], 0)
@@ -232,7 +248,7 @@ class AttnGraphBase(nn.Module):
 
     def _big_linear(self, x, w, b, relu=False):
         if x.is_cuda and self.train_gemm_mode == "bf16x3":
-            from . import hip
+            from . import hip_train as hip
             if hip.linear_supported(x, w):
                 return hip.HipLinear.apply(x, w, b, relu)
         y = F.linear(x, w, b)
@@ -242,7 +258,7 @@ class AttnGraphBase(nn.Module):
         """Per-sample Linear layer of the update: on the GPU the weight gradient (a reduction over all T*N rows into a small
         matrix) goes to the split-K TN kernel, everything else stays a library product."""
         if x.is_cuda and self.train_gemm_mode == "bf16x3":
-            from . import hip
+            from . import hip_train as hip
             if hip.linear_supported(x, w) and x.shape[0] >= 16384:
                 return hip.HipLinear.apply(x, w, b, False)   # [128 a, 128 b] weights: forward, dX and dW on the pipelined bf16x3 kernels
             if hip.wgrad_supported(x, w):
@@ -271,7 +287,7 @@ class AttnGraphBase(nn.Module):
             # human; only the live rows are computed (the others only ever meet an exactly-zero robot-human weight)
             l0, l2 = self.spatial_linear[0], self.spatial_linear[2]
             if x_live.is_cuda and D <= 16:
-                from .hip import Embed0
+                from .hip_train import Embed0
                 e0 = Embed0.apply(x_live, l0.weight, l0.bias)
             else:
                 e0 = F.relu(l0(x_live))
@@ -284,10 +300,10 @@ class AttnGraphBase(nn.Module):
         if x_live.is_cuda and self.train_gemm_mode == "bf16x3" and self.train_fused_hh and H <= 48 and D <= 16 and emb0.weight.shape[0] == 128:
             # ONE launch for the whole block (the rollout's fused kernel on the training weights, writing the activations the backward
             # needs); the affine pairs are composed exactly as below, so both factors still receive their exact gradients
-            from .hip import HHBlockFused
+            from .hip_train import HHBlockFused
             W, b = sa.multihead_attn.in_proj_weight, sa.multihead_attn.in_proj_bias
             lins = (sa.q_linear, sa.k_linear, sa.v_linear)
-            from .hip import weight_mm as mm     # the folds and their backward as cn_small_mm launches
+            from .hip_train import weight_mm as mm     # the folds and their backward as cn_small_mm launches
             Wc = torch.cat([mm(W[i * 512:(i + 1) * 512], lins[i].weight) for i in range(3)], 0)
             bc = torch.cat([mm(W[i * 512:(i + 1) * 512], lins[i].bias) + b[i * 512:(i + 1) * 512] for i in range(3)], 0)
             op, sl = sa.multihead_attn.out_proj, self.spatial_linear[0]
@@ -297,7 +313,7 @@ class AttnGraphBase(nn.Module):
                                    mm(sl.weight, op.weight), mm(sl.weight, op.bias) + sl.bias)
             return o, row_off
         if x_live.is_cuda and D <= 16 and emb0.weight.shape[0] == 128:
-            from .hip import Embed0
+            from .hip_train import Embed0
             e0 = Embed0.apply(x_live, emb0.weight, emb0.bias)
         else:
             e0 = F.relu(emb0(x_live))
@@ -312,7 +328,7 @@ class AttnGraphBase(nn.Module):
         qkv = self._big_linear(e, Wc, bc)                                                   # [rows, 1536] = [q | k | v]
         if qkv.is_cuda:
             # attention core on the compacted rows, forward AND backward as hand-written HIP kernels
-            from .hip import HHAttention
+            from .hip_train import HHAttention
             nd = det.clamp(1, H).to(torch.int32)   # 1..H rows per sample, like the rollout kernels (crowd_sim_var_num.py:290-292)
             row_off = torch.cat([nd.new_zeros(1), nd.cumsum(0, dtype=torch.int32)])
             o_live = HHAttention.apply(qkv, row_off, B, H, 0.125)
@@ -368,10 +384,10 @@ class AttnGraphBase(nn.Module):
             # compacted rows [R,256] + row offsets: HIP robot-human attention forward/backward (no dense [B,H,256] tensors)
             # t . (Ws o_j + bs) = (Ws^T t) . o_j + const: the spatial_edge_layer projection moves to the robot side (B rows
             # instead of ~6B) and its bias, which the softmax cannot see, keeps an exactly-zero gradient
-            from .hip import HRAttention
+            from .hip_train import HRAttention
             sl = self.attn.spatial_edge_layer[0]
             tl = self.attn.temporal_edge_layer[0]
-            from .hip import RightMatmul
+            from .hip_train import RightMatmul
             t_emb = self._lin(robot_states, tl.weight, tl.bias)
             u = (RightMatmul.apply(t_emb, sl.weight) if t_emb.shape[0] >= 4096 else t_emb @ sl.weight) + 0.0 * sl.bias.sum()
             hr = HRAttention.apply(u, out_sp, valid, self.human_num)
@@ -384,7 +400,7 @@ class AttnGraphBase(nn.Module):
         m = masks.reshape(T, N, 1)
         h = h0.reshape(N, -1)
         if gi.is_cuda:
-            from .hip import GRUSequence
+            from .hip_train import GRUSequence
             hs_all = GRUSequence.apply(gi, h, m, rnn.gru.weight_hh_l0, rnn.gru.bias_hh_l0)
             h = hs_all[-1]
         else:
@@ -450,14 +466,14 @@ class SRNNBase(nn.Module):
     Three modules never reach the output and never get a gradient (humanNodeRNN.edge_embed, human_node_final_linear, spatial_linear)."""
 
     DEAD_MODULES = ("humanNodeRNN.edge_embed", "human_node_final_linear", "spatial_linear")
-    # forward_sequence on GPU tensors: both edge GRUs over all T steps as hip.SrnnEdgeSequence (cn_srnn_seq_fwd / cn_srnn_seq_bwd) instead of
+    # forward_sequence on GPU tensors: both edge GRUs over all T steps as hip_train.SrnnEdgeSequence (cn_srnn_seq_fwd / cn_srnn_seq_bwd) instead of
     # the torch-op loop, which stays the definition (False, CPU tensors, or a shape cn_srnn_seq_workspace_bytes refuses)
     train_edge_kernels = True
 
     def __init__(self, obs_space_dict, args):
         super().__init__()
         self.is_recurrent = True
-        self.hip_provider = None            # Policy sets it: (N, device) -> the HipSrnn handle with the current weights
+        self.hip_provider = None            # Policy sets it (_hip_handle): (N, device) -> the HipSrnn handle with the current weights
         self.args = args
         self.human_num = obs_space_dict["spatial_edges"].shape[0]
         self.edge_width = obs_space_dict["spatial_edges"].shape[1]
@@ -494,6 +510,16 @@ class SRNNBase(nn.Module):
         self.robot_linear = _ortho(nn.Linear(7, 3), gain)
         self.human_node_final_linear = _ortho(nn.Linear(self.output_size, 2), gain)
         self.spatial_linear = _ortho(nn.Linear(self.edge_width, 2), gain)
+
+    gemm_mode_attr = "srnn_gemm_mode"
+
+    def make_hip_handle(self, E, device):
+        from .hip_policy import HipSrnn
+        return HipSrnn(self.human_num, self.edge_width, E, device=device)
+
+    def forward_rnn(self, inputs, rnn_hxs, masks, T, N):
+        value, feat, h, e = self.forward_sequence(inputs, rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"], masks, T, N)
+        return value, feat, {"human_node_rnn": h.view(N, 1, -1), "human_human_edge_rnn": e}
 
     def counted_inputs(self, inputs):
         return inputs
@@ -543,7 +569,7 @@ class SRNNBase(nn.Module):
         edge_h0 = edge_h0.reshape(N, H + 1, -1)
         hip = self._edge_sequence_handle(inputs, edge_h0, masks, T, N)
         if hip is not None:
-            from .hip import SrnnEdgeSequence
+            from .hip_train import SrnnEdgeSequence
             h_all = SrnnEdgeSequence.apply(hip, inputs["temporal_edges"].reshape(B, 2), inputs["spatial_edges"].reshape(B, H, self.edge_width), edge_h0,
                                            masks.reshape(B, 1), *self._edge_parameters())
             ht_all, hs_all = h_all[:, :, 0], h_all[:, :, 1:]                            # views of [T,N,H+1,256]
@@ -587,11 +613,11 @@ class Policy(nn.Module):
             raise NotImplementedError("only Box(2) action spaces (holonomic robot) are implemented")
         self.base = (SRNNBase if base == "srnn" else AttnGraphBase)(obs_shape, base_kwargs)
         if base == "srnn":
-            self.base.hip_provider = self._hip_srnn
+            self.base.hip_provider = self._hip_handle
         self.srnn = True
         self.dist = _DiagGaussian(self.base.output_size, action_space.shape[0])
         self._hip = None
-        self._hip_version = None
+        self._hip_version = self._hip_mode = None
         self._zero_edge = {}
 
     @property
@@ -607,92 +633,34 @@ class Policy(nn.Module):
     # separate launches whose per-env results are independent of the batch composition, 'fp32' = exact fp32 MFMA
     rollout_gemm_mode = "fused"
 
-    def _hip_policy(self, E, device):
-        from .hip import HipPolicy
+    def _hip_handle(self, E, device):
+        """The base's rollout handle (HipPolicy / HipSrnn) for E envs on `device`, in the gemm mode and with the weights of this moment."""
         if self._hip is None or self._hip.maxE < E or self._hip.device != device:
-            self._hip = HipPolicy(self.base.human_num, self.base.edge_width, E, device=device)
-            self._hip.set_self_attention(self.base.use_self_attn)
-            self._hip.set_taps(False)          # rollout path: nobody reads the test taps
-            self._hip_version = None
-            self._hip_mode = None
-        if getattr(self, "_hip_mode", None) != self.rollout_gemm_mode:
-            self._hip.set_gemm_mode(self.rollout_gemm_mode)
-            self._hip_mode = self.rollout_gemm_mode
+            self._hip = self.base.make_hip_handle(E, device)
+            self._hip_version = self._hip_mode = None
+        mode = getattr(self, self.base.gemm_mode_attr)
+        if self._hip_mode != mode:
+            self._hip.set_gemm_mode(mode)
+            self._hip_mode = mode
         ver = self._weights_version()
         if ver != self._hip_version:
             self._hip.set_weights(self.state_dict())
             self._hip_version = ver
         return self._hip
+
+    _hip_policy = _hip_srnn = _hip_handle     # the per-base names the handle had before: the existing tests reach it through them
 
     def weights_changed(self):
         """Tell the rollout path that parameter storage was written through raw pointers (the fused Adam kernel): the next
         act / get_value re-snapshots the weights (cn_policy_set_weights / cn_srnn_set_weights)."""
         self._hip_version = None
 
-    # ---- DS-RNN baseline (base='srnn'): cn_srnn handle, managed like the cn_policy one above ----
     # arithmetic of the two edge-GRU products (cn_srnn_set_gemm_mode): 'bf16x3' = split-precision MFMA (default), 'fp32' = exact fp32 MFMA
     srnn_gemm_mode = "bf16x3"
 
     @property
     def is_srnn_baseline(self):
         return isinstance(self.base, SRNNBase)
-
-    def _hip_srnn(self, E, device):
-        from .hip import HipSrnn
-        if self._hip is None or self._hip.maxE < E or self._hip.device != device:
-            self._hip = HipSrnn(self.base.human_num, self.base.edge_width, E, device=device)
-            self._hip_version = None
-            self._hip_mode = None
-        if getattr(self, "_hip_mode", None) != self.srnn_gemm_mode:
-            self._hip.set_gemm_mode(self.srnn_gemm_mode)
-            self._hip_mode = self.srnn_gemm_mode
-        ver = self._weights_version()
-        if ver != self._hip_version:
-            self._hip.set_weights(self.state_dict())
-            self._hip_version = ver
-        return self._hip
-
-    def _srnn_obs32(self, inputs):
-        return {k: (v if v.dtype == torch.float32 else v.float()).contiguous() for k, v in inputs.items() if k in ("robot_node", "temporal_edges", "spatial_edges")}
-
-    def _srnn_act(self, inputs, rnn_hxs, masks, deterministic):
-        E, H = inputs["robot_node"].shape[0], self.base.human_num
-        hx, ex = rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"]
-        if hx.is_cuda:
-            pol = self._hip_srnn(E, hx.device)
-            eps = None if deterministic else torch.randn(E, 2, device=hx.device)
-            out = pol.act(self._srnn_obs32(inputs), hx.reshape(E, 128).float(), ex.reshape(E, H + 1, 256).float(), masks.reshape(E, 1).float(), eps=eps)
-            return out["value"], out["action"], out["logp"], {"human_node_rnn": out["hxs"], "human_human_edge_rnn": out["edge_hxs"]}
-        with torch.no_grad():
-            value, feat, h, e = self.base.forward_sequence(inputs, hx, ex, masks, 1, E)
-            mean = self.dist.fc_mean(feat)
-            std = self.dist.logstd(torch.zeros_like(mean)).exp()
-            action = mean if deterministic else mean + std * torch.randn_like(mean)
-            logp = self._log_prob(mean, std, action)
-        return value, action, logp, {"human_node_rnn": h.view(E, 1, 128), "human_human_edge_rnn": e}
-
-    def _srnn_get_value(self, inputs, rnn_hxs, masks):
-        E, H = inputs["robot_node"].shape[0], self.base.human_num
-        hx, ex = rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"]
-        if hx.is_cuda:
-            return self._hip_srnn(E, hx.device).get_value(self._srnn_obs32(inputs), hx.reshape(E, 128).float(), ex.reshape(E, H + 1, 256).float(),
-                                                          masks.reshape(E, 1).float())
-        with torch.no_grad():
-            value, _, _, _ = self.base.forward_sequence(inputs, hx, ex, masks, 1, E)
-        return value
-
-    def _srnn_evaluate_actions(self, inputs, rnn_hxs, masks, action):
-        """The T-step sequence under autograd.  On the GPU the two edge GRUs -- the recurrent core, N (H+1) rows of 256 per step -- run as
-        hip.SrnnEdgeSequence (SRNNBase.train_edge_kernels); attention, the node GRU, the trunks and the heads are torch ops over all T at
-        once.  On the CPU everything is torch ops: that graph is the definition."""
-        B = inputs["robot_node"].shape[0]
-        N = rnn_hxs["human_node_rnn"].shape[0]
-        value, feat, h, e = self.base.forward_sequence(inputs, rnn_hxs["human_node_rnn"], rnn_hxs["human_human_edge_rnn"], masks, B // N, N)
-        mean = _skinny_linear(feat, self.dist.fc_mean.weight, self.dist.fc_mean.bias)
-        logstd = self.dist.logstd(torch.zeros_like(mean))
-        logp = self._log_prob(mean, logstd.exp(), action)
-        entropy = (0.5 + 0.5 * math.log(2 * math.pi) + logstd).mean()
-        return value, logp, entropy, {"human_node_rnn": h.view(N, 1, -1), "human_human_edge_rnn": e}
 
     def _edge_zeros(self, E, device):
         key = (E, str(device))
@@ -704,35 +672,40 @@ class Policy(nn.Module):
         inputs = self.base.counted_inputs(inputs)      # sort_humans = False: visible humans first + their count (cn_obs_compact_visible)
         return {k: (v if v.dtype == torch.float32 else v.float()).contiguous() for k, v in inputs.items() if k != "visible_masks"}
 
+    def _all_states(self, hxs, N, device):
+        """rnn_hxs as the reference returns it: the state the base carries plus, where the edge state is not live, its zeros."""
+        if "human_human_edge_rnn" not in hxs:
+            hxs["human_human_edge_rnn"] = self._edge_zeros(N, device)
+        return hxs
+
+    def _hip_args(self, pol, E, inputs, rnn_hxs, masks):
+        return self._obs32(inputs), {k: rnn_hxs[k].reshape(shape).float() for k, shape in pol.state_shapes(E).items()}, masks.reshape(E, 1).float()
+
     def act(self, inputs, rnn_hxs, masks, deterministic=False):
-        if self.is_srnn_baseline:
-            return self._srnn_act(inputs, rnn_hxs, masks, deterministic)
         E = inputs["robot_node"].shape[0]
-        hx = rnn_hxs["human_node_rnn"]
-        if hx.is_cuda:
-            pol = self._hip_policy(E, hx.device)
-            eps = None if deterministic else torch.randn(E, 2, device=hx.device)
-            out = pol.act(self._obs32(inputs), hx.reshape(E, 1, 128), masks.reshape(E, 1).float(), eps=eps)
-            value, action, logp, h = out["value"], out["action"], out["logp"], out["hxs"]
+        dev = rnn_hxs["human_node_rnn"].device
+        if dev.type == "cuda":
+            pol = self._hip_handle(E, dev)
+            eps = None if deterministic else torch.randn(E, 2, device=dev)
+            out, h = pol.act_rnn(*self._hip_args(pol, E, inputs, rnn_hxs, masks), eps=eps)
+            value, action, logp = out["value"], out["action"], out["logp"]
         else:
             with torch.no_grad():
-                value, feat, h = self.base.forward_sequence(inputs, hx, masks, 1, E)
+                value, feat, h = self.base.forward_rnn(inputs, rnn_hxs, masks, 1, E)
                 mean = self.dist.fc_mean(feat)
                 std = self.dist.logstd(torch.zeros_like(mean)).exp()
                 action = mean if deterministic else mean + std * torch.randn_like(mean)
                 logp = self._log_prob(mean, std, action)
-            h = h.view(E, 1, 128)
-        return value, action, logp, {"human_node_rnn": h, "human_human_edge_rnn": self._edge_zeros(E, hx.device)}
+        return value, action, logp, self._all_states(h, E, dev)
 
     def get_value(self, inputs, rnn_hxs, masks):
-        if self.is_srnn_baseline:
-            return self._srnn_get_value(inputs, rnn_hxs, masks)
         E = inputs["robot_node"].shape[0]
-        hx = rnn_hxs["human_node_rnn"]
-        if hx.is_cuda:
-            return self._hip_policy(E, hx.device).get_value(self._obs32(inputs), hx.reshape(E, 1, 128), masks.reshape(E, 1).float())
+        dev = rnn_hxs["human_node_rnn"].device
+        if dev.type == "cuda":
+            pol = self._hip_handle(E, dev)
+            return pol.get_value_rnn(*self._hip_args(pol, E, inputs, rnn_hxs, masks))
         with torch.no_grad():
-            value, _, _ = self.base.forward_sequence(inputs, hx, masks, 1, E)
+            value, _, _ = self.base.forward_rnn(inputs, rnn_hxs, masks, 1, E)
         return value
 
     @staticmethod
@@ -741,26 +714,26 @@ class Policy(nn.Module):
         return (-((action - mean) ** 2) / (2 * var) - std.log() - math.log(math.sqrt(2 * math.pi))).sum(-1, keepdim=True)
 
     def evaluate_actions(self, inputs, rnn_hxs, masks, action):
-        """inputs [T*N,...] (T = seq_length, N = num_processes / num_mini_batch), rnn_hxs at t=0 ([N,...])."""
-        if self.is_srnn_baseline:
-            return self._srnn_evaluate_actions(inputs, rnn_hxs, masks, action)
+        """inputs [T*N,...] (T = seq_length, N = num_processes / num_mini_batch), rnn_hxs at t=0 ([N,...]).  The T-step sequence under
+        autograd: on the GPU its heavy stages are HIP kernels behind autograd.Functions (the attention-graph base: the whole of it, below;
+        DS-RNN: the two edge GRUs, SRNNBase.train_edge_kernels), on the CPU everything is torch ops: that graph is the definition."""
         B = inputs["robot_node"].shape[0]
         N = rnn_hxs["human_node_rnn"].shape[0]
         T = B // N
         base = self.base
-        if inputs["robot_node"].is_cuda and base.train_fused_rn and base.train_gemm_mode == "bf16x3" and base.fused_rn_shapes_ok():
-            # train-mode forward as two boundary calls: the human-human block (cn_hh_block_fwd behind _hh_block) and the robot-node sequence
-            # (cn_rn_seq_fwd), each with ONE backward entry
+        if getattr(base, "train_fused_rn", False) and inputs["robot_node"].is_cuda and base.train_gemm_mode == "bf16x3" and base.fused_rn_shapes_ok():
+            # the attention-graph base's train-mode forward as two boundary calls: the human-human block (cn_hh_block_fwd behind _hh_block)
+            # and the robot-node sequence (cn_rn_seq_fwd), each with ONE backward entry
             inputs = base.counted_inputs(inputs)
             det = inputs["detected_human_num"].reshape(B).to(torch.int64).clamp(min=1)
             out_sp, row_off = base._hh_block(inputs["spatial_edges"].reshape(B, base.human_num, base.edge_width), det)
             value, logp, h = base.rn_sequence(inputs, out_sp, row_off, rnn_hxs["human_node_rnn"], masks, action, T, N, self.dist)
             logstd = self.dist.logstd._bias.t().view(1, -1)
             entropy = (0.5 + 0.5 * math.log(2 * math.pi) + logstd).mean()   # FixedNormal.entropy().mean(): the same for every sample
-            return value, logp, entropy, {"human_node_rnn": h.view(N, 1, -1), "human_human_edge_rnn": self._edge_zeros(N, h.device)}
-        value, feat, h = self.base.forward_sequence(inputs, rnn_hxs["human_node_rnn"], masks, T, N)
+            return value, logp, entropy, self._all_states({"human_node_rnn": h.view(N, 1, -1)}, N, h.device)
+        value, feat, h = base.forward_rnn(inputs, rnn_hxs, masks, T, N)
         mean = _skinny_linear(feat, self.dist.fc_mean.weight, self.dist.fc_mean.bias)
         logstd = self.dist.logstd(torch.zeros_like(mean))
         logp = self._log_prob(mean, logstd.exp(), action)
         entropy = (0.5 + 0.5 * math.log(2 * math.pi) + logstd).mean()   # FixedNormal.entropy().mean(): over batch and dims
-        return value, logp, entropy, {"human_node_rnn": h.view(N, 1, -1), "human_human_edge_rnn": self._edge_zeros(N, h.device)}
+        return value, logp, entropy, self._all_states(h, N, value.device)

@@ -27,8 +27,7 @@ class EpisodeStats:
         if (done.is_cuda and done.dtype == torch.uint8 and info.dtype == torch.uint8 and ep_return.dtype == torch.float64 and ep_len.dtype == torch.int32
                 and all(t.is_contiguous() for t in (done, info, ep_return, ep_len))):
             from . import _abi as A      # the step outputs of HipEnvBatch as they are: ONE launch, fixed summation order
-            A.check(A.lib().cn_episode_stats_update(done.numel(), A.ptr(done), A.ptr(info), A.ptr(ep_return), A.ptr(ep_len), A.ptr(self.acc), A.stream_ptr()),
-                    "cn_episode_stats_update")
+            A.call("cn_episode_stats_update", done.numel(), A.ptr(done), A.ptr(info), A.ptr(ep_return), A.ptr(ep_len), A.ptr(self.acc), A.stream_ptr())
             return
         d = done.to(torch.float64)
         self.acc[0] += d.sum()
@@ -55,27 +54,25 @@ def collect_rollout(envs, actor_critic, rollouts, stats=None, generator=None):
     """Fill `rollouts` (row 0 must hold the current observation / hidden state / mask).  Zero host syncs."""
     env = envs._env
     E, dev = envs.num_envs, envs.device
-    srnn = getattr(actor_critic, "is_srnn_baseline", False)
-    pol = actor_critic._hip_srnn(E, dev) if srnn else actor_critic._hip_policy(E, dev)
+    pol = actor_critic._hip_handle(E, dev)
     T = rollouts.num_steps
-    hx = rollouts.recurrent_hidden_states["human_node_rnn"]
-    ex = rollouts.materialize_edge_rnn() if srnn else None                # DS-RNN: the live edge state, written row by row like the node state
+    if "human_human_edge_rnn" in pol.state_shapes(E):                     # a live edge state (DS-RNN) is written row by row like the node state
+        rollouts.materialize_edge_rnn()
+    hxs = {k: rollouts.recurrent_hidden_states[k] for k in pol.state_shapes(E)}
     eps = torch.empty(T, E, 2, device=dev).normal_(generator=generator)   # the action noise of the whole rollout in one launch
-    # the simulator writes a row plan beside every observation (hip.HipEnvBatch.row_plan): row t of the storage IS the newest observation of
+    # the simulator writes a row plan beside every observation (hip_env.HipEnvBatch.row_plan): row t of the storage IS the newest observation of
     # `env` at every t of this loop (row 0: the last one of the previous rollout, or the reset), so the plan in the buffer is the one made
     # for it.  Not through the GST wrapper, which post-processes the observation.
     base = actor_critic.base
-    plan = env.row_plan if (envs._pretext is None and base.use_self_attn and base.sort_humans and not srnn) else None
+    plan = env.row_plan if (envs._pretext is None and base.use_self_attn and base.sort_humans and pol.uses_row_plan) else None
     for t in range(T):
         obs_t = {k: rollouts.obs[k][t] for k in ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num")}
-        out = dict(value=rollouts.value_preds[t], action=rollouts.actions[t], logp=rollouts.action_log_probs[t], hxs=hx[t + 1])
+        out = dict(value=rollouts.value_preds[t], action=rollouts.actions[t], logp=rollouts.action_log_probs[t])
         pol_obs = obs_t
         if not base.sort_humans:   # args.sort_humans = False: attention masked by visible_masks -> visible humans first + their count
             pol_obs = base.counted_inputs(dict(obs_t, visible_masks=rollouts.obs["visible_masks"][t]))
-        if srnn:                   # no row plan: DS-RNN runs every slot of every env
-            pol.act(pol_obs, hx[t], ex[t], rollouts.masks[t], eps=eps[t], out=dict(out, edge_hxs=ex[t + 1]))
-        else:
-            pol.act(pol_obs, hx[t], rollouts.masks[t], eps=eps[t], out=out, row_plan=plan)
+        pol.act_rnn(pol_obs, {k: v[t] for k, v in hxs.items()}, rollouts.masks[t], eps=eps[t], out=out,
+                    rnn_hxs_out={k: v[t + 1] for k, v in hxs.items()}, row_plan=plan)
         obs_n = {k: rollouts.obs[k][t + 1] for k in obs_t}
         obs_n["visible_masks"] = None
         if "visible_masks" in rollouts.obs:
@@ -98,25 +95,18 @@ def collect_rollout(envs, actor_critic, rollouts, stats=None, generator=None):
 
 
 def evaluate_policy(actor_critic, env_name, config, seed, eval_cases=None, device=None, predictor=None, logging=None):
-    """The batched test protocol on the current weights through a policy handle of its OWN: Policy._hip_policy hands out one handle per
+    """The batched test protocol on the current weights through a policy handle of its OWN: Policy._hip_handle hands out one handle per
     policy, and what the training rollout has set on it (weight snapshot, gemm mode, a post-hh hook) stays as it is.  No torch RNG draw."""
     from .config import Config
     from .evaluation import _evaluate_batched
-    from .hip import HipPolicy, HipSrnn
     config = config if config is not None else Config()
     if eval_cases is None:
         eval_cases = int(config.env.test_size)
     E = len(set((2 * k) % int(config.env.test_size) for k in range(eval_cases)))     # distinct cases = envs of the batch (evaluation.py)
     base = actor_critic.base
-    srnn = getattr(actor_critic, "is_srnn_baseline", False)
-    pol = (HipSrnn if srnn else HipPolicy)(base.human_num, base.edge_width, E, device=device)
+    pol = base.make_hip_handle(E, device)
     try:
-        if srnn:
-            pol.set_gemm_mode(actor_critic.srnn_gemm_mode)
-        else:
-            pol.set_self_attention(base.use_self_attn)
-            pol.set_taps(False)
-            pol.set_gemm_mode(actor_critic.rollout_gemm_mode)
+        pol.set_gemm_mode(getattr(actor_critic, base.gemm_mode_attr))
         pol.set_weights(actor_critic.state_dict())
         return _evaluate_batched(actor_critic, env_name, config, seed, eval_cases, device, logging, predictor=predictor, hip_policy=pol)
     finally:

@@ -112,7 +112,7 @@ def edge_seq_leg(torch, pol, dev, E, H, D, T, repeats=7):
     se[:, H // 2:] = 15.0
     e0 = torch.rand(N, H + 1, 256, device=dev, generator=g) - 0.5
     m = (torch.rand(T * N, 1, device=dev, generator=g) > 0.02).float()
-    hip = pol._hip_srnn(E, dev)
+    hip = pol._hip_handle(E, dev)
     grads = [torch.empty_like(p) for p in pol.base._edge_parameters()]
     d_e0 = torch.empty_like(e0)
     ws = torch.empty(hip.seq_workspace_bytes(T, N) // 4, device=dev)
@@ -227,7 +227,7 @@ def main():
     f_obs = {k: ro.obs[k][0] for k in ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num")}
     node, edge, masks = ro.recurrent_hidden_states["human_node_rnn"][0], ro.recurrent_hidden_states["human_human_edge_rnn"][0], ro.masks[0]
     eps = torch.randn(E, 2, device=dev)
-    h = pol._hip_srnn(E, dev)
+    h = pol._hip_handle(E, dev)
     bufs = dict(value=torch.empty(E, 1, device=dev), action=torch.empty(E, 2, device=dev), logp=torch.empty(E, 1, device=dev),
                 hxs=torch.empty(E, 1, 128, device=dev), edge_hxs=torch.empty(E, H + 1, 256, device=dev))
 
