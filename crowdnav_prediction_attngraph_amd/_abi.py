@@ -184,6 +184,7 @@ ABI_SYMBOLS = [
     "cn_ppo_minibatch_max_rows", "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
     "cn_env_get_visibility", "cn_render_scenes",
+    "cn_env_trace_append", "cn_trace_metrics", "cn_render_trajectories",
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
     "cn_srnn_create", "cn_srnn_destroy", "cn_srnn_set_weights", "cn_srnn_act", "cn_srnn_get_value", "cn_srnn_get_taps", "cn_srnn_set_gemm_mode",
     "cn_srnn_seq_workspace_bytes", "cn_srnn_seq_fwd", "cn_srnn_seq_bwd",
@@ -234,6 +235,9 @@ def lib():
         L.cn_env_get_human_actions.argtypes = [vp, vp, vp]
         L.cn_env_get_visibility.argtypes = [vp, vp, vp]
         L.cn_render_scenes.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, i32, f32, vp, vp]
+        L.cn_env_trace_append.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.cn_trace_metrics.argtypes = [i32, i32, i32, vp, vp, vp, f64, f64, vp, vp]
+        L.cn_render_trajectories.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, i32, f32, vp, vp]
         L.cn_env_snapshot_bytes.argtypes = [vp]
         L.cn_env_snapshot_bytes.restype = i64
         L.cn_env_save.argtypes = [vp, vp, vp]

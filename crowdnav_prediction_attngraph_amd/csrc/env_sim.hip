@@ -597,6 +597,43 @@ __global__ void export_visibility_kernel(EnvDev s, uint8_t *out)
     out[idx] = vis ? 1 : 0;
 }
 
+// cn_env_trace_append: one thread per (env, agent slot) writes record index[e] of env e from the CURRENT state -- what export_state_kernel,
+// cn_env_get_human_counts and export_visibility_kernel report, rounded once to float32 -- for the envs `active` / `index` select.  A kernel of
+// its own: nothing of it is compiled into the step kernels.
+__global__ void trace_append_kernel(EnvDev s, const int64_t *active, const int64_t *index, int cap, float *agents, uint8_t *flags, float *goal,
+                                    int32_t *length)
+{
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const int H = s.H, A = H + 1;
+    if (idx >= s.E * A) return;
+    const int e = idx / A, a = idx % A;
+    if (active && active[e] == 0) return;
+    const int64_t t = index[e];
+    if (t < 0 || t >= (int64_t)cap) return;
+    const size_t slot = ((size_t)e * cap + (size_t)t) * A + a;
+    const double *r = s.rob + (size_t)e * 8;
+    float v[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    uint8_t fl = 0;
+    if (a == 0) {
+        v[0] = (float)r[R_PX]; v[1] = (float)r[R_PY]; v[2] = (float)r[R_VX]; v[3] = (float)r[R_VY];
+        v[4] = (float)s.cfg.robot_radius; v[5] = (float)r[R_THETA];
+        fl = 1;
+        length[e] = (int32_t)t + 1;
+        if (t == 0 && goal) { goal[(size_t)e * 2] = (float)r[R_GX]; goal[(size_t)e * 2 + 1] = (float)r[R_GY]; }
+    } else if (a - 1 < crowd_size(s, e)) {
+        const int j = a - 1;
+        const double *h = s.hum + (size_t)e * 8 * H + j;
+        const Robot rb = {r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]};
+        const double px = h[(size_t)F_PX * H], py = h[(size_t)F_PY * H], rad = h[(size_t)F_RAD * H];
+        v[0] = (float)px; v[1] = (float)py; v[2] = (float)h[(size_t)F_VX * H]; v[3] = (float)h[(size_t)F_VY * H];
+        v[4] = (float)rad; v[5] = (float)h[(size_t)F_VPREF * H];
+        fl = robot_sees(s.cfg, rb, true, px, py, rad) ? 3 : 1;
+    }
+    float2 *dst = reinterpret_cast<float2 *>(agents + slot * 6); // 24-byte records: 8-byte aligned
+    dst[0] = make_float2(v[0], v[1]); dst[1] = make_float2(v[2], v[3]); dst[2] = make_float2(v[4], v[5]);
+    flags[slot] = fl;
+}
+
 __global__ void fill_i32_kernel(int n, int v, int32_t *out)
 {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1131,6 +1168,21 @@ extern "C" int cn_env_get_visibility(cn_env_batch *env, uint8_t *out, void *stre
     if (int rc = sync_side(env, (hipStream_t)stream)) return rc; // ordered like cn_env_get_state
     const int n = env->d.E * env->d.H;
     hipLaunchKernelGGL(export_visibility_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, env->d, out);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_env_trace_append(cn_env_batch *env, const int64_t *active, const int64_t *index, int cap, float *agents, uint8_t *flags,
+                                   float *goal, int32_t *length, void *stream)
+{
+    CN_REQUIRE(env, "cn_env_trace_append: null handle");
+    CN_REQUIRE(cap >= 1, "cn_env_trace_append: cap=%d records per env (at least 1)", cap);
+    CN_REQUIRE(index && agents && flags && length, "cn_env_trace_append: index, agents, flags and length are required");
+    CN_REQUIRE(((uintptr_t)agents & 7u) == 0, "cn_env_trace_append: agents must be 8-byte aligned");
+    if (int rc = sync_side(env, (hipStream_t)stream)) return rc; // ordered like cn_env_get_state
+    const int n = env->d.E * (env->d.H + 1);
+    hipLaunchKernelGGL(trace_append_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, env->d, active, index, cap, agents, flags, goal,
+                       length);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

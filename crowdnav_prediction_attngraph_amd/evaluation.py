@@ -187,25 +187,36 @@ class EvalAccumulator(object):
                     ep_return=h[self.RETURN].view(torch.float64).tolist())
 
 
-def evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, *, batch_invariant=False, predictor=None):
+def evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, *, batch_invariant=False, predictor=None,
+                     traces=False):
     """The same protocol with every distinct test case as one env of one batch (all tensors stay on the GPU).  batch_invariant=True on both
     this and evaluate() makes the two report bit-identical episodes (tests/test_gpu_eval.py); by default both run the fused kernels and
     agree to the policy's 1e-7-level sensitivity to its tile neighbours (which can flip a chaotic episode's outcome).
     CrowdSimPredRealGST-v0 runs behind the VecPretextNormalize processing (gst.PretextProcessor over the batch): predictor = a
-    gst.GSTPredictor, or None to load config.pred.model_dir."""
+    gst.GSTPredictor, or None to load config.pred.model_dir.
+    traces=True: every episode is also recorded on the device (one more launch per step, see record_episodes) and the call returns
+    (summary, EpisodeTraces); the summary is the one traces=False gives, bit for bit."""
     with _batch_invariant(actor_critic, batch_invariant):
-        return _evaluate_batched(actor_critic, env_name, config, seed, test_size, device, logging, predictor=predictor)
+        if not traces:
+            return _evaluate_batched(actor_critic, env_name, config, seed, test_size, device, logging, predictor=predictor)
+        rec = _TraceRecorder(config, env_name)
+        summary = _evaluate_batched(actor_critic, env_name, config, seed, test_size, device, logging, predictor=predictor, per_env=rec.per_env,
+                                    pre_step_fn=rec)
+        return summary, rec.finish()
 
 
 def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, predictor=None, poll_every=16, act_fn=None,
-                      hip_policy=None, use_kernel=True, per_env=None, frame_fn=None):
+                      hip_policy=None, use_kernel=True, per_env=None, frame_fn=None, pre_step_fn=None):
     """test_size: the episode count of the sequential protocol (episode k runs case 2 k mod the config's test_size), or a sequence of case
     numbers to run instead (render_episodes).  poll_every: the count of running episodes is read back (the loop's only host synchronisation)
     every that many steps; steps taken after the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
     hip_policy: a policy handle (base.make_hip_handle) to run instead of actor_critic's own (train() evaluates through a second handle so that the training
     rollout finds its handle as it left it); use_kernel=False: the torch-op bookkeeping; per_env: a dict that receives the per-env results;
     frame_fn(t, env, obs): called once after the reset (t = 0) and once after every step (t = steps taken) with the HipEnvBatch and the
-    observation it returned, e.g. to draw the state (render_episodes); it must leave both as they are."""
+    observation it returned, e.g. to draw the state (render_episodes); it must leave both as they are.  pre_step_fn(t, env, acc): called
+    immediately BEFORE step t is taken with the HipEnvBatch and the accumulator, whose `active` / `steps` arrays then say which envs' first
+    episode is still running and how many steps it has taken -- the moment to record the state a step is taken from (record_episodes;
+    after the step the env of a finished episode already holds its next episode's start); it must leave both as they are."""
     from .hip_env import HipEnvBatch
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = to_env_config(config, env_name, 1, "test")          # nenv = 1: case counters advance by one, as in the sequential run
@@ -266,6 +277,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
                 # deterministic: dist.mode() (model.py:66-67); the masks zero the state at episode ends inside the kernels
                 out, _ = pol.act_rnn(pobs, hxs[t & 1], masks, eps=None, rnn_hxs_out=hxs[(t + 1) & 1])
                 action = out["action"]
+        if pre_step_fn is not None:
+            pre_step_fn(t, env, acc)
         obs, rew, done, info, ep_ret, _ = env.step(action)
         env.get_danger_min_dist(out=danger_dist)
         if frame_fn is not None:
@@ -325,3 +338,132 @@ def render_episodes(actor_critic, env_name, config, seed, cases, size=256, devic
     frames = buf[:last + 1, :, :, :, :3].contiguous().cpu().numpy()
     return {c: dict(frames=frames[:per_env["steps"][e] + 1, e].copy(), outcome=per_env["outcome"][e], steps=per_env["steps"][e])
             for e, c in enumerate(per_env["cases"])}
+
+
+class EpisodeTraces(object):
+    """n recorded episodes on the device, in the layout of cn_env_trace_append (include/crowdnav_hip.h): agents float32 [n,cap,A,6] (slot 0 the
+    robot: px, py, vx, vy, radius, theta; slot 1 + h human slot h: px, py, vx, vy, radius, v_pref), flags uint8 [n,cap,A] (bit 0 present, bit 1
+    visible to the robot), goal float32 [n,2], length int32 [n]; cases / outcome / steps as host lists, and the config values measuring and
+    drawing need.  Record t is the state step t was taken FROM (record 0: the reset state; length == steps); the state after the final step
+    is not in a trace -- the simulator replaces it with the next episode's start inside the step -- and nothing here pretends otherwise."""
+    CONFIG_KEYS = ("time_step", "discomfort_dist", "robot_radius", "arena_size", "sensor_range", "human_radius", "kinematics")
+
+    def __init__(self, agents, flags, goal, length, cases, outcome, steps, **config):
+        missing = [k for k in self.CONFIG_KEYS if k not in config]
+        if missing or len(config) != len(self.CONFIG_KEYS):
+            raise ValueError("EpisodeTraces: config values %s expected" % (self.CONFIG_KEYS,))
+        self.agents, self.flags, self.goal, self.length = agents, flags, goal, length
+        self.cases, self.outcome, self.steps = [int(c) for c in cases], [int(o) for o in outcome], [int(x) for x in steps]
+        for k in self.CONFIG_KEYS:
+            setattr(self, k, int(config[k]) if k == "kinematics" else float(config[k]))
+
+    @property
+    def n(self):
+        return int(self.agents.shape[0])
+
+    def config(self):
+        return {k: getattr(self, k) for k in self.CONFIG_KEYS}
+
+    def metrics(self):
+        """{column name: numpy [n]} of cn_trace_metrics (hip_env.TRACE_METRICS; the counts as int64, the rest float64): one launch, one
+        read-back."""
+        from .hip_env import TRACE_METRICS, trace_metrics
+        m = trace_metrics(self.agents, self.flags, self.length, self.time_step, self.discomfort_dist).cpu().numpy()
+        ints = ("records", "intrusion_steps", "visible_intrusion_steps")
+        return {k: (m[:, j].astype(np.int64) if k in ints else m[:, j].copy()) for j, k in enumerate(TRACE_METRICS)}
+
+    def figure(self, size=256, stride=8):
+        """One picture per episode (cn_render_trajectories): uint8 [n,size,size,4] RGBA on the device, the view render() uses
+        (half width arena_size + 1)."""
+        from .hip_env import render_trajectories as draw
+        return draw(self.agents, self.flags, self.length, self.goal, stride=stride, size=size, half_width=self.arena_size + 1.0)
+
+    def frames(self, case, size=256):
+        """The episode of `case` re-drawn record by record through render_scenes: uint8 [steps,size,size,3] (numpy).  The float64 inputs of
+        render_scenes are rebuilt from the float32 records (float32 -> float64 -> float32 is the identity), so with a holonomic robot
+        (CrowdSimVarNum-v0) these are the pixels render_episodes produced for frames 0..steps-1; a unicycle robot's heading mark is drawn
+        from the recorded float32 theta."""
+        from .hip_env import render_scenes
+        e = self.cases.index(int(case))
+        L = int(self.length[e].item())
+        if L < 1:
+            return np.zeros((0, int(size), int(size), 3), dtype=np.uint8)
+        ag, fl = self.agents[e, :L].to(torch.float64), self.flags[e, :L, 1:]
+        H = ag.shape[1] - 1
+        humans = torch.zeros(L, H, 8, dtype=torch.float64, device=ag.device)
+        humans[:, :, 0:4], humans[:, :, 6:8] = ag[:, 1:, 0:4], ag[:, 1:, 4:6]
+        robot = torch.zeros(L, 8, dtype=torch.float64, device=ag.device)
+        robot[:, 0:4], robot[:, 4:6], robot[:, 6] = ag[:, 0, 0:4], self.goal[e].to(torch.float64), ag[:, 0, 5]
+        counts = (fl & 1).sum(dim=1).to(torch.int32)
+        visible = ((fl >> 1) & 1).contiguous()
+        if self.kinematics == 0:
+            heading = robot[:, 2:4].to(torch.float32)
+        else:
+            heading = torch.stack((torch.cos(robot[:, 6]), torch.sin(robot[:, 6])), dim=1).to(torch.float32)
+        img = render_scenes(humans, robot, counts=counts, visible=visible, robot_heading=heading.contiguous(), robot_radius=self.robot_radius,
+                            ring_radius=self.sensor_range + self.robot_radius + self.human_radius, size=size, half_width=self.arena_size + 1.0)
+        return img[..., :3].contiguous().cpu().numpy()
+
+    def save(self, path):
+        """Everything into one .npz."""
+        np.savez_compressed(path, agents=self.agents.cpu().numpy(), flags=self.flags.cpu().numpy(), goal=self.goal.cpu().numpy(),
+                            length=self.length.cpu().numpy(), cases=np.asarray(self.cases, dtype=np.int64),
+                            outcome=np.asarray(self.outcome, dtype=np.int64), steps=np.asarray(self.steps, dtype=np.int64),
+                            **{k: np.asarray(getattr(self, k)) for k in self.CONFIG_KEYS})
+
+    @classmethod
+    def load(cls, path, device=None):
+        """device None: the tensors stay on the CPU (metrics / figure / frames need them on the GPU)."""
+        with np.load(path) as z:
+            dev = torch.device(device) if device is not None else torch.device("cpu")
+            t = {k: torch.from_numpy(z[k]).to(dev) for k in ("agents", "flags", "goal", "length")}
+            return cls(t["agents"], t["flags"], t["goal"], t["length"], z["cases"].tolist(), z["outcome"].tolist(), z["steps"].tolist(),
+                       **{k: z[k].item() for k in cls.CONFIG_KEYS})
+
+
+class _TraceRecorder(object):
+    """The pre_step_fn of _evaluate_batched that records: buffers allocated once at the first call, then one cn_env_trace_append per step fed
+    with the accumulator's ACTIVE and STEPS arrays as they are."""
+
+    def __init__(self, config, env_name):
+        self.cfg = to_env_config(config, env_name, 1, "test")
+        self.cap = int(round(float(self.cfg.time_limit) / float(self.cfg.time_step))) + 1
+        self.per_env, self.trace = {}, None
+
+    def __call__(self, t, env, acc):
+        if self.trace is None:
+            E, A_, dev = env.E, env.H + 1, env.device
+            self.trace = EpisodeTraces(torch.zeros(E, self.cap, A_, 6, device=dev), torch.zeros(E, self.cap, A_, dtype=torch.uint8, device=dev),
+                                       torch.zeros(E, 2, device=dev), torch.zeros(E, dtype=torch.int32, device=dev), [], [], [],
+                                       **{k: getattr(self.cfg, k) for k in EpisodeTraces.CONFIG_KEYS})
+        env.trace_append(acc.active, acc.steps, self.trace)
+
+    def finish(self):
+        tr, r = self.trace, self.per_env
+        tr.cases, tr.outcome, tr.steps = list(r["cases"]), list(r["outcome"]), list(r["steps"])
+        return tr
+
+
+def record_episodes(actor_critic, env_name, config, seed, cases, device=None, predictor=None, batch_invariant=False):
+    """Run the test cases `cases` exactly as evaluate_batched runs them (one env per case, its first episode; actor_critic=None: the ORCA
+    robot) and record every state a step was taken from on the device: one cn_env_trace_append launch per step in front of the step, no
+    allocation inside the loop, no host synchronisation.  Returns EpisodeTraces with cap = round(time_limit / time_step) + 1 records per
+    episode, in the order of sorted(set(cases)).  The state after an episode's final step is not recorded (see EpisodeTraces)."""
+    cases = sorted(set(int(c) for c in cases))
+    if not cases:
+        raise ValueError("record_episodes: no cases given")
+    rec = _TraceRecorder(config, env_name)
+    with _batch_invariant(actor_critic, batch_invariant):
+        _evaluate_batched(actor_critic, env_name, config, seed, cases, device, None, predictor=predictor, per_env=rec.per_env, pre_step_fn=rec)
+    return rec.finish()
+
+
+def render_trajectories(actor_critic, env_name, config, seed, cases, size=256, stride=8, device=None, predictor=None, batch_invariant=False):
+    """The per-episode trajectory figure (the reference's test.py --render_traj, which it announces and never draws): record_episodes, then
+    one cn_render_trajectories launch and one cn_trace_metrics launch.  Returns {case: dict(image=uint8 [size,size,3], outcome, steps,
+    metrics={column: value})}."""
+    tr = record_episodes(actor_critic, env_name, config, seed, cases, device=device, predictor=predictor, batch_invariant=batch_invariant)
+    img = tr.figure(size=size, stride=stride)[..., :3].contiguous().cpu().numpy()
+    m = tr.metrics()
+    return {c: dict(image=img[e], outcome=tr.outcome[e], steps=tr.steps[e], metrics={k: v[e].item() for k, v in m.items()})
+            for e, c in enumerate(tr.cases)}

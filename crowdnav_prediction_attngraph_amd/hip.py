@@ -7,7 +7,8 @@ import torch  # noqa: F401
 
 from . import _abi as A  # noqa: F401
 from .gst_hip import HipGST  # noqa: F401
-from .hip_env import HipEnvBatch, StepStamps, orca_solve, prediction_dots, render_scenes, tile_images  # noqa: F401
+from .hip_env import (HipEnvBatch, StepStamps, orca_solve, prediction_dots, render_scenes, render_trajectories, tile_images,  # noqa: F401
+                      trace_metrics)
 from .hip_policy import HipHandle, HipPolicy, HipSrnn, compact_visible  # noqa: F401
 from .hip_train import (Embed0, GRUSequence, HHAttention, HHBlockFused, HipLinear, HRAttention, MinibatchStepper, PPOLoss, RightMatmul,  # noqa: F401
                         RnSequence, SmallMM, SrnnEdgeSequence, WgradLinear, adam_clip_step, adv_normalize, adv_stats, gae, linear_act,

@@ -1,5 +1,5 @@
-"""The simulator's handle (cn_env_batch: HipEnvBatch), drawing (render_scenes, prediction_dots, tile_images), the stand-alone ORCA solve and the
-device-side launch stamps of the step's kernels (StepStamps)."""
+"""The simulator's handle (cn_env_batch: HipEnvBatch), drawing (render_scenes, prediction_dots, tile_images), recorded episodes (trace_metrics,
+render_trajectories), the stand-alone ORCA solve and the device-side launch stamps of the step's kernels (StepStamps)."""
 import ctypes as C
 
 import torch
@@ -167,6 +167,27 @@ class HipEnvBatch(HipHandle):
         A.call("cn_env_get_visibility", self._h, A.ptr(out), A.stream_ptr(), device=self.device)
         return out
 
+    def trace_append(self, active, index, trace):
+        """Append the CURRENT state of the envs `active` / `index` select to `trace` in one launch (cn_env_trace_append): every env e with
+        active[e] != 0 (active None: all) and 0 <= index[e] < cap gets record index[e] written and length[e] = index[e] + 1, the others are
+        left alone.  active / index: contiguous int64 [E] device tensors -- EvalAccumulator.active / .steps as they are.  trace: anything with
+        agents float32 [E,cap,H+1,6], flags uint8 [E,cap,H+1], goal float32 [E,2] (or None) and length int32 [E] on the device
+        (evaluation.EpisodeTraces).  Called before every step, record t is the state step t was taken from; the state after an episode's
+        final step is never recorded (the step replaces it with the next episode's start).  No allocation, no host synchronisation."""
+        E, A_ = self.E, self.H + 1
+        agents, flags, goal, length = trace.agents, trace.flags, trace.goal, trace.length
+        _check_tensors("trace_append", (("active", active, torch.int64), ("index", index, torch.int64), ("agents", agents, torch.float32),
+                                        ("flags", flags, torch.uint8), ("goal", goal, torch.float32), ("length", length, torch.int32)))
+        if index is None or agents is None or flags is None or length is None:
+            raise A.CnError("trace_append: index, agents, flags and length are required")
+        if agents.dim() != 4 or agents.shape[0] != E or tuple(agents.shape[2:]) != (A_, 6) or agents.shape[1] < 1:
+            raise A.CnError("trace_append: agents must be [%d,cap,%d,6]" % (E, A_))
+        cap = int(agents.shape[1])
+        _check_shapes("trace_append", (("active", active, (E,)), ("index", index, (E,)), ("flags", flags, (E, cap, A_)), ("goal", goal, (E, 2)),
+                                       ("length", length, (E,))))
+        A.call("cn_env_trace_append", self._h, A.ptr(active), A.ptr(index), cap, A.ptr(agents), A.ptr(flags), A.ptr(goal), A.ptr(length),
+               A.stream_ptr(), device=self.device)
+
     def render(self, size=128, env_ids=None, half_width=None, dots=None, dot_counts=None, out=None):
         """The current state of the envs (all, or those `env_ids` -- an int tensor or list -- selects) as uint8 [n,size,size,4] RGBA images
         on the device: get_state, get_human_counts, get_visibility and the robot's heading (its velocity when holonomic, (cos theta, sin theta)
@@ -188,22 +209,32 @@ class HipEnvBatch(HipHandle):
                              half_width=cfg.arena_size + 1.0 if half_width is None else half_width, out=out)
 
 
+def _check_tensors(who, items):
+    for name, t, dt in items:
+        if t is None:
+            continue
+        if not t.is_cuda:
+            raise A.CnError("%s: %s must live on the GPU (no CPU fallback)" % (who, name))
+        if t.dtype != dt or not t.is_contiguous():
+            raise A.CnError("%s: %s must be a contiguous %s tensor" % (who, name, dt))
+    _need_cuda()
+
+
+def _check_shapes(who, items):
+    for name, t, shape in items:
+        if t is not None and tuple(t.shape) != tuple(shape):
+            raise A.CnError("%s: %s must have shape %s" % (who, name, list(shape)))
+
+
 def render_scenes(humans, robot, counts=None, visible=None, robot_heading=None, dots=None, dot_counts=None, robot_radius=0.3,
                   ring_radius=0.0, size=128, half_width=7.0, out=None):
     """cn_render_scenes: n scenes -> uint8 [n,size,size,4] RGBA images on the device, one launch, by the exact fp32 rule of
     include/crowdnav_hip.h.  humans float64 [n,H,8] / robot float64 [n,8] in the layout of HipEnvBatch.get_state(); counts int32 [n], visible
     uint8 [n,H], robot_heading float32 [n,2], dots float32 [n,max_dots,2] + dot_counts int32 [n] are optional (None: every slot holds a human,
     all visible, heading = robot velocity, no dots).  out: optional uint8 [n,size,size,4] tensor to draw into."""
-    for name, t, dt in (("humans", humans, torch.float64), ("robot", robot, torch.float64), ("counts", counts, torch.int32),
-                        ("visible", visible, torch.uint8), ("robot_heading", robot_heading, torch.float32), ("dots", dots, torch.float32),
-                        ("dot_counts", dot_counts, torch.int32), ("out", out, torch.uint8)):
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise A.CnError("render_scenes: %s must live on the GPU (no CPU fallback)" % name)
-        if t.dtype != dt or not t.is_contiguous():
-            raise A.CnError("render_scenes: %s must be a contiguous %s tensor" % (name, dt))
-    _need_cuda()
+    _check_tensors("render_scenes", (("humans", humans, torch.float64), ("robot", robot, torch.float64), ("counts", counts, torch.int32),
+                                     ("visible", visible, torch.uint8), ("robot_heading", robot_heading, torch.float32),
+                                     ("dots", dots, torch.float32), ("dot_counts", dot_counts, torch.int32), ("out", out, torch.uint8)))
     if humans.dim() != 3 or humans.shape[2] != 8 or robot.shape != (humans.shape[0], 8):
         raise A.CnError("render_scenes: humans must be [n,H,8] and robot [n,8]")
     n, H, size = int(humans.shape[0]), int(humans.shape[1]), int(size)
@@ -216,15 +247,58 @@ def render_scenes(humans, robot, counts=None, visible=None, robot_heading=None, 
             dots = dot_counts = None
     elif dot_counts is not None:
         raise A.CnError("render_scenes: dot_counts given without dots")
-    for name, t, shape in (("counts", counts, (n,)), ("visible", visible, (n, H)), ("robot_heading", robot_heading, (n, 2)),
-                           ("dot_counts", dot_counts, (n,)), ("out", out, (n, size, size, 4))):
-        if t is not None and tuple(t.shape) != shape:
-            raise A.CnError("render_scenes: %s must have shape %s" % (name, list(shape)))
+    _check_shapes("render_scenes", (("counts", counts, (n,)), ("visible", visible, (n, H)), ("robot_heading", robot_heading, (n, 2)),
+                                    ("dot_counts", dot_counts, (n,)), ("out", out, (n, size, size, 4))))
     if out is None:
         out = torch.empty(n, size, size, 4, dtype=torch.uint8, device=humans.device)
     A.call("cn_render_scenes", n, H, A.ptr(humans), A.ptr(robot), A.ptr(counts), A.ptr(visible), A.ptr(robot_heading), A.ptr(dots),
            A.ptr(dot_counts), max_dots, float(robot_radius), float(ring_radius), size, float(half_width),
            A.ptr(out), A.stream_ptr(), device=humans.device)
+    return out
+
+
+TRACE_METRICS = ("records", "path_length", "min_clearance", "intrusion_steps", "visible_intrusion_steps", "mean_speed", "mean_accel",
+                 "mean_crowd")           # the CN_TRACE_* columns of include/crowdnav_hip.h, in order
+
+
+def _trace_shape(who, agents, flags, length):
+    _check_tensors(who, (("agents", agents, torch.float32), ("flags", flags, torch.uint8), ("length", length, torch.int32)))
+    if agents.dim() != 4 or agents.shape[3] != 6 or min(agents.shape[:3]) < 1:
+        raise A.CnError("%s: agents must be [n,cap,A,6]" % who)
+    n, cap, A_ = (int(x) for x in agents.shape[:3])
+    _check_shapes(who, (("flags", flags, (n, cap, A_)), ("length", length, (n,))))
+    return n, cap, A_
+
+
+def trace_metrics(agents, flags, length, time_step=0.25, discomfort_dist=0.25, out=None):
+    """cn_trace_metrics: n recorded episodes (agents float32 [n,cap,A,6], flags uint8 [n,cap,A], length int32 [n], the layout of
+    HipEnvBatch.trace_append) -> float64 [n,8] on the device, columns TRACE_METRICS as include/crowdnav_hip.h defines them (path length over
+    the recorded segments only, minimum clearance, intrusion steps, ...).  One launch, no host synchronisation."""
+    n, cap, A_ = _trace_shape("trace_metrics", agents, flags, length)
+    _check_tensors("trace_metrics", (("out", out, torch.float64),))
+    _check_shapes("trace_metrics", (("out", out, (n, len(TRACE_METRICS))),))
+    if out is None:
+        out = torch.empty(n, len(TRACE_METRICS), dtype=torch.float64, device=agents.device)
+    A.call("cn_trace_metrics", n, cap, A_, A.ptr(agents), A.ptr(flags), A.ptr(length), float(time_step), float(discomfort_dist), A.ptr(out),
+           A.stream_ptr(), device=agents.device)
+    return out
+
+
+def render_trajectories(agents, flags, length, goal, stride=8, size=256, half_width=7.0, out=None):
+    """cn_render_trajectories: n recorded episodes -> uint8 [n,size,size,4] RGBA images on the device, one picture per episode, one launch, by
+    the exact fp32 rule of include/crowdnav_hip.h: every record leaves a small trail disc per agent, shaded by the record index, every
+    `stride`-th record and the last one also the agent's outline, the robot's last record its full disc.  goal float32 [n,2]; out: optional
+    uint8 [n,size,size,4] tensor to draw into."""
+    n, cap, A_ = _trace_shape("render_trajectories", agents, flags, length)
+    size = int(size)
+    _check_tensors("render_trajectories", (("goal", goal, torch.float32), ("out", out, torch.uint8)))
+    if goal is None:
+        raise A.CnError("render_trajectories: goal is required")
+    _check_shapes("render_trajectories", (("goal", goal, (n, 2)), ("out", out, (n, size, size, 4))))
+    if out is None:
+        out = torch.empty(n, size, size, 4, dtype=torch.uint8, device=agents.device)
+    A.call("cn_render_trajectories", n, cap, A_, A.ptr(agents), A.ptr(flags), A.ptr(length), A.ptr(goal), int(stride), size, float(half_width),
+           A.ptr(out), A.stream_ptr(), device=agents.device)
     return out
 
 

@@ -210,6 +210,24 @@ int cn_env_get_human_counts(cn_env_batch *env, int32_t *out, void *stream);
  * reference's render colours its humans by (crowd_sim_pred.py:236-370, crowd_sim_var_num.py render: `self.human_visibility`).
  * out [E,H] uint8 (device), 0 in the slots beyond the env's crowd size.  Ordered like cn_env_get_state. */
 int cn_env_get_visibility(cn_env_batch *env, uint8_t *out, void *stream);
+/* Episode traces: append the CURRENT state of selected envs to caller-owned DEVICE buffers in ONE launch, with no allocation and no host
+ * synchronisation -- the recording half of the per-episode trajectory figure the reference announces (test.py:31 --render_traj,
+ * rl/networks/envs.py:226 VecPyTorch.render_traj) and never delivers; cn_trace_metrics and cn_render_trajectories below consume it.
+ * Acts on every env e with (active == NULL || active[e] != 0) and 0 <= index[e] < cap: writes record index[e] of env e and sets
+ * length[e] = index[e] + 1; every other env's buffers are left untouched.  active / index [E] int64 are meant to be the CN_EVAL_ACTIVE and
+ * CN_EVAL_STEPS arrays of the cn_eval_accumulate state block as they are.  With A = H + 1 agent slots (H = the H of cn_env_get_state):
+ *   agents [E,cap,A,6] float32, 8-byte aligned.  Slot 0 is the robot: px, py, vx, vy, radius (the configured one), theta.  Slot 1 + h is human
+ *          slot h of cn_env_get_state: px, py, vx, vy, radius, v_pref.  Every value is the float64 state rounded once to float32; slots at or
+ *          beyond the env's crowd size are written as zeros.
+ *   flags  [E,cap,A] uint8.  Bit 0: the slot holds an agent (the robot: always; human slot h: h < cn_env_get_human_counts).  Bit 1: the
+ *          cn_env_get_visibility decision, by the same device function; 0 in the robot's own slot.
+ *   goal   [E,2] float32 (may be NULL): the robot's goal, written when index[e] == 0.
+ *   length [E] int32.
+ * Called once before every cn_env_step with index = the steps taken so far, record t of an episode is the state its t-th step was taken
+ * FROM: record 0 is the reset state and length == the episode's step count.  The state AFTER the final step is not recorded: cn_env_step
+ * replaces it with the next episode's start in the same launch, so no caller ever sees it.  Ordered like cn_env_get_state. */
+int cn_env_trace_append(cn_env_batch *env, const int64_t *active, const int64_t *index, int cap, float *agents, uint8_t *flags, float *goal,
+                        int32_t *length, void *stream);
 /* Overwrite the per-env case counters (crowd_sim_var_num.py:316-318 `case_counter[phase] = test_case`, :337
  * rand_seed = offset[phase] + case_counter + thisSeed): the NEXT reset of env e generates the scenario of that case.
  * counters [E] uint64 (device).  Lets a batch replay chosen test cases (one per env) instead of consecutive ones. */
@@ -248,6 +266,46 @@ int cn_env_load(cn_env_batch *env, const void *src, void *stream);
 int cn_render_scenes(int n, int H, const double *humans, const double *robot, const int32_t *counts, const uint8_t *visible,
                      const float *robot_heading, const float *dots, const int32_t *dot_counts, int max_dots, float robot_radius,
                      float ring_radius, int size, float half_width, uint32_t *out, void *stream);
+
+/* ---- recorded episodes: metrics and the trajectory figure ----
+ * Both read n traces in the layout of cn_env_trace_append (agents [n,cap,A,6] float32, flags [n,cap,A] uint8, length [n] int32; caller-owned
+ * device buffers, 2 <= A <= CN_MAX_HUMANS + 1, 1 <= cap <= 65536) and use L = clamp(length, 0, cap) records of each.  They stand in for the
+ * reference's test.py:31 --render_traj / rl/networks/envs.py:226 render_traj(path, episode_num), which forwards to an env method no env class
+ * defines.  A trace ends with the state the final step was taken from (see cn_env_trace_append): neither pretends to know the state after it.
+ * (CN_ABI_VERSION is unchanged: these are additions, no existing signature or struct layout moved.)
+ *
+ * cn_trace_metrics: out [n,CN_TRACE_METRICS] float64.  Positions, velocities and radii are widened to float64 first; every operation below is
+ * a single correctly rounded fp64 operation (no contraction), norms are sqrt(x*x + y*y), and every sum runs over the records in ascending
+ * order starting from 0.0 -- a rerun, or a loop in the same order elsewhere, gives the same bits.  A human slot is PRESENT in a record when
+ * its flag bit 0 is set; its clearance there is ||p_robot - p_human|| - r_robot - r_human (the subtractions in that order).
+ *   CN_TRACE_RECORDS                  L
+ *   CN_TRACE_PATH_LENGTH              sum over t = 1..L-1 of ||p_robot[t] - p_robot[t-1]||: the L - 1 recorded segments, no jump to a next episode
+ *   CN_TRACE_MIN_CLEARANCE            minimum clearance over all records and present humans; +inf if there is none
+ *   CN_TRACE_INTRUSION_STEPS          records in which some present human has clearance < discomfort_dist
+ *   CN_TRACE_VISIBLE_INTRUSION_STEPS  the same, counting only humans whose flag bit 1 (visible) is set
+ *   CN_TRACE_MEAN_SPEED               (sum over t = 0..L-1 of ||v_robot[t]||) / L; 0 for L == 0
+ *   CN_TRACE_MEAN_ACCEL               (sum over t = 1..L-1 of ||v_robot[t] - v_robot[t-1]||) / ((L-1) * time_step); 0 for L < 2
+ *   CN_TRACE_MEAN_CROWD               (sum over t of the present humans of record t) / L; 0 for L == 0 */
+enum { CN_TRACE_RECORDS = 0, CN_TRACE_PATH_LENGTH = 1, CN_TRACE_MIN_CLEARANCE = 2, CN_TRACE_INTRUSION_STEPS = 3,
+       CN_TRACE_VISIBLE_INTRUSION_STEPS = 4, CN_TRACE_MEAN_SPEED = 5, CN_TRACE_MEAN_ACCEL = 6, CN_TRACE_MEAN_CROWD = 7, CN_TRACE_METRICS = 8 };
+int cn_trace_metrics(int n, int cap, int A, const float *agents, const uint8_t *flags, const int32_t *length, double time_step,
+                     double discomfort_dist, double *out, void *stream);
+/* cn_render_trajectories: n recorded episodes -> n RGBA8 images in one launch, each episode as ONE picture.  Pixel grid, fp32 arithmetic
+ * (every operation rounded once; only + - *, comparisons and int -> float conversions per pixel) and output format are those of
+ * cn_render_scenes: S = size (16..1024, S % 4 == 0), L_w = half_width, q = (2*L_w)/S, pixel (row i, col j) has centre x = (j + 0.5f)*q - L_w,
+ * y = L_w - (i + 0.5f)*q; for a mark centred at c: dx = x - cx, dy = y - cy, d2 = dx*dx + dy*dy; t = 1.5f*q.  goal [n,2] float32; stride >= 1;
+ * out [n,S,S] RGBA8 words R | G<<8 | B<<16 | 255<<24, 16-byte aligned.  With L = clamp(length, 0, cap), D = max(L - 1, 1), the shade of
+ * record k is s = (k*160)/D in integer arithmetic (0 for the first record, 160 for the last), and record k is a STAMP when k % stride == 0
+ * or k == L - 1.  Three shapes of radius r (a record's radius field): TRAIL d2 <= (0.4f*r)*(0.4f*r); OUTLINE d2 <= r*r && (r - t <= 0 ||
+ * d2 >= (r-t)*(r-t)); DISC d2 <= r*r.  Layers, later over earlier:
+ *   0 background white (255,255,255)
+ *   1 the goal: |dx| + |dy| <= 0.3f, red (220,0,0)
+ *   2 humans: for k = 0..L-1, for slots a = 1..A-1 with flag bit 0 set, in that order: TRAIL, then on a stamp OUTLINE, both in
+ *     (200-s, 200-s, 255) if flag bit 1 (visible) is set, else (255, 200-s, 200-s)
+ *   3 the robot (slot 0, whatever its flag): for k = 0..L-1: TRAIL, then on a stamp OUTLINE, then for k == L - 1 DISC, all in (255, 215-s, 0).
+ * L == 0 gives white plus the goal.  One launch, no atomics, no host synchronisation; n * ceil(S/32)^2 must stay below 2^24. */
+int cn_render_trajectories(int n, int cap, int A, const float *agents, const uint8_t *flags, const int32_t *length, const float *goal,
+                           int stride, int size, float half_width, uint32_t *out, void *stream);
 
 /* Stand-alone batched ORCA solve (the rvo2 replacement): B independent agents, each with n_other neighbours.
  * self [B,8] = px,py,vx,vy,radius,max_speed,pref_vx,pref_vy ; others [B,n_other,5] = px,py,vx,vy,radius (float32);
