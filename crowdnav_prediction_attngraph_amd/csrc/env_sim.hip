@@ -661,6 +661,7 @@ struct cn_env_batch {
     hipEvent_t ev_pg;
     bool pg_pending;     // ev_pg was recorded for work the next reader of the staging arrays has to wait for
     bool post_deferred;  // the step just enqueued left its post-observation updates to env_post_kernel (launch_tail runs it before ORCA)
+    int lp3_blocks;      // grid of orca_lp3_kernel (lp3_grid, fixed at creation)
 };
 
 // calc_human_future_traj(method='truth'): P rolls of every human with its own policy
@@ -687,6 +688,17 @@ static int truth_rollout_and_obs(cn_env_batch *env, const cn_obs *obs, hipStream
     hipLaunchKernelGGL(env_obs_kernel, dim3(env->d.E), dim3(64), 0, st, env->d, *obs);
     CN_CHECK_LAUNCH();
     return CN_OK;
+}
+
+// The grid of orca_lp3_kernel.  The list length is only known on the device: a grid for a quarter of the agents (one per wavefront; the
+// rest of the wavefronts exit at once, longer lists are walked with a stride) keeps enough wavefronts in flight to hide the latency of the
+// cooperative routine.  CN_LP3_BLOCKS=n (read when a batch is created) takes n workgroups instead: with a small n every list is walked
+// with a stride (tests/test_gpu_lp3_pairs.py).
+static int lp3_grid(int agents)
+{
+    const char *v = getenv("CN_LP3_BLOCKS");
+    const int n = v ? atoi(v) : 0;
+    return n > 0 ? n : (agents + 15) / 16;
 }
 
 static bool lane_path_of(const cn_env_batch *env)
@@ -796,12 +808,8 @@ static int launch_tail(cn_env_batch *env, hipStream_t main, bool state_bound = f
     const hipEvent_t ev_last = orca_bound ? env->ev_orca : nullptr;
     if (env->d.cfg.humans_policy == CN_HUMANS_ORCA) { // social-force humans act inside env_step_kernel (one lane per human, no solver)
         if (lane_path) {
-            // the infeasible programs are finished by the cooperative routine on the side stream, next to the policy forward.
-            // the list length is only known on the device: a grid for a quarter of the agents (one per wavefront; the rest of the
-            // wavefronts exit at once, longer lists are walked with a stride) keeps enough wavefronts in flight to hide the latency
-            // of the cooperative routine
-            const int blocks = (agents + 15) / 16;
-            launch_ev(orca_lp3_kernel, dim3(blocks), dim3(256), env->side, ev_last, stamped(env->d, CN_K_ORCA_LP3));
+            // the infeasible programs are finished by the cooperative routine on the side stream, next to the policy forward (grid: lp3_grid)
+            launch_ev(orca_lp3_kernel, dim3(env->lp3_blocks), dim3(256), env->side, ev_last, stamped(env->d, CN_K_ORCA_LP3));
             CN_CHECK_LAUNCH();
         } else {
             launch_ev(orca_kernel, dim3((agents + 3) / 4), dim3(256), env->side, ev_last, stamped(env->d, CN_K_ORCA_LP3));
@@ -1032,6 +1040,7 @@ extern "C" int cn_env_create(const cn_env_config *cfg, int num_envs, int64_t see
     // two-team human-human kernel, takes crowds of <= 48 humans)
     b->plan_ok = lane_orca && HM <= RP_HMAX && num_envs <= RP_EMAX;
     b->pregen_ticks = 4000; // 40 us: see prefetch_orca
+    b->lp3_blocks = lp3_grid(num_envs * HM);
     *out = b;
     return CN_OK;
 }

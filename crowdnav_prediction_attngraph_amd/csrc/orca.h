@@ -133,51 +133,80 @@ __device__ __forceinline__ float hw_last(float v, int lane) // lanes 31 / 63 -> 
     const float a = wv_readlane(v, 31), b = wv_readlane(v, 63);
     return (lane & 32) ? b : a;
 }
-__device__ __forceinline__ float hw_min(float v, int lane)
+// Minimum / maximum over a half.  The tree runs on order-preserving integer keys (key(a) < key(b) <=> a < b, -0 below +0 as v_min_f32 has
+// it; no NaN operands here): an unsigned minimum takes its DPP operand itself, one instruction per step, where a float step is four
+// (identity, DPP move, canonicalise, minimum).  Minimum and maximum do not depend on the order of their operands: hw_unkey of the result has
+// the bits of the fminf / fmaxf tree.
+__device__ __forceinline__ uint32_t hw_key(float f)
 {
-    const float I = __builtin_inff();
-    v = fminf(v, wv_dpp<0x111, 0xf>(v, I));
-    v = fminf(v, wv_dpp<0x112, 0xf>(v, I));
-    v = fminf(v, wv_dpp<0x114, 0xf>(v, I));
-    v = fminf(v, wv_dpp<0x118, 0xf>(v, I));
-    v = fminf(v, wv_dpp<0x142, 0xa>(v, I)); // row_bcast:15 into rows 1 and 3: lane 31 = lanes 0..31, lane 63 = lanes 32..63
-    return hw_last(v, lane);
+    const uint32_t u = __float_as_uint(f);
+    return u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u);
 }
-__device__ __forceinline__ float hw_max(float v, int lane)
+__device__ __forceinline__ float hw_unkey(uint32_t k) { return __uint_as_float(k ^ ((uint32_t)((int32_t)~k >> 31) | 0x80000000u)); }
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t hw_dpp(uint32_t v, uint32_t identity)
 {
-    const float I = -__builtin_inff();
-    v = fmaxf(v, wv_dpp<0x111, 0xf>(v, I));
-    v = fmaxf(v, wv_dpp<0x112, 0xf>(v, I));
-    v = fmaxf(v, wv_dpp<0x114, 0xf>(v, I));
-    v = fmaxf(v, wv_dpp<0x118, 0xf>(v, I));
-    v = fmaxf(v, wv_dpp<0x142, 0xa>(v, I));
-    return hw_last(v, lane);
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)identity, (int)v, CTRL, ROW_MASK, 0xf, false);
+}
+__device__ __forceinline__ uint32_t hw_min(uint32_t v, int lane) // keys in, key out
+{
+    v = min(v, hw_dpp<0x111, 0xf>(v, ~0u));
+    v = min(v, hw_dpp<0x112, 0xf>(v, ~0u));
+    v = min(v, hw_dpp<0x114, 0xf>(v, ~0u));
+    v = min(v, hw_dpp<0x118, 0xf>(v, ~0u));
+    v = min(v, hw_dpp<0x142, 0xa>(v, ~0u)); // row_bcast:15 into rows 1 and 3: lane 31 = lanes 0..31, lane 63 = lanes 32..63
+    return __float_as_uint(hw_last(__uint_as_float(v), lane));
+}
+__device__ __forceinline__ uint32_t hw_max(uint32_t v, int lane)
+{
+    v = max(v, hw_dpp<0x111, 0xf>(v, 0u));
+    v = max(v, hw_dpp<0x112, 0xf>(v, 0u));
+    v = max(v, hw_dpp<0x114, 0xf>(v, 0u));
+    v = max(v, hw_dpp<0x118, 0xf>(v, 0u));
+    v = max(v, hw_dpp<0x142, 0xa>(v, 0u));
+    return __float_as_uint(hw_last(__uint_as_float(v), lane));
+}
+
+// What linearProgram1 on line i computes from line i alone: its chord of the disc (the bounds before any clip, whether there is one) and
+// which end the direction of optimisation picks.  Every lane works this out for ITS line once, when the lines are set up; a clip on line
+// i fetches lane i's.  The same operations on the same operands as in lp1_wave, done once per line instead of once per clip by 32 lanes.
+struct LpChord { uint32_t kLeft, kRight, inDisc, pickRight; }; // the bounds as keys (hw_key); masks: bit k = line k, uniform per half
+
+__device__ __forceinline__ LpChord lp_chords(const LpLine &L, float radius, float optx, float opty, int lane)
+{
+    LpChord c;
+    const float dotProduct = L.px * L.dx + L.py * L.dy;
+    const float discriminant = dotProduct * dotProduct + radius * radius - (L.px * L.px + L.py * L.py);
+    const float sq = sqrtf(discriminant);
+    c.kLeft = hw_key(-dotProduct - sq);
+    c.kRight = hw_key(-dotProduct + sq);
+    c.inDisc = hw_ballot(!(discriminant < 0.0f), lane);
+    c.pickRight = hw_ballot(optx * L.dx + opty * L.dy > 0.0f, lane);
+    return c;
 }
 
 // lp1_wave with dirOpt = true for both halves at once; commits the new result only where `act` and the program is feasible
-__device__ __forceinline__ bool lp1_pair(const LpLine &L, uint32_t valid, int i, float ipx, float ipy, float idx, float idy, float radius,
-                                         float optx, float opty, bool act, int lane, float &rx, float &ry)
+__device__ __forceinline__ bool lp1_pair(const LpLine &L, const LpChord &C, uint32_t valid, int i, float ipx, float ipy, float idx, float idy,
+                                         bool act, int lane, float &rx, float &ry)
 {
     const int hl = lane & 31;
-    const float dotProduct = ipx * idx + ipy * idy;
-    const float discriminant = dotProduct * dotProduct + radius * radius - (ipx * ipx + ipy * ipy);
-    bool ok = !(discriminant < 0.0f);
-    const float sq = sqrtf(discriminant);
-    float tLeft = -dotProduct - sq;
-    float tRight = -dotProduct + sq;
+    bool ok = (C.inDisc >> i) & 1u;
+    const uint32_t kLeft = __float_as_uint(hw_read(__uint_as_float(C.kLeft), lane, i));
+    const uint32_t kRight = __float_as_uint(hw_read(__uint_as_float(C.kRight), lane, i));
     const bool mine = hl < i && ((valid >> hl) & 1u);
     const float denominator = idx * L.dy - idy * L.dx;
     const float numerator = L.dx * (ipy - L.py) - L.dy * (ipx - L.px);
     const bool parallel = fabsf(denominator) <= RVO_EPS;
     const bool pfail = mine && parallel && numerator < 0.0f;
     const float t = numerator / denominator;
-    const float candR = (mine && !parallel && denominator >= 0.0f) ? t : INFINITY;
-    const float candL = (mine && !parallel && denominator < 0.0f) ? t : -INFINITY;
-    tRight = fminf(tRight, hw_min(candR, lane));
-    tLeft = fmaxf(tLeft, hw_max(candL, lane));
+    const uint32_t kt = hw_key(t);
+    const uint32_t candR = (mine && !parallel && denominator >= 0.0f) ? kt : 0xff800000u; // key(+inf)
+    const uint32_t candL = (mine && !parallel && denominator < 0.0f) ? kt : 0x007fffffu;  // key(-inf)
+    const float tRight = hw_unkey(min(kRight, hw_min(candR, lane)));
+    const float tLeft = hw_unkey(max(kLeft, hw_max(candL, lane)));
     const uint32_t pf = hw_ballot(pfail, lane); // (every cross-lane operation of these routines sits outside their predicated parts)
     ok = ok & (pf == 0u) & !(tLeft > tRight);
-    const float t_opt = (optx * idx + opty * idy > 0.0f) ? tRight : tLeft;
+    const float t_opt = ((C.pickRight >> i) & 1u) ? tRight : tLeft;
     if (act && ok) {
         rx = ipx + t_opt * idx;
         ry = ipy + t_opt * idy;
@@ -190,6 +219,7 @@ __device__ __forceinline__ int lp2_pair(const LpLine &L, uint32_t valid, int n, 
                                         float &rx, float &ry)
 {
     if (act) { rx = radius * optx; ry = radius * opty; }
+    const LpChord C = lp_chords(L, radius, optx, opty, lane);
     uint32_t todo = valid & ((1u << n) - 1u); // n <= 31: line n itself is the one being projected on
     int res = n;
     bool running = act;
@@ -202,7 +232,7 @@ __device__ __forceinline__ int lp2_pair(const LpLine &L, uint32_t valid, int n, 
         if (go) todo &= ~((2u << i) - 1u);
         const float ipx = hw_read(L.px, lane, i), ipy = hw_read(L.py, lane, i);
         const float idx = hw_read(L.dx, lane, i), idy = hw_read(L.dy, lane, i);
-        const bool ok = lp1_pair(L, valid, i, ipx, ipy, idx, idy, radius, optx, opty, go, lane, rx, ry);
+        const bool ok = lp1_pair(L, C, valid, i, ipx, ipy, idx, idy, go, lane, rx, ry);
         if (go && !ok) { res = i; running = false; } // (lp1_pair left the result alone)
     }
 }
