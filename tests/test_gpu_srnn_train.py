@@ -44,17 +44,7 @@ def _reference(shape):
     return dict(h64=h64, d=float((h32.double() - h64).abs().max()), v=v, lp=lp, grads=g, d_h0=d_h0)
 
 
-def _evaluate(p, seq, dev, dt):
-    """The loss of tests/test_gpu_srnn.py through evaluate_actions; returns value, log-prob, {name: grad or None} and the gradient of edge_h0."""
-    to = lambda t: t.to(device=dev, dtype=dt)  # noqa: E731
-    e0 = to(seq["edge_h0"]).requires_grad_(True)
-    p.zero_grad(set_to_none=True)
-    v, lp, ent, _ = p.evaluate_actions({k: to(t) for k, t in seq["obs"].items()}, {"human_node_rnn": to(seq["node_h0"]), "human_human_edge_rnn": e0},
-                                       to(seq["masks"]), to(seq["actions"]))
-    w = torch.linspace(-1, 1, v.numel(), dtype=dt, device=dev).view_as(v)
-    ((v * w).sum() + (lp * w.flip(0)).sum() + ent).backward()
-    grads = {n: (None if q.grad is None else q.grad.detach().cpu().double().clone()) for n, q in p.named_parameters()}
-    return v.detach().cpu().double(), lp.detach().cpu().double(), grads, e0.grad.detach().cpu().double()
+_evaluate = Q.evaluate
 
 
 def _gpu_policy(shape, mode, kernels=True):
@@ -74,24 +64,7 @@ def _seq_op(pol, seq, N):
 
 
 def _check_grads(got, want, mode, label):
-    rows, bad = [], []
-    for name, g64 in want.items():
-        if name.startswith(SU.DEAD):
-            assert got[name] is None and g64 is None, name
-            continue
-        scale = float(g64.abs().max())
-        err = float((got[name] - g64).abs().max())
-        cos = float((g64 * got[name]).sum() / (g64.norm() * got[name].norm()).clamp(min=1e-30))
-        rows.append((err / max(scale, 1e-30), name, err, scale, 1 - cos))
-        if mode == "bf16x3" and name in CANCELLING:
-            ok = err <= 1e-2 * scale and 1 - cos <= 2e-6
-        else:
-            ok = err <= 5e-4 * scale + 1e-7
-        if not ok:
-            bad.append((name, err, scale, 1 - cos))
-    for r in sorted(rows, reverse=True)[:8]:
-        print("%s %s  %.2e  %-58s err %.3e  max %.3e  1-cos %.2e" % (label, mode, r[0], r[1], r[2], r[3], r[4]))
-    assert not bad, bad
+    Q.check_grads(got, want, mode, label, cancelling=CANCELLING, dead=SU.DEAD)
 
 
 @pytest.mark.parametrize("mode", MODES)
