@@ -8,6 +8,8 @@ import ctypes as C
 
 import numpy as np
 
+from tests.orca_scene_util import orca_inputs
+
 
 def oracle_env_head():
     """The leading members of OrcEnv (oracle/crowdsim_oracle.h) up to the human records."""
@@ -28,37 +30,25 @@ def oracle_env_head():
 def handovers(oe, head, want_lines=False):
     """The humans of oracle env `oe` whose next ORCA action needs linearProgram3, from the state the env is in right now:
     a list of dict(agent, nn, line_fail, radius, pref, out (the oracle's new velocity)[, lines [nn][4] float32]).  Humans: ORCA.predict (crowd_nav/policy/orca.py:64-117) as
-    oracle/crowdsim_oracle.c human_orca_action restates it."""
+    oracle/crowdsim_oracle.c human_orca_action restates it; the neighbour list is tests/orca_scene_util.orca_inputs."""
     from oracle import oracle as O
     cfg = oe.cfg
     assert not cfg.randomize_attributes and cfg.human_fov >= 2.0 and cfg.humans_policy == 0
     st = C.cast(oe._h, C.POINTER(head)).contents
     n = oe.human_count
-    hs = [st.humans[j] for j in range(n)]
-    rob = list(st.robot)   # px, py, vx, vy, gx, gy, theta
+    hs = [tuple(getattr(st.humans[j], k) for k in ("px", "py", "vx", "vy", "gx", "gy", "radius", "v_pref")) for j in range(n)]
+    rob = list(st.robot) if cfg.robot_visible else None   # px, py, vx, vy, gx, gy, theta
     saf = cfg.orca_safety_space
     out = []
-    for i, me in enumerate(hs):
-        others = []
-        for j, o in enumerate(hs):
-            if j == i:
-                continue
-            seen = not (o.px == me.px and o.py == me.py)
-            others.append((o.px, o.py, o.vx, o.vy, o.radius + 0.01 + saf) if seen else (7.0, 7.0, 0.0, 0.0, o.radius + 0.01 + saf))
-        if cfg.robot_visible:
-            seen = not (rob[0] == me.px and rob[1] == me.py)
-            others.append((rob[0], rob[1], rob[2], rob[3], cfg.robot_radius + 0.01 + saf) if seen else (7.0, 7.0, 0.0, 0.0, cfg.robot_radius + 0.01 + saf))
+    for i in range(n):
+        state, others = orca_inputs(hs, i, rob, cfg.robot_radius, saf)
         if not others:
             continue
-        vx, vy = me.gx - me.px, me.gy - me.py
-        speed = np.sqrt(vx * vx + vy * vy)
-        if speed > 1.0:
-            vx, vy = vx / speed, vy / speed
-        vel, lines, fail = O.orca_velocity((me.px, me.py, me.vx, me.vy, me.radius + 0.01 + saf, me.v_pref, vx, vy), others,
-                                         neighbor_dist=cfg.orca_neighbor_dist, time_horizon=cfg.orca_time_horizon, time_step=cfg.time_step,
-                                         want_lines=True)
+        v_pref, (vx, vy) = state[5], state[6:8]
+        vel, lines, fail = O.orca_velocity(state, others, neighbor_dist=cfg.orca_neighbor_dist, time_horizon=cfg.orca_time_horizon,
+                                         time_step=cfg.time_step, want_lines=True)
         if fail < len(lines):
-            rec = dict(agent=i, nn=len(lines), line_fail=fail, radius=np.float32(me.v_pref), pref=(np.float32(vx), np.float32(vy)), out=(np.float32(vel[0]), np.float32(vel[1])))
+            rec = dict(agent=i, nn=len(lines), line_fail=fail, radius=np.float32(v_pref), pref=(np.float32(vx), np.float32(vy)), out=(np.float32(vel[0]), np.float32(vel[1])))
             if want_lines:
                 rec["lines"] = lines
             out.append(rec)
