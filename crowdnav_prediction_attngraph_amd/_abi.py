@@ -47,6 +47,44 @@ class EnvConfig(C.Structure):
     ]
 
 
+class PolicyDims(C.Structure):
+    """cn_policy_dims: the reference's four network-size flags (arguments.py:155-181) as cn_policy_create_sized takes them."""
+    _fields_ = [("rnn_size", C.c_int), ("embedding_size", C.c_int), ("attention_size", C.c_int), ("output_size", C.c_int)]
+
+    def astuple(self):
+        return (self.rnn_size, self.embedding_size, self.attention_size, self.output_size)
+
+    def __eq__(self, other):
+        return isinstance(other, PolicyDims) and self.astuple() == other.astuple()
+
+    __hash__ = None
+
+
+DEFAULT_DIMS = (128, 64, 64, 256)      # (R, M, A, O) = human_node_rnn_size, human_node_embedding_size, attention_size, human_node_output_size
+DIMS_BOX = "human_node_rnn_size in {64, 128, 192, 256}, human_node_embedding_size in {64, 128}, human_node_output_size a multiple of 64 in [64, 512], " \
+           "attention_size in [1, 256]"
+
+
+def policy_dims(dims=None):
+    """dims: None (the default), an (R, M, A, O) tuple, a dict of the four flag names or a PolicyDims -> a PolicyDims inside the device box.
+    Outside the box: NotImplementedError naming the box -- raised here, in Python, before anything is allocated (and without needing a GPU)."""
+    if dims is None:
+        dims = DEFAULT_DIMS
+    elif isinstance(dims, PolicyDims):
+        dims = dims.astuple()
+    elif isinstance(dims, dict):
+        names = ("human_node_rnn_size", "human_node_embedding_size", "attention_size", "human_node_output_size")
+        stray = sorted(set(dims) - set(names))
+        if stray:
+            raise KeyError("unknown network size flag(s) %s: the flags are %s" % (", ".join(stray), ", ".join(names)))
+        dims = tuple(dims.get(n, d) for n, d in zip(names, DEFAULT_DIMS))
+    R, M, A_, O = (int(v) for v in dims)
+    if not (R in (64, 128, 192, 256) and M in (64, 128) and 64 <= O <= 512 and O % 64 == 0 and 1 <= A_ <= 256):
+        raise NotImplementedError("network sizes (human_node_rnn_size %d, human_node_embedding_size %d, attention_size %d, human_node_output_size %d) are "
+                                  "outside the device box: %s (CPU tensors run any sizes the reference accepts)" % (R, M, A_, O, DIMS_BOX))
+    return PolicyDims(R, M, A_, O)
+
+
 class Obs(C.Structure):
     _fields_ = [("robot_node", C.c_void_p), ("temporal_edges", C.c_void_p), ("spatial_edges", C.c_void_p),
                 ("detected_human_num", C.c_void_p), ("visible_masks", C.c_void_p), ("row_plan", C.c_void_p)]
@@ -175,7 +213,7 @@ class PpoHyper(C.Structure):
 ABI_SYMBOLS = [
     "cn_last_error", "cn_version", "cn_device_count", "cn_env_config_default", "cn_env_create", "cn_env_destroy",
     "cn_env_obs_width", "cn_row_plan_words", "cn_env_set_pregen_budget", "cn_env_set_tail_deferral", "cn_env_launch_tail", "cn_policy_set_post_hh_hook", "cn_env_reset", "cn_env_step", "cn_env_join", "cn_env_get_state", "cn_env_get_human_actions", "cn_env_get_danger_min_dist", "cn_env_get_human_counts", "cn_env_set_case_counters", "cn_env_snapshot_bytes", "cn_env_save", "cn_env_load", "cn_orca_solve",
-    "cn_policy_create", "cn_policy_destroy", "cn_policy_set_weights", "cn_policy_act", "cn_policy_get_value",
+    "cn_policy_create", "cn_policy_create_sized", "cn_policy_destroy", "cn_policy_set_weights", "cn_policy_act", "cn_policy_get_value",
     "cn_policy_get_taps", "cn_policy_set_gemm_mode", "cn_policy_set_self_attention", "cn_obs_compact_visible", "cn_policy_set_taps", "cn_policy_set_profiling", "cn_policy_get_profile",
     "cn_policy_get_profile_samples", "cn_policy_reset_profile", "cn_prof_set_stamps", "cn_prof_next_step", "cn_hh_block_workspace_bytes", "cn_hh_block_fwd", "cn_rn_seq_workspace_floats", "cn_rn_seq_fwd_workspace_floats", "cn_rn_seq_fwd", "cn_rn_seq_bwd", "cn_hh_attention_workspace_ints", "cn_hh_attention_fwd", "cn_hh_attention_bwd", "cn_hr_attention_fwd", "cn_hr_attention_bwd", "cn_gru_cell_fwd", "cn_gru_cell_bwd", "cn_gru_seq_fwd", "cn_gru_seq_bwd", "cn_embed0_fwd", "cn_embed0_bwd",
     "cn_split_bf16", "cn_split_bf16_padded", "cn_linear_fwd", "cn_linear_fwd_act", "cn_linear_wgrad_splits", "cn_linear_wgrad", "cn_small_mm", "cn_gst_create", "cn_gst_destroy", "cn_gst_set_weights", "cn_gst_predict",
@@ -244,6 +282,7 @@ def lib():
         L.cn_env_load.argtypes = [vp, vp, vp]
         L.cn_orca_solve.argtypes = [i32, i32, vp, vp, f32, i32, f32, f32, vp, vp]
         L.cn_policy_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+        L.cn_policy_create_sized.argtypes = [i32, i32, i32, C.POINTER(PolicyDims), C.POINTER(vp)]
         L.cn_policy_destroy.argtypes = [vp]
         L.cn_policy_set_weights.argtypes = [vp, C.POINTER(PolicyWeights), vp]
         L.cn_policy_act.argtypes = [vp, i32, C.POINTER(Obs), vp, vp, vp, vp, vp, vp, vp, vp]

@@ -534,7 +534,7 @@ __device__ __forceinline__ void hr_load8(HrRows &r, const float *__restrict__ ou
         for (int c = 0; c < 4; ++c) r.v[q][c] = row[64 * c];
     }
 }
-__global__ __launch_bounds__(256) void hr_attention_kernel(int E, int H, const float *__restrict__ u, int u_ld, const float *__restrict__ out_sp,
+__global__ __launch_bounds__(256) void hr_attention_kernel(int E, int H, float temp, const float *__restrict__ u, int u_ld, const float *__restrict__ out_sp,
                                                            const int *__restrict__ row_off, float *__restrict__ hr_out, float *__restrict__ hr_attn)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) void hr_attention_kernel(int E, int H, const f
     const int r0 = row_off[e], nd = row_off[e + 1] - r0;
     const float *ue = u + (size_t)e * u_ld;
     const float u0 = ue[lane], u1 = ue[64 + lane], u2 = ue[128 + lane], u3 = ue[192 + lane];
-    const float temp = (float)H / 8.0f; // temperature = num_edges / sqrt(attention_size = 64)
+    // temp: the temperature num_edges / sqrt(attention_size), formed by the host (H / 8 at the reference's attention_size = 64)
     float s = -INFINITY; // lane j holds the score of human j
     HrRows k0;
     hr_load8(k0, out_sp, r0, 0, nd, lane);

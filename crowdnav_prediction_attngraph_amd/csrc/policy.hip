@@ -14,6 +14,7 @@
 //   gemm.h            exact-fp32 MFMA GEMM (v_mfma_f32_32x32x2_f32): per-env layers, big layers in gemm mode 0
 //   gemm3.h           bf16x3 split-precision NT GEMM of the big layers in gemm mode 1 (arithmetic: split_bf16.h) and the weight split
 //   hh_fused.h, rn_fused.h   interfaces of the two fused kernels of gemm mode 2 (hh_fused.hip, rn_fused.hip: objects of their own)
+//   rn_sized.h        interface of the robot-node kernel with run-time network sizes (rn_sized.hip): gemm mode 2 of a cn_policy_create_sized handle
 //   policy.hip        part 1, rollout: cn_policy, cn_policy_set_weights (copies, folds, splits, fragment images), policy_forward, taps, profiling
 //                     part 2, training: cn_hh_block_fwd, cn_obs_compact_visible, cn_hh_attention_*, cn_hr_attention_*, cn_rn_seq_* and the
 //                     rn_seq_*_impl / rn_seq_prep_jobs that train_internal.h declares.  Its big products go to linear.hip (cn_linear_*).
@@ -44,6 +45,7 @@
 #include "rn_train.h"
 #include "hh_fused.h"
 #include "rn_fused.h"
+#include "rn_sized.h"
 #include "row_plan.h"
 #include "train_internal.h"
 
@@ -57,24 +59,29 @@
 // =================================================================================================================================
 struct cn_policy {
     int H, D, maxE;
+    // cn_policy_dims: R = human_node_rnn_size, Mb = human_node_embedding_size, A = attention_size, O = human_node_output_size (128 / 64 / 64 / 256)
+    int R, Mb, A, O;
+    bool sized;       // any of them off its default: the robot-node half of gemm mode 2 runs on rn_sized.hip
+    int rn_te;        // ... with this many envs per workgroup (rn_sized_envs_per_group)
+    float hr_scale;   // robot-human score scale (float)((double)H / sqrt((double)A)): H / 8 at the default
     bool weights_set;
     char *blob;
     // weight snapshot (device)
     float *emb0_w, *emb0_b, *emb2_w, *emb2_b;
     float *qkv_w, *qkv_b;   // folded [1536,512], [1536]
     float *os_w, *os_b;     // folded out_proj∘spatial_linear [256,512], [256]
-    float *as_w, *as_b;     // attn.spatial_edge_layer [64,256]
-    float *at_w, *at_b;     // attn.temporal_edge_layer [64,256]
+    float *as_w, *as_b;     // attn.spatial_edge_layer [A,256]
+    float *at_w, *at_b;     // attn.temporal_edge_layer [A,256]
     float *rl_w, *rl_b;     // robot_linear [256,9]
-    float *enc_w, *enc_b, *edge_w, *edge_b; // [64,256] each
-    float *wih, *whh, *bih, *bhh;           // GRU
-    float *out_w, *out_b;                   // [256,128]
-    float *ac0_w, *ac0_b;                   // concat(actor.0, critic.0) [512,256]
-    float *a2_w, *a2_b, *c2_w, *c2_b;       // [256,256]
+    float *enc_w, *enc_b, *edge_w, *edge_b; // [Mb,256] each
+    float *wih, *whh, *bih, *bhh;           // GRU [3R,2Mb], [3R,R]
+    float *out_w, *out_b;                   // [O,R]
+    float *ac0_w, *ac0_b;                   // concat(actor.0, critic.0) [2O,O]
+    float *a2_w, *a2_b, *c2_w, *c2_b;       // [O,O]
     float *cl_w, *cl_b, *fm_w, *fm_b, *logstd;
-    float *te_w, *te_b;       // [spatial_edge_layer^T * temporal_edge_layer (u, 256 rows) ; encoder_linear (64 rows)] stacked [320,256]
-    float *ac0f_w, *ac0f_b;   // (actor.0 ; critic.0) folded with output_linear [512,128]
-    float *z;                 // [E,192] = [t_emb | relu(enc) | relu(edge)]
+    float *te_w, *te_b;       // [spatial_edge_layer^T * temporal_edge_layer (u, 256 rows) ; encoder_linear (Mb rows)] stacked [256 + Mb,256]
+    float *ac0f_w, *ac0f_b;   // (actor.0 ; critic.0) folded with output_linear [2O,R]
+    float *z;                 // [E,256 + 2Mb] = [u | relu(enc) | relu(edge)]
     // activations
     float *emb1, *emb2, *qkv, *attn, *out_sp;
     __bf16 *emb2_hi, *emb2_lo, *qkv_hi, *qkv_lo, *os_hi, *os_lo; // split copies of the three big weight matrices
@@ -121,7 +128,8 @@ static int launch_gemm_env(int M, int N, int K, const float *A, int lda, const f
     return launch_gemm_t<64, 64, ACT>(M, N, K, A, lda, W, bias, C, ldc, st, nullptr, nbatch, gb, relu_from);
 }
 
-extern "C" int cn_policy_create(int human_num, int edge_width, int max_envs, cn_policy **out)
+// The sizes are checked by the callers: cn_policy_create passes the default, cn_policy_create_sized its box.
+static int policy_create(int human_num, int edge_width, int max_envs, int dR, int dM, int dA, int dO, cn_policy **out)
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(out, "cn_policy_create: null out");
@@ -131,32 +139,37 @@ extern "C" int cn_policy_create(int human_num, int edge_width, int max_envs, cn_
     cn_policy *p = new (std::nothrow) cn_policy{};
     CN_REQUIRE(p, "cn_policy_create: out of host memory");
     p->H = human_num; p->D = edge_width; p->maxE = max_envs;
+    p->R = dR; p->Mb = dM; p->A = dA; p->O = dO;
+    p->sized = !(dR == 128 && dM == 64 && dA == 64 && dO == 256);
+    p->rn_te = p->sized ? rn_sized_envs_per_group(dR, dM, dO) : 16;
+    p->hr_scale = (float)((double)human_num / sqrt((double)dA)); // the reference forms it in double and multiplies a float32 tensor by it
     const size_t E = max_envs, M = E * human_num, D = edge_width;
+    const size_t R = dR, Mb = dM, A = dA, O = dO; // at the default every size below is the literal it used to be
     size_t off = 0;
     auto carve = [&](size_t nfloat) { size_t o = off; off += align_up(nfloat * sizeof(float)); return o; };
     const size_t o_emb0w = carve(128 * D), o_emb0b = carve(128), o_emb2w = carve(512 * 128), o_emb2b = carve(512);
     const size_t o_qkvw = carve(1536 * 512), o_qkvb = carve(1536), o_osw = carve(256 * 512), o_osb = carve(256);
-    const size_t o_asw = carve(64 * 256), o_asb = carve(64), o_atw = carve(64 * 256), o_atb = carve(64);
+    const size_t o_asw = carve(A * 256), o_asb = carve(A), o_atw = carve(A * 256), o_atb = carve(A);
     const size_t o_rlw = carve(256 * 9), o_rlb = carve(256);
-    const size_t o_encw = carve(64 * 256), o_encb = carve(64), o_edgew = carve(64 * 256), o_edgeb = carve(64);
-    const size_t o_wih = carve(384 * 128), o_whh = carve(384 * 128), o_bih = carve(384), o_bhh = carve(384);
-    const size_t o_outw = carve(256 * 128), o_outb = carve(256);
-    const size_t o_ac0w = carve(512 * 256), o_ac0b = carve(512);
-    const size_t o_a2w = carve(256 * 256), o_a2b = carve(256), o_c2w = carve(256 * 256), o_c2b = carve(256);
-    const size_t o_clw = carve(256), o_clb = carve(1), o_fmw = carve(512), o_fmb = carve(2), o_ls = carve(2);
+    const size_t o_encw = carve(Mb * 256), o_encb = carve(Mb), o_edgew = carve(Mb * 256), o_edgeb = carve(Mb);
+    const size_t o_wih = carve(3 * R * 2 * Mb), o_whh = carve(3 * R * R), o_bih = carve(3 * R), o_bhh = carve(3 * R);
+    const size_t o_outw = carve(O * R), o_outb = carve(O);
+    const size_t o_ac0w = carve(2 * O * O), o_ac0b = carve(2 * O);
+    const size_t o_a2w = carve(O * O), o_a2b = carve(O), o_c2w = carve(O * O), o_c2b = carve(O);
+    const size_t o_clw = carve(O), o_clb = carve(1), o_fmw = carve(2 * O), o_fmb = carve(2), o_ls = carve(2);
     const size_t o_emb1 = carve(M * 128), o_emb2 = carve(M * 512), o_qkv = carve(M * 1536), o_attn = carve(M * 512);
     const size_t o_outsp = carve(M * 256);
-    const size_t o_rs = carve(E * 256), o_temb = carve(E * 64), o_hr = carve(E * 256), o_hra = carve(M), o_x = carve(E * 128);
-    const size_t o_gi = carve(E * 384), o_gh = carve(E * 384), o_hn = carve(E * 128), o_ro = carve(E * 256);
-    const size_t o_ac1 = carve(E * 512), o_ac2 = carve(E * 512);
+    const size_t o_rs = carve(E * 256), o_temb = carve(E * A), o_hr = carve(E * 256), o_hra = carve(M), o_x = carve(E * 2 * Mb);
+    const size_t o_gi = carve(E * 3 * R), o_gh = carve(E * 3 * R), o_hn = carve(E * R), o_ro = carve(E * O);
+    const size_t o_ac1 = carve(E * 2 * O), o_ac2 = carve(E * 2 * O);
     const size_t o_roff = carve(E + 1);
     const size_t o_live = carve(2);
     const size_t o_ccnt = carve(2), o_clist = carve(2 * E);
-    const size_t o_tew = carve(320 * 256), o_teb = carve(320), o_acfw = carve(512 * 128), o_acfb = carve(512), o_z = carve(E * 384);
+    const size_t o_tew = carve((256 + Mb) * 256), o_teb = carve(256 + Mb), o_acfw = carve(2 * O * R), o_acfb = carve(2 * O), o_z = carve(E * (256 + 2 * Mb));
     const size_t o_e2h = carve(512 * 128 / 2), o_e2l = carve(512 * 128 / 2), o_qh = carve(1536 * 512 / 2), o_ql = carve(1536 * 512 / 2);
     const size_t o_osh = carve(256 * 512 / 2), o_osl = carve(256 * 512 / 2);
-    const size_t o_rte = carve(320 * 256), o_rwhh = carve(384 * 128), o_redge = carve(64 * 256), o_rwih = carve(384 * 128), o_rac0 = carve(512 * 128);
-    const size_t o_ra2 = carve(256 * 256), o_rc2 = carve(256 * 256);
+    const size_t o_rte = carve((256 + Mb) * 256), o_rwhh = carve(3 * R * R), o_redge = carve(Mb * 256), o_rwih = carve(3 * R * 2 * Mb), o_rac0 = carve(2 * O * R);
+    const size_t o_ra2 = carve(O * O), o_rc2 = carve(O * O);
     const size_t o_fe2 = carve(HH_EMB2_FRAG_BYTES / 4), o_fqkv = carve(HH_QKV_FRAG_BYTES / 4), o_fos = carve(HH_OS_FRAG_BYTES / 4);
     char *base = nullptr;
     hipError_t herr = hipMalloc((void **)&base, off);
@@ -199,6 +212,22 @@ extern "C" int cn_policy_create(int human_num, int edge_width, int max_envs, cn_
         }
     *out = p;
     return CN_OK;
+}
+
+extern "C" int cn_policy_create(int human_num, int edge_width, int max_envs, cn_policy **out)
+{
+    return policy_create(human_num, edge_width, max_envs, 128, 64, 64, 256, out);
+}
+
+extern "C" int cn_policy_create_sized(int human_num, int edge_width, int max_envs, const cn_policy_dims *dims, cn_policy **out)
+{
+    if (!dims) return cn_policy_create(human_num, edge_width, max_envs, out);
+    const int R = dims->rnn_size, M = dims->embedding_size, A = dims->attention_size, O = dims->output_size;
+    // multiples of 64: launch_gemm_env needs N % 64, rn_fused_bake N % 16 and K % 32 (and the sized kernel pairs its k-steps: K % 64)
+    CN_REQUIRE((R == 64 || R == 128 || R == 192 || R == 256) && (M == 64 || M == 128) && O >= 64 && O <= 512 && O % 64 == 0 && A >= 1 && A <= 256,
+               "cn_policy_create_sized: (rnn_size %d, embedding_size %d, attention_size %d, output_size %d) outside the device box: rnn_size in "
+               "{64,128,192,256}, embedding_size in {64,128}, output_size a multiple of 64 in [64,512], attention_size in [1,256]", R, M, A, O);
+    return policy_create(human_num, edge_width, max_envs, R, M, A, O, out);
 }
 
 extern "C" int cn_policy_destroy(cn_policy *p)
@@ -261,39 +290,40 @@ extern "C" int cn_policy_set_weights(cn_policy *p, const cn_policy_weights *w, v
     }
     if (int rc = hh_fused_bake(p->emb2_w, p->qkv_w, p->os_w, p->f_emb2, p->f_qkv, p->f_os, st)) return rc;
     } // self_attn
-    CN_D2D(p->as_w, w->attn_spatial_w, 64 * 256); CN_D2D(p->as_b, w->attn_spatial_b, 64);
-    CN_D2D(p->at_w, w->attn_temporal_w, 64 * 256); CN_D2D(p->at_b, w->attn_temporal_b, 64);
+    const int R = p->R, Mb = p->Mb, A = p->A, O = p->O; // cn_policy_dims: 128 / 64 / 64 / 256 by default
+    CN_D2D(p->as_w, w->attn_spatial_w, A * 256); CN_D2D(p->as_b, w->attn_spatial_b, A);
+    CN_D2D(p->at_w, w->attn_temporal_w, A * 256); CN_D2D(p->at_b, w->attn_temporal_b, A);
     CN_D2D(p->rl_w, w->robot_linear_w, 256 * 9); CN_D2D(p->rl_b, w->robot_linear_b, 256);
-    CN_D2D(p->enc_w, w->enc_w, 64 * 256); CN_D2D(p->enc_b, w->enc_b, 64);
-    CN_D2D(p->edge_w, w->edge_embed_w, 64 * 256); CN_D2D(p->edge_b, w->edge_embed_b, 64);
-    CN_D2D(p->wih, w->gru_w_ih, 384 * 128); CN_D2D(p->whh, w->gru_w_hh, 384 * 128);
-    CN_D2D(p->bih, w->gru_b_ih, 384); CN_D2D(p->bhh, w->gru_b_hh, 384);
-    CN_D2D(p->out_w, w->out_w, 256 * 128); CN_D2D(p->out_b, w->out_b, 256);
-    CN_D2D(p->ac0_w, w->actor0_w, 256 * 256); CN_D2D(p->ac0_w + 256 * 256, w->critic0_w, 256 * 256);
-    CN_D2D(p->ac0_b, w->actor0_b, 256); CN_D2D(p->ac0_b + 256, w->critic0_b, 256);
-    CN_D2D(p->a2_w, w->actor2_w, 256 * 256); CN_D2D(p->a2_b, w->actor2_b, 256);
-    CN_D2D(p->c2_w, w->critic2_w, 256 * 256); CN_D2D(p->c2_b, w->critic2_b, 256);
-    // u = Ws^T (Wt r + bt): the robot-human scores become u . o_j (see hr_attention_kernel)
-    hipLaunchKernelGGL(fold_mm_tn_kernel, dim3(1, 256), dim3(256), 0, st, 256, 64, 256, w->attn_spatial_w, w->attn_temporal_w, p->te_w);
+    CN_D2D(p->enc_w, w->enc_w, Mb * 256); CN_D2D(p->enc_b, w->enc_b, Mb);
+    CN_D2D(p->edge_w, w->edge_embed_w, Mb * 256); CN_D2D(p->edge_b, w->edge_embed_b, Mb);
+    CN_D2D(p->wih, w->gru_w_ih, 3 * R * 2 * Mb); CN_D2D(p->whh, w->gru_w_hh, 3 * R * R);
+    CN_D2D(p->bih, w->gru_b_ih, 3 * R); CN_D2D(p->bhh, w->gru_b_hh, 3 * R);
+    CN_D2D(p->out_w, w->out_w, O * R); CN_D2D(p->out_b, w->out_b, O);
+    CN_D2D(p->ac0_w, w->actor0_w, O * O); CN_D2D(p->ac0_w + O * O, w->critic0_w, O * O);
+    CN_D2D(p->ac0_b, w->actor0_b, O); CN_D2D(p->ac0_b + O, w->critic0_b, O);
+    CN_D2D(p->a2_w, w->actor2_w, O * O); CN_D2D(p->a2_b, w->actor2_b, O);
+    CN_D2D(p->c2_w, w->critic2_w, O * O); CN_D2D(p->c2_b, w->critic2_b, O);
+    // u = Ws^T (Wt r + bt): the robot-human scores become u . o_j (see hr_attention_kernel); the attention size A is summed away here
+    hipLaunchKernelGGL(fold_mm_tn_kernel, dim3(1, 256), dim3(256), 0, st, 256, A, 256, w->attn_spatial_w, w->attn_temporal_w, p->te_w);
     CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fold_bias_tn_kernel, dim3(1), dim3(256), 0, st, 256, 64, w->attn_spatial_w, w->attn_temporal_b, p->te_b);
+    hipLaunchKernelGGL(fold_bias_tn_kernel, dim3(1), dim3(256), 0, st, 256, A, w->attn_spatial_w, w->attn_temporal_b, p->te_b);
     CN_CHECK_LAUNCH();
-    CN_D2D(p->te_w + 256 * 256, w->enc_w, 64 * 256);
-    CN_D2D(p->te_b + 256, w->enc_b, 64);
+    CN_D2D(p->te_w + 256 * 256, w->enc_w, Mb * 256);
+    CN_D2D(p->te_b + 256, w->enc_b, Mb);
     // fold output_linear into the first actor / critic layers: tanh(W0 (Wo h + bo) + b0) = tanh((W0 Wo) h + (W0 bo + b0))
-    hipLaunchKernelGGL(fold_mm_kernel, dim3(1, 512), dim3(128), 0, st, 512, 256, 128, p->ac0_w, w->out_w, 1.0f, p->ac0f_w);
+    hipLaunchKernelGGL(fold_mm_kernel, dim3(1, 2 * O), dim3(R), 0, st, 2 * O, O, R, p->ac0_w, w->out_w, 1.0f, p->ac0f_w);
     CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(fold_bias_kernel, dim3(2), dim3(256), 0, st, 512, 256, p->ac0_w, w->out_b, p->ac0_b, 1.0f, p->ac0f_b);
+    hipLaunchKernelGGL(fold_bias_kernel, dim3((2 * O + 255) / 256), dim3(256), 0, st, 2 * O, O, p->ac0_w, w->out_b, p->ac0_b, 1.0f, p->ac0f_b);
     CN_CHECK_LAUNCH();
     {
-        struct { int N, K; const float *w; float *out; } bk[7] = {{320, 256, p->te_w, p->r_te}, {384, 128, p->whh, p->r_whh}, {64, 256, p->edge_w, p->r_edge},
-                                                                  {384, 128, p->wih, p->r_wih}, {512, 128, p->ac0f_w, p->r_ac0}, {256, 256, p->a2_w, p->r_a2},
-                                                                  {256, 256, p->c2_w, p->r_c2}};
+        struct { int N, K; const float *w; float *out; } bk[7] = {{256 + Mb, 256, p->te_w, p->r_te}, {3 * R, R, p->whh, p->r_whh}, {Mb, 256, p->edge_w, p->r_edge},
+                                                                  {3 * R, 2 * Mb, p->wih, p->r_wih}, {2 * O, R, p->ac0f_w, p->r_ac0}, {O, O, p->a2_w, p->r_a2},
+                                                                  {O, O, p->c2_w, p->r_c2}};
         for (auto &b : bk)
             if (int rc = rn_fused_bake(b.N, b.K, b.w, b.out, st)) return rc;
     }
-    CN_D2D(p->cl_w, w->critic_linear_w, 256); CN_D2D(p->cl_b, w->critic_linear_b, 1);
-    CN_D2D(p->fm_w, w->fc_mean_w, 512); CN_D2D(p->fm_b, w->fc_mean_b, 2); CN_D2D(p->logstd, w->logstd, 2);
+    CN_D2D(p->cl_w, w->critic_linear_w, O); CN_D2D(p->cl_b, w->critic_linear_b, 1);
+    CN_D2D(p->fm_w, w->fc_mean_w, 2 * O); CN_D2D(p->fm_b, w->fc_mean_b, 2); CN_D2D(p->logstd, w->logstd, 2);
     p->weights_set = true;
     return CN_OK;
 }
@@ -365,6 +395,7 @@ static int policy_forward(cn_policy *p, int E, const cn_obs *obs, const float *h
         ra.cl_w = p->cl_w; ra.cl_b = p->cl_b; ra.fm_w = p->fm_w; ra.fm_b = p->fm_b; ra.logstd = p->logstd;
         ra.value = value; ra.action = action; ra.logp = logp; ra.hxs_out = hxs_out ? hxs_out : p->hnew;
         if (p->taps_on) { ra.tap_robot = p->robot_states; ra.tap_attn = p->hr_attn; ra.tap_hr = p->hr_out; ra.tap_actor = p->ac2; }
+        if (p->sized) return rn_sized_forward(E, H, ra, RnSizedDims{p->R, p->Mb, p->O, p->rn_te, p->hr_scale}, st);
         return rn_fused_forward(E, H, ra, st);
     }
     // ---- robot node: nothing here depends on the human-human block, so it runs beside it on the side stream ----
@@ -375,9 +406,10 @@ static int policy_forward(cn_policy *p, int E, const cn_obs *obs, const float *h
         hipLaunchKernelGGL(robot_embed_kernel, dim3(blocks), dim3(256), 0, p->side, E, obs->temporal_edges, obs->robot_node, p->rl_w, p->rl_b, p->robot_states);
         CN_CHECK_LAUNCH();
     }
-    // [u | relu(enc)] in one launch (both read robot_states); z = [u (256) | enc (64) | edge (64)], GRU input x = z + 256
-    if ((rc = launch_gemm_env<ACT_NONE>(E, 320, 256, p->robot_states, 256, p->te_w, p->te_b, p->z, 384, p->side, 1, GemmBatch{0, 0, 0, 0}, 256))) return rc;
-    if ((rc = launch_gemm_env<ACT_NONE>(E, 384, 128, hxs_in, 128, p->whh, nullptr, p->gh, 384, p->side))) return rc; // GRU hidden-side gates
+    // [u | relu(enc)] in one launch (both read robot_states); z = [u (256) | enc (Mb) | edge (Mb)], GRU input x = z + 256
+    const int R = p->R, Mb = p->Mb, O = p->O, ZW = 256 + 2 * Mb; // 128, 64, 256, 384 by default
+    if ((rc = launch_gemm_env<ACT_NONE>(E, 256 + Mb, 256, p->robot_states, 256, p->te_w, p->te_b, p->z, ZW, p->side, 1, GemmBatch{0, 0, 0, 0}, 256))) return rc;
+    if ((rc = launch_gemm_env<ACT_NONE>(E, 3 * R, R, hxs_in, R, p->whh, nullptr, p->gh, 3 * R, p->side))) return rc; // GRU hidden-side gates
     CN_HIP(hipEventRecord(p->ev_join, p->side));
     // ---- human-human block on the compacted live rows (row_off[E] rows, known only on the device) ----
     const int *m_dev = p->row_off + E;
@@ -416,20 +448,20 @@ static int policy_forward(cn_policy *p, int E, const cn_obs *obs, const float *h
     // ---- robot-human attention (robot node embeddings arrive from the side stream) ----
     CN_HIP(hipStreamWaitEvent(st, p->ev_join, 0));
     {
-        hipLaunchKernelGGL(hr_attention_kernel, dim3((E + 3) / 4), dim3(256), 0, st, E, H, p->z, 384, p->out_sp, p->row_off, p->hr_out, p->hr_attn);
+        hipLaunchKernelGGL(hr_attention_kernel, dim3((E + 3) / 4), dim3(256), 0, st, E, H, p->hr_scale, p->z, ZW, p->out_sp, p->row_off, p->hr_out, p->hr_attn);
         CN_CHECK_LAUNCH();
     }
     // ---- EndRNN: edge encoder -> GRU (output_linear is folded into the actor / critic trunks) ----
-    if ((rc = launch_gemm_env<ACT_RELU>(E, 64, 256, p->hr_out, 256, p->edge_w, p->edge_b, p->z + 320, 384, st))) return rc;
-    if ((rc = launch_gemm_env<ACT_NONE>(E, 384, 128, p->z + 256, 384, p->wih, p->bih, p->gi, 384, st))) return rc;
+    if ((rc = launch_gemm_env<ACT_RELU>(E, Mb, 256, p->hr_out, 256, p->edge_w, p->edge_b, p->z + 256 + Mb, ZW, st))) return rc;
+    if ((rc = launch_gemm_env<ACT_NONE>(E, 3 * R, 2 * Mb, p->z + 256, ZW, p->wih, p->bih, p->gi, 3 * R, st))) return rc;
     float *hdst = hxs_out ? hxs_out : p->hnew;
-    hipLaunchKernelGGL(gru_pointwise_kernel, dim3(E), dim3(128), 0, st, E, p->gi, p->gh, p->bhh, hxs_in, masks, hdst);
+    hipLaunchKernelGGL(gru_pointwise_kernel, dim3(E), dim3(R), 0, st, E, R, p->gi, p->gh, p->bhh, hxs_in, masks, hdst);
     CN_CHECK_LAUNCH();
     // ---- actor / critic trunks: first layers stacked (+ folded output_linear), second layers as one batched launch ----
-    if ((rc = launch_gemm_env<ACT_TANH>(E, 512, 128, hdst, 128, p->ac0f_w, p->ac0f_b, p->ac1, 512, st))) return rc;
-    if ((rc = launch_gemm_env<ACT_TANH>(E, 256, 256, p->ac1, 512, p->a2_w, p->a2_b, p->ac2, 512, st, 2,
-                                        GemmBatch{256, (long long)(p->c2_w - p->a2_w), (long long)(p->c2_b - p->a2_b), 256}))) return rc;
-    hipLaunchKernelGGL(gauss_head_kernel, dim3((E + 3) / 4), dim3(256), 0, st, E, p->ac2, 512, p->cl_w, p->cl_b, p->fm_w, p->fm_b, p->logstd, eps,
+    if ((rc = launch_gemm_env<ACT_TANH>(E, 2 * O, R, hdst, R, p->ac0f_w, p->ac0f_b, p->ac1, 2 * O, st))) return rc;
+    if ((rc = launch_gemm_env<ACT_TANH>(E, O, O, p->ac1, 2 * O, p->a2_w, p->a2_b, p->ac2, 2 * O, st, 2,
+                                        GemmBatch{O, (long long)(p->c2_w - p->a2_w), (long long)(p->c2_b - p->a2_b), O}))) return rc;
+    hipLaunchKernelGGL(gauss_head_kernel, dim3((E + 3) / 4), dim3(256), 0, st, E, O, p->ac2, 2 * O, p->cl_w, p->cl_b, p->fm_w, p->fm_b, p->logstd, eps,
                        value, action, logp);
     CN_CHECK_LAUNCH();
     return CN_OK;
@@ -462,8 +494,9 @@ extern "C" int cn_policy_get_taps(cn_policy *p, int E, float *spatial_lin, float
     if (hr_attn) CN_D2D(hr_attn, p->hr_attn, M);
     if (hr_out) CN_D2D(hr_out, p->hr_out, (size_t)E * 256);
     if (robot_emb) CN_D2D(robot_emb, p->robot_states, (size_t)E * 256);
-    if (actor_feat && p->gemm_mode == 2) CN_D2D(actor_feat, p->ac2, (size_t)E * 256); // the fused robot-node kernel taps [E,256] directly
-    else if (actor_feat) CN_HIP(hipMemcpy2DAsync(actor_feat, 256 * sizeof(float), p->ac2, 512 * sizeof(float), 256 * sizeof(float), E, hipMemcpyDeviceToDevice, st));
+    const size_t O = p->O;
+    if (actor_feat && p->gemm_mode == 2) CN_D2D(actor_feat, p->ac2, (size_t)E * O); // the fused robot-node kernel taps [E,O] directly
+    else if (actor_feat) CN_HIP(hipMemcpy2DAsync(actor_feat, O * sizeof(float), p->ac2, 2 * O * sizeof(float), O * sizeof(float), E, hipMemcpyDeviceToDevice, st));
     return CN_OK;
 }
 
@@ -598,7 +631,7 @@ extern "C" int cn_hr_attention_fwd(int B, int H, const float *u, const float *ou
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(B >= 1 && H >= 1 && H <= CN_MAX_HUMANS && u && out_sp && row_off && hr_out && attn, "cn_hr_attention_fwd: bad argument");
-    hipLaunchKernelGGL(hr_attention_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, H, u, 256, out_sp, row_off, hr_out, attn);
+    hipLaunchKernelGGL(hr_attention_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, H, (float)H / 8.0f, u, 256, out_sp, row_off, hr_out, attn);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -774,7 +807,7 @@ int rn_seq_fwd_impl(int T, int N, int H, const float *robot_node, const float *t
     // z = [u (256) | relu(enc) (64) | .] in one product (both read robot_states), then the attention over the compacted rows, then edge -> z[320:384]
     // (the padded product writes zeros into z[:, 320:384]; the edge layer below overwrites them)
     if ((rc = rn_gemm3(ACT_NONE, B, 384, 256, sv->rs, 256, ws + F.te, ws + F.teb, sv->z, 384, st, nullptr, 0, 256))) return rc;
-    hipLaunchKernelGGL(hr_attention_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, H, sv->z, 384, out_sp, row_off, sv->hr, sv->attn);
+    hipLaunchKernelGGL(hr_attention_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, H, (float)H / 8.0f, sv->z, 384, out_sp, row_off, sv->hr, sv->attn);
     CN_CHECK_LAUNCH();
     if ((rc = rn_gemm<ACT_RELU>(B, 64, 256, sv->hr, 256, w->edge_w, w->edge_b, sv->z + 320, 384, st))) return rc;
     if ((rc = rn_gemm3(ACT_NONE, B, 384, 128, sv->z + 256, 384, ws + F.wih, w->bih, sv->gi, 384, st))) return rc;

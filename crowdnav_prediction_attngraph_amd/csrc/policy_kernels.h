@@ -126,25 +126,26 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(int E, int H, const f
 
 // GRU cell pointwise part (PyTorch formulation, gate order r,z,n) with the done mask applied to h
 // (rl/networks/srnn_model.py:43-46): gi = x W_ih^T + b_ih (bias already added), gh_raw = h W_hh^T (no bias, unmasked).
-__global__ __launch_bounds__(128) void gru_pointwise_kernel(int E, const float *__restrict__ gi, const float *__restrict__ gh_raw,
+// One block per env, R threads (the hidden size, at most 256).
+__global__ __launch_bounds__(256) void gru_pointwise_kernel(int E, int R, const float *__restrict__ gi, const float *__restrict__ gh_raw,
                                                             const float *__restrict__ b_hh, const float *__restrict__ h_in,
                                                             const float *__restrict__ masks, float *__restrict__ h_out)
 {
     const int e = blockIdx.x, c = threadIdx.x;
     if (e >= E) return;
     const float m = masks[e];
-    const float *gie = gi + (size_t)e * 384, *ghe = gh_raw + (size_t)e * 384;
-    const float hr = m * ghe[c] + b_hh[c], hz = m * ghe[128 + c] + b_hh[128 + c], hn = m * ghe[256 + c] + b_hh[256 + c];
+    const float *gie = gi + (size_t)e * 3 * R, *ghe = gh_raw + (size_t)e * 3 * R;
+    const float hr = m * ghe[c] + b_hh[c], hz = m * ghe[R + c] + b_hh[R + c], hn = m * ghe[2 * R + c] + b_hh[2 * R + c];
     const float r = 1.0f / (1.0f + expf(-(gie[c] + hr)));
-    const float z = 1.0f / (1.0f + expf(-(gie[128 + c] + hz)));
-    const float n = tanhf(gie[256 + c] + r * hn);
-    const float h = m * h_in[(size_t)e * 128 + c];
-    h_out[(size_t)e * 128 + c] = (1.0f - z) * n + z * h;
+    const float z = 1.0f / (1.0f + expf(-(gie[R + c] + hz)));
+    const float n = tanhf(gie[2 * R + c] + r * hn);
+    const float h = m * h_in[(size_t)e * R + c];
+    h_out[(size_t)e * R + c] = (1.0f - z) * n + z * h;
 }
 
 // critic_linear + DiagGaussian head (model.py:64-72, distributions.py:36-44,76-95): one wavefront per env.
-// ac [E,512]: columns 0..255 actor features, 256..511 critic features.
-__global__ __launch_bounds__(256) void gauss_head_kernel(int E, const float *__restrict__ ac, int ld, const float *__restrict__ wv,
+// ac [E,2O]: columns 0..O-1 actor features, O..2O-1 critic features (O = 256 by default, a multiple of 64).
+__global__ __launch_bounds__(256) void gauss_head_kernel(int E, int O, const float *__restrict__ ac, int ld, const float *__restrict__ wv,
                                                          const float *__restrict__ bv, const float *__restrict__ wm,
                                                          const float *__restrict__ bm, const float *__restrict__ logstd,
                                                          const float *__restrict__ eps, float *__restrict__ value,
@@ -153,14 +154,12 @@ __global__ __launch_bounds__(256) void gauss_head_kernel(int E, const float *__r
     const int lane = threadIdx.x & 63;
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= E) return;
-    const float *a = ac + (size_t)e * ld, *c = a + 256;
+    const float *a = ac + (size_t)e * ld, *c = a + O;
     float sv = 0.f, s0 = 0.f, s1 = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int d = lane + 64 * k;
+    for (int d = lane; d < O; d += 64) { // the same terms in the same order as the four unrolled steps this was at O = 256
         sv += c[d] * wv[d];
         s0 += a[d] * wm[d];
-        s1 += a[d] * wm[256 + d];
+        s1 += a[d] * wm[O + d];
     }
     sv = wv_sum(sv); s0 = wv_sum(s0); s1 = wv_sum(s1);
     if (lane == 0) {

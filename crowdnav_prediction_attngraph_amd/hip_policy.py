@@ -18,11 +18,11 @@ class HipHandle:
     <_sym>_destroy in close() / __del__, and set_weights over _weights = (pointer struct, [(field, state-dict key)])."""
     _sym, _weights = None, None
 
-    def _open(self, device, *create_args):
+    def _open(self, device, *create_args, create=None):
         _need_cuda()
         self.device = torch.device(device if device is not None else "cuda:%d" % torch.cuda.current_device())
         h = C.c_void_p()
-        A.call(self._sym + "_create", *create_args, C.byref(h), device=self.device)
+        A.call(create or self._sym + "_create", *create_args, C.byref(h), device=self.device)
         self._h = h
         self._keep = None
 
@@ -62,9 +62,16 @@ class HipPolicy(HipHandle):
     _sym, _weights = "cn_policy", (A.PolicyWeights, A.POLICY_WEIGHT_KEYS)
     uses_row_plan = True      # act takes the row plan the simulator wrote beside the observation
 
-    def __init__(self, human_num, edge_width, max_envs, device=None):
+    def __init__(self, human_num, edge_width, max_envs, device=None, dims=None):
+        """dims: the network sizes (R, M, A, O) -- None, a tuple, a dict of the reference's flag names or an A.PolicyDims (A.policy_dims).  None and
+        the default tuple take cn_policy_create; any other tuple inside the device box cn_policy_create_sized; outside the box NotImplementedError."""
         self.H, self.D, self.maxE = int(human_num), int(edge_width), int(max_envs)
-        self._open(device, self.H, self.D, self.maxE)
+        self.dims = A.policy_dims(dims)                 # refuses sizes outside the box before anything is allocated
+        self.R, self.O = self.dims.rnn_size, self.dims.output_size
+        if self.dims.astuple() == A.DEFAULT_DIMS:
+            self._open(device, self.H, self.D, self.maxE)
+        else:
+            self._open(device, self.H, self.D, self.maxE, C.byref(self.dims), create="cn_policy_create_sized")
 
     def set_self_attention(self, enabled):
         """args.use_self_attn (cn_policy_set_self_attention): False = no human-human attention, spatial_linear is the two-layer MLP
@@ -87,7 +94,9 @@ class HipPolicy(HipHandle):
         dev = self.device
         if out is None:
             out = dict(value=torch.empty(E, 1, device=dev), action=torch.empty(E, 2, device=dev),
-                       logp=torch.empty(E, 1, device=dev), hxs=torch.empty(E, 1, 128, device=dev))
+                       logp=torch.empty(E, 1, device=dev), hxs=torch.empty(E, 1, self.R, device=dev))
+        if hxs.numel() != E * self.R or out["hxs"].numel() != E * self.R:
+            raise A.CnError("HipPolicy.act: the hidden state must be [E,%d] (human_node_rnn_size)" % self.R)
         o = A.obs_struct(obs, row_plan)
         A.call("cn_policy_act", self._h, E, C.byref(o), A.ptr(hxs.contiguous()), A.ptr(masks.contiguous()),
                A.ptr(None if eps is None else eps.contiguous()), A.ptr(out["value"]), A.ptr(out["action"]),
@@ -98,6 +107,8 @@ class HipPolicy(HipHandle):
         E = obs["robot_node"].shape[0]
         if out is None:
             out = torch.empty(E, 1, device=self.device)
+        if hxs.numel() != E * self.R:
+            raise A.CnError("HipPolicy.get_value: the hidden state must be [E,%d] (human_node_rnn_size)" % self.R)
         o = A.obs_struct(obs)
         A.call("cn_policy_get_value", self._h, E, C.byref(o), A.ptr(hxs.contiguous()), A.ptr(masks.contiguous()), A.ptr(out),
                A.stream_ptr(), device=self.device)
@@ -105,7 +116,7 @@ class HipPolicy(HipHandle):
 
     def state_shapes(self, E):
         """The recurrent state this handle carries, under the reference's rnn_hxs names."""
-        return {"human_node_rnn": (E, 1, 128)}
+        return {"human_node_rnn": (E, 1, self.R)}
 
     def act_rnn(self, obs, rnn_hxs, masks, eps=None, out=None, rnn_hxs_out=None, row_plan=None):
         """act under the rollout contract both policy handles share: out = dict(value, action, logp), rnn_hxs / rnn_hxs_out = dicts of the
@@ -114,7 +125,7 @@ class HipPolicy(HipHandle):
         if out is None:
             out = dict(value=torch.empty(E, 1, device=dev), action=torch.empty(E, 2, device=dev), logp=torch.empty(E, 1, device=dev))
         if rnn_hxs_out is None:
-            rnn_hxs_out = {"human_node_rnn": torch.empty(E, 1, 128, device=dev)}
+            rnn_hxs_out = {"human_node_rnn": torch.empty(E, 1, self.R, device=dev)}
         self.act(obs, rnn_hxs["human_node_rnn"], masks, eps=eps, out=dict(out, hxs=rnn_hxs_out["human_node_rnn"]), row_plan=row_plan)
         return out, rnn_hxs_out
 
@@ -124,7 +135,7 @@ class HipPolicy(HipHandle):
     def taps(self, E):
         dev, H = self.device, self.H
         t = dict(spatial_lin=torch.empty(E, H, 256, device=dev), hr_attn=torch.empty(E, H, device=dev),
-                 hr_out=torch.empty(E, 256, device=dev), robot_emb=torch.empty(E, 256, device=dev), actor_feat=torch.empty(E, 256, device=dev))
+                 hr_out=torch.empty(E, 256, device=dev), robot_emb=torch.empty(E, 256, device=dev), actor_feat=torch.empty(E, self.O, device=dev))
         A.call("cn_policy_get_taps", self._h, E, A.ptr(t["spatial_lin"]), A.ptr(t["hr_attn"]), A.ptr(t["hr_out"]),
                A.ptr(t["robot_emb"]), A.ptr(t["actor_feat"]), A.stream_ptr(), device=dev)
         return t

@@ -137,10 +137,15 @@ class AttnGraphBase(nn.Module):
         self.human_node_rnn_size = _arg(args, "human_node_rnn_size", 128)
         self.human_human_edge_rnn_size = _arg(args, "human_human_edge_rnn_size", 256)
         self.output_size = _arg(args, "human_node_output_size", 256)
-        emb = _arg(args, "human_node_embedding_size", 64)
-        attention_size = _arg(args, "attention_size", 64)
-        if (self.human_node_rnn_size, self.human_human_edge_rnn_size, self.output_size, emb, attention_size) != (128, 256, 256, 64, 64):
-            raise NotImplementedError("the HIP kernels are specialised to the reference's network sizes (128/256/256/64/64)")
+        emb = self.embedding_size = _arg(args, "human_node_embedding_size", 64)
+        attention_size = self.attention_size = _arg(args, "attention_size", 64)
+        if self.human_human_edge_rnn_size != 256:
+            # selfAttn_srnn_temp_node.py:330-345: robot_linear and spatial_linear are hard-wired to 256 columns, so the reference's own first forward
+            # fails on the shapes ("mat1 and mat2 shapes cannot be multiplied") for any other value of this flag
+            raise NotImplementedError("human_human_edge_rnn_size = %d: the reference itself cannot run an edge size other than 256 (its robot_linear "
+                                      "and spatial_linear are hard-wired to 256)" % self.human_human_edge_rnn_size)
+        if min(self.human_node_rnn_size, self.output_size, emb, attention_size) < 1:
+            raise ValueError("network sizes must be positive")
         # arguments.py:189, :206.  use_self_attn = False: no human-human attention, spatial_linear embeds the raw edges
         # (selfAttn_srnn_temp_node.py:340-345); sort_humans = False: attention masks from `visible_masks` instead of the detected count (:378-383)
         self.use_self_attn = bool(_arg(args, "use_self_attn", True))
@@ -180,10 +185,21 @@ class AttnGraphBase(nn.Module):
     def make_hip_handle(self, E, device):
         """The rollout handle of this network for up to E envs, configured but without weights."""
         from .hip_policy import HipPolicy
-        hip = HipPolicy(self.human_num, self.edge_width, E, device=device)
+        hip = HipPolicy(self.human_num, self.edge_width, E, device=device, dims=self.dims)     # sizes outside the device box: refused here
         hip.set_self_attention(self.use_self_attn)
         hip.set_taps(False)          # rollout path: nobody reads the test taps
         return hip
+
+    @property
+    def dims(self):
+        """(R, M, A, O) = (human_node_rnn_size, human_node_embedding_size, attention_size, human_node_output_size): cn_policy_dims."""
+        return (self.human_node_rnn_size, self.embedding_size, self.attention_size, self.output_size)
+
+    @property
+    def default_sizes(self):
+        """The reference's default widths: the only ones the hand-written TRAINING kernels of the robot-node half are specialised to."""
+        from ._abi import DEFAULT_DIMS
+        return self.dims == DEFAULT_DIMS
 
     def forward_rnn(self, inputs, rnn_hxs, masks, T, N):
         """forward_sequence under the contract both bases share: (value, actor features, rnn_hxs after step T of the state this base carries)."""
@@ -257,7 +273,7 @@ class AttnGraphBase(nn.Module):
     def _lin(self, x, w, b):
         """Per-sample Linear layer of the update: on the GPU the weight gradient (a reduction over all T*N rows into a small
         matrix) goes to the split-K TN kernel, everything else stays a library product."""
-        if x.is_cuda and self.train_gemm_mode == "bf16x3":
+        if x.is_cuda and self.train_gemm_mode == "bf16x3" and self.default_sizes:    # other widths: the torch-op definition (library products)
             from . import hip_train as hip
             if hip.linear_supported(x, w) and x.shape[0] >= 16384:
                 return hip.HipLinear.apply(x, w, b, False)   # [128 a, 128 b] weights: forward, dX and dW on the pipelined bf16x3 kernels
@@ -356,7 +372,7 @@ class AttnGraphBase(nn.Module):
         H = out_sp.shape[1]
         t = self.attn.temporal_edge_layer[0](robot_states)
         s = self.attn.spatial_edge_layer[0](out_sp)
-        a = (t.unsqueeze(1) * s).sum(-1) * (H / math.sqrt(64.0))
+        a = (t.unsqueeze(1) * s).sum(-1) * (H / math.sqrt(float(self.attention_size)))     # :151-152: a double scalar times a float32 tensor
         a = torch.softmax(a.masked_fill(~valid, -1e9), dim=-1)
         return torch.bmm(a.unsqueeze(1), out_sp).squeeze(1), a
 
@@ -371,8 +387,8 @@ class AttnGraphBase(nn.Module):
         return (1.0 - z) * n + z * h
 
     def forward_sequence(self, inputs, h0, masks, T, N):
-        """inputs: dict of [T*N, ...] (T-major), h0 [N,1,128] or [N,128], masks [T*N,1].
-        Returns value [T*N,1], actor features [T*N,256], h_T [N,128].  Masking h at every step is arithmetically the
+        """inputs: dict of [T*N, ...] (T-major), h0 [N,1,R] or [N,R], masks [T*N,1] (R = human_node_rnn_size, 128 by default).
+        Returns value [T*N,1], actor features [T*N,O], h_T [N,R] (O = human_node_output_size, 256 by default).  Masking h at every step is arithmetically the
         reference's split-at-done trick (rl/networks/srnn_model.py:52-104)."""
         B = T * N
         inputs = self.counted_inputs(inputs)
@@ -389,7 +405,10 @@ class AttnGraphBase(nn.Module):
             tl = self.attn.temporal_edge_layer[0]
             from .hip_train import RightMatmul
             t_emb = self._lin(robot_states, tl.weight, tl.bias)
-            u = (RightMatmul.apply(t_emb, sl.weight) if t_emb.shape[0] >= 4096 else t_emb @ sl.weight) + 0.0 * sl.bias.sum()
+            u = (RightMatmul.apply(t_emb, sl.weight) if t_emb.shape[0] >= 4096 and self.default_sizes else t_emb @ sl.weight) + 0.0 * sl.bias.sum()
+            if self.attention_size != 64:
+                # cn_hr_attention_fwd / _bwd scale the scores by H / 8 = H / sqrt(64); H / sqrt(A) is that times 8 / sqrt(A), carried by u
+                u = u * (8.0 / math.sqrt(float(self.attention_size)))
             hr = HRAttention.apply(u, out_sp, valid, self.human_num)
         else:
             hr, _ = self._hr_attention(robot_states, out_sp, valid)
@@ -399,7 +418,7 @@ class AttnGraphBase(nn.Module):
         gi = self._lin(x, rnn.gru.weight_ih_l0, rnn.gru.bias_ih_l0).view(T, N, -1)
         m = masks.reshape(T, N, 1)
         h = h0.reshape(N, -1)
-        if gi.is_cuda:
+        if gi.is_cuda and tuple(rnn.gru.weight_hh_l0.shape) == (384, 128):      # cn_gru_seq_* are specialised to R = 128
             from .hip_train import GRUSequence
             hs_all = GRUSequence.apply(gi, h, m, rnn.gru.weight_hh_l0, rnn.gru.bias_hh_l0)
             h = hs_all[-1]

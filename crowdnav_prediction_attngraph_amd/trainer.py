@@ -185,10 +185,29 @@ def update_flops(live_rows, samples, ppo_epoch):
     return 3.0 * ppo_epoch * (live_rows * hh + samples * rn)
 
 
+NETWORK_FLAGS = ("human_node_rnn_size", "human_node_embedding_size", "attention_size", "human_node_output_size")     # arguments.py:155-181
+
+
+def network_kwargs(network):
+    """train(network=...): a dict of the reference's four network-size flags (any subset; the others keep 128 / 64 / 64 / 256) -> the entries it
+    adds to the policy's base_kwargs."""
+    network = dict(network or {})
+    stray = sorted(set(network) - set(NETWORK_FLAGS))
+    if stray:
+        raise KeyError("train(network=...): unknown flag(s) %s; the network-size flags are %s" % (", ".join(stray), ", ".join(NETWORK_FLAGS)))
+    return {k: int(v) for k, v in network.items()}
+
+
+def new_rollouts(actor_critic, num_steps, num_processes, obs_spaces, action_space):
+    """The rollout storage of `actor_critic`: its node state is as wide as the policy's GRU (human_node_rnn_size), the edge state 256."""
+    base = actor_critic.base
+    return RolloutStorage(num_steps, num_processes, obs_spaces, action_space, base.human_node_rnn_size, base.human_human_edge_rnn_size)
+
+
 def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_updates=10, seed=425, config=None, ppo_epoch=5,
           num_mini_batch=2, lr=4e-5, eps=1e-5, clip_param=0.2, value_loss_coef=0.5, entropy_coef=0.0, max_grad_norm=0.5, gamma=0.99,
           gae_lambda=0.95, log=print, device=None, save_dir=None, save_interval=0, resume=None, use_self_attn=True, sort_humans=None,
-          pretext_wrapper=None, predictor=None, eval_interval=0, eval_cases=None, base=None):
+          pretext_wrapper=None, predictor=None, eval_interval=0, eval_cases=None, base=None, network=None):
     """Returns a list of per-update dicts (losses, timings, episode stats).  Works single- or multi-GPU (one process per
     GPU, torch.distributed initialised by the caller).  save_dir / save_interval: write checkpoints like train.py:213-219 (every
     `save_interval` updates and after the last one); resume = path of a `NNNNN.pt` written by this function: continue that run
@@ -201,7 +220,10 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
     rec["eval"].  The training run itself -- losses, statistics, checkpoints, weights -- is bit-identical with and without it: the evaluation
     owns its simulator, wrapper and policy handle and draws from no torch RNG stream.  Under torch.distributed rank 0 evaluates.
     base: the network, 'selfAttn_merge_srnn' or 'srnn' (the DS-RNN baseline).  None follows config.robot.policy when it names one of the two, as
-    the reference's train.py:94 does, and is 'selfAttn_merge_srnn' otherwise."""
+    the reference's train.py:94 does, and is 'selfAttn_merge_srnn' otherwise.
+    network: a dict of the reference's network-size flags (NETWORK_FLAGS: human_node_rnn_size, human_node_embedding_size, attention_size,
+    human_node_output_size) for the attention-graph network; sizes outside the device box (_abi.DIMS_BOX) are refused before the first rollout.
+    The rollout runs on the HIP kernels at any sizes in the box; the update's robot-node part runs in torch ops off the default sizes."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     if pretext_wrapper is None:
@@ -220,7 +242,7 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
     if not sort_humans and "visible_masks" not in envs.observation_space.spaces:
         raise ValueError("sort_humans=False needs the `visible_masks` observation, which %s does not provide" % env_name)
     base_kwargs = dict(env_name=env_name, num_processes=num_processes, num_mini_batch=num_mini_batch, seq_length=num_steps, use_self_attn=use_self_attn,
-                       sort_humans=sort_humans)
+                       sort_humans=sort_humans, **network_kwargs(network))
     if base is None:
         base = getattr(getattr(config, "robot", None), "policy", None)
         if base not in ("selfAttn_merge_srnn", "srnn"):
@@ -229,7 +251,10 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
     if torch.distributed.is_available() and torch.distributed.is_initialized():
         # identical weights on every rank (seeded above), but each env shard explores with its own action noise
         torch.cuda.manual_seed(seed + 1000003 * torch.distributed.get_rank())
-    rollouts = RolloutStorage(num_steps, num_processes, envs.observation_space.spaces, envs.action_space, 128, 256)
+    if not actor_critic.is_srnn_baseline:
+        from ._abi import policy_dims
+        policy_dims(actor_critic.base.dims)       # sizes outside the device box: refused here, before anything else is allocated
+    rollouts = new_rollouts(actor_critic, num_steps, num_processes, envs.observation_space.spaces, envs.action_space)
     rollouts.to(device)
     if actor_critic.is_srnn_baseline:
         rollouts.materialize_edge_rnn()

@@ -22,10 +22,16 @@ def main():
     ap.add_argument("--randomized", action="store_true")
     ap.add_argument("--seed", type=int, default=425)
     ap.add_argument("--save", default=None)
+    # the reference's network-size flags (arguments.py:155-181); the device path takes rnn 64/128/192/256, embedding 64/128, output 64..512 in
+    # steps of 64, attention 1..256
+    ap.add_argument("--human_node_rnn_size", type=int, default=128)
+    ap.add_argument("--human_node_embedding_size", type=int, default=64)
+    ap.add_argument("--attention_size", type=int, default=64)
+    ap.add_argument("--human_node_output_size", type=int, default=256)
     a = ap.parse_args()
     import torch
     from crowdnav_prediction_attngraph_amd import config as C
-    from crowdnav_prediction_attngraph_amd.trainer import train
+    from crowdnav_prediction_attngraph_amd.trainer import NETWORK_FLAGS, train
     world = int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     if world > 1:
@@ -33,7 +39,7 @@ def main():
         dist.init_process_group("nccl")
     cfg = (C.Config if a.randomized else C.non_randomized)(**{"sim.human_num": a.humans})
     rank = int(os.environ.get("RANK", "0"))
-    hist, pol = train(a.env_name, a.num_processes, a.num_steps, a.updates, a.seed, config=cfg,
+    hist, pol = train(a.env_name, a.num_processes, a.num_steps, a.updates, a.seed, config=cfg, network={k: getattr(a, k) for k in NETWORK_FLAGS},
                       log=(lambda r: print(json.dumps(r))) if rank == 0 else None)
     if a.save and rank == 0:
         torch.save(pol.state_dict(), a.save)

@@ -338,18 +338,33 @@ typedef struct {
 
 /* H humans, D = spatial edge width, max_envs = largest batch any later call will pass. */
 int cn_policy_create(int human_num, int edge_width, int max_envs, cn_policy **out);
+/* The four network-size flags of the reference (arguments.py:155-181): rnn_size R = human_node_rnn_size (GRU hidden size), embedding_size M =
+ * human_node_embedding_size (encoder_linear, edge_attention_embed; the GRU input is 2M), attention_size A, output_size O =
+ * human_node_output_size (output_linear, both trunks, the heads).  human_human_edge_rnn_size is not a dimension: the reference itself runs
+ * with 256 only.  Device box: R in {64, 128, 192, 256}, M in {64, 128}, O a multiple of 64 in [64, 512], 1 <= A <= 256; anything else is
+ * CN_ERR_INVALID.  The default is {128, 64, 64, 256}.  Under dims the tensors of cn_policy_weights have these shapes (the others keep theirs):
+ *   attn_temporal_w / attn_spatial_w [A,256] (_b [A])     enc_w [M,256] (_b [M])      edge_embed_w [M,256] (_b [M])
+ *   gru_w_ih [3R,2M]   gru_w_hh [3R,R]   gru_b_ih / gru_b_hh [3R]                     out_w [O,R] (_b [O])
+ *   actor0 / actor2 / critic0 / critic2 _w [O,O] (_b [O])   critic_linear_w [1,O]     fc_mean_w [2,O]
+ * and hxs_in / hxs_out are [E,R], the actor_feat tap [E,O] in cn_policy_act / cn_policy_get_value / cn_policy_get_taps.  A never reaches a kernel
+ * as a dimension: it disappears in the fold u = Ws^T (Wt r + bt) and survives as the score scale (float)((double)H / sqrt((double)A)).
+ * dims == NULL or the default tuple: the handle of cn_policy_create -- the same kernels, the same launches, the same bits.  Any other tuple:
+ * gemm mode 2 runs the robot-node half on a kernel with run-time sizes (csrc/rn_sized.hip), modes 0 / 1 the separate launches with their
+ * buffers and leading dimensions taken from dims; the human-human block in front of out_sp [rows,256] does not depend on dims. */
+typedef struct { int rnn_size, embedding_size, attention_size, output_size; } cn_policy_dims;
+int cn_policy_create_sized(int human_num, int edge_width, int max_envs, const cn_policy_dims *dims, cn_policy **out);
 int cn_policy_destroy(cn_policy *p);
 /* Snapshot the weights (copies + pre-folds the affine pairs q/k/v_linear∘in_proj and out_proj∘spatial_linear).
  * Call again after every optimiser step that changed them. */
 int cn_policy_set_weights(cn_policy *p, const cn_policy_weights *w, void *stream);
-/* One rollout-time forward for E envs.  hxs_in/out [E,128] (human_node_rnn), masks [E,1].  eps [E,2] standard-normal
+/* One rollout-time forward for E envs.  hxs_in/out [E,128] (human_node_rnn; [E,R] under cn_policy_dims), masks [E,1].  eps [E,2] standard-normal
  * noise or NULL for the deterministic mode() action.  Outputs value [E,1], action [E,2], logp [E,1]. */
 int cn_policy_act(cn_policy *p, int E, const cn_obs *obs, const float *hxs_in, const float *masks, const float *eps,
                   float *value, float *action, float *logp, float *hxs_out, void *stream);
 int cn_policy_get_value(cn_policy *p, int E, const cn_obs *obs, const float *hxs_in, const float *masks, float *value,
                         void *stream);
 /* Test taps of the last act/get_value call: hh_out [E,H,512] is not materialised by the folded pipeline, so the taps
- * are spatial_lin [E,H,256], hr_attn [E,H], hr_out [E,256], robot_emb [E,256], actor_feat [E,256] (NULL to skip). */
+ * are spatial_lin [E,H,256], hr_attn [E,H], hr_out [E,256], robot_emb [E,256], actor_feat [E,256] ([E,O] under cn_policy_dims) (NULL to skip). */
 int cn_policy_get_taps(cn_policy *p, int E, float *spatial_lin, float *hr_attn, float *hr_out, float *robot_emb,
                        float *actor_feat, void *stream);
 /* Fused mode (cn_policy_set_gemm_mode 2): the robot-node kernel writes the taps above only while they are enabled (default 1);
