@@ -484,12 +484,7 @@ static int launch_hh_attention_bwd(int B, const float *qkv, const int *row_off, 
         const int wpb = CAP == 16 ? 4 : 2, per_cu = 2;                                    // 8 / 4 wavefronts per CU
         int blocks = (B * 8 + wpb - 1) / wpb;
         if (blocks > 256 * per_cu) blocks = 256 * per_cu;
-        static CnLdsOptIn opt_in; // per device
-        int opt_dev;
-        if (opt_in.needed(&opt_dev)) {
-            CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hh_attention_bwd_mfma_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            opt_in.done(opt_dev);
-        }
+        if (int rc = cn_lds_opt_in<&hh_attention_bwd_mfma_kernel<NT>>(160 * 1024)) return rc;
         hipLaunchKernelGGL(hh_attention_bwd_mfma_kernel<NT>, dim3(blocks), dim3(64 * wpb), per_wave * wpb, st, B, qkv, row_off, cls + c, cls + 4 + (size_t)c * B,
                            d_out, d_qkv, scale);
         CN_CHECK_LAUNCH();
@@ -500,14 +495,8 @@ static int launch_hh_attention_bwd(int B, const float *qkv, const int *row_off, 
     int per_cu = (int)((160 * 1024) / (per_wave * wpb)); per_cu = per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu);
     int blocks = (B * 8 + wpb - 1) / wpb;
     if (blocks > 256 * per_cu) blocks = 256 * per_cu; // resident-sized grid walking the class list
-    if (per_wave * wpb > 65536) {
-        static CnLdsOptIn opt_in; // per device
-        int opt_dev;
-        if (opt_in.needed(&opt_dev)) {
-            CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hh_attention_bwd_kernel<CAP>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            opt_in.done(opt_dev);
-        }
-    }
+    if (per_wave * wpb > 65536)
+        if (int rc = cn_lds_opt_in<&hh_attention_bwd_kernel<CAP>>(160 * 1024)) return rc;
     hipLaunchKernelGGL(hh_attention_bwd_kernel<CAP>, dim3(blocks), dim3(64 * wpb), per_wave * wpb, st, B, qkv, row_off, cls + c, cls + 4 + (size_t)c * B,
                        d_out, d_qkv, scale);
     CN_CHECK_LAUNCH();

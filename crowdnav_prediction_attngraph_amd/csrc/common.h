@@ -29,20 +29,20 @@ void cn_set_error(const char *fmt, ...);
         }                                   \
     } while (0)
 
-// The opt-in above 64 KB of dynamic LDS (hipFuncSetAttribute) is per DEVICE: a call site keeps one of these as a function-local static and
-// repeats the opt-in whenever the calling thread's current device is one it has not served yet (a process-wide "done" flag left every
-// device but the first without the attribute: the launch then fails there).  Races between threads only repeat an idempotent call.
-struct CnLdsOptIn {
-    unsigned long long served = 0; // bit d: done on device d
-    bool needed(int *dev_out)
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        *dev_out = dev;
-        return !(served & (1ull << (dev & 63)));
-    }
-    void done(int dev) { served |= 1ull << (dev & 63); }
-};
+// The opt-in above 64 KB of dynamic LDS (hipFuncSetAttribute) is per DEVICE: a launch site calls cn_lds_opt_in<&kernel>(bytes) in front of the
+// launch, and the opt-in is repeated whenever the calling thread's current device is one that kernel has not been served on yet (a process-wide
+// "done" flag left every device but the first without the attribute: the launch then fails there).  Races between threads only repeat an
+// idempotent call.
+template <auto Kernel> int cn_lds_opt_in(int bytes)
+{
+    static unsigned long long served = 0; // bit d: done on device d
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
+    if (served & (1ull << (dev & 63))) return CN_OK;
+    CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    served |= 1ull << (dev & 63);
+    return CN_OK;
+}
 
 int cn_require_device();
 
@@ -93,6 +93,14 @@ template <class T> __device__ __forceinline__ T held_uniform(T v)
     __builtin_memcpy(&v, w, sizeof(T));
     return v;
 }
+
+// tanh(x) = 1 - 2 / (1 + e^{2x}) and the sigmoid on v_exp_f32: absolute error < 3e-7 (e^{2x} overflows to inf -> 1, underflows to 0 -> -1)
+__device__ __forceinline__ float fast_tanh(float x)
+{
+    const float e = __builtin_amdgcn_exp2f(x * 2.88539008177792681472f); // 2 * log2(e)
+    return 1.0f - 2.0f / (1.0f + e);
+}
+__device__ __forceinline__ float fast_sigmoid(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }
 
 __device__ __forceinline__ float wv_readlane(float x, int lane_uniform)
 {

@@ -177,12 +177,7 @@ static int launch_gemm3(int M, int N, int K, const float *A, int lda, const __bf
     if (M == 0) return CN_OK;
     dim3 grid(N / BN, (((M + BM - 1) / BM) + 7) & ~7);
     constexpr size_t lds = (size_t)(2 * BM + 2 * BN) * NT_STRIDE * sizeof(__bf16); // 73.7 KB at 128 x 128: needs the opt-in above 64 KB
-    static CnLdsOptIn opt_in; // per device
-    int opt_dev;
-    if (opt_in.needed(&opt_dev)) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gemm3_nt_kernel<BM, BN, ACT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        opt_in.done(opt_dev);
-    }
+    if (int rc = cn_lds_opt_in<&gemm3_nt_kernel<BM, BN, ACT>>((int)lds)) return rc;
     hipLaunchKernelGGL((gemm3_nt_kernel<BM, BN, ACT>), grid, dim3(256), lds, st, M, N, K, A, lda, Whi, Wlo, bias, C, ldc, m_dev);
     CN_CHECK_LAUNCH();
     return CN_OK;

@@ -357,10 +357,6 @@ struct GstLstmArgs {
     float *acc, *out_traj, *x_sample;
 };
 
-// tanh / sigmoid on v_exp_f32 (|err| < 3e-7; e^{2x} overflowing to inf gives 1, underflowing to 0 gives -1)
-__device__ __forceinline__ float gl_tanh(float x) { return 1.0f - 2.0f / (1.0f + __builtin_amdgcn_exp2f(x * 2.88539008177792681472f)); }
-__device__ __forceinline__ float gl_sigmoid(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }
-
 template <int LS_ROWS>
 __global__ __launch_bounds__(512, 2) void gst_lstm_kernel(int E, int H, int S, GstLstmArgs a)
 {
@@ -471,8 +467,8 @@ __global__ __launch_bounds__(512, 2) void gst_lstm_kernel(int E, int H, int S, G
                 const float *gr = G + nl * LS_SG;
                 const float gi = gr[d], gf = gr[64 + d], gg = gr[128 + d], go = gr[192 + d];
                 const float c0 = creg[k], h0 = X[nl * LS_SX + 64 + d];
-                float cn = gl_sigmoid(gf) * c0 + gl_sigmoid(gi) * gl_tanh(gg);
-                float hn = gl_sigmoid(go) * gl_tanh(cn);
+                float cn = fast_sigmoid(gf) * c0 + fast_sigmoid(gi) * fast_tanh(gg);
+                float hn = fast_sigmoid(go) * fast_tanh(cn);
                 if (a.blend_mask && n < N) { const float bm = a.blend_mask[n]; hn = hn * bm + h0 * (1.0f - bm); cn = cn * bm + c0 * (1.0f - bm); }
                 if (last && a.post_mask && n < N) { const float pm = a.post_mask[n]; hn *= pm; cn *= pm; }
                 creg[k] = cn;
@@ -762,13 +758,7 @@ static int gst_layer(cn_gst *g, int rows, const float *x2, const float *mask, hi
     const int H = g->H;
     int TG = GL_ROWS / H; TG = TG < 1 ? 1 : TG;
     CN_REQUIRE(TG * H <= GL_ROWS, "cn_gst: more than %d humans per group is not supported by the fused encoder layer", GL_ROWS);
-    static thread_local int attr_dev = -1;
-    int dev = 0;
-    CN_HIP(hipGetDevice(&dev));
-    if (dev != attr_dev) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gst_layer_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(GL_LDS_FLOATS * sizeof(float))));
-        attr_dev = dev;
-    }
+    if (int rc = cn_lds_opt_in<&gst_layer_kernel>((int)(GL_LDS_FLOATS * sizeof(float)))) return rc;
     const int n_tiles = (rows + TG * H - 1) / (TG * H);
     GstLayerArgs a{x2, mask, g->emb_w, g->emb_b, g->n_w, g->n_b, g->n1_w, g->n1_b, g->f_in, g->in_b, g->f_out, g->out_b, g->f_l1, g->l1_b, g->f_l2, g->l2_b,
                    xs_out ? xs_out : g->xs, listed ? g->glist : nullptr, listed ? g->gcount : nullptr, listed ? 2 * (rows / (GT * H)) : 0};
@@ -781,14 +771,6 @@ static int gst_layer(cn_gst *g, int rows, const float *x2, const float *mask, hi
 static int gst_lstm(cn_gst *g, int E, int S, const float *in_mask, const float *blend_mask, const float *post_mask, int tt, float *out_traj, hipStream_t st,
                     int zero_state = 0, const float *xs_in = nullptr)
 {
-    static thread_local int attr_dev = -1;
-    int dev = 0;
-    CN_HIP(hipGetDevice(&dev));
-    if (dev != attr_dev) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gst_lstm_kernel<32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ls_lds_floats(32) * sizeof(float))));
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gst_lstm_kernel<80>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ls_lds_floats(80) * sizeof(float))));
-        attr_dev = dev;
-    }
     GstLstmArgs a{xs_in ? xs_in : g->xs, in_mask, g->f_lstm, g->bih, g->bhh, g->h, g->c, blend_mask, post_mask, tt, zero_state, g->h2p_w, g->h2p_b, g->lm_fp, g->last_pos,
                   g->acc, out_traj, g->x_sample};
     // Tile size: a pass over an 80-node tile costs ~2.25x a pass over a 32-node one (measured at 2048 envs x 20 nodes: 2 tiles of 80 per workgroup
@@ -798,8 +780,13 @@ static int gst_lstm(cn_gst *g, int E, int S, const float *in_mask, const float *
     const int t32 = (N + 31) / 32, t80 = (N + 79) / 80;
     const double c32 = (double)((t32 + wgs - 1) / wgs), c80 = 2.25 * (double)((t80 + wgs - 1) / wgs);
     const bool big = c80 < c32;
-    if (big) hipLaunchKernelGGL(gst_lstm_kernel<80>, dim3(t80 < wgs ? t80 : wgs), dim3(512), ls_lds_floats(80) * sizeof(float), st, E, g->H, S, a);
-    else hipLaunchKernelGGL(gst_lstm_kernel<32>, dim3(t32 < wgs ? t32 : wgs), dim3(512), ls_lds_floats(32) * sizeof(float), st, E, g->H, S, a);
+    if (!big) {
+        if (int rc = cn_lds_opt_in<&gst_lstm_kernel<32>>((int)(ls_lds_floats(32) * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(gst_lstm_kernel<32>, dim3(t32 < wgs ? t32 : wgs), dim3(512), ls_lds_floats(32) * sizeof(float), st, E, g->H, S, a);
+    } else {
+        if (int rc = cn_lds_opt_in<&gst_lstm_kernel<80>>((int)(ls_lds_floats(80) * sizeof(float)))) return rc;
+        hipLaunchKernelGGL(gst_lstm_kernel<80>, dim3(t80 < wgs ? t80 : wgs), dim3(512), ls_lds_floats(80) * sizeof(float), st, E, g->H, S, a);
+    }
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

@@ -369,14 +369,9 @@ extern "C" int cn_gst_eval_step(int B, int N, int S, const float *v_obs, const f
     }
     const int S1 = S > 0 ? S : 1;
     const size_t lds = (size_t)eval_lds_floats(N) * sizeof(float);
-    static CnLdsOptIn opt_in; // per device
-    int opt_dev;
-    if (opt_in.needed(&opt_dev)) {
-        const int max_lds = eval_lds_floats(MAXN) * (int)sizeof(float);
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gst_eval_encode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&gst_eval_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        opt_in.done(opt_dev);
-    }
+    const int max_lds = eval_lds_floats(MAXN) * (int)sizeof(float);
+    if (int rc = cn_lds_opt_in<&gst_eval_encode_kernel>(max_lds)) return rc;
+    if (int rc = cn_lds_opt_in<&gst_eval_decode_kernel>(max_lds)) return rc;
     hipStream_t st = (hipStream_t)stream;
     float *state = (float *)workspace;
     hipLaunchKernelGGL(gst_eval_encode_kernel, dim3(B), dim3(NT), lds, st, N, v_obs, loss_mask_rel, W, state);

@@ -1608,30 +1608,25 @@ int hh_fused_forward(int E, int H, int D, const float *spatial_edges, const floa
                      const HhFusedWeights &w, float *out_sp, hipStream_t st, const int32_t *row_plan)
 {
     unsigned long long *stamp = cn_stamp_slot(CN_K_HH_FUSED);
-    static thread_local int attr_dev = -1; // the opt-in above 64 KB of dynamic LDS is per device
-    int dev = 0;
-    CN_HIP(hipGetDevice(&dev));
-    if (dev != attr_dev) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hh_fused_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, team::LDS_BYTES));
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hh_fused_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, team::LDS_BYTES));
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&hh_fused_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, wide::LDS_BYTES));
-        attr_dev = dev;
-    }
     // one workgroup per CU (the LDS footprint admits exactly one); small batches get fewer so that a chunk is >= one row block
     const int grid = rp_workgroups(E, H);
     // an env must fit one tile: the two-team kernel holds 63 rows, the wide one 64
     // (round 6: crowds of 49..63 humans also go through the two-team kernel -- an env of <= 63 rows fits its 4-row-block layout; measured at 50
     // randomised humans x 8192 envs: 1.39 -> 1.14 ms beside the simulator's side-stream kernels.)
     const bool train = w.e0_out != nullptr;
-    if (train) {
-        CN_REQUIRE(H <= 48 && w.x_out && w.qkv_out && w.attn_out, "hh_fused_forward: the training outputs need H <= 48 and all four buffers");
-        hipLaunchKernelGGL(hh_fused_kernel<true>, dim3(grid), dim3(512), team::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp,
-                           (const int32_t *)nullptr, stamp);
-    } else if (H > team::FR)
-        hipLaunchKernelGGL(hh_fused_wide_kernel, dim3(grid), dim3(256), wide::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp, stamp);
-    else
+    if (!train && H <= team::FR) {
+        if (int rc = cn_lds_opt_in<&hh_fused_kernel<false>>(team::LDS_BYTES)) return rc;
         hipLaunchKernelGGL(hh_fused_kernel<false>, dim3(grid), dim3(512), team::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp,
                            row_plan, stamp);
+    } else if (train) {
+        CN_REQUIRE(H <= 48 && w.x_out && w.qkv_out && w.attn_out, "hh_fused_forward: the training outputs need H <= 48 and all four buffers");
+        if (int rc = cn_lds_opt_in<&hh_fused_kernel<true>>(team::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(hh_fused_kernel<true>, dim3(grid), dim3(512), team::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp,
+                           (const int32_t *)nullptr, stamp);
+    } else {
+        if (int rc = cn_lds_opt_in<&hh_fused_wide_kernel>(wide::LDS_BYTES)) return rc;
+        hipLaunchKernelGGL(hh_fused_wide_kernel, dim3(grid), dim3(256), wide::LDS_BYTES, st, E, H, D, spatial_edges, det, row_off, live_total, w, out_sp, stamp);
+    }
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

@@ -15,6 +15,8 @@
 //   gemm3.h           bf16x3 split-precision NT GEMM of the big layers in gemm mode 1 (arithmetic: split_bf16.h) and the weight split
 //   hh_fused.h, rn_fused.h   interfaces of the two fused kernels of gemm mode 2 (hh_fused.hip, rn_fused.hip: objects of their own)
 //   rn_sized.h        interface of the robot-node kernel with run-time network sizes (rn_sized.hip): gemm mode 2 of a cn_policy_create_sized handle
+//   rn_chain.h        the robot-node chain's arithmetic, stated once for rn_fused.hip and rn_sized.hip; here (through policy_kernels.h and
+//                     rn_train.h) for the DiagGaussian sample / log-prob of gauss_head_kernel and rn_head_fwd_kernel
 //   policy.hip        part 1, rollout: cn_policy, cn_policy_set_weights (copies, folds, splits, fragment images), policy_forward, taps, profiling
 //                     part 2, training: cn_hh_block_fwd, cn_obs_compact_visible, cn_hh_attention_*, cn_hr_attention_*, cn_rn_seq_* and the
 //                     rn_seq_*_impl / rn_seq_prep_jobs that train_internal.h declares.  Its big products go to linear.hip (cn_linear_*).

@@ -2,7 +2,7 @@
 // scatter_rows_kernel), the two narrow input layers (embed0_kernel, robot_embed_kernel), the GRU cell's pointwise part, the
 // critic / DiagGaussian head and the weight folds of cn_policy_set_weights.  Part of policy.hip's translation unit.
 #pragma once
-#include "common.h"
+#include "rn_chain.h"
 
 namespace {
 
@@ -165,15 +165,11 @@ __global__ __launch_bounds__(256) void gauss_head_kernel(int E, int O, const flo
     if (lane == 0) {
         value[e] = sv + bv[0];
         if (action) {
-            const float mean0 = s0 + bm[0], mean1 = s1 + bm[1];
-            const float ls0 = logstd[0], ls1 = logstd[1];
-            const float sd0 = expf(ls0), sd1 = expf(ls1);
-            const float a0 = eps ? mean0 + sd0 * eps[2 * e] : mean0;
-            const float a1 = eps ? mean1 + sd1 * eps[2 * e + 1] : mean1;
+            float a0, a1;
+            const float lp = rn_gauss_sample(s0 + bm[0], s1 + bm[1], logstd[0], logstd[1], eps != nullptr, eps ? eps[2 * e] : 0.0f, eps ? eps[2 * e + 1] : 0.0f,
+                                             a0, a1);
             action[2 * e] = a0; action[2 * e + 1] = a1;
-            const float HALF_LOG_2PI = 0.91893853320467274178f;
-            const float d0 = a0 - mean0, d1 = a1 - mean1;
-            logp[e] = (-(d0 * d0) / (2.0f * sd0 * sd0) - ls0 - HALF_LOG_2PI) + (-(d1 * d1) / (2.0f * sd1 * sd1) - ls1 - HALF_LOG_2PI);
+            logp[e] = lp;
         }
     }
 }

@@ -18,13 +18,10 @@
 // every small operand (observation, hidden state, masks, noise, biases, head weights) into registers and a 12 KB LDS table; behind it a
 // wavefront waits for weight fragments and out_sp rows only, and no stage call is longer than 8 k-steps (32 in sequence on the longest path:
 // te 8, edge 8, W_ih 4, ac0 4, a2 / c2 8).  Two instantiations: with the four test taps and without.
-#include "rn_fused.h"
+#include "rn_chain.h"
 #include "row_plan.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TE = 16;     // envs per workgroup
 // LDS activation images [16 envs][stride] floats; strides are K + 4 so that the 16 lanes of a float4 read hit distinct banks
@@ -40,23 +37,10 @@ constexpr int O_T = O_R5 + TE * S128;
 constexpr int T_TEB = 0, T_EDGEB = T_TEB + 320, T_BIH = T_EDGEB + 64, T_BHH = T_BIH + 384, T_AC0B = T_BHH + 384, T_A2B = T_AC0B + 512;
 constexpr int T_C2B = T_A2B + 256, T_CLW = T_C2B + 256, T_FMW = T_CLW + 256;
 constexpr int T_VEC4 = (T_FMW + 512) / 4;   // 736 float4
-constexpr int T_SM = T_FMW + 512;           // 64 words: masks (16) | eps (32) | cl_b | fm_b (2) | logstd (2)
-constexpr int SM_MASK = 0, SM_EPS = 16, SM_CLB = 48, SM_FMB = 49, SM_LS = 51, SM_WORDS = 53;
-constexpr int T_FLOATS = T_SM + 64;         // 3008 floats, 12 032 B
+constexpr int T_SM = T_FMW + 512;           // the small words (rn_chain.h)
+constexpr int T_FLOATS = T_SM + SM_WORDS;   // 3008 floats, 12 032 B
 constexpr int LDS_FLOATS = O_T + T_FLOATS;  // 144 640 B of the 160 KB: one workgroup per CU, as before
 static_assert(LDS_FLOATS * sizeof(float) <= 160 * 1024, "rn_fused: LDS");
-
-__device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-enum { A_NONE = 0, A_RELU = 1, A_TANH = 2 };
-
-// tanh(x) = 1 - 2 / (1 + e^{2x}) on v_exp_f32: absolute error < 3e-7 (e^{2x} overflows to inf -> 1, underflows to 0 -> -1)
-__device__ __forceinline__ float fast_tanh(float x)
-{
-    const float e = __builtin_amdgcn_exp2f(x * 2.88539008177792681472f); // 2 * log2(e)
-    return 1.0f - 2.0f / (1.0f + e);
-}
-__device__ __forceinline__ float fast_sigmoid(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }
 
 // out[env][out_off + 16*fb + ..] = act(W[fb] . in[env][in_off ..] + bias) for the feature blocks fb = fb_first, fb_first + fb_step, ...
 // Wfrag: baked fragments [fb][K/32][plane hi,lo][64 lanes][8 bf16]; NFB = feature blocks of this wavefront; bias: the LDS copy (table, below),
@@ -71,16 +55,7 @@ __device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_f
     // activations of env i, k = 32 ks + 8 g .. + 7, as bf16 hi / lo (the B operand of every feature block of this stage), split per k-step
     // inside the loop rather than up front (64 registers less at K = 256)
     bf16x8 bh, bl;
-    auto split = [&](int ks, bf16x8 &h, bf16x8 &l) {
-        const f32x4 x0 = *reinterpret_cast<const f32x4 *>(in + i * in_stride + 32 * ks + 8 * g);
-        const f32x4 x1 = *reinterpret_cast<const f32x4 *>(in + i * in_stride + 32 * ks + 8 * g + 4);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const __bf16 h0 = (__bf16)x0[u], h1 = (__bf16)x1[u];
-            h[u] = h0; h[4 + u] = h1;
-            l[u] = (__bf16)(x0[u] - (float)h0); l[4 + u] = (__bf16)(x1[u] - (float)h1);
-        }
-    };
+    const float *xrow = in + i * in_stride + 8 * g;
     f32x4 acc[NFB];
 #pragma unroll
     for (int j = 0; j < NFB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -102,7 +77,7 @@ __device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_f
             const size_t base = ((size_t)(fb_first + j * fb_step) * KS + kp) * 128 + lane;
             ah[(ks + PF - 1) % PF][j] = Wfrag[base]; al[(ks + PF - 1) % PF][j] = Wfrag[base + 64];
         }
-        split(ks, bh, bl);
+        rn_split(xrow, ks, bh, bl);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int j = 0; j < NFB; ++j) {
@@ -113,17 +88,8 @@ __device__ __forceinline__ void stage(const float *__restrict__ Wfrag_, int fb_f
         __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (int j = 0; j < NFB; ++j) {
-        const int f0 = (fb_first + j * fb_step) * 16 + 4 * g;
-        f32x4 v = acc[j];
-        if (BIAS) v += *reinterpret_cast<const f32x4 *>(bias + f0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (ACT == A_RELU) { if (f0 + q >= relu_from) v[q] = fmaxf(v[q], 0.0f); }
-            if (ACT == A_TANH) v[q] = fast_tanh(v[q]);
-        }
-        *reinterpret_cast<f32x4 *>(out + i * out_stride + out_off + f0) = v;
-    }
+    for (int j = 0; j < NFB; ++j)
+        rn_epilogue<ACT, BIAS>(acc[j], (fb_first + j * fb_step) * 16 + 4 * g, bias, relu_from, out + i * out_stride + out_off);
 }
 
 // The chain runs in 128 registers per lane (activations split per k-step, two k-steps of weight fragments in flight, at most four feature blocks
@@ -204,7 +170,7 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
     {
         const float *const p_masks = a.masks, *const p_eps = a.eps, *const p_clb = a.cl_b, *const p_fmb = a.fm_b, *const p_ls = a.logstd;
         const bool has_eps = p_eps != nullptr;
-        const int sl = lane < SM_WORDS ? lane : SM_WORDS - 1;
+        const int sl = lane < SM_USED ? lane : SM_USED - 1;
         const int i = sl < SM_EPS ? sl : (sl - SM_EPS) >> 1;
         const int e = e0 + i < E ? e0 + i : E - 1;
         const bool is_eps = sl >= SM_EPS && has_eps;
@@ -261,80 +227,8 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
         stage<128, 4, A_NONE, false>(a.f_whh, wave - 5 + 12, 3, nullptr, R4, S128, R2, S384, 0, 0, lane);
     }
     __syncthreads();
-    // ---- robot-human attention (u-form, see hr_attention_kernel in attention.h): wavefront w owns envs 2w, 2w+1 ----
-    // out_sp was written a moment ago by the human-human kernel on (mostly) other XCDs: every row read is a trip to the fabric.  A
-    // row-by-row loop is a chain of such trips (two passes x nd rows x 2 envs: ~25 of them, the largest single item of this kernel),
-    // so the first 8 rows of BOTH envs are fetched up front into registers; envs with more rows walk the rest in chunks of 8.
-    {
-        constexpr int CH = 8;
-        int ndq[2];
-        float x[2][CH][4];
-#pragma unroll
-        for (int q = 0; q < 2; ++q) ndq[q] = r1q[q] - r0q[q];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const float *row = a.out_sp + (size_t)(r0q[q] + (u < ndq[q] ? u : ndq[q] - 1)) * 256;
-                x[q][u][0] = row[lane]; x[q][u][1] = row[64 + lane]; x[q][u][2] = row[128 + lane]; x[q][u][3] = row[192 + lane];
-            }
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int i = 2 * wave + q;
-            const int r0 = r0q[q], nd = ndq[q];
-            const float *ue = R1 + i * S512;
-            const float u0 = ue[lane], u1 = ue[64 + lane], u2 = ue[128 + lane], u3 = ue[192 + lane];
-            float s = -INFINITY;
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const float tot = wv_sum(u0 * x[q][u][0] + u1 * x[q][u][1] + u2 * x[q][u][2] + u3 * x[q][u][3]);
-                if (lane == u && u < nd) s = tot * ((float)H / 8.0f);
-            }
-            for (int j0 = CH; j0 < nd; j0 += CH) {
-                float y[CH][4];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const float *row = a.out_sp + (size_t)(r0 + (j0 + u < nd ? j0 + u : nd - 1)) * 256;
-                    y[u][0] = row[lane]; y[u][1] = row[64 + lane]; y[u][2] = row[128 + lane]; y[u][3] = row[192 + lane];
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const float tot = wv_sum(u0 * y[u][0] + u1 * y[u][1] + u2 * y[u][2] + u3 * y[u][3]);
-                    if (lane == j0 + u && j0 + u < nd) s = tot * ((float)H / 8.0f);
-                }
-            }
-            const float mx = wv_max(s);
-            const float p = lane < nd ? expf(s - mx) : 0.0f;
-            const float denom = wv_sum(p);
-            const float at = p / denom;
-            float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
-#pragma unroll
-            for (int u = 0; u < CH; ++u) {
-                const float aj = u < nd ? wv_readlane(at, u) : 0.0f;
-                if (u < nd) { o0 += aj * x[q][u][0]; o1 += aj * x[q][u][1]; o2 += aj * x[q][u][2]; o3 += aj * x[q][u][3]; }
-            }
-            for (int j0 = CH; j0 < nd; j0 += CH) {
-                float y[CH][4];
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const float *row = a.out_sp + (size_t)(r0 + (j0 + u < nd ? j0 + u : nd - 1)) * 256;
-                    y[u][0] = row[lane]; y[u][1] = row[64 + lane]; y[u][2] = row[128 + lane]; y[u][3] = row[192 + lane];
-                }
-#pragma unroll
-                for (int u = 0; u < CH; ++u) {
-                    const float aj = wv_readlane(at, j0 + u < nd ? j0 + u : 0);
-                    if (j0 + u < nd) { o0 += aj * y[u][0]; o1 += aj * y[u][1]; o2 += aj * y[u][2]; o3 += aj * y[u][3]; }
-                }
-            }
-            float *o = R0 + i * S512; // robot_states are dead: hr takes their place
-            o[lane] = o0; o[64 + lane] = o1; o[128 + lane] = o2; o[192 + lane] = o3;
-            if (TAPS && e0 + i < E) { // (behind the env's last out_sp row, not between the two passes)
-                if (lane < H) a.tap_attn[(size_t)(e0 + i) * H + lane] = at;
-                float *t = a.tap_hr + (size_t)(e0 + i) * 256;
-                t[lane] = o0; t[64 + lane] = o1; t[128 + lane] = o2; t[192 + lane] = o3;
-            }
-        }
-    }
+    // ---- robot-human attention (rn_chain.h): wavefront w owns envs 2w, 2w+1 ----
+    rn_hr_attention<2, TAPS, false>(a, r0q, r1q, R1, S512, R0, S512, 2 * wave, e0, E, H, (float)H / 8.0f, lane);
     __syncthreads();
     // ---- edge = relu(edge_attention_embed [64,256] . hr + b) -> z[320:384] ----
     if (hi == 0) stage<256, 1, A_RELU, true>(a.f_edge, w4, 4, T + T_EDGEB, R0, S512, R1, S512, 320, 0, lane);
@@ -346,14 +240,9 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int i = (tid >> 7) + 4 * k, c = tid & 127;
-        const float m = T[T_SM + SM_MASK + i];
         const float *gie = R3 + i * S384, *ghe = R2 + i * S384, *bhh = T + T_BHH;
-        const float hr = m * ghe[c] + bhh[c], hz = m * ghe[128 + c] + bhh[128 + c], hn = m * ghe[256 + c] + bhh[256 + c];
-        const float r = fast_sigmoid(gie[c] + hr);
-        const float z = fast_sigmoid(gie[128 + c] + hz);
-        const float nn = fast_tanh(gie[256 + c] + r * hn);
-        const float h = m * R4[i * S128 + c];
-        const float hnew = (1.0f - z) * nn + z * h;
+        const float hnew = rn_gru_cell(gie[c], gie[128 + c], gie[256 + c], ghe[c], ghe[128 + c], ghe[256 + c], bhh[c], bhh[128 + c], bhh[256 + c],
+                                       T[T_SM + SM_MASK + i], R4[i * S128 + c]);
         R5[i * S128 + c] = hnew;
         if (e0 + i < E) a.hxs_out[(size_t)(e0 + i) * 128 + c] = hnew;
     }
@@ -385,15 +274,12 @@ __global__ __launch_bounds__(512, 4) void rn_fused_kernel(int E, int H, RnFusedA
         if (lane == 0) {
             a.value[e] = sv + sm[SM_CLB];
             if (a.action) {
-                const float mean0 = s0 + sm[SM_FMB], mean1 = s1 + sm[SM_FMB + 1];
-                const float ls0 = sm[SM_LS], ls1 = sm[SM_LS + 1];
-                const float sd0 = expf(ls0), sd1 = expf(ls1);
-                const float a0 = a.eps ? mean0 + sd0 * sm[SM_EPS + 2 * i] : mean0;
-                const float a1 = a.eps ? mean1 + sd1 * sm[SM_EPS + 2 * i + 1] : mean1;
+                float a0, a1;
+                const bool noise = a.eps != nullptr; // (without noise the eps words hold the masks again: not read)
+                const float lp = rn_gauss_sample(s0 + sm[SM_FMB], s1 + sm[SM_FMB + 1], sm[SM_LS], sm[SM_LS + 1], noise, noise ? sm[SM_EPS + 2 * i] : 0.0f,
+                                                 noise ? sm[SM_EPS + 2 * i + 1] : 0.0f, a0, a1);
                 a.action[2 * e] = a0; a.action[2 * e + 1] = a1;
-                const float HALF_LOG_2PI = 0.91893853320467274178f;
-                const float d0 = a0 - mean0, d1 = a1 - mean1;
-                a.logp[e] = (-(d0 * d0) / (2.0f * sd0 * sd0) - ls0 - HALF_LOG_2PI) + (-(d1 * d1) / (2.0f * sd1 * sd1) - ls1 - HALF_LOG_2PI);
+                a.logp[e] = lp;
             }
         }
         if (TAPS) {
@@ -434,13 +320,7 @@ template <bool TAPS>
 static int rn_fused_launch(int E, int H, const RnFusedArgs &a, hipStream_t st)
 {
     constexpr size_t lds = (size_t)LDS_FLOATS * sizeof(float);
-    static thread_local int attr_dev = -1;
-    int dev = 0;
-    CN_HIP(hipGetDevice(&dev));
-    if (dev != attr_dev) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rn_fused_kernel<TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_dev = dev;
-    }
+    if (int rc = cn_lds_opt_in<&rn_fused_kernel<TAPS>>((int)lds)) return rc;
     hipLaunchKernelGGL(rn_fused_kernel<TAPS>, dim3((E + TE - 1) / TE), dim3(512), lds, st, E, H, a);
     CN_CHECK_LAUNCH();
     return CN_OK;
@@ -449,12 +329,8 @@ static int rn_fused_launch(int E, int H, const RnFusedArgs &a, hipStream_t st)
 int rn_fused_forward(int E, int H, const RnFusedArgs &args, hipStream_t st)
 {
     CN_REQUIRE(E >= 1, "rn_fused_forward: E must be positive");
-    const bool taps = args.tap_robot || args.tap_attn || args.tap_hr || args.tap_actor;
-    CN_REQUIRE(!taps || (args.tap_robot && args.tap_attn && args.tap_hr && args.tap_actor), "rn_fused_forward: the four taps come together");
-    // the table's vectors are fetched as float4
-    for (const float *p : {args.te_b, args.edge_b, args.bih, args.bhh, args.ac0_b, args.a2_b, args.c2_b, args.cl_w, args.fm_w})
-        CN_REQUIRE(p && ((uintptr_t)p & 15) == 0, "rn_fused_forward: biases and head weights must be 16-byte aligned");
+    if (int rc = rn_check_args(args, "rn_fused_forward")) return rc;
     RnFusedArgs a = args;
     a.stamp = cn_stamp_slot(CN_K_RN_FUSED);
-    return taps ? rn_fused_launch<true>(E, H, a, st) : rn_fused_launch<false>(E, H, a, st);
+    return args.tap_robot ? rn_fused_launch<true>(E, H, a, st) : rn_fused_launch<false>(E, H, a, st);
 }

@@ -3,7 +3,7 @@
 // rn_fused.hip's:
 //   robot_linear -> [u = Ws^T temporal_edge_layer(.) | encoder_linear] -> robot-human attention over out_sp -> edge_attention_embed ->
 //   GRU cell (with the done mask) -> actor / critic trunks (output_linear folded in) -> critic_linear + DiagGaussian head
-// and so is the arithmetic: products as bf16x3 splits on v_mfma_f32_16x16x32_bf16 from rn_fused_bake's fragment images ("transposed": A operand =
+// and so is the arithmetic (rn_chain.h holds what the two kernels share): products as bf16x3 splits on v_mfma_f32_16x16x32_bf16 from rn_fused_bake's fragment images ("transposed": A operand =
 // weight fragment, B operand = the envs' activations from LDS, the C layout is a float4 of four consecutive features of one env), small operands
 // in exact fp32, rn_fused's exp2-based tanh / sigmoid.  What the run-time sizes change:
 //   * the LDS images are laid out from (R, M, O) (RnLayout below), and a workgroup owns 16 envs only where sixteen images fit -- else 8, the MFMA's
@@ -14,11 +14,9 @@
 //     (the next k-step's fragments are in flight behind the current one's MFMAs; a run-time index would send the buffers to scratch).
 // The default sizes never come here: they keep rn_fused_kernel, whose fixed shapes buy the one-batch operand fetch and the hand-dealt stages.
 #include "rn_sized.h"
+#include "rn_chain.h"
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // ---- LDS ----
 // Per env, in floats (each image row is K + 4 floats, so that the 16 lanes of a float4 read hit distinct banks):
@@ -32,7 +30,6 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 // rn_fused_kernel's own figure).  Largest corner (256, 128, 512): 1028 + 1028 + 772 + 772 + 260 + 260 = 4120 per env; 16 envs would be 286 464 B, 8 envs
 // are 32 960 + 5696 floats = 154 624 B: 8 envs.
 constexpr int LDS_LIMIT_BYTES = 160 * 1024;
-constexpr int SM_MASK = 0, SM_EPS = 16, SM_CLB = 48, SM_FMB = 49, SM_LS = 51, SM_WORDS = 64;
 
 struct RnLayout {
     int S0, S1, S2, S4;                          // row strides of R0, R1, R2 / R3, R4 / R5
@@ -53,18 +50,6 @@ __host__ __device__ inline RnLayout rn_layout(int R, int M, int O, int te)
     return L;
 }
 
-__device__ __forceinline__ f32x4 mfma32(bf16x8 a, bf16x8 b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
-
-enum { A_NONE = 0, A_RELU = 1, A_TANH = 2 };
-
-// rn_fused.hip's: tanh(x) = 1 - 2 / (1 + e^{2x}) on v_exp_f32, absolute error < 3e-7
-__device__ __forceinline__ float fast_tanh(float x)
-{
-    const float e = __builtin_amdgcn_exp2f(x * 2.88539008177792681472f); // 2 * log2(e)
-    return 1.0f - 2.0f / (1.0f + e);
-}
-__device__ __forceinline__ float fast_sigmoid(float x) { return 1.0f / (1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); }
-
 // NB feature blocks fb0, fb0 + fb_step, ... of one product: acc = W[fb] . x over KS k-steps (KS even), then bias / activation / store.
 // W: baked fragments [fb][KS][plane hi,lo][64 lanes][8 bf16]; xrow: this lane's env row + 8 * (lane >> 4); orow: this lane's output row + out_off,
 // or nullptr for the lanes whose env column is a repeat (8 envs per workgroup)
@@ -77,16 +62,6 @@ __device__ __forceinline__ void stage_group(const bf16x8 *__restrict__ W, int fb
 #pragma unroll
     for (int j = 0; j < NB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     bf16x8 a0h[NB], a0l[NB], a1h[NB], a1l[NB];
-    auto split = [&](int ks, bf16x8 &h, bf16x8 &l) {
-        const f32x4 x0 = *reinterpret_cast<const f32x4 *>(xrow + 32 * ks);
-        const f32x4 x1 = *reinterpret_cast<const f32x4 *>(xrow + 32 * ks + 4);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const __bf16 h0 = (__bf16)x0[u], h1 = (__bf16)x1[u];
-            h[u] = h0; h[4 + u] = h1;
-            l[u] = (__bf16)(x0[u] - (float)h0); l[4 + u] = (__bf16)(x1[u] - (float)h1);
-        }
-    };
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
         const int base = ((fb0 + j * fb_step) * KS) * 128 + lane;
@@ -99,7 +74,7 @@ __device__ __forceinline__ void stage_group(const bf16x8 *__restrict__ W, int fb
             const int base = ((fb0 + j * fb_step) * KS + ks + 1) * 128 + lane;
             a1h[j] = W[base]; a1l[j] = W[base + 64];
         }
-        split(ks, bh, bl);
+        rn_split(xrow, ks, bh, bl);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             acc[j] = mfma32(a0l[j], bh, acc[j]);
@@ -112,7 +87,7 @@ __device__ __forceinline__ void stage_group(const bf16x8 *__restrict__ W, int fb
             const int base = ((fb0 + j * fb_step) * KS + kn) * 128 + lane;
             a0h[j] = W[base]; a0l[j] = W[base + 64];
         }
-        split(ks + 1, bh, bl);
+        rn_split(xrow, ks + 1, bh, bl);
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
             acc[j] = mfma32(a1l[j], bh, acc[j]);
@@ -121,17 +96,7 @@ __device__ __forceinline__ void stage_group(const bf16x8 *__restrict__ W, int fb
         }
     }
 #pragma unroll
-    for (int j = 0; j < NB; ++j) {
-        const int f0 = (fb0 + j * fb_step) * 16 + 4 * g;
-        f32x4 v = acc[j];
-        if (BIAS) v += *reinterpret_cast<const f32x4 *>(bias + f0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            if (ACT == A_RELU) { if (f0 + q >= relu_from) v[q] = fmaxf(v[q], 0.0f); }
-            if (ACT == A_TANH) v[q] = fast_tanh(v[q]);
-        }
-        if (orow) *reinterpret_cast<f32x4 *>(orow + f0) = v;
-    }
+    for (int j = 0; j < NB; ++j) rn_epilogue<ACT, BIAS>(acc[j], (fb0 + j * fb_step) * 16 + 4 * g, bias, relu_from, orow);
 }
 
 // out[env][out_off + f] = act(W . in[env] + bias) for all nfb feature blocks of 16: wavefront w takes the blocks (w + rot) % 8, + 8, + 16, ...
@@ -152,17 +117,18 @@ __device__ __forceinline__ void stage(const float *__restrict__ Wfrag, int nfb, 
     else if (fb < nfb) stage_group<1, ACT, BIAS>(W, fb, 8, KS, bias, xrow, orow, relu_from, lane);
 }
 
-// eight out_sp rows j0 .. j0 + 7 of one env, this lane's four columns (rows past nd repeat the last one: loaded, never used)
-struct HrRows { float v[8][4]; };
-__device__ __forceinline__ void hr_load8(HrRows &r, const float *__restrict__ out_sp, int r0, int j0, int nd, int lane)
+// the robot-human attention of this wavefront's PER envs: their row offsets (the tail workgroup repeats env E - 1), then the shared block
+template <int PER, bool TAPS>
+__device__ __forceinline__ void hr_attention(const RnFusedArgs &a, const float *R1, int S1, float *R0, int S0, int wave, int e0, int E, int H, float scale,
+                                             int lane)
 {
+    int r0q[PER], r1q[PER];
 #pragma unroll
-    for (int q = 0; q < 8; ++q) {
-        const int j = j0 + q < nd ? j0 + q : nd - 1;
-        const float *row = out_sp + (size_t)(r0 + j) * 256 + lane;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) r.v[q][c] = row[64 * c];
+    for (int q = 0; q < PER; ++q) {
+        const int e = e0 + PER * wave + q < E ? e0 + PER * wave + q : E - 1;
+        r0q[q] = __builtin_amdgcn_readfirstlane(a.row_off[e]); r1q[q] = __builtin_amdgcn_readfirstlane(a.row_off[e + 1]);
     }
+    rn_hr_attention<PER, TAPS, true>(a, r0q, r1q, R1, S1, R0, S0, PER * wave, e0, E, H, scale, lane);
 }
 
 // No register target: the LDS leaves one workgroup per CU, so its eight wavefronts may take 256 registers each.  The compiler's figures per
@@ -230,63 +196,9 @@ __global__ __launch_bounds__(512) void rn_sized_kernel(int E, int H, RnFusedArgs
     stage<A_RELU, true>(a.f_te, (256 + M) >> 4, 256, T + L.tTEB, R0, L.S0, R1, L.S1, 0, 256, te, wave, 0, lane);
     stage<A_NONE, false>(a.f_whh, (3 * R) >> 4, R, nullptr, R4, L.S4, R2, L.S2, 0, 0, te, wave, ((256 + M) >> 4) & 7, lane);
     __syncthreads();
-    // ---- robot-human attention (u-form, hr_attention_kernel in attention.h): wavefront w owns te / 8 envs ----
-    {
-        const int per = te >> 3;
-        for (int q = 0; q < per; ++q) {
-            const int i = per * wave + q, e = e0 + i < E ? e0 + i : E - 1;
-            const int r0 = __builtin_amdgcn_readfirstlane(a.row_off[e]), nd = __builtin_amdgcn_readfirstlane(a.row_off[e + 1]) - r0;
-            const float *ue = R1 + i * L.S1;
-            const float u0 = ue[lane], u1 = ue[64 + lane], u2 = ue[128 + lane], u3 = ue[192 + lane];
-            float s = -INFINITY; // lane j holds the score of human j
-            HrRows k0;
-            hr_load8(k0, a.out_sp, r0, 0, nd, lane);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (u < nd) {
-                    const float tot = wv_sum(u0 * k0.v[u][0] + u1 * k0.v[u][1] + u2 * k0.v[u][2] + u3 * k0.v[u][3]);
-                    if (lane == u) s = tot * d.scale;
-                }
-            for (int j0 = 8; j0 < nd; j0 += 8) {
-                HrRows r;
-                hr_load8(r, a.out_sp, r0, j0, nd, lane);
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (j0 + u < nd) {
-                        const float tot = wv_sum(u0 * r.v[u][0] + u1 * r.v[u][1] + u2 * r.v[u][2] + u3 * r.v[u][3]);
-                        if (lane == j0 + u) s = tot * d.scale;
-                    }
-            }
-            const float mx = wv_max(s);
-            const float p = lane < nd ? expf(s - mx) : 0.0f;
-            const float denom = wv_sum(p);
-            const float at = p / denom;
-            float o0 = 0.f, o1 = 0.f, o2 = 0.f, o3 = 0.f;
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (u < nd) {
-                    const float aj = wv_readlane(at, u);
-                    o0 += aj * k0.v[u][0]; o1 += aj * k0.v[u][1]; o2 += aj * k0.v[u][2]; o3 += aj * k0.v[u][3];
-                }
-            for (int j0 = 8; j0 < nd; j0 += 8) {
-                HrRows r;
-                hr_load8(r, a.out_sp, r0, j0, nd, lane);
-#pragma unroll
-                for (int u = 0; u < 8; ++u)
-                    if (j0 + u < nd) {
-                        const float aj = wv_readlane(at, j0 + u);
-                        o0 += aj * r.v[u][0]; o1 += aj * r.v[u][1]; o2 += aj * r.v[u][2]; o3 += aj * r.v[u][3];
-                    }
-            }
-            float *o = R0 + i * L.S0; // robot_states are dead: hr takes their place
-            o[lane] = o0; o[64 + lane] = o1; o[128 + lane] = o2; o[192 + lane] = o3;
-            if (TAPS && e0 + i < E) {
-                if (lane < H) a.tap_attn[(size_t)(e0 + i) * H + lane] = at;
-                float *t = a.tap_hr + (size_t)(e0 + i) * 256;
-                t[lane] = o0; t[64 + lane] = o1; t[128 + lane] = o2; t[192 + lane] = o3;
-            }
-        }
-    }
+    // ---- robot-human attention (rn_chain.h): wavefront w owns te / 8 envs ----
+    if (te == 16) hr_attention<2, TAPS>(a, R1, L.S1, R0, L.S0, wave, e0, E, H, d.scale, lane);
+    else hr_attention<1, TAPS>(a, R1, L.S1, R0, L.S0, wave, e0, E, H, d.scale, lane);
     __syncthreads();
     // ---- edge = relu(edge_attention_embed [M,256] . hr + b) -> z[256 + M : 256 + 2M] ----
     stage<A_RELU, true>(a.f_edge, M >> 4, 256, T + L.tEDGEB, R0, L.S0, R1, L.S1, 256 + M, 0, te, wave, 0, lane);
@@ -297,14 +209,9 @@ __global__ __launch_bounds__(512) void rn_sized_kernel(int E, int H, RnFusedArgs
     // ---- GRU cell, pointwise part (gate order r,z,n; h and gh masked by the done mask: srnn_model.py:43-46) ----
     for (int idx = tid; idx < te * R; idx += 512) {
         const int i = idx / R, c = idx - i * R;
-        const float m = T[L.tSM + SM_MASK + i];
         const float *gie = R3 + i * L.S2, *ghe = R2 + i * L.S2, *bhh = T + L.tBHH;
-        const float hr = m * ghe[c] + bhh[c], hz = m * ghe[R + c] + bhh[R + c], hn = m * ghe[2 * R + c] + bhh[2 * R + c];
-        const float r = fast_sigmoid(gie[c] + hr);
-        const float z = fast_sigmoid(gie[R + c] + hz);
-        const float nn = fast_tanh(gie[2 * R + c] + r * hn);
-        const float h = m * R4[i * L.S4 + c];
-        const float hnew = (1.0f - z) * nn + z * h;
+        const float hnew = rn_gru_cell(gie[c], gie[R + c], gie[2 * R + c], ghe[c], ghe[R + c], ghe[2 * R + c], bhh[c], bhh[R + c], bhh[2 * R + c],
+                                       T[L.tSM + SM_MASK + i], R4[i * L.S4 + c]);
         R5[i * L.S4 + c] = hnew;
         if (e0 + i < E) a.hxs_out[(size_t)(e0 + i) * R + c] = hnew;
     }
@@ -333,15 +240,11 @@ __global__ __launch_bounds__(512) void rn_sized_kernel(int E, int H, RnFusedArgs
             if (lane == 0) {
                 a.value[e] = sv + sm[SM_CLB];
                 if (a.action) {
-                    const float mean0 = s0 + sm[SM_FMB], mean1 = s1 + sm[SM_FMB + 1];
-                    const float ls0 = sm[SM_LS], ls1 = sm[SM_LS + 1];
-                    const float sd0 = expf(ls0), sd1 = expf(ls1);
-                    const float a0 = a.eps ? mean0 + sd0 * sm[SM_EPS + 2 * i] : mean0;
-                    const float a1 = a.eps ? mean1 + sd1 * sm[SM_EPS + 2 * i + 1] : mean1;
+                    float a0, a1; // (the eps words are zero without noise)
+                    const float lp = rn_gauss_sample(s0 + sm[SM_FMB], s1 + sm[SM_FMB + 1], sm[SM_LS], sm[SM_LS + 1], a.eps != nullptr, sm[SM_EPS + 2 * i],
+                                                     sm[SM_EPS + 2 * i + 1], a0, a1);
                     a.action[2 * e] = a0; a.action[2 * e + 1] = a1;
-                    const float HALF_LOG_2PI = 0.91893853320467274178f;
-                    const float d0 = a0 - mean0, d1 = a1 - mean1;
-                    a.logp[e] = (-(d0 * d0) / (2.0f * sd0 * sd0) - ls0 - HALF_LOG_2PI) + (-(d1 * d1) / (2.0f * sd1 * sd1) - ls1 - HALF_LOG_2PI);
+                    a.logp[e] = lp;
                 }
             }
             if (TAPS)
@@ -365,12 +268,7 @@ size_t rn_sized_lds_bytes(int R, int M, int O, int te) { return (size_t)rn_layou
 template <bool TAPS>
 static int rn_sized_launch(int E, int H, const RnFusedArgs &a, const RnSizedDims &d, size_t lds, hipStream_t st)
 {
-    static CnLdsOptIn opt_in; // per device
-    int dev;
-    if (opt_in.needed(&dev)) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&rn_sized_kernel<TAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT_BYTES));
-        opt_in.done(dev);
-    }
+    if (int rc = cn_lds_opt_in<&rn_sized_kernel<TAPS>>(LDS_LIMIT_BYTES)) return rc;
     hipLaunchKernelGGL(rn_sized_kernel<TAPS>, dim3((E + d.te - 1) / d.te), dim3(512), lds, st, E, H, a, d);
     CN_CHECK_LAUNCH();
     return CN_OK;
@@ -383,16 +281,8 @@ int rn_sized_forward(int E, int H, const RnFusedArgs &args, const RnSizedDims &d
     CN_REQUIRE(te != 0 && te == dims.te, "rn_sized_forward: sizes (%d, %d, %d) outside the box, or envs per workgroup %d not the layout's", dims.R, dims.M, dims.O, dims.te);
     const size_t lds = rn_sized_lds_bytes(dims.R, dims.M, dims.O, te);
     CN_REQUIRE(lds <= (size_t)LDS_LIMIT_BYTES, "rn_sized_forward: %zu B of LDS exceed the workgroup's 160 KB", lds);
-    const bool taps = args.tap_robot || args.tap_attn || args.tap_hr || args.tap_actor;
-    CN_REQUIRE(!taps || (args.tap_robot && args.tap_attn && args.tap_hr && args.tap_actor), "rn_sized_forward: the four taps come together");
-    for (const float *p : {args.te_b, args.edge_b, args.bih, args.bhh, args.ac0_b, args.a2_b, args.c2_b, args.cl_w, args.fm_w})
-        CN_REQUIRE(p && ((uintptr_t)p & 15) == 0, "rn_sized_forward: biases and head weights must be 16-byte aligned"); // the table is filled in float4
-    for (const float *p : {args.f_te, args.f_whh, args.f_edge, args.f_wih, args.f_ac0, args.f_a2, args.f_c2})
-        CN_REQUIRE(p && ((uintptr_t)p & 15) == 0, "rn_sized_forward: fragment images must be 16-byte aligned");
-    CN_REQUIRE(args.temporal && args.robot_node && args.hxs_in && args.masks && args.out_sp && args.row_off && args.rl_w && args.rl_b && args.cl_b &&
-               args.fm_b && args.logstd && args.value && args.hxs_out, "rn_sized_forward: null pointer");
-    CN_REQUIRE(!args.action || args.logp, "rn_sized_forward: action and logp go together");
+    if (int rc = rn_check_args(args, "rn_sized_forward")) return rc;
     RnFusedArgs a = args;
     a.stamp = cn_stamp_slot(CN_K_RN_FUSED);
-    return taps ? rn_sized_launch<true>(E, H, a, dims, lds, st) : rn_sized_launch<false>(E, H, a, dims, lds, st);
+    return args.tap_robot ? rn_sized_launch<true>(E, H, a, dims, lds, st) : rn_sized_launch<false>(E, H, a, dims, lds, st);
 }

@@ -2,7 +2,7 @@
 // the value / log-probability head on given actions and its backward, the fixed-order row reduction of their partials, and
 // robot_linear.0's weight gradient.  Part of policy.hip's translation unit.
 #pragma once
-#include "common.h"
+#include "rn_chain.h"
 
 namespace {
 
@@ -25,10 +25,7 @@ __global__ __launch_bounds__(256) void rn_head_fwd_kernel(int B, const float *__
     if (lane == 0) {
         value[e] = sv + bv[0];
         const float mean0 = s0 + bm[0], mean1 = s1 + bm[1], ls0 = logstd[0], ls1 = logstd[1];
-        const float sd0 = expf(ls0), sd1 = expf(ls1);
-        const float HALF_LOG_2PI = 0.91893853320467274178f;
-        const float d0 = actions[2 * e] - mean0, d1 = actions[2 * e + 1] - mean1;
-        logp[e] = (-(d0 * d0) / (2.0f * sd0 * sd0) - ls0 - HALF_LOG_2PI) + (-(d1 * d1) / (2.0f * sd1 * sd1) - ls1 - HALF_LOG_2PI);
+        logp[e] = rn_gauss_logp(actions[2 * e], actions[2 * e + 1], mean0, mean1, ls0, ls1, expf(ls0), expf(ls1));
     }
 }
 

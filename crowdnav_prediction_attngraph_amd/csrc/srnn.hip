@@ -32,14 +32,9 @@ int srnn_forward(cn_srnn *p, int E, const cn_obs *obs, const float *node_in, con
     const int tiles_t = (E + SR_TILE - 1) / SR_TILE;
     const long long tiles_s = ((long long)E * H + SR_TILE - 1) / SR_TILE;
     CN_REQUIRE(tiles_t + tiles_s < (1ll << 31), "cn_srnn: too many edge rows");
-    static CnLdsOptIn opt_in; // per device
-    int opt_dev;
-    if (opt_in.needed(&opt_dev)) {
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&srnn_edge_gru_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SR_EDGE_LDS));
-        CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&srnn_edge_gru_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)SR_EDGE_LDS));
-        opt_in.done(opt_dev);
-    }
     const dim3 grid((unsigned)(tiles_t + tiles_s));
+    if (int rc = cn_lds_opt_in<&srnn_edge_gru_kernel<1>>((int)SR_EDGE_LDS)) return rc;
+    if (int rc = cn_lds_opt_in<&srnn_edge_gru_kernel<0>>((int)SR_EDGE_LDS)) return rc;
     if (p->mode)
         hipLaunchKernelGGL(srnn_edge_gru_kernel<1>, grid, dim3(SR_EDGE_THREADS), SR_EDGE_LDS, st, E, H, tiles_t, wt, ws, obs->temporal_edges, obs->spatial_edges,
                            edge_in, masks, edge_out);

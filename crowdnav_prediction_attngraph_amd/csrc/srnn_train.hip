@@ -45,12 +45,6 @@ int seq_check(const cn_srnn *p, int T, int N, const float *temporal, const float
     return CN_OK;
 }
 
-template <class K> int lds_opt_in(K *kernel, size_t bytes)
-{
-    CN_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return CN_OK;
-}
-
 SrnnBwdW bwd_weights(const cn_srnn *p, int spatial)
 {
     const int gru = spatial ? W_GRU_S : W_GRU_T, plane = spatial ? 0 : 2;
@@ -121,13 +115,8 @@ extern "C" int cn_srnn_seq_fwd(cn_srnn *p, int T, int N, const float *temporal_e
     CN_REQUIRE(h_all, "cn_srnn_seq_fwd: null output");
     hipStream_t st = (hipStream_t)stream;
     const int H = p->H;
-    static CnLdsOptIn opt_in; // per device
-    int opt_dev;
-    if (opt_in.needed(&opt_dev)) {
-        if (int rc = lds_opt_in(&srnn_edge_gru_kernel<1, 1>, SR_EDGE_LDS)) return rc;
-        if (int rc = lds_opt_in(&srnn_edge_gru_kernel<0, 1>, SR_EDGE_LDS)) return rc;
-        opt_in.done(opt_dev);
-    }
+    if (int rc = cn_lds_opt_in<&srnn_edge_gru_kernel<1, 1>>((int)SR_EDGE_LDS)) return rc;
+    if (int rc = cn_lds_opt_in<&srnn_edge_gru_kernel<0, 1>>((int)SR_EDGE_LDS)) return rc;
     const SrnnEdgeW ws = srnn_edge_weights(p, 1), wt = srnn_edge_weights(p, 0);
     const int tiles_t = (N + SR_TILE - 1) / SR_TILE;
     const int tiles_s = (int)((L.rows_s + SR_TILE - 1) / SR_TILE);
@@ -165,13 +154,8 @@ extern "C" int cn_srnn_seq_bwd(cn_srnn *p, int T, int N, const float *temporal_e
     for (int i = 0; i < 12; ++i) CN_REQUIRE(gp[i], "cn_srnn_seq_bwd: gradient pointer #%d is null", i);
     hipStream_t st = (hipStream_t)stream;
     const int H = p->H;
-    static CnLdsOptIn opt_in; // per device
-    int opt_dev;
-    if (opt_in.needed(&opt_dev)) {
-        if (int rc = lds_opt_in(&srnn_edge_bwd_kernel<1>, SR_BWD_LDS)) return rc;
-        if (int rc = lds_opt_in(&srnn_edge_bwd_kernel<0>, SR_BWD_LDS)) return rc;
-        opt_in.done(opt_dev);
-    }
+    if (int rc = cn_lds_opt_in<&srnn_edge_bwd_kernel<1>>((int)SR_BWD_LDS)) return rc;
+    if (int rc = cn_lds_opt_in<&srnn_edge_bwd_kernel<0>>((int)SR_BWD_LDS)) return rc;
     const SrnnBwdW ws = bwd_weights(p, 1), wt = bwd_weights(p, 0);
     const int tiles_t = (N + SR_TILE - 1) / SR_TILE;
     const int tiles_s = (int)((L.rows_s + SR_TILE - 1) / SR_TILE);
