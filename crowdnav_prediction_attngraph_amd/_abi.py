@@ -168,6 +168,35 @@ RN_WEIGHT_SHAPES = [(256, 9), (256,), (320, 256), (320,), (64, 256), (64,), (384
 RN_SAVED_FIELDS = ["rs", "z", "hr", "attn", "gi", "hs", "hms", "gates", "a1", "a2"]   # cn_rn_saved
 
 
+def rn_weight_shapes(dims=None):
+    """Shapes of cn_rn_weights / cn_rn_grads, in field order, under cn_policy_dims (R, M, A, O); RN_WEIGHT_SHAPES at the default.  The edge
+    width stays 256 and A is not a dimension (it disappears in the fold u = Ws^T (Wt r + bt) and survives as the score temperature)."""
+    R, M, _, O = policy_dims(dims).astuple()
+    return [(256, 9), (256,), (256 + M, 256), (256 + M,), (M, 256), (M,), (3 * R, 2 * M), (3 * R,), (3 * R, R), (3 * R,), (2 * O, R), (2 * O,),
+            (O, O), (O,), (O, O), (O,), (1, O), (1,), (2, O), (2,), (2, 1)]
+
+
+def rn_saved_widths(dims=None, H=1):
+    """Row widths of the cn_rn_saved buffers (each [B, width], dense) under cn_policy_dims."""
+    R, M, _, O = policy_dims(dims).astuple()
+    return dict(rs=256, z=256 + 2 * M, hr=256, attn=H, gi=3 * R, hs=R, hms=R, gates=4 * R, a1=2 * O, a2=2 * O)
+
+
+def rn_seq_plan(dims=None):
+    """Which of its size-dependent code paths the robot-node sequence takes under cn_policy_dims -- the host-side dispatch of csrc/policy.hip
+    and csrc/linear.hip written out (tests/test_rn_seq_sizes.py pins the table; DESIGN.md section 4 mirrors it):
+      padded_n     the forward / dX products whose output width is not a multiple of 128 (planes zero-padded, guarded store), as (name, N)
+      ragged_k     the weight gradients whose K is 64 (2 a + 1) (half-empty last X tile of the two-barrier split-K kernel), as (name, K)
+      gru          'resident128' (the R = 128 kernels), 'resident' (sized kernel, W_hh in registers) or 'streamed' (W_hh re-read every step)
+      gru_rows     rows (envs) per GRU workgroup: a [T, N] slice runs ceil(N / gru_rows) workgroups
+      head_strides O / 64: the strides of the 64 lanes of the head kernels over the trunk features"""
+    R, M, _, O = policy_dims(dims).astuple()
+    fwd = [("te", 256 + M), ("gi", 3 * R), ("a2", O), ("c2", O), ("d1_a", O), ("d1_c", O), ("dhs", R)]
+    wg = [("a2_w", O), ("c2_w", O), ("ac0_w", R), ("whh", R)]
+    return dict(padded_n=[(n, w) for n, w in fwd if w % 128], ragged_k=[(n, k) for n, k in wg if k % 128],
+                gru="resident128" if R == 128 else ("resident" if R == 64 else "streamed"), gru_rows=16, head_strides=O // 64)
+
+
 class RnWeights(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in RN_WEIGHT_FIELDS]
 
@@ -215,7 +244,7 @@ ABI_SYMBOLS = [
     "cn_env_obs_width", "cn_row_plan_words", "cn_env_set_pregen_budget", "cn_env_set_tail_deferral", "cn_env_launch_tail", "cn_policy_set_post_hh_hook", "cn_env_reset", "cn_env_step", "cn_env_join", "cn_env_get_state", "cn_env_get_human_actions", "cn_env_get_danger_min_dist", "cn_env_get_human_counts", "cn_env_set_case_counters", "cn_env_snapshot_bytes", "cn_env_save", "cn_env_load", "cn_orca_solve",
     "cn_policy_create", "cn_policy_create_sized", "cn_policy_destroy", "cn_policy_set_weights", "cn_policy_act", "cn_policy_get_value",
     "cn_policy_get_taps", "cn_policy_set_gemm_mode", "cn_policy_set_self_attention", "cn_obs_compact_visible", "cn_policy_set_taps", "cn_policy_set_profiling", "cn_policy_get_profile",
-    "cn_policy_get_profile_samples", "cn_policy_reset_profile", "cn_prof_set_stamps", "cn_prof_next_step", "cn_hh_block_workspace_bytes", "cn_hh_block_fwd", "cn_rn_seq_workspace_floats", "cn_rn_seq_fwd_workspace_floats", "cn_rn_seq_fwd", "cn_rn_seq_bwd", "cn_hh_attention_workspace_ints", "cn_hh_attention_fwd", "cn_hh_attention_bwd", "cn_hr_attention_fwd", "cn_hr_attention_bwd", "cn_gru_cell_fwd", "cn_gru_cell_bwd", "cn_gru_seq_fwd", "cn_gru_seq_bwd", "cn_embed0_fwd", "cn_embed0_bwd",
+    "cn_policy_get_profile_samples", "cn_policy_reset_profile", "cn_prof_set_stamps", "cn_prof_next_step", "cn_hh_block_workspace_bytes", "cn_hh_block_fwd", "cn_rn_seq_workspace_floats", "cn_rn_seq_fwd_workspace_floats", "cn_rn_seq_fwd", "cn_rn_seq_bwd", "cn_rn_seq_workspace_floats_sized", "cn_rn_seq_fwd_workspace_floats_sized", "cn_rn_seq_fwd_sized", "cn_rn_seq_bwd_sized", "cn_gru_seq_fwd_sized", "cn_gru_seq_bwd_sized", "cn_hh_attention_workspace_ints", "cn_hh_attention_fwd", "cn_hh_attention_bwd", "cn_hr_attention_fwd", "cn_hr_attention_bwd", "cn_gru_cell_fwd", "cn_gru_cell_bwd", "cn_gru_seq_fwd", "cn_gru_seq_bwd", "cn_embed0_fwd", "cn_embed0_bwd",
     "cn_split_bf16", "cn_split_bf16_padded", "cn_linear_fwd", "cn_linear_fwd_act", "cn_linear_wgrad_splits", "cn_linear_wgrad", "cn_small_mm", "cn_gst_create", "cn_gst_destroy", "cn_gst_set_weights", "cn_gst_predict",
     "cn_gst_wrapper_reset", "cn_gst_wrapper_step", "cn_gst_wrapper_set_interval", "cn_gst_wrapper_history_len", "cn_gst_wrapper_save", "cn_gst_wrapper_load", "cn_gae", "cn_adv_stats", "cn_adv_normalize", "cn_episode_stats_update", "cn_eval_state_words", "cn_eval_accumulate",
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
@@ -324,6 +353,15 @@ def lib():
         L.cn_hh_attention_bwd.argtypes = [i32, i32, vp, vp, vp, f32, vp, vp, i32, vp]
         L.cn_hr_attention_fwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp]
         L.cn_hr_attention_bwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_rn_seq_workspace_floats_sized.restype = C.c_int64
+        L.cn_rn_seq_workspace_floats_sized.argtypes = [i32, i32, C.POINTER(PolicyDims)]
+        L.cn_rn_seq_fwd_workspace_floats_sized.restype = C.c_int64
+        L.cn_rn_seq_fwd_workspace_floats_sized.argtypes = [C.POINTER(PolicyDims)]
+        L.cn_rn_seq_fwd_sized.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(RnWeights), C.POINTER(RnSaved), vp, vp, vp, C.POINTER(PolicyDims), vp]
+        L.cn_rn_seq_bwd_sized.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(RnWeights), C.POINTER(RnSaved), vp, vp, vp, vp, vp, C.POINTER(RnWeights),
+                                          C.POINTER(PolicyDims), vp]
+        L.cn_gru_seq_fwd_sized.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_gru_seq_bwd_sized.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gru_seq_fwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gru_seq_bwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gru_cell_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp]

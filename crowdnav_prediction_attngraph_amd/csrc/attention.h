@@ -579,11 +579,12 @@ __global__ __launch_bounds__(256) void hr_attention_kernel(int E, int H, float t
 }
 
 // Backward of hr_attention_kernel for the PPO update: one wavefront per sample on the compacted rows.
-//   a_j = T (u . o_j), p = softmax(a), hr = sum_j p_j o_j         (T = H / 8)
+//   a_j = T (u . o_j), p = softmax(a), hr = sum_j p_j o_j         (T = temp, the forward's temperature: H / 8 at attention_size = 64)
 //   dp_j = d_hr . o_j ; g_j = T p_j (dp_j - sum_k p_k dp_k) ; d_u = sum_j g_j o_j ; d_o_j = p_j d_hr + g_j u
 __global__ __launch_bounds__(256) void hr_attention_bwd_kernel(int B, int H, const float *__restrict__ u, const float *__restrict__ out_sp,
                                                                const int *__restrict__ row_off, const float *__restrict__ attn,
-                                                               const float *__restrict__ d_hr, float *__restrict__ d_u, float *__restrict__ d_o, int u_ld, int du_ld)
+                                                               const float *__restrict__ d_hr, float *__restrict__ d_u, float *__restrict__ d_o, int u_ld, int du_ld,
+                                                               float temp)
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int e = blockIdx.x * 4 + wave;
@@ -613,7 +614,7 @@ __global__ __launch_bounds__(256) void hr_attention_bwd_kernel(int B, int H, con
             }
     }
     const float dot = wv_sum(a * dp);
-    const float gg = a * (dp - dot) * ((float)H / 8.0f);
+    const float gg = a * (dp - dot) * temp;
     float d0 = 0.f, d1 = 0.f, d2 = 0.f, d3 = 0.f;
     auto second = [&](const HrRows &r, int j0) {
 #pragma unroll

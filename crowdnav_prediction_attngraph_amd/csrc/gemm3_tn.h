@@ -41,6 +41,7 @@ __global__ __launch_bounds__(256, GATE ? 3 : 4) void gemm3_tn_kernel(int M, int 
     const int m_end = min(M, m_begin + rows_per_split);
     const int c = tid & 127, g0 = tid >> 7;
     const bool n_ok = n_blk + c < N; // N may end inside the tile (64-wide layers): the surplus columns stay zero
+    const bool k_ok = k_blk + c < K; // and so may K (a multiple of 64): the surplus X columns are zero and their products are not stored
     const bool want_db = db_part != nullptr && blockIdx.y == 0;
 
     f32x16 acc[2][NB];
@@ -64,7 +65,7 @@ __global__ __launch_bounds__(256, GATE ? 3 : 4) void gemm3_tn_kernel(int M, int 
                 const bool ok = m < m_end;
                 pa[p][u] = ok && n_ok ? a_col[(size_t)m * ldy] : 0.0f;
                 if (GATE) pg[p][u] = ok && n_ok ? g_col[(size_t)m * ldy] : 0.0f; // raw load; the select happens in store_chunk
-                pb[p][u] = ok ? b_col[(size_t)m * ldx] : 0.0f;
+                pb[p][u] = ok && k_ok ? b_col[(size_t)m * ldx] : 0.0f;
             }
     };
     float colsum = 0.0f;
@@ -134,7 +135,7 @@ __global__ __launch_bounds__(256, GATE ? 3 : 4) void gemm3_tn_kernel(int M, int 
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = n_blk + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (row < N) P[(size_t)row * K + col] = acc[i][j][r];
+                if (row < N && col < K) P[(size_t)row * K + col] = acc[i][j][r];
             }
         }
     if (want_db) { // uniform per block

@@ -74,8 +74,11 @@ template <int NB, int ACT, bool GATE>
 __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, const float *__restrict__ A, int lda, const float *__restrict__ Agate,
                                                            const __bf16 *__restrict__ Whi, const __bf16 *__restrict__ Wlo,
                                                            const float *__restrict__ bias, float *__restrict__ C, int ldc,
-                                                           const float *__restrict__ aux, int ldaux, int relu_from)
+                                                           const float *__restrict__ aux, int ldaux, int relu_from, int n_store)
 {
+    // n_store <= N, a multiple of 64: the real column count of a product whose weight planes are zero-padded to N (a multiple of 128).  A wavefront
+    // owns 32 NB columns starting at a multiple of 32 NB, so it is either wholly inside n_store or wholly surplus: a surplus wavefront computes
+    // like the others (the barriers are shared) but reads no bias and stores nothing -- C and bias need no padded columns.
     // Epilogues (the ACT_* enum of gemm.h): none / ReLU / tanh on the sum, or -- backward products of the robot-node sequence -- the sum times the
     // derivative of the activation whose forward VALUE y sits in aux [M, ldaux]: [y > 0] (ACT_MUL_DRELU) or 1 - y^2 (ACT_MUL_DTANH).
     // Columns >= relu_from get a ReLU on top of ACT (one launch produces [u | relu(enc)]); pass relu_from >= N for none.
@@ -198,7 +201,7 @@ __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, 
     for (int s = 0; s < 8; ++s) read_a(0, s, 0);
     float bv[NB]; // this output tile's bias (requested a whole tile ahead of its use)
 #pragma unroll
-    for (int j = 0; j < NB; ++j) bv[j] = bias ? bias[n_blk + j * 32 + l31] : 0.0f;
+    for (int j = 0; j < NB; ++j) bv[j] = bias && n_blk < n_store ? bias[n_blk + j * 32 + l31] : 0.0f;
     for (;;) {
     // T % WD == 0 (K % 64 == 0): WD tiles per trip so that register sets are compile-time indices
     for (int t = 0; t < T; t += WD) {
@@ -272,7 +275,14 @@ __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, 
                 }
             }
     };
-    if (m_blk + TBM <= M) store_all([](int) { return true; });
+    if (n_blk >= n_store) {
+#pragma unroll
+        for (int i = 0; i < MI; ++i)
+#pragma unroll
+            for (int j = 0; j < NB; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+    } else if (m_blk + TBM <= M) store_all([](int) { return true; });
     else store_all([&](int row) { return row < M; });
     if (!more) break;
     // the next output tile becomes the current one
@@ -281,7 +291,7 @@ __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, 
 #pragma unroll
     for (int p = 0; p < 4; ++p) ao[p] = ao_n[p];
 #pragma unroll
-    for (int j = 0; j < NB; ++j) bv[j] = bias ? bias[n_blk + j * 32 + l31] : 0.0f;
+    for (int j = 0; j < NB; ++j) bv[j] = bias && n_blk < n_store ? bias[n_blk + j * 32 + l31] : 0.0f;
     look_ahead();
     }
 }
@@ -290,8 +300,10 @@ __global__ __launch_bounds__(256, 1) void gemm3p_nt_kernel(int M, int N, int K, 
 // for ACT_NONE and ACT_RELU only -- what cn_linear_fwd, the one caller with a gate, admits.
 template <int ACT>
 static int launch_gemm3p(int M, int N, int K, const float *A, int lda, const __bf16 *Whi, const __bf16 *Wlo, const float *bias, float *C, int ldc,
-                         hipStream_t st, const float *Agate, const float *aux = nullptr, int ldaux = 0, int relu_from = 1 << 30)
+                         hipStream_t st, const float *Agate, const float *aux = nullptr, int ldaux = 0, int relu_from = 1 << 30, int n_store = -1)
 {
+    if (n_store < 0) n_store = N;
+    CN_REQUIRE(n_store == N || (n_store >= 64 && n_store < N && n_store % 64 == 0),"gemm3p: %d stored columns of N=%d (a multiple of 64 expected)", n_store, N);
     constexpr bool CAN_GATE = ACT == ACT_NONE || ACT == ACT_RELU;
     CN_REQUIRE(CAN_GATE || !Agate, "gemm3p: no gated kernel for act %d (a ReLU gate on A goes with act 0 or 1)", ACT);
     CN_REQUIRE(N % 128 == 0 && K % 64 == 0 && lda % 4 == 0, "gemm3p: unsupported shape M=%d N=%d K=%d lda=%d", M, N, K, lda);
@@ -304,14 +316,14 @@ static int launch_gemm3p(int M, int N, int K, const float *A, int lda, const __b
     const dim3 grid(8 * (per_xcd < 32 ? per_xcd : 32));          // persistent: one workgroup per CU, 32 CUs per XCD
     if constexpr (CAN_GATE) {
         if (Agate) {
-            if (nb == 2) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
-            else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
+            if (nb == 2) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from, n_store);
+            else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, true>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from, n_store);
             CN_CHECK_LAUNCH();
             return CN_OK;
         }
     }
-    if (nb == 2) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
-    else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from);
+    if (nb == 2) hipLaunchKernelGGL((gemm3p_nt_kernel<2, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from, n_store);
+    else hipLaunchKernelGGL((gemm3p_nt_kernel<1, ACT, false>), grid, dim3(256), lds, st, M, N, K, A, lda, Agate, Whi, Wlo, bias, C, ldc, aux, ldaux, relu_from, n_store);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }

@@ -343,6 +343,8 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_kernel(int T, int N, const fl
 
 } // namespace
 
+#include "gru_seq_sized.h"
+
 extern "C" int cn_embed0_fwd(int R, int D, const float *x, const float *W, const float *b, float *y, void *stream)
 {
     if (int rc = cn_require_device()) return rc;
@@ -383,6 +385,46 @@ extern "C" int cn_gru_seq_bwd(int T, int N, const float *gates, const float *hms
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(T >= 1 && N >= 1 && gates && hms && masks && w_hh && d_hs && dgi && dgh && dh0, "cn_gru_seq_bwd: bad argument");
     hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3((N + GR - 1) / GR), dim3(256), 0, (hipStream_t)stream, T, N, gates, hms, masks, w_hh, d_hs, dgi, dgh, dh0);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+// R = 128: the kernels above, untouched.  Other R: the fragment image of W_hh into the workspace (3 R^2 floats), then gru_seq_sized.h's kernel
+// (R = 64 keeps its slice in registers, R = 192 / 256 stream it every step).
+extern "C" int cn_gru_seq_fwd_sized(int T, int N, int R, const float *gi, const float *h0, const float *masks, const float *w_hh, const float *b_hh,
+                                    float *hs, float *hms, float *gates, float *workspace, void *stream)
+{
+    CN_REQUIRE(R == 64 || R == 128 || R == 192 || R == 256, "cn_gru_seq_fwd_sized: rnn_size %d outside the device box: rnn_size in {64, 128, 192, 256}", R);
+    if (R == 128) return cn_gru_seq_fwd(T, N, gi, h0, masks, w_hh, b_hh, hs, hms, gates, stream);
+    if (int rc = cn_require_device()) return rc;
+    CN_REQUIRE(T >= 1 && N >= 1 && gi && h0 && masks && w_hh && b_hh && hs && hms && gates && workspace, "cn_gru_seq_fwd_sized: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    __bf16 *img = reinterpret_cast<__bf16 *>(workspace);
+    hipLaunchKernelGGL(gru_image_kernel, dim3((3 * R * R + 255) / 256), dim3(256), 0, st, R, 0, w_hh, img);
+    CN_CHECK_LAUNCH();
+    const dim3 grid((N + GR - 1) / GR);
+    if (R == 64) hipLaunchKernelGGL((gru_seq_fwd_sized_kernel<64, false>), grid, dim3(256), 0, st, T, N, gi, h0, masks, img, b_hh, hs, hms, gates);
+    else if (R == 192) hipLaunchKernelGGL((gru_seq_fwd_sized_kernel<192, true>), grid, dim3(256), 0, st, T, N, gi, h0, masks, img, b_hh, hs, hms, gates);
+    else hipLaunchKernelGGL((gru_seq_fwd_sized_kernel<256, true>), grid, dim3(256), 0, st, T, N, gi, h0, masks, img, b_hh, hs, hms, gates);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
+extern "C" int cn_gru_seq_bwd_sized(int T, int N, int R, const float *gates, const float *hms, const float *masks, const float *w_hh, const float *d_hs,
+                                    float *dgi, float *dgh, float *dh0, float *workspace, void *stream)
+{
+    CN_REQUIRE(R == 64 || R == 128 || R == 192 || R == 256, "cn_gru_seq_bwd_sized: rnn_size %d outside the device box: rnn_size in {64, 128, 192, 256}", R);
+    if (R == 128) return cn_gru_seq_bwd(T, N, gates, hms, masks, w_hh, d_hs, dgi, dgh, dh0, stream);
+    if (int rc = cn_require_device()) return rc;
+    CN_REQUIRE(T >= 1 && N >= 1 && gates && hms && masks && w_hh && d_hs && dgi && dgh && dh0 && workspace, "cn_gru_seq_bwd_sized: bad argument");
+    hipStream_t st = (hipStream_t)stream;
+    __bf16 *img = reinterpret_cast<__bf16 *>(workspace);
+    hipLaunchKernelGGL(gru_image_kernel, dim3((3 * R * R + 255) / 256), dim3(256), 0, st, R, 1, w_hh, img);
+    CN_CHECK_LAUNCH();
+    const dim3 grid((N + GR - 1) / GR);
+    if (R == 64) hipLaunchKernelGGL((gru_seq_bwd_sized_kernel<64, false>), grid, dim3(256), 0, st, T, N, gates, hms, masks, img, d_hs, dgi, dgh, dh0);
+    else if (R == 192) hipLaunchKernelGGL((gru_seq_bwd_sized_kernel<192, true>), grid, dim3(256), 0, st, T, N, gates, hms, masks, img, d_hs, dgi, dgh, dh0);
+    else hipLaunchKernelGGL((gru_seq_bwd_sized_kernel<256, true>), grid, dim3(256), 0, st, T, N, gates, hms, masks, img, d_hs, dgi, dgh, dh0);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -468,19 +510,28 @@ extern "C" int cn_linear_fwd(int M, int N, int K, const float *X, int ldx, const
 extern "C" int cn_linear_fwd_act(int M, int N, int K, const float *X, int ldx, const void *Whi, const void *Wlo, const float *bias, int act,
                                  const float *aux, int ldaux, int relu_from, float *Y, int ldy, void *stream)
 {
+    return cn_linear_fwd_act_cols(M, N, N, K, X, ldx, Whi, Wlo, bias, act, aux, ldaux, relu_from, Y, ldy, stream);
+}
+
+// The same product with planes zero-padded to N rows and only the first n_store (a multiple of 64) columns real: bias [n_store], aux and Y
+// with leading dimensions >= n_store; columns n_store .. N-1 are computed and dropped (gemm3p.h), nothing is written past a row's real columns.
+int cn_linear_fwd_act_cols(int M, int N, int n_store, int K, const float *X, int ldx, const void *Whi, const void *Wlo, const float *bias, int act,
+                           const float *aux, int ldaux, int relu_from, float *Y, int ldy, void *stream)
+{
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(X && Whi && Wlo && Y && M >= 0, "cn_linear_fwd_act: bad argument");
     CN_REQUIRE(act >= 0 && act <= 4, "cn_linear_fwd_act: act must be 0 (none), 1 (relu), 2 (tanh), 3 (x relu'(aux)) or 4 (x tanh'(aux))");
-    CN_REQUIRE(act < 3 || (aux && ldaux >= N), "cn_linear_fwd_act: act %d needs the forward activation aux [M, ldaux >= N]", act);
-    CN_REQUIRE(ldx >= K && ldy >= N, "cn_linear_fwd_act: leading dimension smaller than the row length");
+    CN_REQUIRE(n_store >= 1 && n_store <= N, "cn_linear_fwd_act: %d stored columns of %d", n_store, N);
+    CN_REQUIRE(act < 3 || (aux && ldaux >= n_store), "cn_linear_fwd_act: act %d needs the forward activation aux [M, ldaux >= N]", act);
+    CN_REQUIRE(ldx >= K && ldy >= n_store, "cn_linear_fwd_act: leading dimension smaller than the row length");
     hipStream_t st = (hipStream_t)stream;
     const __bf16 *wh = (const __bf16 *)Whi, *wl = (const __bf16 *)Wlo;
     switch (act) {
-    case 0: return launch_gemm3p<ACT_NONE>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, nullptr, 0, relu_from);
-    case 1: return launch_gemm3p<ACT_RELU>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, nullptr, 0, relu_from);
-    case 2: return launch_gemm3p<ACT_TANH>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, nullptr, 0, relu_from);
-    case 3: return launch_gemm3p<ACT_MUL_DRELU>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, aux, ldaux, relu_from);
-    default: return launch_gemm3p<ACT_MUL_DTANH>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, aux, ldaux, relu_from);
+    case 0: return launch_gemm3p<ACT_NONE>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, nullptr, 0, relu_from, n_store);
+    case 1: return launch_gemm3p<ACT_RELU>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, nullptr, 0, relu_from, n_store);
+    case 2: return launch_gemm3p<ACT_TANH>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, nullptr, 0, relu_from, n_store);
+    case 3: return launch_gemm3p<ACT_MUL_DRELU>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, aux, ldaux, relu_from, n_store);
+    default: return launch_gemm3p<ACT_MUL_DTANH>(M, N, K, X, ldx, wh, wl, bias, Y, ldy, st, nullptr, aux, ldaux, relu_from, n_store);
     }
 }
 
@@ -500,7 +551,7 @@ static int tn_nb(int N, int K)
 
 extern "C" int cn_linear_wgrad_splits(int M, int N, int K)
 {
-    if (M <= 0 || N <= 0 || K <= 0 || N % 64 || K % 128) return 0;
+    if (M <= 0 || N <= 0 || K <= 0 || N % 64 || K % 64) return 0;
     if (wgrad_pipelined(M, N, K)) { // gemm3p_tn_kernel: one workgroup per CU, tiles of 128 x 512 / 256 / 128 (tn_nb)
         // every XCD (32 CUs, one workgroup each) takes whole splits: s = 8 a with a * tiles a multiple of 32 fills the XCDs in
         // whole rounds; prefer the smallest such s with at least two rounds of work, bounded by 64 partials
@@ -512,7 +563,7 @@ extern "C" int cn_linear_wgrad_splits(int M, int N, int K)
         if (s > chunks) s = chunks;
         return (int)(s < 1 ? 1 : s) + (M % 32 ? 1 : 0); // + one partial for the last M % 32 rows (gemm3_tn_kernel takes those)
     }
-    const long long tiles = (long long)((N + 127) / 128) * (K / 128);
+    const long long tiles = (long long)((N + 127) / 128) * ((K + 127) / 128); // K = 64 (2 a + 1): the last X tile is half empty (gemm3_tn_kernel)
     long long s = (768 + tiles - 1) / tiles;             // 1.5 resident rounds of blocks on 256 CUs (shorter blocks, small tail) ...
     if (s > 64) s = 64;                                  // ... but bounded: every split costs an [N,K] partial to write and re-read
     const long long chunks = ((long long)M + TN_BK - 1) / TN_BK;
@@ -525,7 +576,7 @@ extern "C" int cn_linear_wgrad(int M, int N, int K, const float *dY, int ldy, co
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(dY && X && partials && dW && M > 0 && splits >= 1, "cn_linear_wgrad: bad argument");
-    CN_REQUIRE(N % 64 == 0 && K % 128 == 0, "cn_linear_wgrad: N=%d must be a multiple of 64 and K=%d of 128", N, K);
+    CN_REQUIRE(N % 64 == 0 && K % 64 == 0, "cn_linear_wgrad: N=%d and K=%d must be multiples of 64", N, K);
     CN_REQUIRE((db == nullptr) == (db_partials == nullptr), "cn_linear_wgrad: db and db_partials go together");
     CN_REQUIRE(ldy >= N && ldx >= K, "cn_linear_wgrad: leading dimension smaller than the row length");
     hipStream_t st = (hipStream_t)stream;
@@ -533,8 +584,8 @@ extern "C" int cn_linear_wgrad(int M, int N, int K, const float *dY, int ldy, co
     if (int rc = cn_lds_opt_in<&gemm3_tn_kernel<false>>((int)lds)) return rc;
     if (int rc = cn_lds_opt_in<&gemm3_tn_kernel<true>>((int)lds)) return rc;
     auto launch_tn = [&](int m, const float *dy, const float *gate, const float *x, int rows_per, int nsplit, float *part, float *dbp) {
-        if (gate) hipLaunchKernelGGL(gemm3_tn_kernel<true>, dim3((N + 127) / 128, K / 128, nsplit), dim3(256), lds, st, m, N, K, dy, ldy, gate, x, ldx, rows_per, part, dbp);
-        else hipLaunchKernelGGL(gemm3_tn_kernel<false>, dim3((N + 127) / 128, K / 128, nsplit), dim3(256), lds, st, m, N, K, dy, ldy, gate, x, ldx, rows_per, part, dbp);
+        if (gate) hipLaunchKernelGGL(gemm3_tn_kernel<true>, dim3((N + 127) / 128, (K + 127) / 128, nsplit), dim3(256), lds, st, m, N, K, dy, ldy, gate, x, ldx, rows_per, part, dbp);
+        else hipLaunchKernelGGL(gemm3_tn_kernel<false>, dim3((N + 127) / 128, (K + 127) / 128, nsplit), dim3(256), lds, st, m, N, K, dy, ldy, gate, x, ldx, rows_per, part, dbp);
     };
     int used;
     if (wgrad_pipelined(M, N, K)) {

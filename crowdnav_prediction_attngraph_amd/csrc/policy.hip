@@ -643,7 +643,7 @@ extern "C" int cn_hr_attention_bwd(int B, int H, const float *u, const float *ou
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(B >= 1 && H >= 1 && H <= CN_MAX_HUMANS && u && out_sp && row_off && attn && d_hr && d_u && d_o, "cn_hr_attention_bwd: bad argument");
-    hipLaunchKernelGGL(hr_attention_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, H, u, out_sp, row_off, attn, d_hr, d_u, d_o, 256, 256);
+    hipLaunchKernelGGL(hr_attention_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, B, H, u, out_sp, row_off, attn, d_hr, d_u, d_o, 256, 256, (float)H / 8.0f);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -676,32 +676,56 @@ extern "C" int cn_hh_attention_bwd(int B, int H, const float *qkv, const int *ro
 // reductions in fixed order.
 // ---------------------------------------------------------------------------------------------------------------------------------
 namespace {
+// The sizes of the sequence: cn_policy_dims checked against the device box (the default when dims == NULL).
+struct RnDims {
+    int R, M, A, O; // rnn_size, embedding_size, attention_size, output_size
+    int ZW;         // row of saved z: u (256) | relu(enc) (M) | relu(edge) (M)
+    int TE;         // rows of te_w: 256 + M
+    bool ok;
+};
+constexpr int rn_pad128(int n) { return (n + 127) & ~127; }
+RnDims rn_dims(const cn_policy_dims *d)
+{
+    RnDims q{128, 64, 64, 256, 0, 0, true};
+    if (d) { q.R = d->rnn_size; q.M = d->embedding_size; q.A = d->attention_size; q.O = d->output_size; }
+    q.ok = (q.R == 64 || q.R == 128 || q.R == 192 || q.R == 256) && (q.M == 64 || q.M == 128) && q.O >= 64 && q.O <= 512 && q.O % 64 == 0 && q.A >= 1 && q.A <= 256;
+    q.ZW = 256 + 2 * q.M; q.TE = 256 + q.M;
+    return q;
+}
+#define RN_REQUIRE_BOX(D, WHO)                                                                                                                      \
+    CN_REQUIRE((D).ok, WHO ": (rnn_size %d, embedding_size %d, attention_size %d, output_size %d) outside the device box: rnn_size in {64, 128, 192, " \
+               "256}, embedding_size in {64, 128}, output_size a multiple of 64 in [64, 512], attention_size in [1, 256]", (D).R, (D).M, (D).A, (D).O)
+
 struct RnWs { // carve-up of the backward workspace (floats)
-    size_t d2, d1, dhs, dgi, dgh, dz, dhr, drs, a2T, c2T, ac0T, wihT, edgeT, teT, part, dbp, small, total;
+    size_t d2, d1, dhs, dgi, dgh, dz, dhr, drs, a2T, c2T, ac0T, wihT, edgeT, teT, part, dbp, small, gru, total;
     int small_rows;
 };
-RnWs rn_ws(int T, int N)
+RnWs rn_ws(int T, int N, const RnDims &D)
 {
     const size_t B = (size_t)T * N;
+    const int R = D.R, M = D.M, O = D.O;
     RnWs w{};
     size_t off = 0;
     auto carve = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-    w.d2 = carve(B * 512); w.d1 = carve(B * 512); w.dhs = carve(B * 128); w.dgi = carve(B * 384); w.dgh = carve(B * 384); w.dz = carve(B * 384);
+    w.d2 = carve(B * 2 * O); w.d1 = carve(B * 2 * O); w.dhs = carve(B * R); w.dgi = carve(B * 3 * R); w.dgh = carve(B * 3 * R); w.dz = carve(B * D.ZW);
     w.dhr = carve(B * 256); w.drs = carve(B * 256);
-    w.a2T = carve(256 * 256); w.c2T = carve(256 * 256); w.ac0T = carve(128 * 512); w.wihT = carve(128 * 384); w.edgeT = carve(256 * 64); w.teT = carve(256 * 320);
+    // transposed planes of the dX products; a product with N % 128 != 0 output columns gets planes zero-padded to the next multiple of 128
+    w.a2T = carve((size_t)rn_pad128(O) * O); w.c2T = carve((size_t)rn_pad128(O) * O); w.ac0T = carve((size_t)rn_pad128(R) * 2 * O);
+    w.wihT = carve((size_t)2 * M * 3 * R); w.edgeT = carve((size_t)256 * M); w.teT = carve((size_t)256 * D.TE);
     // weight-gradient partials: the largest of the seven products (splits <= 66 by construction of cn_linear_wgrad_splits)
     size_t pmax = 0, bmax = 0;
-    const int shp[7][2] = {{256, 256}, {256, 256}, {512, 128}, {384, 128}, {384, 128}, {64, 256}, {320, 256}};
+    const int shp[7][2] = {{O, O}, {O, O}, {2 * O, R}, {3 * R, R}, {3 * R, 2 * M}, {M, 256}, {D.TE, 256}};
     for (auto &q : shp) {
         const size_t sp = (size_t)cn_linear_wgrad_splits((int)B, q[0], q[1]);
         pmax = pmax > sp * q[0] * q[1] ? pmax : sp * q[0] * q[1];
         bmax = bmax > sp * q[0] ? bmax : sp * q[0];
     }
-    if (bmax < (size_t)RN_HEAD_COLS) bmax = RN_HEAD_COLS; // dbp also receives the reduced head gradients (cn_rn_seq_bwd): with one split per product
-                                                          // (a few samples) 512 floats would let them run into `small`, which that reduction is reading
+    if (bmax < (size_t)rn_head_cols(O)) bmax = rn_head_cols(O); // dbp also receives the reduced head gradients (cn_rn_seq_bwd): with one split per product
+                                                                // (a few samples) 512 floats would let them run into `small`, which that reduction is reading
     w.part = carve(pmax); w.dbp = carve(bmax);
     w.small_rows = 1024;
-    w.small = carve((size_t)w.small_rows * (RN_HEAD_COLS > 2560 ? RN_HEAD_COLS : 2560)); // head partials [1024, 776] / robot_linear partials [1024, 256, 10]
+    w.small = carve((size_t)w.small_rows * 2560); // head partials [1024, 3 O + 8 <= 1544] / robot_linear partials [1024, 256, 10]
+    w.gru = carve(R == 128 ? 0 : (size_t)3 * R * R); // fragment image of W_hh for cn_gru_seq_bwd_sized (R = 128 keeps the weights in registers)
     w.total = off;
     return w;
 }
@@ -716,33 +740,44 @@ int rn_gemm(int M, int N, int K, const float *A, int lda, const float *W, const 
 {
     return launch_gemm_t<64, 64, ACT>(M, N, K, A, lda, W, bias, C, ldc, st, nullptr, 1, GemmBatch{0, 0, 0, 0}, 1 << 30);
 }
-// The products with N % 128 == 0 and K % 64 == 0 -- all but edge_attention_embed's forward (64 outputs) -- run on the split-precision
-// kernel of the update's big layers (cn_linear_fwd_act, gemm3p.h): three bf16 MFMA products per term at ~5x the rate of the exact-fp32
-// instruction.  `planes` = hi plane followed by lo plane (N * K bf16 each = the N * K floats of the slot) in that kernel's fragment order.
-int rn_split(const float *w, int rows, int cols, int transpose, int n_padded, float *planes, hipStream_t st)
-{
-    const size_t n = (size_t)(n_padded ? n_padded : (transpose ? cols : rows)) * (transpose ? rows : cols);
-    return cn_split_bf16_padded(w, rows, cols, transpose, n_padded, planes, reinterpret_cast<uint16_t *>(planes) + n, (void *)st);
-}
+// The products with K % 64 == 0 -- all but edge_attention_embed's forward -- run on the split-precision kernel of the update's big layers
+// (cn_linear_fwd_act, gemm3p.h): three bf16 MFMA products per term at ~5x the rate of the exact-fp32 instruction.  `planes` = hi plane followed by
+// lo plane (Np * K bf16 each = the Np * K floats of the slot) in that kernel's fragment order, Np = N rounded up to a multiple of 128 with zero rows
+// behind the real ones: the kernel computes Np columns and stores the N real ones (a guarded store: no output or bias has padded columns).
 int rn_gemm3(int act, int M, int N, int K, const float *A, int lda, const float *planes, const float *bias, float *C, int ldc, hipStream_t st,
              const float *aux = nullptr, int ldaux = 0, int relu_from = 1 << 30)
 {
-    return cn_linear_fwd_act(M, N, K, A, lda, planes, reinterpret_cast<const uint16_t *>(planes) + (size_t)N * K, bias, act, aux, ldaux, relu_from, C, ldc, (void *)st);
+    const int Np = rn_pad128(N);
+    return cn_linear_fwd_act_cols(M, Np, N, K, A, lda, planes, reinterpret_cast<const uint16_t *>(planes) + (size_t)Np * K, bias, act, aux, ldaux, relu_from, C,
+                                  ldc, (void *)st);
 }
-struct RnFwdWs { size_t te, teb, wih, ac0, a2, c2, total; }; // forward workspace (floats): split planes of the five weights + the padded te bias
-RnFwdWs rn_fwd_ws()
+struct RnFwdWs { size_t te, teb, wih, ac0, a2, c2, gru, total; }; // forward workspace (floats): split planes of the five weights + the padded te bias
+RnFwdWs rn_fwd_ws(const RnDims &D)
 {
+    const int R = D.R, M = D.M, O = D.O;
     RnFwdWs w{};
     size_t off = 0;
     auto carve = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
-    w.te = carve(384 * 256); w.teb = carve(384); w.wih = carve(384 * 128); w.ac0 = carve(512 * 128); w.a2 = carve(256 * 256); w.c2 = carve(256 * 256);
+    w.te = carve((size_t)rn_pad128(D.TE) * 256); w.teb = carve(rn_pad128(D.TE)); w.wih = carve((size_t)rn_pad128(3 * R) * 2 * M); w.ac0 = carve((size_t)2 * O * R);
+    w.a2 = carve((size_t)rn_pad128(O) * O); w.c2 = carve((size_t)rn_pad128(O) * O);
+    w.gru = carve(R == 128 ? 0 : (size_t)3 * R * R); // fragment image of W_hh for cn_gru_seq_fwd_sized
     w.total = off;
     return w;
 }
 } // namespace
 
-extern "C" int64_t cn_rn_seq_workspace_floats(int T, int N) { return (T > 0 && N > 0) ? (int64_t)rn_ws(T, N).total : 0; }
-extern "C" int64_t cn_rn_seq_fwd_workspace_floats(void) { return (int64_t)rn_fwd_ws().total; }
+extern "C" int64_t cn_rn_seq_workspace_floats_sized(int T, int N, const cn_policy_dims *dims)
+{
+    const RnDims D = rn_dims(dims);
+    return (T > 0 && N > 0 && D.ok) ? (int64_t)rn_ws(T, N, D).total : 0;
+}
+extern "C" int64_t cn_rn_seq_fwd_workspace_floats_sized(const cn_policy_dims *dims)
+{
+    const RnDims D = rn_dims(dims);
+    return D.ok ? (int64_t)rn_fwd_ws(D).total : 0;
+}
+extern "C" int64_t cn_rn_seq_workspace_floats(int T, int N) { return cn_rn_seq_workspace_floats_sized(T, N, nullptr); }
+extern "C" int64_t cn_rn_seq_fwd_workspace_floats(void) { return cn_rn_seq_fwd_workspace_floats_sized(nullptr); }
 
 static int rn_check(int T, int N, int H, const void *a, const void *b, const void *c, const void *d, const cn_rn_weights *w, const cn_rn_saved *sv)
 {
@@ -755,28 +790,31 @@ static int rn_check(int T, int N, int H, const void *a, const void *b, const voi
     return CN_OK;
 }
 
-// The weight preparation of one optimiser step's sequence as jobs of ONE grouped launch (cn_split_group_launch): forward planes (te: 320 rows
-// padded to 384 = three 128-column tiles; its bias padded with zeros) and the transposed planes of the backward's dX products.
-int rn_seq_prep_jobs(const cn_rn_weights *w, float *fwd_ws, float *bwd_ws, int T, int N, CnSplitJob *out)
+// The weight preparation of one optimiser step's sequence as jobs of ONE grouped launch (cn_split_group_launch): forward planes (rows padded to
+// whole 128-column tiles, e.g. te: 320 rows -> 384; its bias padded with zeros) and the transposed planes of the backward's dX products.
+int rn_seq_prep_jobs(const cn_rn_weights *w, float *fwd_ws, float *bwd_ws, int T, int N, CnSplitJob *out, const cn_policy_dims *dims)
 {
+    const RnDims D = rn_dims(dims);
+    const int R = D.R, M = D.M, O = D.O;
+    auto padded = [](int n) { return n % 128 ? rn_pad128(n) : 0; };
     int n = 0;
     if (fwd_ws) {
-        const RnFwdWs F = rn_fwd_ws();
-        out[n++] = cn_split_job(w->te_w, 320, 256, 0, 384, fwd_ws + F.te);
-        out[n++] = cn_split_job(w->wih, 384, 128, 0, 0, fwd_ws + F.wih);
-        out[n++] = cn_split_job(w->ac0_w, 512, 128, 0, 0, fwd_ws + F.ac0);
-        out[n++] = cn_split_job(w->a2_w, 256, 256, 0, 0, fwd_ws + F.a2);
-        out[n++] = cn_split_job(w->c2_w, 256, 256, 0, 0, fwd_ws + F.c2);
-        out[n++] = CnSplitJob{w->te_b, fwd_ws + F.teb, nullptr, 384, 0, 0, 320, 0};
+        const RnFwdWs F = rn_fwd_ws(D);
+        out[n++] = cn_split_job(w->te_w, D.TE, 256, 0, padded(D.TE), fwd_ws + F.te);
+        out[n++] = cn_split_job(w->wih, 3 * R, 2 * M, 0, padded(3 * R), fwd_ws + F.wih);
+        out[n++] = cn_split_job(w->ac0_w, 2 * O, R, 0, 0, fwd_ws + F.ac0);
+        out[n++] = cn_split_job(w->a2_w, O, O, 0, padded(O), fwd_ws + F.a2);
+        out[n++] = cn_split_job(w->c2_w, O, O, 0, padded(O), fwd_ws + F.c2);
+        out[n++] = CnSplitJob{w->te_b, fwd_ws + F.teb, nullptr, rn_pad128(D.TE), 0, 0, D.TE, 0};
     }
     if (bwd_ws) {
-        const RnWs L = rn_ws(T, N);
-        out[n++] = cn_split_job(w->a2_w, 256, 256, 1, 0, bwd_ws + L.a2T);
-        out[n++] = cn_split_job(w->c2_w, 256, 256, 1, 0, bwd_ws + L.c2T);
-        out[n++] = cn_split_job(w->ac0_w, 512, 128, 1, 0, bwd_ws + L.ac0T);
-        out[n++] = cn_split_job(w->wih, 384, 128, 1, 0, bwd_ws + L.wihT);
-        out[n++] = cn_split_job(w->edge_w, 64, 256, 1, 0, bwd_ws + L.edgeT);
-        out[n++] = cn_split_job(w->te_w, 320, 256, 1, 0, bwd_ws + L.teT);
+        const RnWs L = rn_ws(T, N, D);
+        out[n++] = cn_split_job(w->a2_w, O, O, 1, padded(O), bwd_ws + L.a2T);
+        out[n++] = cn_split_job(w->c2_w, O, O, 1, padded(O), bwd_ws + L.c2T);
+        out[n++] = cn_split_job(w->ac0_w, 2 * O, R, 1, padded(R), bwd_ws + L.ac0T);
+        out[n++] = cn_split_job(w->wih, 3 * R, 2 * M, 1, 0, bwd_ws + L.wihT);
+        out[n++] = cn_split_job(w->edge_w, M, 256, 1, 0, bwd_ws + L.edgeT);
+        out[n++] = cn_split_job(w->te_w, D.TE, 256, 1, 0, bwd_ws + L.teT);
     }
     return n;
 }
@@ -785,39 +823,50 @@ extern "C" int cn_rn_seq_fwd(int T, int N, int H, const float *robot_node, const
                              const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, float *ws, float *value, float *logp,
                              void *stream)
 {
-    return rn_seq_fwd_impl(T, N, H, robot_node, temporal, out_sp, row_off, h0, masks, actions, w, sv, ws, value, logp, stream, false);
+    return rn_seq_fwd_impl(T, N, H, robot_node, temporal, out_sp, row_off, h0, masks, actions, w, sv, ws, value, logp, stream, false, nullptr);
+}
+
+extern "C" int cn_rn_seq_fwd_sized(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off,
+                                   const float *h0, const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, float *ws,
+                                   float *value, float *logp, const cn_policy_dims *dims, void *stream)
+{
+    return rn_seq_fwd_impl(T, N, H, robot_node, temporal, out_sp, row_off, h0, masks, actions, w, sv, ws, value, logp, stream, false, dims);
 }
 
 int rn_seq_fwd_impl(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off, const float *h0,
                     const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, float *ws, float *value, float *logp,
-                    void *stream, bool prepared)
+                    void *stream, bool prepared, const cn_policy_dims *dims)
 {
+    const RnDims D = rn_dims(dims);
+    RN_REQUIRE_BOX(D, "cn_rn_seq_fwd");
     if (int rc = cn_require_device()) return rc;
     if (int rc = rn_check(T, N, H, robot_node, temporal, out_sp, row_off, w, sv)) return rc;
     CN_REQUIRE(h0 && masks && actions && ws && value && logp, "cn_rn_seq_fwd: null argument");
     hipStream_t st = (hipStream_t)stream;
-    const int B = T * N;
-    const RnFwdWs F = rn_fwd_ws();
+    const int B = T * N, R = D.R, M = D.M, O = D.O, ZW = D.ZW;
+    const RnFwdWs F = rn_fwd_ws(D);
+    // the temperature num_edges / sqrt(attention_size) of the robot-human scores, as the rollout kernels form it (H / 8 at attention_size = 64)
+    const float temp = (float)((double)H / sqrt((double)D.A));
     int rc;
     if (!prepared) { // split planes of this optimiser step's weights, one grouped launch
         CnSplitJob jobs[8];
-        const int nj = rn_seq_prep_jobs(w, ws, nullptr, T, N, jobs);
+        const int nj = rn_seq_prep_jobs(w, ws, nullptr, T, N, jobs, dims);
         if ((rc = cn_split_group_launch(jobs, nj, st))) return rc;
     }
     hipLaunchKernelGGL(robot_embed_kernel, dim3(B < 2048 ? B : 2048), dim3(256), 0, st, B, temporal, robot_node, w->rl_w, w->rl_b, sv->rs);
     CN_CHECK_LAUNCH();
-    // z = [u (256) | relu(enc) (64) | .] in one product (both read robot_states), then the attention over the compacted rows, then edge -> z[320:384]
-    // (the padded product writes zeros into z[:, 320:384]; the edge layer below overwrites them)
-    if ((rc = rn_gemm3(ACT_NONE, B, 384, 256, sv->rs, 256, ws + F.te, ws + F.teb, sv->z, 384, st, nullptr, 0, 256))) return rc;
-    hipLaunchKernelGGL(hr_attention_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, H, (float)H / 8.0f, sv->z, 384, out_sp, row_off, sv->hr, sv->attn);
+    // z = [u (256) | relu(enc) (M) | .] in one product (both read robot_states), then the attention over the compacted rows, then edge -> z[256+M:]
+    if ((rc = rn_gemm3(ACT_NONE, B, D.TE, 256, sv->rs, 256, ws + F.te, ws + F.teb, sv->z, ZW, st, nullptr, 0, 256))) return rc;
+    hipLaunchKernelGGL(hr_attention_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, H, temp, sv->z, ZW, out_sp, row_off, sv->hr, sv->attn);
     CN_CHECK_LAUNCH();
-    if ((rc = rn_gemm<ACT_RELU>(B, 64, 256, sv->hr, 256, w->edge_w, w->edge_b, sv->z + 320, 384, st))) return rc;
-    if ((rc = rn_gemm3(ACT_NONE, B, 384, 128, sv->z + 256, 384, ws + F.wih, w->bih, sv->gi, 384, st))) return rc;
-    if ((rc = cn_gru_seq_fwd(T, N, sv->gi, h0, masks, w->whh, w->bhh, sv->hs, sv->hms, sv->gates, stream))) return rc;
-    if ((rc = rn_gemm3(ACT_TANH, B, 512, 128, sv->hs, 128, ws + F.ac0, w->ac0_b, sv->a1, 512, st))) return rc;
-    if ((rc = rn_gemm3(ACT_TANH, B, 256, 256, sv->a1, 512, ws + F.a2, w->a2_b, sv->a2, 512, st))) return rc;
-    if ((rc = rn_gemm3(ACT_TANH, B, 256, 256, sv->a1 + 256, 512, ws + F.c2, w->c2_b, sv->a2 + 256, 512, st))) return rc;
-    hipLaunchKernelGGL(rn_head_fwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, sv->a2, w->cl_w, w->cl_b, w->fm_w, w->fm_b, w->logstd, actions, value, logp);
+    if ((rc = rn_gemm<ACT_RELU>(B, M, 256, sv->hr, 256, w->edge_w, w->edge_b, sv->z + D.TE, ZW, st))) return rc;
+    if ((rc = rn_gemm3(ACT_NONE, B, 3 * R, 2 * M, sv->z + 256, ZW, ws + F.wih, w->bih, sv->gi, 3 * R, st))) return rc;
+    if ((rc = cn_gru_seq_fwd_sized(T, N, R, sv->gi, h0, masks, w->whh, w->bhh, sv->hs, sv->hms, sv->gates, ws + F.gru, stream))) return rc;
+    if ((rc = rn_gemm3(ACT_TANH, B, 2 * O, R, sv->hs, R, ws + F.ac0, w->ac0_b, sv->a1, 2 * O, st))) return rc;
+    if ((rc = rn_gemm3(ACT_TANH, B, O, O, sv->a1, 2 * O, ws + F.a2, w->a2_b, sv->a2, 2 * O, st))) return rc;
+    if ((rc = rn_gemm3(ACT_TANH, B, O, O, sv->a1 + O, 2 * O, ws + F.c2, w->c2_b, sv->a2 + O, 2 * O, st))) return rc;
+    RN_HEAD_DISPATCH(O / 64, hipLaunchKernelGGL(rn_head_fwd_kernel<NS>, dim3((B + 3) / 4), dim3(256), 0, st, B, sv->a2, w->cl_w, w->cl_b, w->fm_w, w->fm_b,
+                                                w->logstd, actions, value, logp));
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -826,13 +875,24 @@ extern "C" int cn_rn_seq_bwd(int T, int N, int H, const float *robot_node, const
                              const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, const float *d_value, const float *d_logp, float *ws,
                              float *d_out_sp, float *d_h0, const cn_rn_grads *g, void *stream)
 {
-    return rn_seq_bwd_impl(T, N, H, robot_node, temporal, out_sp, row_off, masks, actions, w, sv, d_value, d_logp, ws, d_out_sp, d_h0, g, stream, false, nullptr);
+    return rn_seq_bwd_impl(T, N, H, robot_node, temporal, out_sp, row_off, masks, actions, w, sv, d_value, d_logp, ws, d_out_sp, d_h0, g, stream, false, nullptr,
+                           nullptr);
+}
+
+extern "C" int cn_rn_seq_bwd_sized(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off,
+                                   const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, const float *d_value,
+                                   const float *d_logp, float *ws, float *d_out_sp, float *d_h0, const cn_rn_grads *g, const cn_policy_dims *dims, void *stream)
+{
+    return rn_seq_bwd_impl(T, N, H, robot_node, temporal, out_sp, row_off, masks, actions, w, sv, d_value, d_logp, ws, d_out_sp, d_h0, g, stream, false, nullptr,
+                           dims);
 }
 
 int rn_seq_bwd_impl(int T, int N, int H, const float *robot_node, const float *temporal, const float *out_sp, const int *row_off, const float *masks,
                     const float *actions, const cn_rn_weights *w, const cn_rn_saved *sv, const float *d_value, const float *d_logp, float *ws,
-                    float *d_out_sp, float *d_h0, const cn_rn_grads *g, void *stream, bool prepared, float **packed_heads)
+                    float *d_out_sp, float *d_h0, const cn_rn_grads *g, void *stream, bool prepared, float **packed_heads, const cn_policy_dims *dims)
 {
+    const RnDims D = rn_dims(dims);
+    RN_REQUIRE_BOX(D, "cn_rn_seq_bwd");
     if (int rc = cn_require_device()) return rc;
     if (int rc = rn_check(T, N, H, robot_node, temporal, out_sp, row_off, w, sv)) return rc;
     CN_REQUIRE(masks && actions && d_value && d_logp && ws && d_out_sp && d_h0 && g, "cn_rn_seq_bwd: null argument");
@@ -841,57 +901,59 @@ int rn_seq_bwd_impl(int T, int N, int H, const float *robot_node, const float *t
         for (size_t i = 0; i < sizeof(cn_rn_grads) / sizeof(void *); ++i) CN_REQUIRE(gp[i], "cn_rn_seq_bwd: gradient pointer #%zu is null", i);
     }
     hipStream_t st = (hipStream_t)stream;
-    const int B = T * N;
-    const RnWs L = rn_ws(T, N);
+    const int B = T * N, R = D.R, M = D.M, O = D.O, ZW = D.ZW, HC = rn_head_cols(O);
+    const float temp = (float)((double)H / sqrt((double)D.A));
+    const RnWs L = rn_ws(T, N, D);
     float *d2 = ws + L.d2, *d1 = ws + L.d1, *dhs = ws + L.dhs, *dgi = ws + L.dgi, *dgh = ws + L.dgh, *dz = ws + L.dz, *dhr = ws + L.dhr, *drs = ws + L.drs;
     int rc;
     // ---- heads + the tanh of the second trunk layers; the heads' own weight gradients ----
     {
         const int blocks = B < 4 * L.small_rows ? (B + 3) / 4 : L.small_rows;
-        hipLaunchKernelGGL(rn_head_bwd_kernel, dim3(blocks), dim3(256), 0, st, B, sv->a2, w->cl_w, w->fm_w, w->fm_b, w->logstd, actions, d_value, d_logp, d2, ws + L.small);
+        RN_HEAD_DISPATCH(O / 64, hipLaunchKernelGGL(rn_head_bwd_kernel<NS>, dim3(blocks), dim3(256), 0, st, B, sv->a2, w->cl_w, w->fm_w, w->fm_b, w->logstd, actions,
+                                                    d_value, d_logp, d2, ws + L.small));
         CN_CHECK_LAUNCH();
-        // the reduced head gradients: RN_HEAD_COLS floats in the bias-partial region (free until the first weight gradient below) -- or, for a
+        // the reduced head gradients: 3 O + 8 floats in the bias-partial region (free until the first weight gradient below) -- or, for a
         // caller that scatters them itself (packed_heads), at the end of the head partials' region, which nothing writes before robot_linear's
         // partials at the very end of this call
-        float *red = packed_heads ? ws + L.small + (size_t)(L.small_rows - 1) * (RN_HEAD_COLS > 2560 ? RN_HEAD_COLS : 2560) + 1024 : ws + L.dbp;
-        hipLaunchKernelGGL(rn_reduce_rows_kernel, dim3((RN_HEAD_COLS + 15) / 16), dim3(256), 0, st, blocks, RN_HEAD_COLS, ws + L.small, red, nullptr, 0);
+        float *red = packed_heads ? ws + L.small + (size_t)(L.small_rows - 1) * 2560 + (HC <= 1536 ? 1024 : 2560 - HC) : ws + L.dbp;
+        hipLaunchKernelGGL(rn_reduce_rows_kernel, dim3((HC + 15) / 16), dim3(256), 0, st, blocks, HC, ws + L.small, red, nullptr, 0);
         CN_CHECK_LAUNCH();
         if (packed_heads) *packed_heads = red;
         else {
-            CN_HIP(hipMemcpyAsync(g->fm_w, red, 512 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            CN_HIP(hipMemcpyAsync(g->cl_w, red + 512, 256 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            CN_HIP(hipMemcpyAsync(g->fm_b, red + 768, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            CN_HIP(hipMemcpyAsync(g->cl_b, red + 770, 1 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            CN_HIP(hipMemcpyAsync(g->logstd, red + 771, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            CN_HIP(hipMemcpyAsync(g->fm_w, red, 2 * O * sizeof(float), hipMemcpyDeviceToDevice, st));
+            CN_HIP(hipMemcpyAsync(g->cl_w, red + 2 * O, O * sizeof(float), hipMemcpyDeviceToDevice, st));
+            CN_HIP(hipMemcpyAsync(g->fm_b, red + 3 * O, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            CN_HIP(hipMemcpyAsync(g->cl_b, red + 3 * O + 2, 1 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            CN_HIP(hipMemcpyAsync(g->logstd, red + 3 * O + 3, 2 * sizeof(float), hipMemcpyDeviceToDevice, st));
         }
     }
     // ---- split planes of the transposed weights for the dX products (dX = dY W as an NT product with W^T), one grouped launch ----
     if (!prepared) {
         CnSplitJob jobs[8];
-        const int nj = rn_seq_prep_jobs(w, nullptr, ws, T, N, jobs);
+        const int nj = rn_seq_prep_jobs(w, nullptr, ws, T, N, jobs, dims);
         if ((rc = cn_split_group_launch(jobs, nj, st))) return rc;
     }
     // ---- second trunk layers: weight gradients, then d1 = (d2 W2) (1 - a1^2) ----
-    if ((rc = rn_wgrad(B, 256, 256, d2, 512, sv->a1, 512, ws, L, g->a2_w, g->a2_b, st))) return rc;
-    if ((rc = rn_wgrad(B, 256, 256, d2 + 256, 512, sv->a1 + 256, 512, ws, L, g->c2_w, g->c2_b, st))) return rc;
-    if ((rc = rn_gemm3(ACT_MUL_DTANH, B, 256, 256, d2, 512, ws + L.a2T, nullptr, d1, 512, st, sv->a1, 512))) return rc;
-    if ((rc = rn_gemm3(ACT_MUL_DTANH, B, 256, 256, d2 + 256, 512, ws + L.c2T, nullptr, d1 + 256, 512, st, sv->a1 + 256, 512))) return rc;
+    if ((rc = rn_wgrad(B, O, O, d2, 2 * O, sv->a1, 2 * O, ws, L, g->a2_w, g->a2_b, st))) return rc;
+    if ((rc = rn_wgrad(B, O, O, d2 + O, 2 * O, sv->a1 + O, 2 * O, ws, L, g->c2_w, g->c2_b, st))) return rc;
+    if ((rc = rn_gemm3(ACT_MUL_DTANH, B, O, O, d2, 2 * O, ws + L.a2T, nullptr, d1, 2 * O, st, sv->a1, 2 * O))) return rc;
+    if ((rc = rn_gemm3(ACT_MUL_DTANH, B, O, O, d2 + O, 2 * O, ws + L.c2T, nullptr, d1 + O, 2 * O, st, sv->a1 + O, 2 * O))) return rc;
     // ---- first trunk layers (output_linear folded in) ----
-    if ((rc = rn_wgrad(B, 512, 128, d1, 512, sv->hs, 128, ws, L, g->ac0_w, g->ac0_b, st))) return rc;
-    if ((rc = rn_gemm3(ACT_NONE, B, 128, 512, d1, 512, ws + L.ac0T, nullptr, dhs, 128, st))) return rc;
+    if ((rc = rn_wgrad(B, 2 * O, R, d1, 2 * O, sv->hs, R, ws, L, g->ac0_w, g->ac0_b, st))) return rc;
+    if ((rc = rn_gemm3(ACT_NONE, B, R, 2 * O, d1, 2 * O, ws + L.ac0T, nullptr, dhs, R, st))) return rc;
     // ---- GRU over the sequence ----
-    if ((rc = cn_gru_seq_bwd(T, N, sv->gates, sv->hms, masks, w->whh, dhs, dgi, dgh, d_h0, stream))) return rc;
-    if ((rc = rn_wgrad(B, 384, 128, dgh, 384, sv->hms, 128, ws, L, g->whh, g->bhh, st))) return rc;
-    if ((rc = rn_wgrad(B, 384, 128, dgi, 384, sv->z + 256, 384, ws, L, g->wih, g->bih, st))) return rc;
-    // ---- d[enc | edge] = (dgi W_ih) relu'(.) -> dz[:, 256:384]; d hr = d edge W_e; attention backward; d u -> dz[:, 0:256] ----
-    if ((rc = rn_gemm3(ACT_MUL_DRELU, B, 128, 384, dgi, 384, ws + L.wihT, nullptr, dz + 256, 384, st, sv->z + 256, 384))) return rc;
-    if ((rc = rn_wgrad(B, 64, 256, dz + 320, 384, sv->hr, 256, ws, L, g->edge_w, g->edge_b, st))) return rc;
-    if ((rc = rn_gemm3(ACT_NONE, B, 256, 64, dz + 320, 384, ws + L.edgeT, nullptr, dhr, 256, st))) return rc;
-    hipLaunchKernelGGL(hr_attention_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, H, sv->z, out_sp, row_off, sv->attn, dhr, dz, d_out_sp, 384, 384);
+    if ((rc = cn_gru_seq_bwd_sized(T, N, R, sv->gates, sv->hms, masks, w->whh, dhs, dgi, dgh, d_h0, ws + L.gru, stream))) return rc;
+    if ((rc = rn_wgrad(B, 3 * R, R, dgh, 3 * R, sv->hms, R, ws, L, g->whh, g->bhh, st))) return rc;
+    if ((rc = rn_wgrad(B, 3 * R, 2 * M, dgi, 3 * R, sv->z + 256, ZW, ws, L, g->wih, g->bih, st))) return rc;
+    // ---- d[enc | edge] = (dgi W_ih) relu'(.) -> dz[:, 256:]; d hr = d edge W_e; attention backward; d u -> dz[:, 0:256] ----
+    if ((rc = rn_gemm3(ACT_MUL_DRELU, B, 2 * M, 3 * R, dgi, 3 * R, ws + L.wihT, nullptr, dz + 256, ZW, st, sv->z + 256, ZW))) return rc;
+    if ((rc = rn_wgrad(B, M, 256, dz + D.TE, ZW, sv->hr, 256, ws, L, g->edge_w, g->edge_b, st))) return rc;
+    if ((rc = rn_gemm3(ACT_NONE, B, 256, M, dz + D.TE, ZW, ws + L.edgeT, nullptr, dhr, 256, st))) return rc;
+    hipLaunchKernelGGL(hr_attention_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, st, B, H, sv->z, out_sp, row_off, sv->attn, dhr, dz, d_out_sp, ZW, ZW, temp);
     CN_CHECK_LAUNCH();
     // ---- [u | enc] layer and robot_linear ----
-    if ((rc = rn_wgrad(B, 320, 256, dz, 384, sv->rs, 256, ws, L, g->te_w, g->te_b, st))) return rc;
-    if ((rc = rn_gemm3(ACT_MUL_DRELU, B, 256, 320, dz, 384, ws + L.teT, nullptr, drs, 256, st, sv->rs, 256))) return rc;
+    if ((rc = rn_wgrad(B, D.TE, 256, dz, ZW, sv->rs, 256, ws, L, g->te_w, g->te_b, st))) return rc;
+    if ((rc = rn_gemm3(ACT_MUL_DRELU, B, 256, D.TE, dz, ZW, ws + L.teT, nullptr, drs, 256, st, sv->rs, 256))) return rc;
     {
         const int blocks = B < 512 ? B : 512;
         hipLaunchKernelGGL(rn_rl_wgrad_kernel, dim3(blocks), dim3(256), 0, st, B, drs, temporal, robot_node, ws + L.small);

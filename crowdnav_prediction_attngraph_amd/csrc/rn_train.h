@@ -7,6 +7,8 @@
 namespace {
 
 // critic_linear + DiagGaussian.log_probs of GIVEN actions (model.py:82-90, distributions.py:36-44): one wavefront per sample
+// NS = O / 64 strides of the 64 lanes over the O = human_node_output_size trunk features (4 at the default 256, up to 8)
+template <int NS>
 __global__ __launch_bounds__(256) void rn_head_fwd_kernel(int B, const float *__restrict__ ac, const float *__restrict__ wv, const float *__restrict__ bv,
                                                           const float *__restrict__ wm, const float *__restrict__ bm, const float *__restrict__ logstd,
                                                           const float *__restrict__ actions, float *__restrict__ value, float *__restrict__ logp)
@@ -14,12 +16,13 @@ __global__ __launch_bounds__(256) void rn_head_fwd_kernel(int B, const float *__
     const int lane = threadIdx.x & 63;
     const int e = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (e >= B) return;
-    const float *a = ac + (size_t)e * 512, *c = a + 256;
+    constexpr int O = 64 * NS;
+    const float *a = ac + (size_t)e * (2 * O), *c = a + O;
     float sv = 0.f, s0 = 0.f, s1 = 0.f;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < NS; ++k) {
         const int d = lane + 64 * k;
-        sv += c[d] * wv[d]; s0 += a[d] * wm[d]; s1 += a[d] * wm[256 + d];
+        sv += c[d] * wv[d]; s0 += a[d] * wm[d]; s1 += a[d] * wm[O + d];
     }
     sv = wv_sum(sv); s0 = wv_sum(s0); s1 = wv_sum(s1);
     if (lane == 0) {
@@ -31,50 +34,64 @@ __global__ __launch_bounds__(256) void rn_head_fwd_kernel(int B, const float *__
 
 // Backward of the heads AND of the second trunk layers' tanh: from d_value [B], d_logp [B]
 //   d_mean_j = d_logp (a_j - mean_j) / sd_j^2 ; d_logstd_j += d_logp ((a_j - mean_j)^2 / sd_j^2 - 1)
-//   d2[:, 0:256]   = (d_mean_0 wm[0] + d_mean_1 wm[1]) (1 - actor^2) ;  d2[:, 256:512] = d_value wv (1 - critic^2)
-// and the heads' own weight gradients (they are reductions over all B samples into 3 x 256 + 5 numbers): every workgroup keeps its sums in
+//   d2[:, 0:O]   = (d_mean_0 wm[0] + d_mean_1 wm[1]) (1 - actor^2) ;  d2[:, O:2 O] = d_value wv (1 - critic^2)
+// and the heads' own weight gradients (they are reductions over all B samples into 3 O + 5 numbers): every workgroup keeps its sums in
 // registers and writes ONE partial row; rn_reduce_rows_kernel adds the rows in order (deterministic).
-constexpr int RN_HEAD_COLS = 3 * 256 + 8; // d fm_w[0] | d fm_w[1] | d cl_w | d fm_b (2) d cl_b d logstd (2) pad (3)
+constexpr int rn_head_cols(int O) { return 3 * O + 8; } // d fm_w[0] | d fm_w[1] | d cl_w | d fm_b (2) d cl_b d logstd (2) pad (3)
+constexpr int RN_HEAD_COLS = rn_head_cols(256);         // the default output size
+template <int NS>
 __global__ __launch_bounds__(256) void rn_head_bwd_kernel(int B, const float *__restrict__ ac, const float *__restrict__ wv, const float *__restrict__ wm,
                                                           const float *__restrict__ bm, const float *__restrict__ logstd, const float *__restrict__ actions,
                                                           const float *__restrict__ d_value, const float *__restrict__ d_logp, float *__restrict__ d2,
                                                           float *__restrict__ partials)
 {
-    __shared__ float red[4][RN_HEAD_COLS];
+    constexpr int O = 64 * NS, COLS = rn_head_cols(O);
+    __shared__ float red[4][COLS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    float w0[4], w1[4], wc[4];
+    float w0[NS], w1[NS], wc[NS];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { const int d = lane + 64 * k; w0[k] = wm[d]; w1[k] = wm[256 + d]; wc[k] = wv[d]; }
+    for (int k = 0; k < NS; ++k) { const int d = lane + 64 * k; w0[k] = wm[d]; w1[k] = wm[O + d]; wc[k] = wv[d]; }
     const float ls0 = logstd[0], ls1 = logstd[1];
     const float iv0 = expf(-2.0f * ls0), iv1 = expf(-2.0f * ls1);
-    float g0[4] = {0.f, 0.f, 0.f, 0.f}, g1[4] = {0.f, 0.f, 0.f, 0.f}, gc[4] = {0.f, 0.f, 0.f, 0.f};
+    float g0[NS], g1[NS], gc[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) g0[k] = g1[k] = gc[k] = 0.f;
     float sb0 = 0.f, sb1 = 0.f, sbc = 0.f, sl0 = 0.f, sl1 = 0.f;
     for (int e = blockIdx.x * 4 + wave; e < B; e += gridDim.x * 4) {
-        const float *a = ac + (size_t)e * 512, *c = a + 256;
-        float av[4], cv[4], s0 = 0.f, s1 = 0.f;
+        const float *a = ac + (size_t)e * (2 * O), *c = a + O;
+        float av[NS], cv[NS], s0 = 0.f, s1 = 0.f;
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { const int d = lane + 64 * k; av[k] = a[d]; cv[k] = c[d]; s0 += av[k] * w0[k]; s1 += av[k] * w1[k]; }
+        for (int k = 0; k < NS; ++k) { const int d = lane + 64 * k; av[k] = a[d]; cv[k] = c[d]; s0 += av[k] * w0[k]; s1 += av[k] * w1[k]; }
         s0 = wv_sum(s0); s1 = wv_sum(s1);
         const float dv = d_value[e], dl = d_logp[e];
         const float e0 = actions[2 * e] - (s0 + bm[0]), e1 = actions[2 * e + 1] - (s1 + bm[1]);
         const float dm0 = dl * e0 * iv0, dm1 = dl * e1 * iv1;
-        float *o = d2 + (size_t)e * 512;
+        float *o = d2 + (size_t)e * (2 * O);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
+        for (int k = 0; k < NS; ++k) {
             const int d = lane + 64 * k;
             o[d] = (dm0 * w0[k] + dm1 * w1[k]) * (1.0f - av[k] * av[k]);
-            o[256 + d] = dv * wc[k] * (1.0f - cv[k] * cv[k]);
+            o[O + d] = dv * wc[k] * (1.0f - cv[k] * cv[k]);
             g0[k] += dm0 * av[k]; g1[k] += dm1 * av[k]; gc[k] += dv * cv[k];
         }
         sb0 += dm0; sb1 += dm1; sbc += dv; sl0 += dl * (e0 * e0 * iv0 - 1.0f); sl1 += dl * (e1 * e1 * iv1 - 1.0f);
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { const int d = lane + 64 * k; red[wave][d] = g0[k]; red[wave][256 + d] = g1[k]; red[wave][512 + d] = gc[k]; }
-    if (lane == 0) { red[wave][768] = sb0; red[wave][769] = sb1; red[wave][770] = sbc; red[wave][771] = sl0; red[wave][772] = sl1; red[wave][773] = red[wave][774] = red[wave][775] = 0.f; }
+    for (int k = 0; k < NS; ++k) { const int d = lane + 64 * k; red[wave][d] = g0[k]; red[wave][O + d] = g1[k]; red[wave][2 * O + d] = gc[k]; }
+    if (lane == 0) {
+        float *q = &red[wave][3 * O];
+        q[0] = sb0; q[1] = sb1; q[2] = sbc; q[3] = sl0; q[4] = sl1; q[5] = q[6] = q[7] = 0.f;
+    }
     __syncthreads();
-    for (int j = threadIdx.x; j < RN_HEAD_COLS; j += 256)
-        partials[(size_t)blockIdx.x * RN_HEAD_COLS + j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
+    for (int j = threadIdx.x; j < COLS; j += 256)
+        partials[(size_t)blockIdx.x * COLS + j] = (red[0][j] + red[1][j]) + (red[2][j] + red[3][j]);
 }
+
+// NS = O / 64 is a template parameter (register arrays, the LDS row): one instantiation per output size of the device box
+#define RN_HEAD_DISPATCH(NSV, CALL) \
+    switch (NSV) { case 1: { constexpr int NS = 1; CALL; } break; case 2: { constexpr int NS = 2; CALL; } break; case 3: { constexpr int NS = 3; CALL; } break; \
+                   case 4: { constexpr int NS = 4; CALL; } break; case 5: { constexpr int NS = 5; CALL; } break; case 6: { constexpr int NS = 6; CALL; } break; \
+                   case 7: { constexpr int NS = 7; CALL; } break; default: { constexpr int NS = 8; CALL; } break; }
 
 // out[j] = sum over the rows of part[R][Cn], in a fixed order: a workgroup owns 16 columns, its sixteen thread groups each walk every
 // sixteenth row (independent loads) and meet in LDS as a fixed binary tree.  rl_layout: the columns are robot_linear's [10][256] partials

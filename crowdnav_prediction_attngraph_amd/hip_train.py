@@ -409,37 +409,52 @@ class HHBlockFused(torch.autograd.Function):
 class RnSequence(torch.autograd.Function):
     """Everything behind the human-human block in evaluate_actions for a [T, N] rollout slice -- robot_linear, [u | encoder_linear], robot-human
     attention, edge_attention_embed, the GRU over the T steps with the done mask, the actor / critic trunks, critic_linear and the log-probability
-    of the given actions -- as ONE call forward (cn_rn_seq_fwd) and ONE backward (cn_rn_seq_bwd).  robot_node [B,7], temporal [B,2], out_sp [R,256]
-    (compacted rows of the human-human block), row_off [B+1] int32, h0 [N,128], masks [B], actions [B,2]; weights in the order of
+    of the given actions -- as ONE call forward (cn_rn_seq_fwd_sized) and ONE backward (cn_rn_seq_bwd_sized).  robot_node [B,7], temporal [B,2],
+    out_sp [rows,256] (compacted rows of the human-human block), row_off [B+1] int32, h0 [N,R], masks [B], actions [B,2]; weights in the order of
     _abi.RN_WEIGHT_FIELDS as the mirror composes them (te = [Ws^T Wt ; encoder_linear], ac0 = (actor.0 ; critic.0) o output_linear).
-    Returns value [B,1], logp [B,1] and the final hidden state [N,128] (not differentiable)."""
+    The network sizes (R, M, O) are read off the weight shapes (whh [3R,R], edge_w [M,256], a2_w [O,O]) and must lie in the device box
+    (_abi.DIMS_BOX); the attention size A, which no shape carries, comes with H: pass H = (human_num, attention_size), or a plain int for the
+    reference's 64.  Returns value [B,1], logp [B,1] and the final hidden state [N,R] (not differentiable)."""
+
+    @staticmethod
+    def dims_of(weights, attention_size=64):
+        """cn_policy_dims of a weight list in _abi.RN_WEIGHT_FIELDS order, checked against the box and against every other shape."""
+        idx = {n: i for i, n in enumerate(A.RN_WEIGHT_FIELDS)}
+        try:
+            dims = A.policy_dims((int(weights[idx["whh"]].shape[1]), int(weights[idx["edge_w"]].shape[0]), int(attention_size), int(weights[idx["a2_w"]].shape[0])))
+        except NotImplementedError as e:
+            raise A.CnError("RnSequence: %s" % e)
+        for w, shp, name in zip(weights, A.rn_weight_shapes(dims), A.RN_WEIGHT_FIELDS):
+            if tuple(w.shape) != shp:
+                raise A.CnError("RnSequence: weight %s has shape %s, expected %s at sizes %s" % (name, tuple(w.shape), shp, dims.astuple()))
+        return dims
 
     @staticmethod
     def forward(ctx, robot_node, temporal, out_sp, row_off, h0, masks, actions, T, N, H, *weights):
         B, dev = T * N, out_sp.device
+        H, attention_size = H if isinstance(H, (tuple, list)) else (H, 64)
         f = lambda t: t.detach().to(torch.float32).contiguous()   # noqa: E731
-        rn, te, osp, h0c, m, act = f(robot_node).view(B, 7), f(temporal).view(B, 2), f(out_sp), f(h0).view(N, 128), f(masks).view(B), f(actions).view(B, 2)
         ws = [f(w) for w in weights]
-        for w, shp, name in zip(ws, A.RN_WEIGHT_SHAPES, A.RN_WEIGHT_FIELDS):
-            if tuple(w.shape) != shp:
-                raise A.CnError("RnSequence: weight %s has shape %s, expected %s" % (name, tuple(w.shape), shp))
+        dims = RnSequence.dims_of(ws, attention_size)
+        rn, te, osp, h0c, m, act = f(robot_node).view(B, 7), f(temporal).view(B, 2), f(out_sp), f(h0).view(N, dims.rnn_size), f(masks).view(B), f(actions).view(B, 2)
         wst = A.RnWeights(*[w.data_ptr() for w in ws])
-        widths = dict(rs=256, z=384, hr=256, attn=H, gi=384, hs=128, hms=128, gates=512, a1=512, a2=512)
+        widths = A.rn_saved_widths(dims, H)
         saved = {k: torch.empty(B, widths[k], device=dev) for k in A.RN_SAVED_FIELDS}
         sst = A.RnSaved(*[saved[k].data_ptr() for k in A.RN_SAVED_FIELDS])
         value, logp = torch.empty(B, 1, device=dev), torch.empty(B, 1, device=dev)
-        work = torch.empty(int(A.lib().cn_rn_seq_fwd_workspace_floats()), device=dev)
-        A.call("cn_rn_seq_fwd", T, N, H, A.ptr(rn), A.ptr(te), A.ptr(osp), A.ptr(row_off), A.ptr(h0c), A.ptr(m), A.ptr(act), C.byref(wst), C.byref(sst),
-               A.ptr(work), A.ptr(value), A.ptr(logp), A.stream_ptr())
+        work = torch.empty(int(A.lib().cn_rn_seq_fwd_workspace_floats_sized(C.byref(dims))), device=dev)
+        A.call("cn_rn_seq_fwd_sized", T, N, H, A.ptr(rn), A.ptr(te), A.ptr(osp), A.ptr(row_off), A.ptr(h0c), A.ptr(m), A.ptr(act), C.byref(wst), C.byref(sst),
+               A.ptr(work), A.ptr(value), A.ptr(logp), C.byref(dims), A.stream_ptr())
         ctx.save_for_backward(rn, te, osp, row_off, m, act, *ws, *[saved[k] for k in A.RN_SAVED_FIELDS])
-        ctx.meta = (T, N, H, len(ws))
+        ctx.meta = (T, N, H, len(ws), dims.astuple())
         h_last = saved["hs"][(T - 1) * N:].clone()
         ctx.mark_non_differentiable(h_last)
         return value, logp, h_last
 
     @staticmethod
     def backward(ctx, d_value, d_logp, _d_h):
-        T, N, H, nw = ctx.meta
+        T, N, H, nw, dims = ctx.meta
+        dims = A.PolicyDims(*dims)
         t = ctx.saved_tensors
         rn, te, osp, row_off, m, act = t[:6]
         ws, sv = t[6:6 + nw], t[6 + nw:]
@@ -448,12 +463,12 @@ class RnSequence(torch.autograd.Function):
         sst = A.RnSaved(*[x.data_ptr() for x in sv])
         grads = [torch.empty_like(w) for w in ws]
         gst = A.RnWeights(*[g.data_ptr() for g in grads])
-        work = torch.empty(int(A.lib().cn_rn_seq_workspace_floats(T, N)), device=dev)
-        d_osp, d_h0 = torch.empty_like(osp), torch.empty(N, 128, device=dev)
+        work = torch.empty(int(A.lib().cn_rn_seq_workspace_floats_sized(T, N, C.byref(dims))), device=dev)
+        d_osp, d_h0 = torch.empty_like(osp), torch.empty(N, dims.rnn_size, device=dev)
         dv = d_value.reshape(B).to(torch.float32).contiguous()
         dl = d_logp.reshape(B).to(torch.float32).contiguous()
-        A.call("cn_rn_seq_bwd", T, N, H, A.ptr(rn), A.ptr(te), A.ptr(osp), A.ptr(row_off), A.ptr(m), A.ptr(act), C.byref(wst), C.byref(sst), A.ptr(dv), A.ptr(dl),
-               A.ptr(work), A.ptr(d_osp), A.ptr(d_h0), C.byref(gst), A.stream_ptr())
+        A.call("cn_rn_seq_bwd_sized", T, N, H, A.ptr(rn), A.ptr(te), A.ptr(osp), A.ptr(row_off), A.ptr(m), A.ptr(act), C.byref(wst), C.byref(sst), A.ptr(dv), A.ptr(dl),
+               A.ptr(work), A.ptr(d_osp), A.ptr(d_h0), C.byref(gst), C.byref(dims), A.stream_ptr())
         return (None, None, d_osp, None, None, None, None, None, None, None, *grads)
 
 

@@ -197,7 +197,8 @@ class AttnGraphBase(nn.Module):
 
     @property
     def default_sizes(self):
-        """The reference's default widths: the only ones the hand-written TRAINING kernels of the robot-node half are specialised to."""
+        """The reference's default widths: the ones the per-op training Functions of the torch-op route (train_fused_rn = False, 'fp32') and
+        cn_ppo_minibatch_step are specialised to.  The robot-node sequence itself (rn_sequence) runs any sizes in the device box."""
         from ._abi import DEFAULT_DIMS
         return self.dims == DEFAULT_DIMS
 
@@ -230,9 +231,9 @@ class AttnGraphBase(nn.Module):
         return out
 
     def fused_rn_shapes_ok(self):
-        """hip_train.RnSequence hard-codes every layer shape of the robot-node sequence (_abi.RN_WEIGHT_SHAPES) and computes its products as bf16x3
-        splits: evaluate_actions takes it only when the modules have exactly those shapes and train_gemm_mode asks for that arithmetic
-        ('fp32' keeps the torch / exact-fp32 path of forward_sequence)."""
+        """The modules have exactly the DEFAULT layer shapes of the robot-node sequence (_abi.RN_WEIGHT_SHAPES): what cn_ppo_minibatch_step is
+        specialised to (hip_train.MinibatchStepper.supported).  evaluate_actions itself asks sized_rn_ok(): hip_train.RnSequence runs every
+        sizes tuple inside the device box."""
         rnn, g = self.humanNodeRNN, self.humanNodeRNN.gru
         return (tuple(self.robot_linear[0].weight.shape) == (256, 9) and tuple(rnn.edge_attention_embed.weight.shape) == (64, 256)
                 and tuple(rnn.encoder_linear.weight.shape) == (64, 256) and tuple(self.attn.temporal_edge_layer[0].weight.shape) == (64, 256)
@@ -241,8 +242,21 @@ class AttnGraphBase(nn.Module):
                 and tuple(rnn.output_linear.weight.shape) == (256, 128) and tuple(self.actor[2].weight.shape) == (256, 256)
                 and tuple(self.critic_linear.weight.shape) == (1, 256))
 
+    def sized_rn_ok(self):
+        """The robot-node sequence (hip_train.RnSequence: cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized) runs at these sizes: every dims tuple inside
+        the device box with the reference's 256-wide edge features.  Wider than fused_rn_shapes_ok(), which keeps meaning "the default shapes"
+        (what cn_ppo_minibatch_step is specialised to, hip_train.MinibatchStepper.supported)."""
+        from ._abi import policy_dims
+        try:
+            policy_dims(self.dims)
+        except NotImplementedError:
+            return False
+        rnn = self.humanNodeRNN
+        return (tuple(self.robot_linear[0].weight.shape) == (256, 9) and rnn.edge_attention_embed.weight.shape[1] == 256
+                and rnn.encoder_linear.weight.shape[1] == 256 and self.attn.spatial_edge_layer[0].weight.shape[1] == 256)
+
     def rn_sequence(self, inputs, out_sp, row_off, h0, masks, actions, T, N, dist):
-        """(value [B,1], logp [B,1], h_T [N,128]) through hip_train.RnSequence.  The two affine pairs without a nonlinearity in between are composed
+        """(value [B,1], logp [B,1], h_T [N,R]) through hip_train.RnSequence.  The two affine pairs without a nonlinearity in between are composed
         here in torch ops (tiny products, autograd carries the folded gradients back to both factors): u = Ws^T (Wt r + bt) -- the
         spatial_edge_layer projection moved to the robot side, its bias keeps an exactly-zero gradient -- and (actor.0 ; critic.0) o output_linear."""
         from .hip_train import RnSequence
@@ -256,7 +270,7 @@ class AttnGraphBase(nn.Module):
         ac0_b = mm(w0, rnn.output_linear.bias) + torch.cat([self.actor[0].bias, self.critic[0].bias], 0)
         g = rnn.gru
         return RnSequence.apply(inputs["robot_node"].reshape(B, 7), inputs["temporal_edges"].reshape(B, 2), out_sp, row_off, h0.reshape(N, -1), masks.reshape(B),
-                                actions.reshape(B, 2), T, N, self.human_num,
+                                actions.reshape(B, 2), T, N, (self.human_num, self.attention_size),
                                 self.robot_linear[0].weight, self.robot_linear[0].bias, te_w, te_b, rnn.edge_attention_embed.weight, rnn.edge_attention_embed.bias,
                                 g.weight_ih_l0, g.bias_ih_l0, g.weight_hh_l0, g.bias_hh_l0, ac0_w, ac0_b, self.actor[2].weight, self.actor[2].bias,
                                 self.critic[2].weight, self.critic[2].bias, self.critic_linear.weight, self.critic_linear.bias, dist.fc_mean.weight, dist.fc_mean.bias,
@@ -740,9 +754,9 @@ class Policy(nn.Module):
         N = rnn_hxs["human_node_rnn"].shape[0]
         T = B // N
         base = self.base
-        if getattr(base, "train_fused_rn", False) and inputs["robot_node"].is_cuda and base.train_gemm_mode == "bf16x3" and base.fused_rn_shapes_ok():
+        if getattr(base, "train_fused_rn", False) and inputs["robot_node"].is_cuda and base.train_gemm_mode == "bf16x3" and base.sized_rn_ok():
             # the attention-graph base's train-mode forward as two boundary calls: the human-human block (cn_hh_block_fwd behind _hh_block)
-            # and the robot-node sequence (cn_rn_seq_fwd), each with ONE backward entry
+            # and the robot-node sequence (cn_rn_seq_fwd_sized: any sizes inside the device box), each with ONE backward entry
             inputs = base.counted_inputs(inputs)
             det = inputs["detected_human_num"].reshape(B).to(torch.int64).clamp(min=1)
             out_sp, row_off = base._hh_block(inputs["spatial_edges"].reshape(B, base.human_num, base.edge_width), det)

@@ -573,6 +573,41 @@ int cn_rn_seq_fwd(int T, int N, int H, const float *robot_node /*[B,7]*/, const 
 int cn_rn_seq_bwd(int T, int N, int H, const float *robot_node, const float *temporal_edges, const float *out_sp, const int *row_off, const float *masks,
                   const float *actions, const cn_rn_weights *w, const cn_rn_saved *saved, const float *d_value /*[B]*/, const float *d_logp /*[B]*/,
                   float *workspace, float *d_out_sp /*[R,256]*/, float *d_h0 /*[N,128]*/, const cn_rn_grads *grads, void *stream);
+/* The same sequence at the network sizes of cn_policy_dims (R, M, A, O) inside the device box of cn_policy_create_sized; outside it every
+ * *_sized call below fails with CN_ERR_INVALID naming the box (the two workspace functions, which run on the host, return 0) and launches
+ * nothing.  dims == NULL or the default tuple: cn_rn_seq_fwd / cn_rn_seq_bwd themselves (they forward here) -- the same launches on the same
+ * buffers, the same bits.  The edge width stays 256.  Layouts under dims:
+ *   cn_rn_weights / cn_rn_grads:  rl_w [256,9]   te_w [256+M,256] (rows 0..255 u, rows 256.. encoder_linear; te_b [256+M])   edge_w [M,256]
+ *                                 wih [3R,2M]    whh [3R,R] (bih / bhh [3R])   ac0_w [2O,R] (ac0_b [2O])   a2_w / c2_w [O,O] (_b [O])
+ *                                 cl_w [1,O]     fm_w [2,O]    cl_b [1], fm_b [2], logstd [2] as before
+ *   cn_rn_saved:                  rs [B,256]   z [B,256+2M] = u (256) | relu(enc) (M) | relu(edge) (M)   hr [B,256]   attn [B,H]   gi [B,3R]
+ *                                 hs / hms [B,R]   gates [B,4R]   a1 / a2 [B,2O]
+ *   h0 / d_h0 [N,R]; every buffer is dense: NO leading dimension is padded.
+ * A appears only in the caller's fold u = Ws^T (Wt r + bt) and in the score temperature (float)((double)H / sqrt((double)A)), which both
+ * robot-human attention kernels take from here (H / 8 at A = 64).
+ * Products whose output width is not a multiple of 128 (3R at R = 64 / 192, O at O = 64 (2 a + 1), R at R = 64 / 192, 256 + M at M = 64) run on
+ * weight planes zero-padded to the next multiple of 128 with a GUARDED STORE: the wavefronts that own the surplus 64 columns compute and store
+ * nothing (cn_linear_fwd_act's kernel), so no output row is written past its real columns and no bias is read past its end.  Weight gradients
+ * whose reduction-side width K is 64 (2 a + 1) (K = R for whh / ac0, K = O for a2 / c2) run on the two-barrier split-K kernel with a half-empty
+ * last X tile; the split count depends on the shape alone (cn_linear_wgrad_splits), so the summation order is fixed.
+ * The GRU runs on cn_gru_seq_fwd_sized / cn_gru_seq_bwd_sized (below). */
+int64_t cn_rn_seq_workspace_floats_sized(int T, int N, const cn_policy_dims *dims);
+int64_t cn_rn_seq_fwd_workspace_floats_sized(const cn_policy_dims *dims);
+int cn_rn_seq_fwd_sized(int T, int N, int H, const float *robot_node, const float *temporal_edges, const float *out_sp, const int *row_off, const float *h0,
+                        const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *saved, float *workspace, float *value,
+                        float *logp, const cn_policy_dims *dims, void *stream);
+int cn_rn_seq_bwd_sized(int T, int N, int H, const float *robot_node, const float *temporal_edges, const float *out_sp, const int *row_off,
+                        const float *masks, const float *actions, const cn_rn_weights *w, const cn_rn_saved *saved, const float *d_value,
+                        const float *d_logp, float *workspace, float *d_out_sp, float *d_h0, const cn_rn_grads *grads, const cn_policy_dims *dims,
+                        void *stream);
+/* cn_gru_seq_fwd / cn_gru_seq_bwd at a hidden size R in {64, 128, 192, 256}: gi / dgi / dgh [T,N,3R], h0 / dh0 [N,R], hs / hms / d_hs [T,N,R],
+ * gates [T,N,4R], w_hh [3R,R].  R = 128 is cn_gru_seq_fwd / _bwd (workspace unused, may be NULL).  Otherwise workspace holds 3 R^2 floats: the
+ * call first writes W_hh there as bf16 hi / lo MFMA fragments, which the sequence kernel keeps in registers (R = 64) or re-reads from the L2
+ * every step (R = 192, 256: the slice of a wavefront would need 432 / 768 of its 512 registers).  16 rows per workgroup, fixed summation order. */
+int cn_gru_seq_fwd_sized(int T, int N, int R, const float *gi, const float *h0, const float *masks, const float *w_hh, const float *b_hh, float *hs,
+                         float *hms, float *gates, float *workspace, void *stream);
+int cn_gru_seq_bwd_sized(int T, int N, int R, const float *gates, const float *hms, const float *masks, const float *w_hh, const float *d_hs,
+                         float *dgi, float *dgh, float *dh0, float *workspace, void *stream);
 
 /* ---- human-human attention core, stand-alone (training path) ----
  * The (env, head) units of torch.nn.MultiheadAttention's scaled-dot-product core (selfAttn_srnn_temp_node.py:89) on COMPACTED
