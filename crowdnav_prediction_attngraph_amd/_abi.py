@@ -187,7 +187,8 @@ def rn_seq_plan(dims=None):
     and csrc/linear.hip written out (tests/test_rn_seq_sizes.py pins the table; DESIGN.md section 4 mirrors it):
       padded_n     the forward / dX products whose output width is not a multiple of 128 (planes zero-padded, guarded store), as (name, N)
       ragged_k     the weight gradients whose K is 64 (2 a + 1) (half-empty last X tile of the two-barrier split-K kernel), as (name, K)
-      gru          'resident128' (the R = 128 kernels), 'resident' (sized kernel, W_hh in registers) or 'streamed' (W_hh re-read every step)
+      gru          the instantiation of csrc/gru_seq.h: 'resident128' / 'resident' (R = 128 / 64: W_hh split once, kept in registers) or 'streamed'
+                   (R = 192 / 256: W_hh re-read every step from its fragment image)
       gru_rows     rows (envs) per GRU workgroup: a [T, N] slice runs ceil(N / gru_rows) workgroups
       head_strides O / 64: the strides of the 64 lanes of the head kernels over the trunk features"""
     R, M, _, O = policy_dims(dims).astuple()
@@ -244,7 +245,7 @@ ABI_SYMBOLS = [
     "cn_env_obs_width", "cn_row_plan_words", "cn_env_set_pregen_budget", "cn_env_set_tail_deferral", "cn_env_launch_tail", "cn_policy_set_post_hh_hook", "cn_env_reset", "cn_env_step", "cn_env_join", "cn_env_get_state", "cn_env_get_human_actions", "cn_env_get_danger_min_dist", "cn_env_get_human_counts", "cn_env_set_case_counters", "cn_env_snapshot_bytes", "cn_env_save", "cn_env_load", "cn_orca_solve",
     "cn_policy_create", "cn_policy_create_sized", "cn_policy_destroy", "cn_policy_set_weights", "cn_policy_act", "cn_policy_get_value",
     "cn_policy_get_taps", "cn_policy_set_gemm_mode", "cn_policy_set_self_attention", "cn_obs_compact_visible", "cn_policy_set_taps", "cn_policy_set_profiling", "cn_policy_get_profile",
-    "cn_policy_get_profile_samples", "cn_policy_reset_profile", "cn_prof_set_stamps", "cn_prof_next_step", "cn_hh_block_workspace_bytes", "cn_hh_block_fwd", "cn_rn_seq_workspace_floats", "cn_rn_seq_fwd_workspace_floats", "cn_rn_seq_fwd", "cn_rn_seq_bwd", "cn_rn_seq_workspace_floats_sized", "cn_rn_seq_fwd_workspace_floats_sized", "cn_rn_seq_fwd_sized", "cn_rn_seq_bwd_sized", "cn_gru_seq_fwd_sized", "cn_gru_seq_bwd_sized", "cn_hh_attention_workspace_ints", "cn_hh_attention_fwd", "cn_hh_attention_bwd", "cn_hr_attention_fwd", "cn_hr_attention_bwd", "cn_gru_cell_fwd", "cn_gru_cell_bwd", "cn_gru_seq_fwd", "cn_gru_seq_bwd", "cn_embed0_fwd", "cn_embed0_bwd",
+    "cn_policy_get_profile_samples", "cn_policy_reset_profile", "cn_prof_set_stamps", "cn_prof_next_step", "cn_hh_block_workspace_bytes", "cn_hh_block_fwd", "cn_rn_seq_workspace_floats", "cn_rn_seq_fwd_workspace_floats", "cn_rn_seq_fwd", "cn_rn_seq_bwd", "cn_rn_seq_workspace_floats_sized", "cn_rn_seq_fwd_workspace_floats_sized", "cn_rn_seq_fwd_sized", "cn_rn_seq_bwd_sized", "cn_gru_seq_fwd_sized", "cn_gru_seq_bwd_sized", "cn_hh_attention_workspace_ints", "cn_hh_attention_fwd", "cn_hh_attention_bwd", "cn_hr_attention_fwd", "cn_hr_attention_bwd", "cn_gru_seq_fwd", "cn_gru_seq_bwd", "cn_embed0_fwd", "cn_embed0_bwd",
     "cn_split_bf16", "cn_split_bf16_padded", "cn_linear_fwd", "cn_linear_fwd_act", "cn_linear_wgrad_splits", "cn_linear_wgrad", "cn_small_mm", "cn_gst_create", "cn_gst_destroy", "cn_gst_set_weights", "cn_gst_predict",
     "cn_gst_wrapper_reset", "cn_gst_wrapper_step", "cn_gst_wrapper_set_interval", "cn_gst_wrapper_history_len", "cn_gst_wrapper_save", "cn_gst_wrapper_load", "cn_gae", "cn_adv_stats", "cn_adv_normalize", "cn_episode_stats_update", "cn_eval_state_words", "cn_eval_accumulate",
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
@@ -364,8 +365,6 @@ def lib():
         L.cn_gru_seq_bwd_sized.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gru_seq_fwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gru_seq_bwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.cn_gru_cell_fwd.argtypes = [i32, vp, vp, vp, vp, vp, vp]
-        L.cn_gru_cell_bwd.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp]
         L.cn_embed0_fwd.argtypes = [i32, i32, vp, vp, vp, vp, vp]
         L.cn_embed0_bwd.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp]
         L.cn_split_bf16.argtypes = [vp, i32, i32, i32, vp, vp, vp]

@@ -24,9 +24,9 @@ namespace {
 
 // W in fragment order: element (cb, kk, lane, e) = W'[cb * 32 + (lane & 31)][kk * 16 + (lane >> 5) * 8 + e], W' = w or w^T
 // Nreal <= Nw: rows Nreal .. Nw-1 of W' are zero padding (a weight whose row count is not a multiple of the 128-column tile)
-__global__ void split_bf16_frag_kernel(int Nw, int Kw, int transpose, const float *__restrict__ w, __bf16 *__restrict__ hi, __bf16 *__restrict__ lo, int Nreal)
+__device__ __forceinline__ void split_bf16_frag_element(size_t idx, int Nw, int Kw, int transpose, const float *__restrict__ w, __bf16 *__restrict__ hi,
+                                                        __bf16 *__restrict__ lo, int Nreal)
 {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)Nw * Kw) return;
     const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
     const size_t blk = idx >> 9;
@@ -36,6 +36,10 @@ __global__ void split_bf16_frag_kernel(int Nw, int Kw, int transpose, const floa
     const __bf16 h = (__bf16)x;
     hi[idx] = h;
     lo[idx] = (__bf16)(x - (float)h);
+}
+__global__ void split_bf16_frag_kernel(int Nw, int Kw, int transpose, const float *__restrict__ w, __bf16 *__restrict__ hi, __bf16 *__restrict__ lo, int Nreal)
+{
+    split_bf16_frag_element((size_t)blockIdx.x * blockDim.x + threadIdx.x, Nw, Kw, transpose, w, hi, lo, Nreal);
 }
 
 // several weights in one launch (the robot-node sequence splits eleven per optimiser step): block b serves the job whose block range holds it
@@ -58,16 +62,7 @@ __global__ void split_bf16_group_kernel(const SplitGroupTable tab)
         if (idx < (size_t)J.Nw) reinterpret_cast<float *>(J.hi)[idx] = idx < (size_t)J.Nreal ? J.w[idx] : 0.0f;
         return;
     }
-    const int Nw = J.Nw, Kw = J.Kw, Nreal = J.Nreal;
-    if (idx >= (size_t)Nw * Kw) return;
-    const int e = (int)(idx & 7), lane = (int)((idx >> 3) & 63);
-    const size_t blk = idx >> 9;
-    const int kk = (int)(blk % (Kw / 16)), cb = (int)(blk / (Kw / 16));
-    const int n = cb * 32 + (lane & 31), k = kk * 16 + (lane >> 5) * 8 + e;
-    const float x = n >= Nreal ? 0.0f : (J.transpose ? J.w[(size_t)k * Nreal + n] : J.w[(size_t)n * Kw + k]);
-    const __bf16 h = (__bf16)x;
-    J.hi[idx] = h;
-    J.lo[idx] = (__bf16)(x - (float)h);
+    split_bf16_frag_element(idx, J.Nw, J.Kw, J.transpose, J.w, J.hi, J.lo, J.Nreal);
 }
 
 template <int NB, int ACT, bool GATE>

@@ -1,24 +1,50 @@
-// gru_seq_sized.h -- the GRU sequence of the PPO update at a hidden size R other than 128 (cn_gru_seq_fwd_sized / cn_gru_seq_bwd_sized; R = 128
-// keeps gru_seq_fwd_kernel / gru_seq_bwd_kernel of linear.hip, bit for bit).  Part of linear.hip's translation unit (split8, sigmoidf_, f32x4g).
+// gru_seq.h -- the human-node GRU of the PPO update over a whole sequence: one launch forward, one backward (cn_gru_seq_fwd / _bwd and their
+// _sized forms in linear.hip), for a hidden size R in {64, 128, 192, 256}.  torch.nn.GRU gate order r, z, n; rl/networks/srnn_model.py:35-105 runs
+// the cell per time step with the hidden state multiplied by the done mask first: gi = x W_ih^T + b_ih (given), gh = hm W_hh^T + b_hh.
 //
-// Same division of labour as the R = 128 kernels: a workgroup of four wavefronts owns GR = 16 rows (envs) for the whole sequence, wavefront w
-// owns the hidden units (R/4) w .. (R/4) (w+1) - 1 as NA = R/64 blocks of 16, the r, z, n accumulators of one (row, unit) sit in the same lane
-// and register index, one barrier per step forward (two backward, as at R = 128: the d(gh) planes are written, read by everyone, overwritten).
-// What differs is where W_hh lives.  A wavefront's slice as bf16 hi / lo MFMA fragments is 3 R^2 / 256 VGPRs per lane: 48 at R = 64, 432 at
-// R = 192, 768 at R = 256 -- against a 512-entry file that also holds the accumulators and the prefetched step inputs.  So:
-//   * STREAM = false (R = 64): the slice is loaded once and stays in registers.
-//   * STREAM = true (R = 192, 256): every step re-reads the slice from a PRE-SPLIT fragment image (gru_image_kernel below; 12 R^2 bytes, L2
-//     resident: every workgroup of the launch reads the same image every step), one k-step's fragments per trip into the register set the
-//     previous k-step has just released, so the loads of k-step kk+1 travel behind the MFMAs of k-step kk; the last k-step of a step already
-//     requests k-step 0 of the next one, which then crosses the cell's pointwise part and the barrier.
-// Both forms read the image, so the arithmetic (operands, MFMA order, summation order) is one code path.  The previous state of the cell's
-// z * h term stays in the lane that computed it (registers), so the only LDS is the two bf16 planes of the A operand.
+// The update runs the GRU over T = 30 steps with only N x R of state: as separate launches (a product and a pointwise kernel per step and
+// direction) it is launch- and latency-bound.  Here a workgroup of four wavefronts owns GR = 16 rows (envs) for the whole sequence (2048 envs of a
+// minibatch = 128 workgroups; with 32 rows it was 64 of 256 CUs) and wavefront w owns the hidden units (R/4) w .. (R/4) (w+1) - 1 as NA = R/64
+// blocks of 16:
+//   * forward: 3 NA column blocks (gate j, block a) per wavefront.  Per step the masked state hm (16 x R, LDS, double buffered as bf16 hi / lo
+//     planes written by the lane that computed the value) is the A operand of the split-precision MFMAs (v_mfma_f32_16x16x32_bf16: lo*hi, hi*lo,
+//     hi*hi per column block and k-step, term-major so that consecutive MFMAs write different accumulators); the accumulators of the r, z, n gates
+//     of one (row, unit) sit in the same lane and register index, so the cell's pointwise part needs no exchange at all, and the previous state of
+//     its z * h term stays in the lane that computed it; one barrier per step.  The forward keeps (r, z, n, gh_n) for the backward.
+//   * backward (reverse time): the same wavefront computes d(gates) for its units from the saved (r, z, n, gh_n), publishes d(gh) [16 x 3R] as
+//     hi / lo planes in LDS (written, read by everyone, overwritten: two barriers per step), and multiplies it with its 3R x R/4 slice of W_hh to
+//     get d(hm) -- one accumulator per term and column block: the MFMAs of a step into NA accumulators would each wait for the one before; the
+//     carried gradient stays in registers in the accumulator layout.  d(W_hh) is one product over all T*N rows afterwards.
+// What depends on R is where W_hh lives.  A wavefront's slice as bf16 hi / lo MFMA fragments is 3 R^2 / 256 VGPRs per lane: 48 at R = 64, 192 at
+// R = 128, 432 at R = 192, 768 at R = 256 -- against a 512-entry file that also holds the accumulators and the prefetched step inputs.  So:
+//   * STREAM = false (R = 64, 128): the slice is read once from the fp32 W_hh, split in registers (split8) and stays there.  W = W_hh.
+//   * STREAM = true (R = 192, 256): every step re-reads the slice from a PRE-SPLIT fragment image (gru_image_kernel; 12 R^2 bytes, L2 resident:
+//     every workgroup of the launch reads the same image every step), one k-step's fragments per trip into the register set the previous k-step
+//     has just released, so the loads of k-step kk+1 travel behind the MFMAs of k-step kk; the last k-step of a step already requests k-step 0
+//     of the next one, which then crosses the cell's pointwise part and the barrier.  W = the image.
+// The split is the same expression in both (split1), so operands, MFMA order and summation order are one code path for every R.
 // Image layouts (elements of 8 bf16 = one lane's fragment; a wavefront's fragment is one contiguous 1 KB read):
 //   forward : [wave][kk < R/32][gate j][block a][plane hi|lo][lane][8]   element = W_hh[j R + u][32 kk + 8 kg + e],  u = (R/4) wave + 16 a + l15
 //   backward: [wave][kk < 3R/32][block a][plane hi|lo][lane][8]          element = W_hh[32 kk + 8 kg + e][u]
+// Accumulator layout of the 16 x 16 MFMA: lane (l15 = lane & 15, kg = lane >> 4) holds rows 4 kg + r (r = 0..3) of column l15.
+// Operand layout of v_mfma_f32_16x16x32_bf16: lane (l15, kg) supplies 8 consecutive k = 32 kk + 8 kg + e of row / column l15.
 #pragma once
+#include <hip/hip_runtime.h>
+#include "split_bf16.h"
 
 namespace {
+
+constexpr int GR = 16; // rows per workgroup.  The LDS planes' row strides are R + 8 / 3R + 8 bf16: 16 bytes past a multiple of 128, so the 16-byte
+                       // fragment reads of 16 rows tile all banks
+typedef float f32x4g __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
+__device__ __forceinline__ void split1(float x, __bf16 &hi, __bf16 &lo) { const __bf16 h = (__bf16)x; hi = h; lo = (__bf16)(x - (float)h); }
+__device__ __forceinline__ void split8(const float (&x)[8], bf16x8 &hi, bf16x8 &lo)
+{
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { __bf16 h, l; split1(x[e], h, l); hi[e] = h; lo[e] = l; }
+}
 
 __global__ __launch_bounds__(256) void gru_image_kernel(int R, int backward, const float *__restrict__ Whh, __bf16 *__restrict__ img)
 {
@@ -29,33 +55,40 @@ __global__ __launch_bounds__(256) void gru_image_kernel(int R, int backward, con
     const int e = idx & 7, lane = (idx >> 3) & 63, f = idx >> 9;
     const int a = f % NA, j = (f / NA) % G, kk = (f / (NA * G)) % KK, wave = f / (NA * G * KK);
     const int kg = lane >> 4, l15 = lane & 15, u = (R / 4) * wave + 16 * a + l15, k = 32 * kk + 8 * kg + e;
-    const float x = backward ? Whh[(size_t)k * R + u] : Whh[(size_t)(j * R + u) * R + k];
-    const __bf16 h = (__bf16)x;
     const size_t o = ((size_t)(2 * f) * 64 + lane) * 8 + e;
-    img[o] = h;
-    img[o + 512] = (__bf16)(x - (float)h);
+    split1(backward ? Whh[(size_t)k * R + u] : Whh[(size_t)(j * R + u) * R + k], img[o], img[o + 512]);
 }
 
+// W: the fp32 W_hh [3R, R] (STREAM = false) or its forward fragment image (STREAM = true)
 template <int R, bool STREAM>
-__global__ __launch_bounds__(256) void gru_seq_fwd_sized_kernel(int T, int N, const float *__restrict__ gi, const float *__restrict__ h0,
-                                                                const float *__restrict__ m, const __bf16 *__restrict__ img, const float *__restrict__ bhh,
-                                                                float *__restrict__ hs, float *__restrict__ hms, float *__restrict__ gates)
+__global__ __launch_bounds__(256) void gru_seq_fwd_kernel(int T, int N, const float *__restrict__ gi, const float *__restrict__ h0,
+                                                          const float *__restrict__ m, const void *__restrict__ W, const float *__restrict__ bhh,
+                                                          float *__restrict__ hs, float *__restrict__ hms, float *__restrict__ gates)
 {
     constexpr int NA = R / 64, KK = R / 32, UW = R / 4, PS = R + 8; // blocks per wavefront, k-steps, units per wavefront, plane row stride (bf16)
     constexpr int NSET = STREAM ? 2 : KK;
     __shared__ __attribute__((aligned(16))) __bf16 hmh[2][GR * PS], hml[2][GR * PS];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kg = lane >> 4, l15 = lane & 15;
     const int row0 = blockIdx.x * GR;
+    // B fragments: column = unit u(a) = UW wave + 16 a + l15 of gate j, k = 32 kk + 8 kg + e
     bf16x8 wf[NSET][3][NA][2];
     int opaque = 0; // keeps the (step-invariant) image loads of the streamed form inside the time loop
     auto load_w = [&](int set, int kk) {
-        const __bf16 *p = img + ((size_t)((wave * KK + kk) * 3 * NA * 2) * 64 + lane) * 8 + opaque;
+        const __bf16 *p = static_cast<const __bf16 *>(W) + ((size_t)((wave * KK + kk) * 3 * NA * 2) * 64 + lane) * 8 + opaque; // streamed: this k-step's fragments
+        const float *wr = static_cast<const float *>(W) + (size_t)(UW * wave + l15) * R + 32 * kk + 8 * kg;                   // resident: this lane's k of unit u(0)
 #pragma unroll
         for (int j = 0; j < 3; ++j)
 #pragma unroll
             for (int a = 0; a < NA; ++a) {
-                wf[set][j][a][0] = *reinterpret_cast<const bf16x8 *>(p + (size_t)((j * NA + a) * 2) * 512);
-                wf[set][j][a][1] = *reinterpret_cast<const bf16x8 *>(p + (size_t)((j * NA + a) * 2 + 1) * 512);
+                if (STREAM) {
+                    wf[set][j][a][0] = *reinterpret_cast<const bf16x8 *>(p + (size_t)((j * NA + a) * 2) * 512);
+                    wf[set][j][a][1] = *reinterpret_cast<const bf16x8 *>(p + (size_t)((j * NA + a) * 2 + 1) * 512);
+                } else {
+                    float x[8];
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) x[e] = wr[(size_t)(j * R + 16 * a) * R + e];
+                    split8(x, wf[set][j][a][0], wf[set][j][a][1]);
+                }
             }
     };
     if (STREAM) load_w(0, 0);
@@ -71,8 +104,7 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_sized_kernel(int T, int N, co
     for (int i = tid; i < GR * R; i += 256) {
         const int r = i / R, c = i % R, row = row0 + r;
         const float v = row < N ? h0[(size_t)row * R + c] * m[row] : 0.0f;
-        const __bf16 h = (__bf16)v;
-        hmh[0][r * PS + c] = h; hml[0][r * PS + c] = (__bf16)(v - (float)h);
+        split1(v, hmh[0][r * PS + c], hml[0][r * PS + c]);
         if (row < N) hms[(size_t)row * R + c] = v;
     }
     float hprev[NA][4]; // the masked previous state of this lane's cells (what the LDS planes hold, unsplit)
@@ -85,7 +117,9 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_sized_kernel(int T, int N, co
             hprev[a][r] = row < N ? v : 0.0f;
         }
     __syncthreads();
-    // a step's inputs are requested one step ahead, unpredicated (surplus rows of the last workgroup read row N-1), as at R = 128
+    // A step's inputs (gi of the step, the mask of the next) do not depend on the state: they are requested one step ahead, right after the
+    // cells have used the current ones, unpredicated (surplus rows of the last workgroup read row N-1) -- a whole step hides the round trip.
+    // Loaded inside the per-row `if (row < N)` blocks below, every row paid its own memory round trip.
     float gir[NA][4], giz[NA][4], gin[NA][4], mk[4];
     auto request = [&](int a, int r, int t) {
         const int rowc = min(row0 + 4 * kg + r, N - 1);
@@ -111,7 +145,6 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_sized_kernel(int T, int N, co
             if (STREAM) load_w((kk + 1) & 1, (kk + 1) % KK); // the other set is free since the previous k-step (KK is even)
             const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(&hmh[cur][l15 * PS + 32 * kk + 8 * kg]);
             const bf16x8 al = *reinterpret_cast<const bf16x8 *>(&hml[cur][l15 * PS + 32 * kk + 8 * kg]);
-            // term-major inside a k-step: consecutive MFMAs write different accumulators
 #pragma unroll
             for (int j = 0; j < 3; ++j)
 #pragma unroll
@@ -144,10 +177,7 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_sized_kernel(int T, int N, co
                     if (t + 1 < T) hms[(tr + N) * R + u] = next;
                 }
                 hprev[a][r] = next;
-                if (t + 1 < T) {
-                    const __bf16 h = (__bf16)next;
-                    hmh[cur ^ 1][rl * PS + u] = h; hml[cur ^ 1][rl * PS + u] = (__bf16)(next - (float)h);
-                }
+                if (t + 1 < T) split1(next, hmh[cur ^ 1][rl * PS + u], hml[cur ^ 1][rl * PS + u]);
             }
         // (mk[r] is shared by the blocks of a row: the reloads go behind the last block's use)
 #pragma unroll
@@ -158,10 +188,11 @@ __global__ __launch_bounds__(256) void gru_seq_fwd_sized_kernel(int T, int N, co
     }
 }
 
+// W: the fp32 W_hh [3R, R] (STREAM = false) or its backward fragment image (STREAM = true)
 template <int R, bool STREAM>
-__global__ __launch_bounds__(256) void gru_seq_bwd_sized_kernel(int T, int N, const float *__restrict__ gates, const float *__restrict__ hms,
-                                                                const float *__restrict__ m, const __bf16 *__restrict__ img, const float *__restrict__ d_hs,
-                                                                float *__restrict__ dgi, float *__restrict__ dgh, float *__restrict__ dh0)
+__global__ __launch_bounds__(256) void gru_seq_bwd_kernel(int T, int N, const float *__restrict__ gates, const float *__restrict__ hms,
+                                                          const float *__restrict__ m, const void *__restrict__ W, const float *__restrict__ d_hs,
+                                                          float *__restrict__ dgi, float *__restrict__ dgh, float *__restrict__ dh0)
 {
     constexpr int NA = R / 64, KK = 3 * R / 32, UW = R / 4, QS = 3 * R + 8; // k-steps over the 3R gate columns; row stride (bf16) of the d(gh) planes
     constexpr int NSET = STREAM ? 2 : KK;
@@ -172,11 +203,19 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_sized_kernel(int T, int N, co
     bf16x8 wf[NSET][NA][2];
     int opaque = 0;
     auto load_w = [&](int set, int kk) {
-        const __bf16 *p = img + ((size_t)((wave * KK + kk) * NA * 2) * 64 + lane) * 8 + opaque;
+        const __bf16 *p = static_cast<const __bf16 *>(W) + ((size_t)((wave * KK + kk) * NA * 2) * 64 + lane) * 8 + opaque;
+        const float *wc = static_cast<const float *>(W) + (size_t)(32 * kk + 8 * kg) * R + UW * wave + l15;
 #pragma unroll
         for (int a = 0; a < NA; ++a) {
-            wf[set][a][0] = *reinterpret_cast<const bf16x8 *>(p + (size_t)(a * 2) * 512);
-            wf[set][a][1] = *reinterpret_cast<const bf16x8 *>(p + (size_t)(a * 2 + 1) * 512);
+            if (STREAM) {
+                wf[set][a][0] = *reinterpret_cast<const bf16x8 *>(p + (size_t)(a * 2) * 512);
+                wf[set][a][1] = *reinterpret_cast<const bf16x8 *>(p + (size_t)(a * 2 + 1) * 512);
+            } else {
+                float x[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) x[e] = wc[(size_t)e * R + 16 * a];
+                split8(x, wf[set][a][0], wf[set][a][1]);
+            }
         }
     };
     if (!STREAM) {
@@ -188,7 +227,9 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_sized_kernel(int T, int N, co
     for (int a = 0; a < NA; ++a)
 #pragma unroll
         for (int r = 0; r < 4; ++r) carry[a][r] = 0.0f;
-    // the saved gates / states / incoming gradients of a step are requested one step ahead, unpredicated (surplus rows read row N-1)
+    // The saved gates / states / incoming gradients of a step do not depend on the carried gradient: they are requested one step ahead,
+    // unpredicated (surplus rows read row N-1), right behind the barrier that ends their last use -- the MFMAs of the current step hide the
+    // round trip.
     float s_rg[NA][4], s_zg[NA][4], s_ng[NA][4], s_hn[NA][4], s_h[NA][4], s_d[NA][4], s_m[4];
     auto preload = [&](int t) {
 #pragma unroll
@@ -206,7 +247,7 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_sized_kernel(int T, int N, co
             s_m[r] = m[tr];
         }
     };
-    auto put = [&](int off, float v) { const __bf16 h = (__bf16)v; dgp_h[off] = h; dgp_l[off] = (__bf16)(v - (float)h); };
+    auto put = [&](int off, float v) { split1(v, dgp_h[off], dgp_l[off]); };
     preload(T - 1);
     for (int t = T - 1; t >= 0; --t) {
         if (STREAM) { asm volatile("" : "+s"(opaque)); load_w(0, 0); }
@@ -221,11 +262,11 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_sized_kernel(int T, int N, co
                 const int u = UW * wave + 16 * a + l15;
                 const float rg = s_rg[a][r], zg = s_zg[a][r], ng = s_ng[a][r], hn = s_hn[a][r], h = s_h[a][r];
                 const float d = s_d[a][r] + carry[a][r];
-                const float din = d * (1.0f - zg) * (1.0f - ng * ng);
-                const float dr = ok ? din * hn * rg * (1.0f - rg) : 0.0f;
-                const float dz = ok ? d * (h - ng) * zg * (1.0f - zg) : 0.0f;
+                const float din = d * (1.0f - zg) * (1.0f - ng * ng); // d(i_n)
+                const float dr = ok ? din * hn * rg * (1.0f - rg) : 0.0f; // d(i_r) = d(h_r)
+                const float dz = ok ? d * (h - ng) * zg * (1.0f - zg) : 0.0f; // d(i_z) = d(h_z)
                 const float dn = ok ? din * rg : 0.0f;
-                direct[a][r] = ok ? d * zg : 0.0f;
+                direct[a][r] = ok ? d * zg : 0.0f; // the direct path d(hm) = dh' * z
                 if (ok) { // stores only
                     const size_t tr = (size_t)t * N + row;
                     float *p1 = dgi + tr * (3 * R), *p2 = dgh + tr * (3 * R);
@@ -237,7 +278,6 @@ __global__ __launch_bounds__(256) void gru_seq_bwd_sized_kernel(int T, int N, co
         }
         __syncthreads();
         preload(t > 0 ? t - 1 : 0);
-        // one accumulator per term and column block
         f32x4g acc[3][NA];
 #pragma unroll
         for (int q = 0; q < 3; ++q)

@@ -725,7 +725,7 @@ RnWs rn_ws(int T, int N, const RnDims &D)
     w.part = carve(pmax); w.dbp = carve(bmax);
     w.small_rows = 1024;
     w.small = carve((size_t)w.small_rows * 2560); // head partials [1024, 3 O + 8 <= 1544] / robot_linear partials [1024, 256, 10]
-    w.gru = carve(R == 128 ? 0 : (size_t)3 * R * R); // fragment image of W_hh for cn_gru_seq_bwd_sized (R = 128 keeps the weights in registers)
+    w.gru = carve(R <= 128 ? 0 : (size_t)3 * R * R); // fragment image of W_hh for cn_gru_seq_bwd_sized (R = 64 / 128 keep the weights in registers)
     w.total = off;
     return w;
 }
@@ -760,7 +760,7 @@ RnFwdWs rn_fwd_ws(const RnDims &D)
     auto carve = [&](size_t n) { size_t o = off; off += (n + 63) & ~size_t(63); return o; };
     w.te = carve((size_t)rn_pad128(D.TE) * 256); w.teb = carve(rn_pad128(D.TE)); w.wih = carve((size_t)rn_pad128(3 * R) * 2 * M); w.ac0 = carve((size_t)2 * O * R);
     w.a2 = carve((size_t)rn_pad128(O) * O); w.c2 = carve((size_t)rn_pad128(O) * O);
-    w.gru = carve(R == 128 ? 0 : (size_t)3 * R * R); // fragment image of W_hh for cn_gru_seq_fwd_sized
+    w.gru = carve(R <= 128 ? 0 : (size_t)3 * R * R); // fragment image of W_hh for cn_gru_seq_fwd_sized (streamed R only)
     w.total = off;
     return w;
 }

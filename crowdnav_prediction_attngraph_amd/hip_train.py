@@ -191,19 +191,26 @@ class Embed0(torch.autograd.Function):
         return None, dwb[:, :D].contiguous(), dwb[:, D].contiguous()
 
 
-def wgrad(dy, x):
-    """(dy^T x [N,K], column sums of dy [N]) over all M rows on the split-K TN kernel (cn_linear_wgrad); N % 64 == 0, K % 128 == 0."""
+def wgrad(dy, x, gate=None, required=False):
+    """((dy * [gate > 0])^T x [N,K], column sums of dy * [gate > 0] [N]) over all M rows on the split-K TN kernel (cn_linear_wgrad); N % 64 == 0,
+    K % 64 == 0.  `gate` = the ReLU output whose backward is applied while dy is loaded (None: no gate).  A shape the kernel has no plan for goes to
+    torch, unless the caller has checked the shape beforehand (`required`): then it is an error."""
     dy, x = dy.contiguous(), x.contiguous()
     M, N = dy.shape
     K = x.shape[1]
     splits = A.lib().cn_linear_wgrad_splits(M, N, K)
     if splits <= 0:
+        if required:
+            raise A.CnError("cn_linear_wgrad: no split-K plan for a %d x %d weight gradient over %d rows" % (N, K, M))
+        if gate is not None:
+            dy = dy * (gate > 0)
         return dy.t() @ x, dy.sum(0)
     part = torch.empty(splits, N, K, device=x.device)
     dbp = torch.empty(splits, N, device=x.device)
     dw = torch.empty(N, K, device=x.device)
     db = torch.empty(N, device=x.device)
-    A.call("cn_linear_wgrad", M, N, K, A.ptr(dy), N, None, A.ptr(x), K, splits, A.ptr(part), A.ptr(dbp), A.ptr(dw), A.ptr(db), A.stream_ptr())
+    A.call("cn_linear_wgrad", M, N, K, A.ptr(dy), N, None if gate is None else A.ptr(gate), A.ptr(x), K, splits, A.ptr(part), A.ptr(dbp), A.ptr(dw), A.ptr(db),
+           A.stream_ptr())
     return dw, db
 
 
@@ -288,16 +295,9 @@ class WgradLinear(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w = ctx.saved_tensors
-        x, dy = x.contiguous(), dy.contiguous()
-        M, K = x.shape
-        N = w.shape[0]
+        dy = dy.contiguous()
         dx = dy @ w if ctx.needs_input_grad[0] else None
-        splits = A.lib().cn_linear_wgrad_splits(M, N, K)
-        part = torch.empty(splits, N, K, device=x.device)
-        dbp = torch.empty(splits, N, device=x.device)
-        dw = torch.empty(N, K, device=x.device)
-        db = torch.empty(N, device=x.device)
-        A.call("cn_linear_wgrad", M, N, K, A.ptr(dy), N, None, A.ptr(x), K, splits, A.ptr(part), A.ptr(dbp), A.ptr(dw), A.ptr(db), A.stream_ptr())
+        dw, db = wgrad(dy, x, required=True)
         return dx, dw, db
 
 
@@ -325,21 +325,17 @@ class HipLinear(torch.autograd.Function):
         M, K = x.shape
         N = w.shape[0]
         dy = dy.contiguous()
-        gate = A.ptr(y) if ctx.relu else None          # ReLU backward is applied while dY is loaded (no masking pass)
+        gate = y if ctx.relu else None                 # ReLU backward is applied while dY is loaded (no masking pass)
         dx = dw = db = None
         if M == 0:
             return torch.zeros_like(x), torch.zeros_like(w), x.new_zeros(N), None
         if ctx.needs_input_grad[0]:
             hi_t, lo_t = split_bf16(w.detach(), transpose=True)              # [K,N]: dX = dY W as an NT product with W^T
             dx = torch.empty(M, K, device=x.device)
-            A.call("cn_linear_fwd", M, K, N, A.ptr(dy), N, gate, A.ptr(hi_t), A.ptr(lo_t), None, 0, A.ptr(dx), K, A.stream_ptr())
+            A.call("cn_linear_fwd", M, K, N, A.ptr(dy), N, None if gate is None else A.ptr(gate), A.ptr(hi_t), A.ptr(lo_t), None, 0, A.ptr(dx), K,
+                   A.stream_ptr())
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            splits = A.lib().cn_linear_wgrad_splits(M, N, K)
-            part = torch.empty(splits, N, K, device=x.device)
-            dbp = torch.empty(splits, N, device=x.device)
-            dw = torch.empty(N, K, device=x.device)
-            db = torch.empty(N, device=x.device)
-            A.call("cn_linear_wgrad", M, N, K, A.ptr(dy), N, gate, A.ptr(x), K, splits, A.ptr(part), A.ptr(dbp), A.ptr(dw), A.ptr(db), A.stream_ptr())
+            dw, db = wgrad(dy, x, gate, required=True)
         return dx, dw, db, None
 
 
@@ -382,10 +378,7 @@ class HHBlockFused(torch.autograd.Function):
             hi_t, lo_t = split_bf16(w.detach(), transpose=True)
             dx = torch.empty(M, K, device=dev)
             A.call("cn_linear_fwd", M, K, N, A.ptr(dy), N, g, A.ptr(hi_t), A.ptr(lo_t), None, 0, A.ptr(dx), K, A.stream_ptr())
-            splits = L.cn_linear_wgrad_splits(M, N, K)
-            part, dbp = torch.empty(splits, N, K, device=dev), torch.empty(splits, N, device=dev)
-            dw, db = torch.empty(N, K, device=dev), torch.empty(N, device=dev)
-            A.call("cn_linear_wgrad", M, N, K, A.ptr(dy), N, g, A.ptr(inp), K, splits, A.ptr(part), A.ptr(dbp), A.ptr(dw), A.ptr(db), A.stream_ptr())
+            dw, db = wgrad(dy, inp, gate, required=True)
             return dx, dw, db
 
         d_out = d_out.contiguous()

@@ -432,7 +432,7 @@ class AttnGraphBase(nn.Module):
         gi = self._lin(x, rnn.gru.weight_ih_l0, rnn.gru.bias_ih_l0).view(T, N, -1)
         m = masks.reshape(T, N, 1)
         h = h0.reshape(N, -1)
-        if gi.is_cuda and tuple(rnn.gru.weight_hh_l0.shape) == (384, 128):      # cn_gru_seq_* are specialised to R = 128
+        if gi.is_cuda and tuple(rnn.gru.weight_hh_l0.shape) == (384, 128):      # hip_train.GRUSequence (this per-op route) takes R = 128 only
             from .hip_train import GRUSequence
             hs_all = GRUSequence.apply(gi, h, m, rnn.gru.weight_hh_l0, rnn.gru.bias_hh_l0)
             h = hs_all[-1]

@@ -601,9 +601,10 @@ int cn_rn_seq_bwd_sized(int T, int N, int H, const float *robot_node, const floa
                         const float *d_logp, float *workspace, float *d_out_sp, float *d_h0, const cn_rn_grads *grads, const cn_policy_dims *dims,
                         void *stream);
 /* cn_gru_seq_fwd / cn_gru_seq_bwd at a hidden size R in {64, 128, 192, 256}: gi / dgi / dgh [T,N,3R], h0 / dh0 [N,R], hs / hms / d_hs [T,N,R],
- * gates [T,N,4R], w_hh [3R,R].  R = 128 is cn_gru_seq_fwd / _bwd (workspace unused, may be NULL).  Otherwise workspace holds 3 R^2 floats: the
- * call first writes W_hh there as bf16 hi / lo MFMA fragments, which the sequence kernel keeps in registers (R = 64) or re-reads from the L2
- * every step (R = 192, 256: the slice of a wavefront would need 432 / 768 of its 512 registers).  16 rows per workgroup, fixed summation order. */
+ * gates [T,N,4R], w_hh [3R,R].  One kernel pair for every R (csrc/gru_seq.h).  R = 64 and 128 read w_hh itself, split it into bf16 hi / lo MFMA
+ * fragments in registers and keep them there for the whole sequence: workspace is unused and may be NULL.  R = 192 and 256 need a workspace of
+ * 3 R^2 floats: the call first writes W_hh there as fragments, which the sequence kernel re-reads from the L2 every step (the slice of a
+ * wavefront would need 432 / 768 of its 512 registers).  16 rows per workgroup, fixed summation order. */
 int cn_gru_seq_fwd_sized(int T, int N, int R, const float *gi, const float *h0, const float *masks, const float *w_hh, const float *b_hh, float *hs,
                          float *hms, float *gates, float *workspace, void *stream);
 int cn_gru_seq_bwd_sized(int T, int N, int R, const float *gates, const float *hms, const float *masks, const float *w_hh, const float *d_hs,
@@ -643,18 +644,12 @@ int cn_embed0_fwd(int R, int D, const float *x, const float *W, const float *b, 
 int cn_embed0_bwd(int R, int D, const float *x, const float *y, const float *dy, int blocks, float *partials, float *dWb,
                   void *stream);
 
-/* ---- GRU cell of the human node RNN, pointwise part (training path) ----
+/* ---- GRU of the human node RNN over a whole sequence (training path) ----
  * torch.nn.GRU (gate order r,z,n) as EndRNN drives it one step at a time with h * done-mask
- * (rl/networks/srnn_model.py:35-105, selfAttn_srnn_temp_node.py:262-285), under autograd in PPO.update.
- * gi [N,384] = x W_ih^T + b_ih, gh [N,384] = hm W_hh^T + b_hh, hm [N,128] = masked previous hidden state.
- * fwd: h_out [N,128] and gates [N,512] = (r, z, n, gh_n) kept for the backward.
- * bwd: from dh [N,128]: dgi [N,384], dgh [N,384] and the direct path dhm [N,128] = dh * z. */
-int cn_gru_cell_fwd(int N, const float *gi, const float *gh, const float *hm, float *h_out, float *gates, void *stream);
-int cn_gru_cell_bwd(int N, const float *gates, const float *hm, const float *dh, float *dgi, float *dgh, float *dhm,
-                    void *stream);
-/* The whole sequence in one launch per direction (W_hh resident in registers, one workgroup per 32 rows):
+ * (rl/networks/srnn_model.py:35-105, selfAttn_srnn_temp_node.py:262-285), under autograd in PPO.update: one launch per direction,
+ * W_hh resident in registers, one workgroup per 16 rows (cn_gru_seq_fwd_sized / _bwd_sized at R = 128, no workspace).
  * gi [T,N,384] = x W_ih^T + b_ih, h0 [N,128], masks [T,N] -> hs [T,N,128]; hms [T,N,128] (masked previous states) and
- * gates [T,N,512] are kept for the backward.  bwd: d_hs [T,N,128] -> dgi [T,N,384], dgh [T,N,384] (the caller forms
+ * gates [T,N,512] = (r, z, n, gh_n) are kept for the backward.  bwd: d_hs [T,N,128] -> dgi [T,N,384], dgh [T,N,384] (the caller forms
  * d(W_hh) = dgh^T hms and d(b_hh) = column sums of dgh) and dh0 [N,128]. */
 int cn_gru_seq_fwd(int T, int N, const float *gi, const float *h0, const float *masks, const float *w_hh, const float *b_hh,
                    float *hs, float *hms, float *gates, void *stream);

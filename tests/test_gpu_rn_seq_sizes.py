@@ -137,17 +137,27 @@ def test_dims_outside_the_box_are_refused_before_anything_is_launched(bad):
                A.ptr(out), A.ptr(out), C.byref(d), A.stream_ptr())
 
 
-@pytest.mark.parametrize("R", [64, 192, 256])
-def test_sized_gru_pair_against_the_fp64_loop(R):
-    """cn_gru_seq_fwd_sized / cn_gru_seq_bwd_sized alone: T = 3 with interior done masks, N = 17 (two workgroups, the second with one row)."""
-    T, N = 3, 17
+GRU_CASES = [(R, 3, 17, False) for R in (64, 128, 192, 256)] + [(128, 1, 1, False), (192, 1, 1, False), (64, 3, 17, True)]
+
+
+def gru_case_id(c):
+    R, T, N, null_ws = c
+    return str(R) + ("" if (T, N) == (3, 17) else "_T%d_N%d" % (T, N)) + ("_null_workspace" if null_ws else "")
+
+
+@pytest.mark.parametrize("case", GRU_CASES, ids=gru_case_id)
+def test_sized_gru_pair_against_the_fp64_loop(case):
+    """cn_gru_seq_fwd_sized / cn_gru_seq_bwd_sized alone: T = 3 with interior done masks, N = 17 (two workgroups, the second with one row) at every R;
+    one step of one row (no next step to publish or to request) on the resident and on the streamed form; and a resident R without a workspace."""
+    R, T, N, null_ws = case
     rs = np.random.RandomState(R)
     gi = rs.uniform(-1, 1, (T, N, 3 * R))
     h0 = rs.uniform(-1, 1, (N, R))
     whh = rs.uniform(-1, 1, (3 * R, R)) * (1.6 / np.sqrt(R))
     bhh = rs.uniform(-0.1, 0.1, 3 * R)
     m = np.ones((T, N))
-    m[0, 0] = m[1, 1] = m[2, 2] = 0.0
+    if T == 3:
+        m[0, 0] = m[1, 1] = m[2, 2] = 0.0      # (a single step keeps its mask: the one zero it could hold would wipe h0, and with it z * h and d(h0))
     d_hs = rs.uniform(-1, 1, (T, N, R))
     t64 = lambda x: torch.from_numpy(x).double().requires_grad_(True)   # noqa: E731
     g, h, w, b = t64(gi), t64(h0), t64(whh), t64(bhh)
@@ -169,25 +179,27 @@ def test_sized_gru_pair_against_the_fp64_loop(R):
 
     f = lambda x: torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)).cuda()   # noqa: E731
     shapes = dict(hs=(T, N, R), hms=(T, N, R), gates=(T, N, 4 * R), dgi=(T, N, 3 * R), dgh=(T, N, 3 * R), dh0=(N, R), ws_f=(3 * R * R,), ws_b=(3 * R * R,))
+    ws = (lambda t: None) if null_ws else A.ptr   # noqa: E731
     outs = []
     d_gi, d_h0, d_m, d_whh, d_bhh, d_dhs = f(gi), f(h0), f(m), f(whh), f(bhh), f(d_hs)
     for _ in range(2):
         bufs = {k: guarded(s) for k, s in shapes.items()}
         v = {k: x[0] for k, x in bufs.items()}
         A.call("cn_gru_seq_fwd_sized", T, N, R, A.ptr(d_gi), A.ptr(d_h0), A.ptr(d_m), A.ptr(d_whh), A.ptr(d_bhh), A.ptr(v["hs"]), A.ptr(v["hms"]),
-               A.ptr(v["gates"]), A.ptr(v["ws_f"]), A.stream_ptr())
+               A.ptr(v["gates"]), ws(v["ws_f"]), A.stream_ptr())
         A.call("cn_gru_seq_bwd_sized", T, N, R, A.ptr(v["gates"]), A.ptr(v["hms"]), A.ptr(d_m), A.ptr(d_whh), A.ptr(d_dhs), A.ptr(v["dgi"]), A.ptr(v["dgh"]),
-               A.ptr(v["dh0"]), A.ptr(v["ws_b"]), A.stream_ptr())
+               A.ptr(v["dh0"]), ws(v["ws_b"]), A.stream_ptr())
         torch.cuda.synchronize()
         for k, (view, whole) in bufs.items():
             assert torch.isnan(whole[view.numel():]).all(), "guard tail behind %s was written" % k
             assert k.startswith("ws_") or not torch.isnan(view).any(), k
+            assert R > 128 or not k.startswith("ws_") or torch.isnan(view).all(), "the resident form wrote into %s" % k
         outs.append({k: v[k].clone() for k in ref})
     for k, r in ref.items():
         got = outs[0][k].double().cpu().numpy()
         err = float(np.abs(got - r).max())
         bar = U.VALUE_BAR if k in ("hs", "hms", "gates") else U.grad_bar(r)
-        print("R = %3d %-5s max |device - fp64| = %.3e  bar %.3e" % (R, k, err, bar))
+        print("%s %-5s max |device - fp64| = %.3e  bar %.3e" % (gru_case_id(case), k, err, bar))
         assert err <= bar, (k, err, bar)
         assert torch.equal(outs[0][k], outs[1][k]), k
 

@@ -14,7 +14,7 @@
             updates per side and tuple): this tree's sized figures must lie below the parent's with intervals that do not overlap, the default
             tuple's median inside the parent's own range.
   gru       one cn_gru_seq_fwd_sized and one cn_gru_seq_bwd_sized launch per R at N = 2048, T = 30: device events, median of 21 after 5 warm-ups
-            (the fragment-image kernel of R != 128 is inside the bracket), beside the kernel's own floor: the W_hh image (12 R^2 bytes) x 128
+            (the fragment-image kernel of R = 192 / 256 is inside the bracket), beside the kernel's own floor: the W_hh image (12 R^2 bytes) x 128
             workgroups x 30 steps over the 34 TB/s L2 rate for the streamed form, a wavefront's serial MFMA count x 16 cycles for the resident forms.
   bench_ab  `python bench.py --gpus 1 --steps 20 --warmup 5` of the tree under --parent-dir (a checkout of the parent commit with its library
             built) and of this tree as alternating child processes, `--rounds` each (the side that goes first alternates as well): ms_per_step of every run.
