@@ -85,6 +85,23 @@ def policy_dims(dims=None):
     return PolicyDims(R, M, A_, O)
 
 
+CN_MAX_PRED = 8                      # include/crowdnav_hip.h
+GST_OBS_LEN = 5
+HORIZON_BOX = "observed length %d, prediction horizon (pred_seq_len = sim.predict_steps) in [1, %d]" % (GST_OBS_LEN, CN_MAX_PRED)
+
+
+def gst_horizon(pred_steps=5, obs_len=GST_OBS_LEN):
+    """The prediction horizon P of the GST device path as an int inside the box -- 5 observed frames (the wrapper's history ring and the frame
+    take-over are built around them), 1 <= P <= CN_MAX_PRED.  Outside it: NotImplementedError naming the box, raised here, in Python, before
+    anything is allocated (and without needing a GPU)."""
+    if int(obs_len) != GST_OBS_LEN or int(obs_len) != obs_len:
+        raise NotImplementedError("an observed length of %s is outside the device box of the GST kernels: %s (CPU tensors run any lengths)" % (obs_len, HORIZON_BOX))
+    if int(pred_steps) != pred_steps or not 1 <= int(pred_steps) <= CN_MAX_PRED:
+        raise NotImplementedError("a prediction horizon of %s steps is outside the device box of the GST kernels: %s (CPU tensors run any horizon)"
+                                  % (pred_steps, HORIZON_BOX))
+    return int(pred_steps)
+
+
 class Obs(C.Structure):
     _fields_ = [("robot_node", C.c_void_p), ("temporal_edges", C.c_void_p), ("spatial_edges", C.c_void_p),
                 ("detected_human_num", C.c_void_p), ("visible_masks", C.c_void_p), ("row_plan", C.c_void_p)]
@@ -246,11 +263,13 @@ ABI_SYMBOLS = [
     "cn_policy_create", "cn_policy_create_sized", "cn_policy_destroy", "cn_policy_set_weights", "cn_policy_act", "cn_policy_get_value",
     "cn_policy_get_taps", "cn_policy_set_gemm_mode", "cn_policy_set_self_attention", "cn_obs_compact_visible", "cn_policy_set_taps", "cn_policy_set_profiling", "cn_policy_get_profile",
     "cn_policy_get_profile_samples", "cn_policy_reset_profile", "cn_prof_set_stamps", "cn_prof_next_step", "cn_hh_block_workspace_bytes", "cn_hh_block_fwd", "cn_rn_seq_workspace_floats", "cn_rn_seq_fwd_workspace_floats", "cn_rn_seq_fwd", "cn_rn_seq_bwd", "cn_rn_seq_workspace_floats_sized", "cn_rn_seq_fwd_workspace_floats_sized", "cn_rn_seq_fwd_sized", "cn_rn_seq_bwd_sized", "cn_gru_seq_fwd_sized", "cn_gru_seq_bwd_sized", "cn_hh_attention_workspace_ints", "cn_hh_attention_fwd", "cn_hh_attention_bwd", "cn_hr_attention_fwd", "cn_hr_attention_bwd", "cn_gru_seq_fwd", "cn_gru_seq_bwd", "cn_embed0_fwd", "cn_embed0_bwd",
-    "cn_split_bf16", "cn_split_bf16_padded", "cn_linear_fwd", "cn_linear_fwd_act", "cn_linear_wgrad_splits", "cn_linear_wgrad", "cn_small_mm", "cn_gst_create", "cn_gst_destroy", "cn_gst_set_weights", "cn_gst_predict",
+    "cn_split_bf16", "cn_split_bf16_padded", "cn_linear_fwd", "cn_linear_fwd_act", "cn_linear_wgrad_splits", "cn_linear_wgrad", "cn_small_mm", "cn_gst_create", "cn_gst_create_horizon", "cn_gst_pred_steps", "cn_gst_destroy", "cn_gst_set_weights", "cn_gst_predict",
     "cn_gst_wrapper_reset", "cn_gst_wrapper_step", "cn_gst_wrapper_set_interval", "cn_gst_wrapper_history_len", "cn_gst_wrapper_save", "cn_gst_wrapper_load", "cn_gae", "cn_adv_stats", "cn_adv_normalize", "cn_episode_stats_update", "cn_eval_state_words", "cn_eval_accumulate",
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
     "cn_ppo_minibatch_max_rows", "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
+    "cn_gst_train_workspace_bytes_horizon", "cn_gst_train_step_horizon", "cn_gst_eval_workspace_bytes_horizon", "cn_gst_eval_step_horizon",
+    "cn_gst_data_frames_horizon", "cn_gst_data_count_horizon", "cn_gst_data_fill_horizon", "cn_gst_gather_batch_horizon",
     "cn_env_get_visibility", "cn_render_scenes",
     "cn_env_trace_append", "cn_trace_metrics", "cn_render_trajectories",
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
@@ -375,6 +394,8 @@ def lib():
         L.cn_small_mm.argtypes = [i32, i32, i32, vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp]
         L.cn_linear_wgrad.argtypes = [i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]
         L.cn_gst_create.argtypes = [i32, i32, C.POINTER(vp)]
+        L.cn_gst_create_horizon.argtypes = [i32, i32, i32, C.POINTER(vp)]
+        L.cn_gst_pred_steps.argtypes = [vp]
         L.cn_gst_destroy.argtypes = [vp]
         L.cn_gst_set_weights.argtypes = [vp, C.POINTER(GstWeights), vp]
         L.cn_gst_predict.argtypes = [vp, i32, vp, vp, vp, vp, vp]
@@ -406,6 +427,17 @@ def lib():
         L.cn_gst_data_count.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gst_data_fill.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
         L.cn_gst_gather_batch.argtypes = [i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        # the same calls with the prediction horizon P (the ones above: P = 5)
+        L.cn_gst_train_workspace_bytes_horizon.restype = C.c_int64
+        L.cn_gst_train_workspace_bytes_horizon.argtypes = [i32, i32, i32]
+        L.cn_gst_train_step_horizon.argtypes = [i32, i32, i32, vp, vp, vp, C.POINTER(GstWeights), C.POINTER(GstWeights), f32, C.c_uint64, vp, i64, vp, vp, vp]
+        L.cn_gst_eval_workspace_bytes_horizon.restype = C.c_int64
+        L.cn_gst_eval_workspace_bytes_horizon.argtypes = [i32, i32, i32, i32]
+        L.cn_gst_eval_step_horizon.argtypes = [i32, i32, i32, i32, vp, vp, vp, C.POINTER(GstWeights), vp, vp, i64, vp, vp, vp, vp]
+        L.cn_gst_data_frames_horizon.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp]
+        L.cn_gst_data_count_horizon.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_gst_data_fill_horizon.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_gst_gather_batch_horizon.argtypes = [i32, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_ppo_minibatch_max_rows.restype = C.c_int64
         L.cn_ppo_minibatch_max_rows.argtypes = []
         L.cn_ppo_minibatch_workspace_bytes.restype = C.c_int64

@@ -5,7 +5,9 @@
 //   .../gumbel_social_transformer.py:43-96, node_encoder_layer_no_ghost.py:25-66, mha.py:236-242 (spatial_num_heads_edges = 0:
 //       fully connected; float adjacency mask multiplied AFTER the softmax, then renormalised)
 //   rl/vec_env/vec_pretext_normalize.py:85-191                            history buffers, social penalty, edge write, sort
-// Shipped hyper-parameters only: embedding 64, 8 heads x 8, 1 encoder layer, FFN 128, LSTM 64, obs 5 / pred 5, output 5.
+// Shipped hyper-parameters only: embedding 64, 8 heads x 8, 1 encoder layer, FFN 128, LSTM 64, obs 5, output 5.  The prediction horizon P
+// (pred_seq_len = sim.predict_steps) is a setting of the handle, 1 .. CN_MAX_PRED (cn_gst_create_horizon; cn_gst_create: the shipped 5): the
+// decode is a recurrence, so the parameters and the observed-frame side (obs prep, take-over, the five encoder passes) do not depend on it.
 //
 // Row index space: a "slab" has S time slices (S = 5 for the observation pass, 1 for each decode step);
 // row = (env * S + t) * H + human.  Round 2: a forward is 16 launches instead of ~66 -- the NodeEncoderLayer is ONE kernel
@@ -22,7 +24,7 @@
 
 namespace {
 
-constexpr int GT = 5, GP = 5; // obs_seq_len, pred_seq_len
+constexpr int GT = 5, GP_DEFAULT = 5; // obs_seq_len; pred_seq_len of cn_gst_create (the handle's P otherwise: 1 .. CN_MAX_PRED)
 constexpr float GST_INVALID = -999.0f;
 
 // masks + displacements (crowd_nav_interface_parallel.py:71-89).  traj element (e,h,t) lives at
@@ -350,8 +352,8 @@ struct GstLstmArgs {
     float *h, *c;                   // [E*H, 64] state, updated in place
     const float *blend_mask, *post_mask; // [E*H] or null
     // decode head of the step that follows this LSTM pass (hidden2pos + raw2gaussian + the running sums of
-    // crowd_nav_interface_parallel.py:99-113), tt = decode step index; head_w == null: no head
-    int tt;
+    // crowd_nav_interface_parallel.py:99-113), tt = decode step index of the handle's P (out_traj is [E*H, P, 5]); head_w == null: no head
+    int tt, P;
     int zero_state;                 // 1: h = c = 0 on entry (the observation pass) instead of two memsets of the state in front of the launch
     const float *head_w, *head_b, *lm_fp, *last_pos;
     float *acc, *out_traj, *x_sample;
@@ -503,7 +505,7 @@ __global__ __launch_bounds__(512, 2) void gst_lstm_kernel(int E, int H, int S, G
                 const float a2 = (tt ? t_acc[2] : 0.f) + sx * sx, a3 = (tt ? t_acc[3] : 0.f) + sy * sy, a4 = (tt ? t_acc[4] : 0.f) + corr * sx * sy;
                 ac[0] = a0; ac[1] = a1; ac[2] = a2; ac[3] = a3; ac[4] = a4;
                 const float sxc = sqrtf(a2), syc = sqrtf(a3);
-                float *o = a.out_traj + ((size_t)n * GP + tt) * 5;
+                float *o = a.out_traj + ((size_t)n * a.P + tt) * 5;
                 o[0] = (a0 + t_lp0) * lm + GST_INVALID * (1.0f - lm);
                 o[1] = (a1 + t_lp1) * lm + GST_INVALID * (1.0f - lm);
                 o[2] = sxc; o[3] = syc; o[4] = a4 / (sxc * syc);
@@ -534,7 +536,9 @@ __global__ void pretext_fill_kernel(size_t n, float *__restrict__ ring_traj, uin
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) { ring_traj[2 * i] = GST_INVALID; ring_traj[2 * i + 1] = GST_INVALID; ring_mask[i] = 0; }
 }
-// social penalty, prediction write-back into spatial_edges[:, :, 2:], stable sort by current distance: one wavefront per env
+// social penalty, prediction write-back into spatial_edges[:, :, 2:], stable sort by current distance: one wavefront per env.  One instantiation
+// per horizon GP (D = 2 (GP + 1)): the row lives in registers at every P, and GP = 5 is the kernel it always was.
+template <int GP>
 __global__ __launch_bounds__(64) void pretext_post_kernel(int E, int H, int D, const float *__restrict__ robot_node, const float *__restrict__ se_in,
                                                           const float *__restrict__ out_traj, const float *__restrict__ out_mask, float dist,
                                                           float collision_penalty, float *__restrict__ rews, float *__restrict__ se_out)
@@ -635,6 +639,7 @@ constexpr size_t g_align(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct cn_gst {
     int H, maxE;
+    int P;             // prediction horizon: decode steps per forward, out_traj [N, P, 5], edge width 2 (P + 1)
     bool weights_set;
     char *blob;
     float *emb_w, *emb_b, *in_w, *in_b, *out_w, *out_b, *n_w, *n_b, *n1_w, *n1_b, *l1_w, *l1_b, *l2_w, *l2_b;
@@ -672,20 +677,25 @@ static int gst_alloc_ring(cn_gst *g, int interval)
     return CN_OK;
 }
 
-extern "C" int cn_gst_create(int human_num, int max_envs, cn_gst **out)
+extern "C" int cn_gst_create(int human_num, int max_envs, cn_gst **out) { return cn_gst_create_horizon(human_num, max_envs, GP_DEFAULT, out); }
+
+extern "C" int cn_gst_pred_steps(const cn_gst *g) { return g ? g->P : 0; }
+
+extern "C" int cn_gst_create_horizon(int human_num, int max_envs, int pred_steps, cn_gst **out)
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(out && human_num >= 1 && human_num <= CN_MAX_HUMANS && max_envs >= 1, "cn_gst_create: bad argument");
+    CN_REQUIRE(pred_steps >= 1 && pred_steps <= CN_MAX_PRED, "cn_gst_create_horizon: pred_steps %d is outside [1, %d]", pred_steps, CN_MAX_PRED);
     cn_gst *g = new (std::nothrow) cn_gst{};
     CN_REQUIRE(g, "cn_gst_create: out of host memory");
-    g->H = human_num; g->maxE = max_envs;
+    g->H = human_num; g->maxE = max_envs; g->P = pred_steps;
     const size_t N = (size_t)max_envs * human_num, R = N * GT;
     size_t off = 0;
     auto carve = [&](size_t nfloat) { size_t o = off; off += g_align(nfloat * sizeof(float)); return o; };
     const size_t o_w[] = {carve(128), carve(64), carve(192 * 64), carve(192), carve(64 * 64), carve(64), carve(64), carve(64), carve(64), carve(64),
                           carve(128 * 64), carve(128), carve(64 * 128), carve(64), carve(256 * 64), carve(256 * 64), carve(256), carve(256), carve(320), carve(5)};
     const size_t o_mrel = carve(R), o_lm = carve(N), o_rel = carve(2 * R), o_lp = carve(2 * N), o_xs = carve(R * 64);
-    const size_t o_h = carve(N * 64), o_c = carve(N * 64), o_acc = carve(N * 5), o_xsamp = carve(N * 2), o_ot = carve(N * GP * 5), o_om = carve(N);
+    const size_t o_h = carve(N * 64), o_c = carve(N * 64), o_acc = carve(N * 5), o_xsamp = carve(N * 2), o_ot = carve(N * pred_steps * 5), o_om = carve(N);
     const size_t o_wcat = carve(256 * 128), o_flstm = carve(256 * 128);
     const size_t o_mrelp = carve(R), o_relp = carve(2 * R), o_xsp = carve(R * 64), o_xsd = carve(N * 64), o_gl = carve(R / human_num + 64);
     const size_t o_fin = carve(192 * 64), o_fout = carve(64 * 64), o_fl1 = carve(128 * 64), o_fl2 = carve(64 * 128);
@@ -752,6 +762,19 @@ extern "C" int cn_gst_set_timing(long long *buf)
 }
 #endif
 
+// pretext_post_kernel of a horizon P = 1 .. CN_MAX_PRED
+static int gst_post(int P, int E, int H, int D, const float *robot_node, const float *se_in, const float *out_traj, const float *out_mask, float dist,
+                    float collision_penalty, float *rews, float *se_out, hipStream_t st)
+{
+    using Post = void (*)(int, int, int, const float *, const float *, const float *, const float *, float, float, float *, float *);
+    static const Post post[CN_MAX_PRED] = {pretext_post_kernel<1>, pretext_post_kernel<2>, pretext_post_kernel<3>, pretext_post_kernel<4>,
+                                           pretext_post_kernel<5>, pretext_post_kernel<6>, pretext_post_kernel<7>, pretext_post_kernel<8>};
+    static_assert(CN_MAX_PRED == 8, "one instantiation per horizon");
+    hipLaunchKernelGGL(post[P - 1], dim3(E), dim3(64), 0, st, E, H, D, robot_node, se_in, out_traj, out_mask, dist, collision_penalty, rews, se_out);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 // NodeEncoderLayer over `rows` rows in groups of H nodes: x2 [rows,2], mask [rows] -> g->xs [rows,64] (one launch)
 static int gst_layer(cn_gst *g, int rows, const float *x2, const float *mask, hipStream_t st, float *xs_out = nullptr, bool listed = false)
 {
@@ -771,7 +794,7 @@ static int gst_layer(cn_gst *g, int rows, const float *x2, const float *mask, hi
 static int gst_lstm(cn_gst *g, int E, int S, const float *in_mask, const float *blend_mask, const float *post_mask, int tt, float *out_traj, hipStream_t st,
                     int zero_state = 0, const float *xs_in = nullptr)
 {
-    GstLstmArgs a{xs_in ? xs_in : g->xs, in_mask, g->f_lstm, g->bih, g->bhh, g->h, g->c, blend_mask, post_mask, tt, zero_state, g->h2p_w, g->h2p_b, g->lm_fp, g->last_pos,
+    GstLstmArgs a{xs_in ? xs_in : g->xs, in_mask, g->f_lstm, g->bih, g->bhh, g->h, g->c, blend_mask, post_mask, tt, g->P, zero_state, g->h2p_w, g->h2p_b, g->lm_fp, g->last_pos,
                   g->acc, out_traj, g->x_sample};
     // Tile size: a pass over an 80-node tile costs ~2.25x a pass over a 32-node one (measured at 2048 envs x 20 nodes: 2 tiles of 80 per workgroup
     // 0.716 ms per step against 5 tiles of 32 0.745, 64-node tiles 0.767: 640 tiles on 256 workgroups leave a third of them idle in the last
@@ -813,7 +836,7 @@ static int gst_forward(cn_gst *g, int E, const float *traj, long long se, long l
     } else if ((rc = gst_layer(g, R, g->rel, g->m_rel, st))) return rc;
     if ((rc = gst_lstm(g, E, GT, g->m_rel, nullptr, g->lm_fp, 0, out_traj, st, 1))) return rc; // from h = c = 0; + the head of decode step 0
     // prediction period (recursive decoding on the mean)
-    for (int tt = 1; tt < GP; ++tt) {
+    for (int tt = 1; tt < g->P; ++tt) {
         if ((rc = gst_layer(g, N, g->x_sample, g->lm_fp, st, g->xs_dec))) return rc;
         if ((rc = gst_lstm(g, E, 1, g->lm_fp, g->lm_fp, nullptr, tt, out_traj, st, 0, g->xs_dec))) return rc; // + the head of decode step tt
     }
@@ -878,7 +901,7 @@ extern "C" int cn_gst_wrapper_step(cn_gst *g, int E, const cn_obs *obs, float ro
     CN_REQUIRE(g && obs && obs->robot_node && obs->spatial_edges && obs->visible_masks && spatial_edges_out, "cn_gst_wrapper_step: null argument");
     if (g->ring_E != E) { cn_set_error("cn_gst_wrapper_step: call cn_gst_wrapper_reset(E=%d) first", E); return CN_ERR_STATE; }
     hipStream_t st = (hipStream_t)stream;
-    const int H = g->H, D = 2 * (GP + 1), N = E * H;
+    const int H = g->H, D = 2 * (g->P + 1), N = E * H;
     // deque.append: the oldest slot is overwritten; time order = slots (pos+1 .. pos+len) % len, of which every interval-th is read
     // (in_traj[:, :, ::pred_interval]: the oldest, ..., the newest -- len = (GT-1) * interval + 1)
     hipLaunchKernelGGL(pretext_push_kernel, dim3((N + 255) / 256), dim3(256), 0, st, E, H, D, obs->robot_node, obs->spatial_edges, obs->visible_masks,
@@ -888,9 +911,6 @@ extern "C" int cn_gst_wrapper_step(cn_gst *g, int E, const cn_obs *obs, float ro
     g->ring_pos = rot;
     if (int rc = gst_forward(g, E, g->ring_traj, (long long)H * 2, 2, (long long)N * 2, g->ring_mask, nullptr, H, 1, N, rot, g->interval, g->ring_len,
                              g->out_traj, g->lm_fp, st)) return rc;
-    float *rw = rewards;
-    hipLaunchKernelGGL(pretext_post_kernel, dim3(E), dim3(64), 0, st, E, H, D, obs->robot_node, obs->spatial_edges, g->out_traj, g->lm_fp,
-                       robot_plus_human_radius, collision_penalty, rw ? rw : g->acc /*scratch*/, spatial_edges_out);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    return gst_post(g->P, E, H, D, obs->robot_node, obs->spatial_edges, g->out_traj, g->lm_fp, robot_plus_human_radius, collision_penalty,
+                    rewards ? rewards : g->acc /*scratch*/, spatial_edges_out, st);
 }

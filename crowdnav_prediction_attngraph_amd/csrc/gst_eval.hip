@@ -6,11 +6,12 @@
 // (average / final offset error).  The same forward as gst_train.hip without the reverse pass.
 //
 // Mapping.  Nothing is kept for a reverse pass, so a sequence's activations live in LDS: seven [N,64] slots (h, c, two temporaries and
-// the q|k|v block, each reused along the layer) -- 112 KB at 64 pedestrians, 35 KB at 20; the attention probabilities are never stored
+// the q|k|v block, each reused along the layer) -- 112 KB at 64 pedestrians, 35 KB at 20, and 133 KB with everything else at 64 pedestrians and
+// P = 8, inside the CU's 160 KiB (asserted below); the attention probabilities are never stored
 // (each (row, head) thread makes two passes over the keys: maximum, then the exponentials with their sums); the 67 k weights stream
 // from L2.  Two launches: gst_eval_encode_kernel, one workgroup per SEQUENCE, runs the five observed encoder passes and LSTM steps --
 // they do not depend on the draws -- and leaves (h, c) in the workspace; gst_eval_decode_kernel, one workgroup per (sequence, sample),
-// starts from that state and runs the five decode steps, the loss and the offset errors.  Plain fp32 FMA arithmetic with the training
+// starts from that state and runs the P decode steps (P = pred_seq_len in 1 .. 8, the kernels' template parameter GP), the loss and the offset errors.  Plain fp32 FMA arithmetic with the training
 // kernel's summation orders; every reduction has a fixed order (no atomics), so equal arguments give equal bits.
 #include "common.h"
 #include "gst_model.h"
@@ -28,9 +29,12 @@ constexpr int RB = 4; // rows per thread in the matrix products: one weight load
 struct Lds {
     float *H, *C, *T0, *T1, *Q, *X2, *MK, *MFP, *LM, *XS5, *RAW, *RED;
 };
-__host__ __device__ inline int eval_lds_floats(int N) { return 7 * N * 64 + ((N * 2 + 3) & ~3) + 64 + 64 + N * TT + GP * N * 2 + GP * N * 5 + 8; }
+__host__ __device__ constexpr int eval_lds_floats(int N, int GP) { return 7 * N * 64 + ((N * 2 + 3) & ~3) + 64 + 64 + N * seq_steps(GP) + GP * N * 2 + GP * N * 5 + 8; }
+static_assert(eval_lds_floats(MAXN, GP_MAX) * sizeof(float) <= 160 * 1024, "the largest (N, P) fits gfx950's 160 KiB of LDS per CU");
+template <int GP>
 __device__ inline Lds carve(float *p, int N)
 {
+    constexpr int TT = seq_steps(GP);
     Lds L;
     const int slot = N * 64;
     L.H = p; p += slot;
@@ -217,10 +221,12 @@ __device__ float block_sum(float v, float *red)
 }
 
 // observed period of one sequence: five encoder passes and LSTM steps -> (h, c) times lm_fp into state [B][2][N,64]
+template <int GP>
 __global__ __launch_bounds__(NT) void gst_eval_encode_kernel(int N, const float *__restrict__ v_obs, const float *__restrict__ lm_all, Wts W, float *__restrict__ state)
 {
+    constexpr int TT = seq_steps(GP);
     extern __shared__ __align__(16) float lds_eval[];
-    const Lds L = carve(lds_eval, N);
+    const Lds L = carve<GP>(lds_eval, N);
     const int b = blockIdx.x;
     for (int i = threadIdx.x; i < N * TT; i += NT) L.LM[i] = lm_all[(size_t)b * N * TT + i];
     for (int idx = threadIdx.x; idx < N * 64; idx += NT) { L.H[idx] = 0.0f; L.C[idx] = 0.0f; }
@@ -240,13 +246,15 @@ __global__ __launch_bounds__(NT) void gst_eval_encode_kernel(int N, const float 
     }
 }
 
-// prediction period of one (sequence, sample): head, sample (or mean), four encoder passes + LSTM steps on what was fed back, loss, offset errors
+// prediction period of one (sequence, sample): head, sample (or mean), GP - 1 encoder passes + LSTM steps on what was fed back, loss, offset errors
+template <int GP>
 __global__ __launch_bounds__(NT) void gst_eval_decode_kernel(int N, int S1, const float *__restrict__ v_pred, const float *__restrict__ lm_all, Wts W,
                                                               const float *__restrict__ noise, const float *__restrict__ state, float *__restrict__ seq_out,
                                                               float *__restrict__ ped_out, float *__restrict__ gauss_out)
 {
+    constexpr int TT = seq_steps(GP);
     extern __shared__ __align__(16) float lds_eval[];
-    const Lds L = carve(lds_eval, N);
+    const Lds L = carve<GP>(lds_eval, N);
     const int bs = blockIdx.x, b = bs / S1;
     const float *st = state + (size_t)b * 2 * N * 64;
     for (int i = threadIdx.x; i < N * TT; i += NT) L.LM[i] = lm_all[(size_t)b * N * TT + i];
@@ -304,7 +312,7 @@ __global__ __launch_bounds__(NT) void gst_eval_decode_kernel(int N, int S1, cons
             cnt += 1.0f;
         }
     }
-    // average / final offset error (mgnn/utils.py:8-28) of the fed-back values, for the pedestrians present at all ten steps; everyone else: exactly 0
+    // average / final offset error (mgnn/utils.py:8-28) of the fed-back values, for the pedestrians present at all TT steps; everyone else: exactly 0
     for (int n = threadIdx.x; n < N; n += NT) {
         float present = 0.0f;
         for (int t = 0; t < TT; ++t) present += L.LM[n * TT + t];
@@ -343,20 +351,28 @@ size_t eval_ws_bytes(int B, int N) { return ((size_t)B * 2 * N * 64 * sizeof(flo
 
 } // namespace
 
-extern "C" int64_t cn_gst_eval_workspace_bytes(int B, int N, int S)
+extern "C" int64_t cn_gst_eval_workspace_bytes_horizon(int B, int N, int S, int P)
 {
-    if (B < 1 || N < 4 || N > MAXN || S < 0 || S > MAXS) return 0;
+    if (B < 1 || N < 4 || N > MAXN || S < 0 || S > MAXS || P < 1 || P > GP_MAX) return 0;
     return (int64_t)eval_ws_bytes(B, N);
 }
+extern "C" int64_t cn_gst_eval_workspace_bytes(int B, int N, int S) { return cn_gst_eval_workspace_bytes_horizon(B, N, S, GP_DEFAULT); }
 
 extern "C" int cn_gst_eval_step(int B, int N, int S, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const float *noise,
+                                void *workspace, int64_t workspace_bytes, float *seq_out, float *ped_out, float *gauss_out, void *stream)
+{
+    return cn_gst_eval_step_horizon(B, N, S, GP_DEFAULT, v_obs, v_pred, loss_mask_rel, w, noise, workspace, workspace_bytes, seq_out, ped_out, gauss_out, stream);
+}
+
+extern "C" int cn_gst_eval_step_horizon(int B, int N, int S, int P, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const float *noise,
                                 void *workspace, int64_t workspace_bytes, float *seq_out, float *ped_out, float *gauss_out, void *stream)
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(B >= 1 && N >= 4 && N <= MAXN, "cn_gst_eval_step: B=%d sequences of N=%d pedestrians outside B >= 1, 4 <= N <= 64 (pad small crowds with absent pedestrians)", B, N);
     CN_REQUIRE(S >= 0 && S <= MAXS, "cn_gst_eval_step: S=%d samples per sequence outside 0 (validation: decode on the mean) .. 64", S);
+    CN_REQUIRE(P >= 1 && P <= GP_MAX, "cn_gst_eval_step: P=%d predicted steps outside [1, %d]", P, GP_MAX);
     CN_REQUIRE(v_obs && v_pred && loss_mask_rel && w && workspace && seq_out, "cn_gst_eval_step: null argument (v_obs, v_pred, loss_mask_rel, w, workspace, seq_out are required)");
-    CN_REQUIRE(S == 0 || noise, "cn_gst_eval_step: noise is NULL with S=%d samples: the caller supplies the [B,S,5,N,2] standard-normal draws", S);
+    CN_REQUIRE(S == 0 || noise, "cn_gst_eval_step: noise is NULL with S=%d samples: the caller supplies the [B,S,P,N,2] standard-normal draws", S);
     CN_REQUIRE(S > 0 || !noise, "cn_gst_eval_step: noise given with S=0 (validation decodes on the mean; pass NULL)");
     const size_t need = eval_ws_bytes(B, N);
     CN_REQUIRE(workspace_bytes >= (int64_t)need && ((uintptr_t)workspace & 15) == 0, "cn_gst_eval_step: workspace of %lld bytes (16-byte aligned) needed, got %lld",
@@ -368,15 +384,19 @@ extern "C" int cn_gst_eval_step(int B, int N, int S, const float *v_obs, const f
         W.p[i] = wp[i];
     }
     const int S1 = S > 0 ? S : 1;
-    const size_t lds = (size_t)eval_lds_floats(N) * sizeof(float);
-    const int max_lds = eval_lds_floats(MAXN) * (int)sizeof(float);
-    if (int rc = cn_lds_opt_in<&gst_eval_encode_kernel>(max_lds)) return rc;
-    if (int rc = cn_lds_opt_in<&gst_eval_decode_kernel>(max_lds)) return rc;
+    const size_t lds = (size_t)eval_lds_floats(N, P) * sizeof(float);
+    CN_REQUIRE(lds <= 160 * 1024, "cn_gst_eval_step: N=%d pedestrians at P=%d predicted steps need %zu bytes of LDS, a CU has 160 KiB", N, P, lds);
     hipStream_t st = (hipStream_t)stream;
     float *state = (float *)workspace;
-    hipLaunchKernelGGL(gst_eval_encode_kernel, dim3(B), dim3(NT), lds, st, N, v_obs, loss_mask_rel, W, state);
-    CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gst_eval_decode_kernel, dim3(B * S1), dim3(NT), lds, st, N, S1, v_pred, loss_mask_rel, W, noise, state, seq_out, ped_out, gauss_out);
-    CN_CHECK_LAUNCH();
-    return CN_OK;
+    return for_horizon(P, [&](auto gp) -> int {
+        constexpr int GP = decltype(gp)::value;
+        constexpr int max_lds = eval_lds_floats(MAXN, GP) * (int)sizeof(float);
+        if (int rc = cn_lds_opt_in<&gst_eval_encode_kernel<GP>>(max_lds)) return rc;
+        if (int rc = cn_lds_opt_in<&gst_eval_decode_kernel<GP>>(max_lds)) return rc;
+        hipLaunchKernelGGL(gst_eval_encode_kernel<GP>, dim3(B), dim3(NT), lds, st, N, v_obs, loss_mask_rel, W, state);
+        CN_CHECK_LAUNCH();
+        hipLaunchKernelGGL(gst_eval_decode_kernel<GP>, dim3(B * S1), dim3(NT), lds, st, N, S1, v_pred, loss_mask_rel, W, noise, state, seq_out, ped_out, gauss_out);
+        CN_CHECK_LAUNCH();
+        return CN_OK;
+    });
 }

@@ -3,15 +3,17 @@
 // Reference: gst_updated/scripts/experiments/train.py:107-146 (the loop body: forward, negative log-likelihood, backward) over
 // gst_updated/src/gumbel_social_transformer/st_model.py:271-455 (training-time forward: 'faster_lstm', recursive decoding on the mean,
 // only_observe_full_period = False) and :62-112 (negative_log_likelihood_full_partial), for the shipped hyper-parameters (embedding 64,
-// 8 heads, one NodeEncoderLayer without ghost / edge heads, LSTM 64, 5 observed + 5 predicted steps).  The host mirror of the same
+// 8 heads, one NodeEncoderLayer without ghost / edge heads, LSTM 64, 5 observed + P predicted steps, P = pred_seq_len in 1 .. 8: the kernels' template parameter GP).  The host mirror of the same
 // math in torch ops is crowdnav_prediction_attngraph_amd/gst_train.py (forward_train / negative_log_likelihood_full_partial).
 //
-// Mapping.  A sequence is <= 64 pedestrians x 10 steps through a 67 k-parameter model: one WORKGROUP per sequence (B sequences of a
-// batch per launch), every activation of the nine encoder-layer passes and nine LSTM steps kept in a per-sequence scratch slab for
+// Mapping.  A sequence is <= 64 pedestrians x (5 + P) steps through a 67 k-parameter model: one WORKGROUP per sequence (B sequences of a
+// batch per launch), every activation of the 4 + P encoder-layer passes and 4 + P LSTM steps (nine each at P = 5) kept in a per-sequence scratch slab for
 // the hand-derived reverse pass, every parameter gradient accumulated in a per-workgroup slab (no atomics, fixed summation orders)
 // and reduced over the batch by a second launch.  Plain fp32 FMA arithmetic: the products are 64 x 64 x 192 at most.
 // Dropout (the reference's four sites: attention probabilities, out_proj output, FFN hidden, FFN output; p = 0.1 in training) draws its
 // masks from a counter-based hash of (seed, layer pass, site, element), regenerated in the backward pass -- its own stream, not torch's.
+// The layer pass (`call`) counts the 4 + P passes of a sequence in forward order: 0 .. 4 the observed slices, 5 + (tt - 1) the pass in front of
+// decode step tt = 1 .. P - 1; the passes a shorter horizon has draw what they draw at a longer one (the rule: include/crowdnav_hip.h).
 #include "common.h"
 #include "gst_model.h"
 
@@ -35,7 +37,7 @@ struct Lay {
     // work buffers inside `work`
     int w_dx, w_dh, w_dc, w_dqkv, w_ds, w_do, w_t64a, w_t64b, w_t128, w_dg, w_dx2, w_hcur, w_ccur, w_xs, w_xsample, w_dmu, work_size;
 };
-__host__ __device__ inline Lay make_lay(int N)
+__host__ __device__ inline Lay make_lay(int N, int GP)
 {
     Lay L{};
     L.N = N;
@@ -52,7 +54,7 @@ __host__ __device__ inline Lay make_lay(int N)
     L.w_t128 = f(N * 128); L.w_dg = f(N * 256); L.w_dx2 = f(N * 2); L.w_hcur = f(N * 64); L.w_ccur = f(N * 64); L.w_xs = f(N * 64); L.w_xsample = f(N * 2); L.w_dmu = f(N * 2);
     L.work_size = o;
     o = 0;
-    L.calls = f(NCALL * L.call_size); L.steps = f(NSTEP * L.step_size); L.hdec = f(GP * N * 64); L.raw = f(GP * N * 5); L.work = f(L.work_size);
+    L.calls = f(ncall(GP) * L.call_size); L.steps = f(nstep(GP) * L.step_size); L.hdec = f(GP * N * 64); L.raw = f(GP * N * 5); L.work = f(L.work_size);
     L.total = o;
     return L;
 }
@@ -379,8 +381,10 @@ __device__ void lstm_bwd(const Lay &L, const float *Sx, const Wts &W, const Grd 
 }
 
 // count of valid (predicted step, pedestrian) pairs of the whole batch: the loss's denominator (train.py:133)
+template <int GP>
 __global__ void gst_count_kernel(int B, int N, const float *__restrict__ lm, float *__restrict__ count)
 {
+    constexpr int TT = seq_steps(GP);
     __shared__ float red[NT];
     float s = 0.0f;
     for (int idx = threadIdx.x; idx < B * N * GP; idx += NT) {
@@ -394,14 +398,16 @@ __global__ void gst_count_kernel(int B, int N, const float *__restrict__ lm, flo
     if (threadIdx.x == 0) count[0] = red[0];
 }
 
+template <int GP>
 __global__ __launch_bounds__(NT) void gst_train_kernel(int N, const float *__restrict__ v_obs, const float *__restrict__ v_pred, const float *__restrict__ lm_all, Wts W,
                                                         float p_drop, unsigned long long seed, float *__restrict__ scratch, float *__restrict__ grad_slabs,
                                                         const float *__restrict__ count, float *__restrict__ loss_part, float *__restrict__ gauss_out)
 {
     __shared__ float lds[768]; // [0,64) row mask of the current pass | [64,128) lm_fp | [128,132) loss partials | [160,672) LayerNorm-backward sums
+    constexpr int TT = seq_steps(GP);
     __shared__ float s_lm[64 * TT];
     const int b = blockIdx.x;
-    const Lay L = make_lay(N);
+    const Lay L = make_lay(N, GP);
     float *base = scratch + (size_t)b * L.total;
     float *Wk = base + L.work;
     float *gs = grad_slabs + (size_t)b * NPARAMS;
@@ -460,7 +466,7 @@ __global__ __launch_bounds__(NT) void gst_train_kernel(int N, const float *__res
     // ================= loss (st_model.py:62-112) and its gradient w.r.t. the raw head outputs =================
     const float inv_count = 1.0f / fmaxf(count[0], 1e-20f);
     float lsum = 0.0f;
-    // d raw [GP][N][5] overwrites RAW's place in a work buffer: reuse w_dg (N * 256 >= GP * N * 5)
+    // d raw [GP][N][5] overwrites RAW's place in a work buffer: reuse w_dg (N * 256 >= GP * N * 5 up to GP = 51)
     float *DRAW = Wk + L.w_dg;
     for (int idx = threadIdx.x; idx < GP * N; idx += NT) {
         const int tt = idx / N, n = idx - tt * N;
@@ -519,7 +525,7 @@ __global__ __launch_bounds__(NT) void gst_train_kernel(int N, const float *__res
             }
             __syncthreads();
             // (lstm_bwd uses w_dg, which holds DRAW: the rows of steps < tt are still needed -> move them out of the way first)
-            float *DRAWS = Wk + L.w_hcur; // (the forward's running state is dead by now; layer_bwd below uses w_ds / w_t128 / w_do itself)
+            float *DRAWS = Wk + L.w_hcur; // ((GP - 1) * N * 5 <= N * 64 floats up to GP = 13; the forward's running state is dead by now; layer_bwd below uses w_ds / w_t128 / w_do itself)
             for (int idx = threadIdx.x; idx < tt * N * 5; idx += NT) DRAWS[idx] = DRAW[idx];
             __syncthreads();
             // T1 / T2 live in w_t64a / w_t64b, which layer_bwd uses: park them in w_xs / w_do
@@ -569,32 +575,42 @@ __global__ void gst_grad_reduce_kernel(int B, const float *__restrict__ slabs, G
 }
 
 struct TrainWs { size_t scratch, slabs, count, loss_part, total; };
-TrainWs train_ws(int B, int N)
+TrainWs train_ws(int B, int N, int P)
 {
     TrainWs w{};
     size_t off = 0;
     auto f = [&](size_t n) { size_t o = off; off += (n * 4 + 255) & ~size_t(255); return o; };
-    w.scratch = f((size_t)B * make_lay(N).total); w.slabs = f((size_t)B * NPARAMS); w.count = f(4); w.loss_part = f((size_t)B);
+    w.scratch = f((size_t)B * make_lay(N, P).total); w.slabs = f((size_t)B * NPARAMS); w.count = f(4); w.loss_part = f((size_t)B);
     w.total = off;
     return w;
 }
 
 } // namespace
 
-extern "C" int64_t cn_gst_train_workspace_bytes(int B, int N)
+static_assert(GP_MAX * 5 <= 256 && (GP_MAX - 1) * 5 <= 64, "d raw [GP][N][5] is parked in w_dg / w_hcur");
+
+extern "C" int64_t cn_gst_train_workspace_bytes_horizon(int B, int N, int P)
 {
-    if (B < 1 || N < 4 || N > 64) return 0;
-    return (int64_t)train_ws(B, N).total;
+    if (B < 1 || N < 4 || N > 64 || P < 1 || P > GP_MAX) return 0;
+    return (int64_t)train_ws(B, N, P).total;
 }
+extern "C" int64_t cn_gst_train_workspace_bytes(int B, int N) { return cn_gst_train_workspace_bytes_horizon(B, N, GP_DEFAULT); }
 
 extern "C" int cn_gst_train_step(int B, int N, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const cn_gst_weights *grads,
                                  float p_drop, uint64_t seed, void *workspace, int64_t workspace_bytes, float *loss_out, float *gauss_out, void *stream)
 {
+    return cn_gst_train_step_horizon(B, N, GP_DEFAULT, v_obs, v_pred, loss_mask_rel, w, grads, p_drop, seed, workspace, workspace_bytes, loss_out, gauss_out, stream);
+}
+
+extern "C" int cn_gst_train_step_horizon(int B, int N, int P, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const cn_gst_weights *grads,
+                                 float p_drop, uint64_t seed, void *workspace, int64_t workspace_bytes, float *loss_out, float *gauss_out, void *stream)
+{
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(B >= 1 && N >= 4 && N <= 64, "cn_gst_train_step: B=%d sequences of N=%d pedestrians outside B >= 1, 4 <= N <= 64 (pad small crowds with absent pedestrians)", B, N);
+    CN_REQUIRE(P >= 1 && P <= GP_MAX, "cn_gst_train_step: P=%d predicted steps outside [1, %d]", P, GP_MAX);
     CN_REQUIRE(v_obs && v_pred && loss_mask_rel && w && grads && workspace && loss_out, "cn_gst_train_step: null argument");
     CN_REQUIRE(p_drop >= 0.0f && p_drop < 1.0f, "cn_gst_train_step: p_drop must be in [0, 1)");
-    const TrainWs L = train_ws(B, N);
+    const TrainWs L = train_ws(B, N, P);
     CN_REQUIRE(workspace_bytes >= (int64_t)L.total && ((uintptr_t)workspace & 15) == 0, "cn_gst_train_step: workspace of %lld bytes needed, got %lld", (long long)L.total,
                (long long)workspace_bytes);
     Wts W;
@@ -609,10 +625,15 @@ extern "C" int cn_gst_train_step(int B, int N, const float *v_obs, const float *
     hipStream_t st = (hipStream_t)stream;
     char *base = (char *)workspace;
     float *scratch = (float *)(base + L.scratch), *slabs = (float *)(base + L.slabs), *count = (float *)(base + L.count), *loss_part = (float *)(base + L.loss_part);
-    hipLaunchKernelGGL(gst_count_kernel, dim3(1), dim3(NT), 0, st, B, N, loss_mask_rel, count);
-    CN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(gst_train_kernel, dim3(B), dim3(NT), 0, st, N, v_obs, v_pred, loss_mask_rel, W, p_drop, (unsigned long long)seed, scratch, slabs, count, loss_part, gauss_out);
-    CN_CHECK_LAUNCH();
+    if (int rc = for_horizon(P, [&](auto gp) -> int {
+            constexpr int GP = decltype(gp)::value;
+            hipLaunchKernelGGL(gst_count_kernel<GP>, dim3(1), dim3(NT), 0, st, B, N, loss_mask_rel, count);
+            CN_CHECK_LAUNCH();
+            hipLaunchKernelGGL(gst_train_kernel<GP>, dim3(B), dim3(NT), 0, st, N, v_obs, v_pred, loss_mask_rel, W, p_drop, (unsigned long long)seed, scratch, slabs, count,
+                               loss_part, gauss_out);
+            CN_CHECK_LAUNCH();
+            return CN_OK;
+        })) return rc;
     hipLaunchKernelGGL(gst_grad_reduce_kernel, dim3((NPARAMS + 255) / 256), dim3(256), 0, st, B, slabs, G, loss_part, count, loss_out);
     CN_CHECK_LAUNCH();
     return CN_OK;

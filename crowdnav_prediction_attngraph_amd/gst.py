@@ -17,6 +17,7 @@ import json
 import os
 import pickle
 import re
+import warnings
 
 import torch
 import torch.nn as nn
@@ -53,7 +54,8 @@ class _GST(nn.Module):
 
 class GSTPredictor(nn.Module):
     """Gumbel Social Transformer with the shipped hyper-parameters (embedding 64, 8 heads, 1 layer, spatial_num_heads_edges = 0,
-    ghost = False, LSTM 64, obs 5 / pred 5, output_dim 5).  Built in eval mode; forward is inference only."""
+    ghost = False, LSTM 64, output_dim 5; obs 5 / pred 5 unless told otherwise -- the parameters do not depend on either, the decode is a
+    recurrence over pred_len steps).  Built in eval mode; forward is inference only."""
 
     def __init__(self, obs_len=5, pred_len=5):
         super().__init__()
@@ -65,9 +67,10 @@ class GSTPredictor(nn.Module):
 
     @staticmethod
     def from_checkpoint(path, device):
-        """path: <model_dir>/checkpoint/epoch_100.pt as shipped with the reference (config.pred.model_dir)."""
+        """path: <model_dir>/checkpoint/epoch_100.pt as shipped with the reference (config.pred.model_dir).  The horizon is the pred_seq_len the
+        run recorded beside it (run_pred_seq_len: args.json, args.pickle, else the shipped 5)."""
         ck = load_checkpoint(path, device)
-        m = GSTPredictor().to(device)
+        m = GSTPredictor(pred_len=run_pred_seq_len(os.path.dirname(path))).to(device)
         m.load_state_dict(ck["model_state_dict"] if "model_state_dict" in ck else ck)
         return m
 
@@ -159,6 +162,10 @@ class PretextProcessor:
                  pred_interval=1):
         self.pred, self.E, self.H, self.P = predictor, num_envs, human_num, predict_steps
         self.dist, self.device = robot_radius + human_radius, torch.device(device)
+        on_device = use_hip if use_hip is not None else self.device.type == "cuda"
+        if on_device:
+            from . import _abi
+            _abi.gst_horizon(predict_steps, getattr(predictor, "obs_len", 5))     # outside the device box: raises before anything is allocated
         self.collision_penalty = float(collision_penalty)
         self.pen = (collision_penalty / 2.0 ** torch.arange(2, predict_steps + 2, device=device, dtype=torch.float32)).view(1, 1, predict_steps)
         # prediction stride (vec_pretext_normalize.py:56-57): the history holds (obs_seq_len - 1) * interval + 1 observations, every
@@ -168,11 +175,12 @@ class PretextProcessor:
             raise ValueError("pred_interval = int(data.pred_timestep // env.time_step) must be >= 1")
         self.buffer_len = 4 * self.interval + 1
         self.hip = None
-        if use_hip if use_hip is not None else self.device.type == "cuda":
-            if predict_steps != 5:
-                raise NotImplementedError("the GST kernels are specialised to the shipped predictor (5 observed / 5 predicted steps)")
+        if getattr(predictor, "pred_len", predict_steps) != predict_steps:
+            raise ValueError("the predictor decodes pred_len = %d steps but the env's sim.predict_steps is %d: train (or load) a predictor of that "
+                             "horizon, or set sim.predict_steps to the predictor's" % (predictor.pred_len, predict_steps))
+        if on_device:
             from .gst_hip import HipGST
-            self.hip = HipGST(human_num, num_envs, device=self.device)     # raises if the extension is missing: no fallback on a GPU
+            self.hip = HipGST(human_num, num_envs, device=self.device, pred_steps=predict_steps)     # raises if the extension is missing: no fallback on a GPU
             self.hip.set_weights(predictor.state_dict())
             self.hip.wrapper_set_interval(self.interval)
         self.reset_buffers()
@@ -249,13 +257,42 @@ def load_predictor(config, device):
     return GSTPredictor.from_checkpoint(find_checkpoint(model_dir), device)
 
 
+class _ForeignClass(pickle.UnpicklingError):
+    """args.pickle names a class other than argparse.Namespace."""
+
+
 class _NamespaceOnlyUnpickler(pickle.Unpickler):
     """args.pickle holds an argparse.Namespace of plain values (gst_updated/scripts/experiments/train.py:88-89); nothing else may load."""
 
     def find_class(self, module, name):
         if (module, name) == ("argparse", "Namespace"):
             return argparse.Namespace
-        raise pickle.UnpicklingError("args.pickle may only contain an argparse.Namespace of plain values, found %s.%s" % (module, name))
+        raise _ForeignClass("args.pickle may only contain an argparse.Namespace of plain values, found %s.%s" % (module, name))
+
+
+def _run_args(ckpt_dir):
+    """What the run recorded beside its checkpoints: args.json (written by gst_train.train) as a dict, else args.pickle through the unpickler
+    restricted to argparse.Namespace, else {}.  A Namespace holding anything but plain values (numpy scalars, say) is refused by that unpickler:
+    then a warning is issued and nothing is known of the run ({}).  A file that cannot be read at all -- truncated, not a pickle -- raises."""
+    if os.path.exists(os.path.join(ckpt_dir, "args.json")):
+        with open(os.path.join(ckpt_dir, "args.json")) as f:
+            return dict(json.load(f))
+    if os.path.exists(os.path.join(ckpt_dir, "args.pickle")):
+        try:
+            with open(os.path.join(ckpt_dir, "args.pickle"), "rb") as f:
+                ns = _NamespaceOnlyUnpickler(f).load()
+        except _ForeignClass as err:
+            warnings.warn("%s: %s -- pred_seq_len is taken as 5" % (os.path.join(ckpt_dir, "args.pickle"), err))
+            return {}
+        return dict(vars(ns)) if isinstance(ns, argparse.Namespace) else {}
+    return {}
+
+
+def run_pred_seq_len(ckpt_dir):
+    """pred_seq_len of the run whose checkpoints lie in ckpt_dir: args.json, then args.pickle, then 5 (the shipped layout records nothing
+    readable, and its predictors decode five steps)."""
+    v = _run_args(ckpt_dir).get("pred_seq_len")
+    return 5 if v is None else int(v)
 
 
 def find_checkpoint(model_dir):

@@ -137,18 +137,19 @@ def rotate_graph(vtx, theta):
 
 
 class DeviceTrajectories(Dataset):
-    """TrajectoriesDataset's content as device tensors: the six ragged arrays (obs_traj, pred_traj, obs_traj_rel, pred_traj_rel [P,2,5],
-    loss_mask, loss_mask_rel [P,10]), seq_start_end, frame_id_seq and the env of every sequence (seq_env).  from_log builds it on the device
-    from collect.collect_log's observations (csrc/gst_data.hip: cn_gst_data_frames / _count / _fill, no files, one read-back); from_dataset
+    """TrajectoriesDataset's content as device tensors: the six ragged arrays (obs_traj, obs_traj_rel [peds,2,5], pred_traj, pred_traj_rel
+    [peds,2,P], loss_mask, loss_mask_rel [peds,5 + P]; P = pred_seq_len in 1 .. 8), seq_start_end, frame_id_seq and the env of every sequence (seq_env).  from_log builds it on the device
+    from collect.collect_log's observations (csrc/gst_data.hip: cn_gst_data_frames_horizon / _count_horizon / _fill_horizon, no files, one read-back); from_dataset
     uploads a TrajectoriesDataset.  __getitem__ returns the host class's 12 entries as device tensors (the graph tensors are made on demand),
     so evaluate / test / the torch backend take it through a DataLoader unchanged; gather() assembles a minibatch for cn_gst_train_step /
-    cn_gst_eval_step on the device (cn_gst_gather_batch)."""
+    cn_gst_eval_step on the device (cn_gst_gather_batch_horizon)."""
 
     FIELDS = ("obs_traj", "pred_traj", "obs_traj_rel", "pred_traj_rel", "loss_mask", "loss_mask_rel")
 
     def __init__(self, arrays, counts, frame_id_seq, seq_env, obs_seq_len=5, pred_seq_len=5):
         super().__init__()
-        self.obs_seq_len, self.pred_seq_len, self.skip, self.seq_len = obs_seq_len, pred_seq_len, 1, obs_seq_len + pred_seq_len
+        self.pred_seq_len = A.gst_horizon(pred_seq_len, obs_seq_len)
+        self.obs_seq_len, self.skip, self.seq_len = obs_seq_len, 1, obs_seq_len + pred_seq_len
         for k, t in zip(self.FIELDS, arrays):
             setattr(self, k, t)
         self.device = self.obs_traj.device
@@ -172,11 +173,13 @@ class DeviceTrajectories(Dataset):
         return cls(arrays, [e - s for s, e in ds.seq_start_end], ds.frame_id_seq, [-1] * len(ds.seq_start_end), ds.obs_seq_len, ds.pred_seq_len)
 
     @classmethod
-    def from_log(cls, log, mode=None, env_ids=None):
-        """log [F,E,H,4] float32 on the device (collect.collect_log) -> what TrajectoriesDataset(dir, mode=mode) holds for the files
-        collect_lines writes from it, files in env order.  env_ids: only these envs, in this order.  Raises on a log the rule does not cover:
+    def from_log(cls, log, mode=None, env_ids=None, pred_seq_len=5):
+        """log [F,E,H,4] float32 on the device (collect.collect_log) -> what TrajectoriesDataset(dir, pred_seq_len=pred_seq_len, mode=mode)
+        holds for the files collect_lines writes from it, files in env order; windows of T = 5 + pred_seq_len frames.  env_ids: only these envs, in this order.  Raises on a log the rule does not cover:
         frame ids that do not strictly increase within an env (an episode boundary), a sample with the same prediction id twice, a sequence
         of more than 64 pedestrians."""
+        P = A.gst_horizon(pred_seq_len)
+        T = 5 + P
         if mode not in A.GSTD_MODES:
             raise RuntimeError("Wrong mode for TrajectoriesDataset.")
         if not (torch.is_tensor(log) and log.is_cuda and log.dtype == torch.float32 and log.dim() == 4 and log.shape[3] == 4):
@@ -188,16 +191,16 @@ class DeviceTrajectories(Dataset):
         F_, E, H, _ = log.shape
         if H > A.CN_MAX_HUMANS:
             raise A.CnError("DeviceTrajectories.from_log: %d rows per observation, the kernels stop at %d" % (H, A.CN_MAX_HUMANS))
-        if F_ < 10 or E < 1:
-            raise RuntimeError("no sequence of 10 frames with a pedestrian present throughout in a log of %d samples of %d envs" % (F_, E))
-        dev, L, md, W = log.device, A.lib(), A.GSTD_MODES[mode], F_ - 9
+        if F_ < T or E < 1:
+            raise RuntimeError("no sequence of %d frames with a pedestrian present throughout in a log of %d samples of %d envs" % (T, F_, E))
+        dev, L, md, W = log.device, A.lib(), A.GSTD_MODES[mode], F_ - (T - 1)
         i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)   # noqa: E731
         visible, frame_id, status = i32(F_, E), torch.empty(F_, E, device=dev), torch.zeros(1, dtype=torch.int32, device=dev)
         frame_list, ped_count, first_frame = i32(E, F_), i32(E * W), torch.empty(E * W, device=dev)
         with torch.cuda.device(dev):
-            A.call("cn_gst_data_frames", F_, E, H, A.ptr(log), A.ptr(visible), A.ptr(frame_id), A.ptr(status), A.stream_ptr())
+            A.call("cn_gst_data_frames_horizon", F_, E, H, P, A.ptr(log), A.ptr(visible), A.ptr(frame_id), A.ptr(status), A.stream_ptr())
             listed_before = (torch.cumsum(visible, 0).to(torch.int32) - visible).contiguous()
-            A.call("cn_gst_data_count", F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
+            A.call("cn_gst_data_count_horizon", F_, E, H, md, P, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
                    A.ptr(first_frame), A.ptr(status), A.stream_ptr())
             ped_offset = (torch.cumsum(ped_count, 0).to(torch.int32) - ped_count).contiguous()
             host = torch.cat((status, ped_count, first_frame.view(torch.int32))).cpu().numpy()       # the one read-back of the build
@@ -211,14 +214,14 @@ class DeviceTrajectories(Dataset):
             is_seq = counts > 0
             total = int(counts.sum())
             if total == 0:
-                raise RuntimeError("no sequence of 10 frames with a pedestrian present throughout in the log (mode %r)" % (mode,))
-            if total >= 2 ** 31 // 10:
+                raise RuntimeError("no sequence of %d frames with a pedestrian present throughout in the log (mode %r)" % (T, mode))
+            if total >= 2 ** 31 // T:
                 raise A.CnError("DeviceTrajectories.from_log: %d pedestrian rows exceed the 32-bit offsets of the build" % total)
-            arrays = [torch.empty(total, 2, 5, device=dev) for _ in range(4)] + [torch.empty(total, 10, device=dev) for _ in range(2)]
-            A.call("cn_gst_data_fill", F_, E, H, md, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
+            arrays = [torch.empty(total, 2, n, device=dev) for n in (5, P, 5, P)] + [torch.empty(total, T, device=dev) for _ in range(2)]
+            A.call("cn_gst_data_fill_horizon", F_, E, H, md, P, A.ptr(log), A.ptr(visible), A.ptr(listed_before), A.ptr(frame_id), A.ptr(frame_list), A.ptr(ped_count),
                    A.ptr(ped_offset), total, *([A.ptr(t) for t in arrays] + [A.stream_ptr()]))
         env_of = np.nonzero(is_seq)[0] // W
-        return cls(arrays, counts[is_seq], first[is_seq], env_of if envs is None else np.asarray(envs, dtype=np.int64)[env_of])
+        return cls(arrays, counts[is_seq], first[is_seq], env_of if envs is None else np.asarray(envs, dtype=np.int64)[env_of], 5, P)
 
     def __len__(self):
         return self.num_seq
@@ -235,14 +238,15 @@ class DeviceTrajectories(Dataset):
 
     def gather(self, index, num_peds, cos_sin=None):
         """index [B] int32 on the device, num_peds = max(4, the largest crowd among them), cos_sin None or [B,2] float32 on the device ->
-        v_obs, v_pred [B,5,num_peds,2] (seq_to_graph's vertices, rotated as rotate_graph does), loss_mask_rel [B,num_peds,10]; rows at or beyond a
+        v_obs [B,5,num_peds,2], v_pred [B,P,num_peds,2] (seq_to_graph's vertices, rotated as rotate_graph does), loss_mask_rel [B,num_peds,5 + P]; rows at or beyond a
         sequence's crowd are zeros."""
         B = int(index.shape[0])
         if index.dtype != torch.int32 or (cos_sin is not None and (cos_sin.dtype != torch.float32 or tuple(cos_sin.shape) != (B, 2))):
             raise A.CnError("DeviceTrajectories.gather: index must be int32 [B] and cos_sin float32 [B,2]")
-        v_obs, v_pred = torch.empty(B, 5, num_peds, 2, device=self.device), torch.empty(B, 5, num_peds, 2, device=self.device)
-        lm = torch.empty(B, num_peds, 10, device=self.device)
-        A.call("cn_gst_gather_batch", B, int(num_peds), self.num_seq, self.total_peds, A.ptr(index), A.ptr(cos_sin), A.ptr(self._seq_start),
+        P = self.pred_seq_len
+        v_obs, v_pred = torch.empty(B, 5, num_peds, 2, device=self.device), torch.empty(B, P, num_peds, 2, device=self.device)
+        lm = torch.empty(B, num_peds, 5 + P, device=self.device)
+        A.call("cn_gst_gather_batch_horizon", B, int(num_peds), P, self.num_seq, self.total_peds, A.ptr(index), A.ptr(cos_sin), A.ptr(self._seq_start),
                A.ptr(self._seq_count), A.ptr(self.obs_traj_rel), A.ptr(self.pred_traj_rel), A.ptr(self.loss_mask_rel),
                A.ptr(v_obs), A.ptr(v_pred), A.ptr(lm), A.stream_ptr(), device=self.device)
         return v_obs, v_pred, lm

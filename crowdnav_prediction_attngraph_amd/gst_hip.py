@@ -29,13 +29,17 @@ def predictor_params(model):
 
 
 def gst_batch(who, dev, v_obs, v_pred, loss_mask_rel, noise=None, max_samples=64):
-    """v_obs, v_pred [B,5,N,2], loss_mask_rel [B,N,10], noise None or [B,S,5,N,2] (any device) -> N and the four as contiguous float32 on
-    `dev`, padded along the pedestrian axis to max(N, 4) with absent pedestrians (zeros)."""
+    """v_obs [B,5,N,2], v_pred [B,P,N,2], loss_mask_rel [B,N,5+P], noise None or [B,S,P,N,2] (any device), P = the prediction horizon in 1 .. 8
+    -> N, P and the four as contiguous float32 on `dev`, padded along the pedestrian axis to max(N, 4) with absent pedestrians (zeros)."""
     B, T, N, _ = v_obs.shape
-    if T != 5 or v_pred.shape[1] != 5 or N > A.CN_MAX_HUMANS:
-        raise A.CnError("%s: 5 observed + 5 predicted steps and at most 64 pedestrians per sequence (got %d + %d steps, %d pedestrians)" % (who, T, v_pred.shape[1], N))
-    if noise is not None and (not 1 <= noise.shape[1] <= max_samples or tuple(noise.shape) != (B, noise.shape[1], 5, N, 2)):
-        raise A.CnError("%s: noise must be [B,S,5,N,2] with 1 <= S <= %d (got %s for B=%d, N=%d)" % (who, max_samples, tuple(noise.shape), B, N))
+    P = int(v_pred.shape[1])
+    if T != A.GST_OBS_LEN or not 1 <= P <= A.CN_MAX_PRED or N > A.CN_MAX_HUMANS:
+        raise A.CnError("%s: %s and at most %d pedestrians per sequence (got %d + %d steps, %d pedestrians)" % (who, A.HORIZON_BOX, A.CN_MAX_HUMANS, T, P, N))
+    if tuple(v_pred.shape) != (B, P, N, 2) or tuple(loss_mask_rel.shape) != (B, N, T + P):
+        raise A.CnError("%s: v_pred must be [B,P,N,2] and loss_mask_rel [B,N,5+P] (got %s and %s for B=%d, N=%d, P=%d)"
+                        % (who, tuple(v_pred.shape), tuple(loss_mask_rel.shape), B, N, P))
+    if noise is not None and (not 1 <= noise.shape[1] <= max_samples or tuple(noise.shape) != (B, noise.shape[1], P, N, 2)):
+        raise A.CnError("%s: noise must be [B,S,P,N,2] with 1 <= S <= %d (got %s for B=%d, N=%d, P=%d)" % (who, max_samples, tuple(noise.shape), B, N, P))
     out = []
     for t in (v_obs, v_pred, loss_mask_rel, noise):
         if t is not None:
@@ -43,7 +47,7 @@ def gst_batch(who, dev, v_obs, v_pred, loss_mask_rel, noise=None, max_samples=64
                 t = torch.nn.functional.pad(t, (0, 0, 0, 4 - N))
             t = t.to(dev, torch.float32, non_blocking=True).contiguous()
         out.append(t)
-    return [N] + out
+    return [N, P] + out
 
 
 def workspace(ws, need, dev):
@@ -52,20 +56,25 @@ def workspace(ws, need, dev):
 
 
 class HipGST(HipHandle):
-    """cn_gst handle: GST predictor (cn_gst_predict) and the VecPretextNormalize processing (cn_gst_wrapper_*)."""
+    """cn_gst handle: GST predictor (cn_gst_predict) and the VecPretextNormalize processing (cn_gst_wrapper_*).  pred_steps: the prediction
+    horizon P = pred_seq_len of the predictor = sim.predict_steps of the env, 1 .. 8 (A.gst_horizon); 5 observed frames always."""
     _sym, _weights = "cn_gst", (A.GstWeights, A.GST_WEIGHT_KEYS)
 
-    def __init__(self, human_num, max_envs, device=None):
+    def __init__(self, human_num, max_envs, device=None, pred_steps=5):
+        self.P = A.gst_horizon(pred_steps)                    # raises outside the box before anything is allocated
         self.H, self.maxE = int(human_num), int(max_envs)
-        self._open(device, self.H, self.maxE)
+        self._open(device, self.H, self.maxE, self.P, create="cn_gst_create_horizon")    # (cn_gst_create is this call with P = 5)
 
     def _weights_struct(self, fields, tensors):
         return gst_weights(tensors, "HipGST")
 
     def predict(self, in_traj, in_mask):
-        """in_traj [E,H,5,2], in_mask [E,H,5] or [E,H,5,1] float -> (out_traj [E,H,5,5], out_mask [E,H,1])."""
+        """in_traj [E,H,5,2], in_mask [E,H,5] or [E,H,5,1] float -> (out_traj [E,H,P,5], out_mask [E,H,1])."""
         E = in_traj.shape[0]
-        out = torch.empty(E, self.H, 5, 5, device=self.device)
+        if tuple(in_traj.shape[1:]) != (self.H, 5, 2) or in_mask.numel() != E * self.H * 5:
+            raise A.CnError("HipGST.predict: in_traj must be [E,%d,5,2] and in_mask [E,%d,5] (got %s and %s): %s"
+                            % (self.H, self.H, tuple(in_traj.shape), tuple(in_mask.shape), A.HORIZON_BOX))
+        out = torch.empty(E, self.H, self.P, 5, device=self.device)
         om = torch.empty(E, self.H, device=self.device)
         A.call("cn_gst_predict", self._h, E, A.ptr(in_traj.float().contiguous()), A.ptr(in_mask.float().reshape(E, self.H, 5).contiguous()),
                A.ptr(out), A.ptr(om), A.stream_ptr(), device=self.device)
@@ -99,10 +108,13 @@ class HipGST(HipHandle):
         self._wrap_E = E
 
     def wrapper_step(self, obs, rewards, dist, collision_penalty, out=None):
-        """obs: raw env observation (spatial_edges [E,H,12] by human id, visible_masks u8/bool); rewards [E] float32 updated in place."""
-        E = obs["robot_node"].shape[0]
+        """obs: raw env observation (spatial_edges [E,H,2(P+1)] by human id, visible_masks u8/bool); rewards [E] float32 updated in place."""
+        E, D = obs["robot_node"].shape[0], 2 * (self.P + 1)
+        if tuple(obs["spatial_edges"].shape) != (E, self.H, D) or (out is not None and tuple(out.shape) != (E, self.H, D)):
+            raise A.CnError("HipGST.wrapper_step: spatial_edges (and out) must be [%d,%d,%d] for a horizon of %d steps (got %s)"
+                            % (E, self.H, D, self.P, tuple(obs["spatial_edges"].shape)))
         if out is None:
-            out = torch.empty(E, self.H, 12, device=self.device)
+            out = torch.empty(E, self.H, D, device=self.device)
         o = A.Obs()
         o.robot_node = A.ptr(obs["robot_node"])
         o.spatial_edges = A.ptr(obs["spatial_edges"])
@@ -134,16 +146,16 @@ class HipGstTrainer:
         return self.flat.step_no
 
     def loss_and_grads(self, v_obs, v_pred, loss_mask_rel, p_drop=0.1, seed=None):
-        """v_obs [B,5,N,2], v_pred [B,5,N,2], loss_mask_rel [B,N,10] (any device) -> (loss_and_count [2] on the device, gauss [B,5,N,5]: mu_x, mu_y,
-        sigma_x, sigma_y, corr); the gradients land in the flat bucket (every parameter's .grad).  Crowds of fewer than 4 pedestrians are padded
+        """v_obs [B,5,N,2], v_pred [B,P,N,2], loss_mask_rel [B,N,5+P] (any device; P = the horizon, 1 .. 8) -> (loss_and_count [2] on the device,
+        gauss [B,P,N,5]: mu_x, mu_y, sigma_x, sigma_y, corr); the gradients land in the flat bucket (every parameter's .grad).  Crowds of fewer than 4 pedestrians are padded
         with absent ones."""
-        N, vo, vp, lm, _ = gst_batch("HipGstTrainer", self.dev, v_obs, v_pred, loss_mask_rel)
+        N, P, vo, vp, lm, _ = gst_batch("HipGstTrainer", self.dev, v_obs, v_pred, loss_mask_rel)
         B, Np = vo.shape[0], vo.shape[2]
-        self.ws = workspace(self.ws, int(A.lib().cn_gst_train_workspace_bytes(B, Np)), self.dev)
+        self.ws = workspace(self.ws, int(A.lib().cn_gst_train_workspace_bytes_horizon(B, Np, P)), self.dev)
         out = torch.empty(2, device=self.dev)
-        gauss = torch.empty(B, 5, Np, 5, device=self.dev)
+        gauss = torch.empty(B, P, Np, 5, device=self.dev)
         sd = self.seed + 7919 * self.step_no if seed is None else int(seed)
-        A.call("cn_gst_train_step", B, Np, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(self.w), C.byref(self.g), float(p_drop), C.c_uint64(sd & (2 ** 64 - 1)),
+        A.call("cn_gst_train_step_horizon", B, Np, P, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(self.w), C.byref(self.g), float(p_drop), C.c_uint64(sd & (2 ** 64 - 1)),
                C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()), A.ptr(out), A.ptr(gauss), A.stream_ptr(), device=self.dev)
         return out, gauss[:, :, :N]
 
@@ -172,19 +184,20 @@ class HipGstEvaluator:
         return [p for _, p in predictor_params(self.model)]
 
     def evaluate_batch(self, v_obs, v_pred, loss_mask_rel, noise=None):
-        """v_obs, v_pred [B,5,N,2], loss_mask_rel [B,N,10] (any device), or lists of B per-sequence tensors ([5,N_b,2] / [N_b,10], a leading
-        axis of one allowed) of different crowd sizes; noise None (validation) or [B,S,5,N,2] / a list of [S,5,N_b,2] (test: S decodes per
+        """v_obs [B,5,N,2], v_pred [B,P,N,2], loss_mask_rel [B,N,5+P] (any device; P = the horizon, 1 .. 8), or lists of B per-sequence tensors
+        ([5,N_b,2] / [P,N_b,2] / [N_b,5+P], a leading axis of one allowed) of different crowd sizes; noise None (validation) or [B,S,P,N,2] / a
+        list of [S,P,N_b,2] (test: S decodes per
         sequence on these standard-normal draws).  Crowds are padded to the batch's largest (at least four) with absent pedestrians.
         -> seq [B,R,4] (NLL sum, valid pairs, sum of masked aoe, sum of masked foe), ped [B,R,N,3] (aoe, foe, loss_mask_per_pedestrian),
-        gauss [B,R,5,N,5] (mu_x, mu_y, sigma_x, sigma_y, corr), R = max(S, 1), all on the device (nothing is read back here)."""
-        N, vo, vp, lm, nz = gst_batch("HipGstEvaluator", self.dev, self._stack(v_obs, 3, 1), self._stack(v_pred, 3, 1), self._stack(loss_mask_rel, 2, 0),
+        gauss [B,R,P,N,5] (mu_x, mu_y, sigma_x, sigma_y, corr), R = max(S, 1), all on the device (nothing is read back here)."""
+        N, P, vo, vp, lm, nz = gst_batch("HipGstEvaluator", self.dev, self._stack(v_obs, 3, 1), self._stack(v_pred, 3, 1), self._stack(loss_mask_rel, 2, 0),
                                       None if noise is None else self._stack(noise, 4, 2), self.MAX_SAMPLES)
         B, Np, S = vo.shape[0], vo.shape[2], 0 if nz is None else int(nz.shape[1])
         w = gst_weights(self._params(), "HipGstEvaluator")    # on every call: the parameters may be views of a trainer's bucket rebound since
-        self.ws = workspace(self.ws, int(A.lib().cn_gst_eval_workspace_bytes(B, Np, S)), self.dev)
+        self.ws = workspace(self.ws, int(A.lib().cn_gst_eval_workspace_bytes_horizon(B, Np, S, P)), self.dev)
         R = max(S, 1)
-        seq, ped, gauss = torch.empty(B, R, 4, device=self.dev), torch.empty(B, R, Np, 3, device=self.dev), torch.empty(B, R, 5, Np, 5, device=self.dev)
-        A.call("cn_gst_eval_step", B, Np, S, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(w), A.ptr(nz), C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()),
+        seq, ped, gauss = torch.empty(B, R, 4, device=self.dev), torch.empty(B, R, Np, 3, device=self.dev), torch.empty(B, R, P, Np, 5, device=self.dev)
+        A.call("cn_gst_eval_step_horizon", B, Np, S, P, A.ptr(vo), A.ptr(vp), A.ptr(lm), C.byref(w), A.ptr(nz), C.c_void_p(self.ws.data_ptr()), int(self.ws.numel()),
                A.ptr(seq), A.ptr(ped), A.ptr(gauss), A.stream_ptr(), device=self.dev)
         return seq, ped[:, :, :N], gauss[:, :, :, :N]
 

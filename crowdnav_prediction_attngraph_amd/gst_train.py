@@ -127,7 +127,7 @@ def _step_sample_and_mask(gauss, lm_rel, obs_len):
     return xs, (lm_rel.sum(2) == lm_rel.shape[2]).float()
 
 
-def _train_epoch_device(hip_tr, ds, order, thetas, batch_size, optimizer, obs_len):
+def _train_epoch_device(hip_tr, ds, order, thetas, batch_size, optimizer, obs_len, p_drop=0.1):
     """One training epoch with the data on the device: per step a gather, the training step, the fused clip + Adam step; the step's loss and
     its aoe / foe terms go into per-epoch device buffers and come back in ONE read-back.  -> (losses [steps] float64, [aoe], [foe], [m]: float32
     arrays of the per-pedestrian terms in step order)."""
@@ -141,7 +141,7 @@ def _train_epoch_device(hip_tr, ds, order, thetas, batch_size, optimizer, obs_le
     for k, (lo, hi) in enumerate(chunks):
         vo, vp, lm_rel = ds.gather(index[lo:hi], ds.num_peds(order[lo:hi]), None if cos_sin is None else cos_sin[lo:hi])
         hip_tr.lr = optimizer.param_groups[0]["lr"]                           # the StepLR schedule drives the fused step too
-        out, gauss = hip_tr.loss_and_grads(vo, vp, lm_rel, p_drop=0.1)
+        out, gauss = hip_tr.loss_and_grads(vo, vp, lm_rel, p_drop=p_drop)
         hip_tr.optimizer_step(grad_scale=1.0 / B)
         loss_buf[k].copy_(out[0])
         seg = terms[:, off[k]:off[k + 1]]
@@ -173,24 +173,24 @@ def _item_terms(loss, xs, lm, v_pred_gt):
     return loss.item(), average_offset_error(xs, v_pred_gt, lm).cpu().numpy(), final_offset_error(xs, v_pred_gt, lm).cpu().numpy(), lm[0].cpu().numpy()
 
 
-def _train_epoch_items_hip(hip_tr, loader, rotation_pattern, optimizer, device, obs_len):
-    """One epoch of one loader item per optimiser step through the kernels: forward, loss, backward (dropout 0.1 like model.train()) as one boundary
+def _train_epoch_items_hip(hip_tr, loader, rotation_pattern, optimizer, device, obs_len, p_drop=0.1):
+    """One epoch of one loader item per optimiser step through the kernels: forward, loss, backward (dropout p_drop: 0.1 like model.train()) as one boundary
     call, then the fused clip + Adam step.  -> (losses, aoes, foes, ms), one entry per step."""
     rows = []
     for item in _train_items(loader, rotation_pattern):
         lm_rel = item[4].to(device)
         hip_tr.lr = optimizer.param_groups[0]["lr"]                           # the StepLR schedule drives the fused step too
-        out, gauss = hip_tr.loss_and_grads(item[6], item[8], lm_rel, p_drop=0.1)
+        out, gauss = hip_tr.loss_and_grads(item[6], item[8], lm_rel, p_drop=p_drop)
         hip_tr.optimizer_step()
         rows.append(_item_terms(out[0], *_step_sample_and_mask(gauss, lm_rel, obs_len), item[8].to(device)))
     return tuple(zip(*rows))
 
 
-def _train_epoch_items_torch(model, loader, rotation_pattern, optimizer, clip_grad, device):
+def _train_epoch_items_torch(model, loader, rotation_pattern, optimizer, clip_grad, device, p_drop=0.1):
     """The same epoch on the op graph under autograd (train.py:121-146)."""
     rows = []
     for item in _train_items(loader, rotation_pattern):
-        loss, gp, xs, info, v_pred_gt = sequence_loss(model, item, device)
+        loss, gp, xs, info, v_pred_gt = sequence_loss(model, item, device, p_drop)
         loss.backward()
         rows.append(_item_terms(loss.detach(), xs.detach(), info["loss_mask_per_pedestrian"], v_pred_gt))
         if clip_grad is not None:
@@ -209,7 +209,7 @@ def _eval_backend(model, backend):
 
 
 def test_sequence(model, item, noise, device):
-    """eval.py:89-107 for one sequence on the op graph: noise [S,5,N,2] -> per-sample (loss [S], sum of masked aoe [S], sum of masked foe [S]) and
+    """eval.py:89-107 for one sequence on the op graph: noise [S,P,N,2] -> per-sample (loss [S], sum of masked aoe [S], sum of masked foe [S]) and
     the number of fully present pedestrians.  noise None: one decode with the mean fed back (the validation pass, eval.py:63-83)."""
     losses, aoes, foes = [], [], []
     with torch.no_grad():
@@ -239,7 +239,7 @@ def _eval_pass(model, seqs, device, row, ev=None, batch_size=32, draw=None, batc
     """One pass over sequences in order: up to batch_size of them per cn_gst_eval_step call, the per-sequence rows kept on the device, ONE
     read-back -> rows [sequences, columns] float64.  seqs: (pedestrians, sequence) pairs; sequences of more than 128 pedestrians are skipped
     (eval.py:66), those of more than 64 -- the kernels' bound -- and all of them without an evaluator (ev None) go to the op graph and enter the
-    rows ahead of the batch still pending.  row: _val_row or _test_row; draw(pedestrians) -> the sequence's [S,5,N,2] draws (None: validation).
+    rows ahead of the batch still pending.  row: _val_row or _test_row; draw(pedestrians) -> the sequence's [S,P,N,2] draws (None: validation).
     A sequence is a loader item unless batch(sequences) -> evaluate_batch's first three arguments and item(sequence) -> its loader item say otherwise."""
     rows, pend = [], []
 
@@ -303,8 +303,8 @@ def test(model, loader, device, num_samples=20, seed=1000, backend=None, batch_s
     """eval.py's `inference` in 'test' mode (:84-117, :148-157): num_samples decodes per sequence with the Gaussian sampled and fed back;
     per sequence the mean / unbiased std / min over the samples of the summed masked aoe and foe and the mean of the losses; over the pass those
     sums divided by the number of fully present pedestrians.  -> (loss, aoe, foe, aoe_std, foe_std, aoe_min, foe_min).
-    The draws come from a CPU torch.Generator seeded with `seed`: torch.randn [num_samples,5,N,2] per sequence in loader order, the same for
-    both backends; `draws` (an iterable of one [S,5,N,2] tensor per sequence) replaces them with recorded ones.  backend None: 'hip' for a model
+    The draws come from a CPU torch.Generator seeded with `seed`: torch.randn [num_samples,P,N,2] per sequence in loader order (P = the model's
+    pred_len), the same for both backends; `draws` (an iterable of one [S,P,N,2] tensor per sequence) replaces them with recorded ones.  backend None: 'hip' for a model
     on the GPU, 'torch' otherwise."""
     model.eval()
     if backend is None:
@@ -312,7 +312,7 @@ def test(model, loader, device, num_samples=20, seed=1000, backend=None, batch_s
     backend = _eval_backend(model, backend)
     gen = torch.Generator().manual_seed(int(seed))
     draws = iter(draws) if draws is not None else None
-    draw = lambda n: torch.randn(num_samples, 5, n, 2, generator=gen) if draws is None else next(draws)   # noqa: E731
+    draw = lambda n: torch.randn(num_samples, model.pred_len, n, 2, generator=gen) if draws is None else next(draws)   # noqa: E731
     r = _eval_pass(model, ((item[6].shape[2], item) for item in loader), device, _test_row, HipGstEvaluator(model) if backend == "hip" else None, batch_size, draw)
     m = max(float(r[:, 7].sum()), 1.0)
     return (float(r[:, 0].mean()), float(r[:, 1].sum() / m), float(r[:, 4].sum() / m), float(r[:, 2].sum() / m), float(r[:, 5].sum() / m),
@@ -320,7 +320,7 @@ def test(model, loader, device, num_samples=20, seed=1000, backend=None, batch_s
 
 
 def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3, clip_grad=10.0, rotation_pattern="random", save_epochs=10, init_temp=0.5,
-          random_seed=1000, device=None, num_workers=0, log=print, backend=None, val_backend=None, dataset=None, batch_size=1):
+          random_seed=1000, device=None, num_workers=0, log=print, backend=None, val_backend=None, dataset=None, batch_size=1, pred_seq_len=5, p_drop=0.1):
     """gst_updated/scripts/experiments/train.py:49-195 for the shipped configuration.  data_dir holds the text files of collect.py /
     collect_data.py; the first 80 % of every file's windows train, the rest validate (TrajectoriesDataset modes).  Writes
     <out_dir>/checkpoint/{epoch_<n>.pt, args.pickle, train_hist.pickle} in the reference's format (+ args.json / train_hist.json): the
@@ -328,7 +328,11 @@ def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3,
     dataset = (train, val) of DeviceTrajectories replaces data_dir.  With backend 'hip' the epoch then runs with the data on the device: the
     order and the angles are drawn up front (epoch_plan: the draws of the per-item loop), minibatches are consecutive chunks of batch_size of that
     order (train.py's args.batch_size; the last may be short), each assembled by cn_gst_gather_batch, and the losses come back once per epoch.
-    batch_size > 1 needs that path (a data_dir is uploaded for it)."""
+    batch_size > 1 needs that path (a data_dir is uploaded for it).
+    pred_seq_len: the prediction horizon P -- windows of 5 + P frames, a predictor that decodes P steps, recorded in args.json / args.pickle for
+    load_predictor; 1 .. 8 on the 'hip' backend (_abi.gst_horizon), any on 'torch'.  A dataset=(train, val) must have been cut for the same P.
+    p_drop: the dropout of the training steps (the reference's 0.1).  The two backends draw their masks from different streams, so their runs
+    differ at the level of the dropout noise; with p_drop = 0 both are deterministic and follow each other step for step."""
     if out_dir is None or (data_dir is None) == (dataset is None):
         raise ValueError("train() needs an out_dir and either a data_dir or dataset=(train, val)")
     batch_size = int(batch_size)
@@ -341,17 +345,28 @@ def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3,
         backend = "hip" if device.type == "cuda" else "torch"
     if batch_size > 1 and backend != "hip":
         raise ValueError("batch_size > 1 needs backend='hip': the op graph trains one sequence per step")
+    pred_seq_len, p_drop = int(pred_seq_len), float(p_drop)
+    if not 0.0 <= p_drop < 1.0:
+        raise ValueError("p_drop must be in [0, 1) (got %s)" % p_drop)
+    if backend == "hip" or val_backend == "hip":
+        from ._abi import gst_horizon
+        gst_horizon(pred_seq_len)                  # outside the device box: refused here, before anything is allocated
+    elif pred_seq_len < 1:
+        raise ValueError("pred_seq_len must be at least 1 (got %d)" % pred_seq_len)
     if dataset is not None:
         ds_train, ds_val = dataset
+        for ds in dataset:
+            if int(getattr(ds, "pred_seq_len", pred_seq_len)) != pred_seq_len:
+                raise ValueError("the dataset holds windows of pred_seq_len = %d, train() was asked for %d" % (ds.pred_seq_len, pred_seq_len))
     else:
-        ds_train = TrajectoriesDataset(data_dir, mode="train")
-        ds_val = TrajectoriesDataset(data_dir, mode="val")
+        ds_train = TrajectoriesDataset(data_dir, pred_seq_len=pred_seq_len, mode="train")
+        ds_val = TrajectoriesDataset(data_dir, pred_seq_len=pred_seq_len, mode="val")
         if batch_size > 1:
             ds_train, ds_val = DeviceTrajectories.from_dataset(ds_train, device), DeviceTrajectories.from_dataset(ds_val, device)
     on_device = backend == "hip" and isinstance(ds_train, DeviceTrajectories)
     loader_train = DataLoader(ds_train, batch_size=1, shuffle=True, num_workers=num_workers)
     loader_val = DataLoader(ds_val, batch_size=1, shuffle=False, num_workers=num_workers)
-    model = GSTPredictor().to(device)
+    model = GSTPredictor(pred_len=pred_seq_len).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=lr)
     scheduler = torch.optim.lr_scheduler.StepLR(optimizer, step_size=max(int(temp_epochs / 4), 1), gamma=0.3)
     # backend: 'hip' = the training step as hand-written kernels through the C ABI (HipGstTrainer; the default on a GPU), 'torch' = the op graph
@@ -366,7 +381,7 @@ def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3,
     os.makedirs(ckpt_dir, exist_ok=True)
     run_args = dict(spatial="gumbel_social_transformer", temporal="faster_lstm", output_dim=5, embedding_size=64, spatial_num_heads=8,
                     spatial_num_heads_edges=0, spatial_num_layers=1, ghost=False, lstm_hidden_size=64, lstm_num_layers=1, decode_style="recursive",
-                    detach_sample=False, motion_dim=2, only_observe_full_period=False, dataset="sj", obs_seq_len=5, pred_seq_len=5, batch_size=batch_size,
+                    detach_sample=False, motion_dim=2, only_observe_full_period=False, dataset="sj", obs_seq_len=5, pred_seq_len=pred_seq_len, batch_size=batch_size,
                     lr=lr, clip_grad=clip_grad, rotation_pattern=rotation_pattern, num_epochs=num_epochs, temp_epochs=temp_epochs,
                     save_epochs=save_epochs, init_temp=init_temp, random_seed=random_seed, deterministic=False, resume_training=False,
                     resume_epoch=None)
@@ -378,11 +393,11 @@ def train(data_dir=None, out_dir=None, num_epochs=100, temp_epochs=100, lr=1e-3,
         pickle.dump(argparse.Namespace(**run_args), f)
     hist = {"epoch": 0, "train_loss_task": [], "val_loss_task": [], "train_aoe_task": [], "val_aoe_task": [], "train_foe_task": [], "val_foe_task": []}
     if on_device:            # the order and the angles drawn up front by the per-item loop's own calls
-        run_epoch = lambda: _train_epoch_device(hip_tr, ds_train, *epoch_plan(len(ds_train), rotation_pattern), batch_size, optimizer, model.obs_len)   # noqa: E731
+        run_epoch = lambda: _train_epoch_device(hip_tr, ds_train, *epoch_plan(len(ds_train), rotation_pattern), batch_size, optimizer, model.obs_len, p_drop)   # noqa: E731
     elif hip_tr is not None:
-        run_epoch = lambda: _train_epoch_items_hip(hip_tr, loader_train, rotation_pattern, optimizer, device, model.obs_len)   # noqa: E731
+        run_epoch = lambda: _train_epoch_items_hip(hip_tr, loader_train, rotation_pattern, optimizer, device, model.obs_len, p_drop)   # noqa: E731
     else:
-        run_epoch = lambda: _train_epoch_items_torch(model, loader_train, rotation_pattern, optimizer, clip_grad, device)   # noqa: E731
+        run_epoch = lambda: _train_epoch_items_torch(model, loader_train, rotation_pattern, optimizer, clip_grad, device, p_drop)   # noqa: E731
     for epoch in range(1, num_epochs + 1):
         model.train()
         t0 = time.time()
@@ -422,8 +437,8 @@ def eval_run(run_dir, data_dir, num_samples=20, seed=1000, device=None, backend=
     path = find_checkpoint(run_dir)
     model = GSTPredictor.from_checkpoint(path, device)
     stored = load_checkpoint(path, "cpu").get("val_loss_epoch")
-    loader_val = DataLoader(TrajectoriesDataset(data_dir, mode="val"), batch_size=1, shuffle=False)
-    loader_test = DataLoader(TrajectoriesDataset(data_dir, mode="test"), batch_size=1, shuffle=False)
+    loader_val = DataLoader(TrajectoriesDataset(data_dir, pred_seq_len=model.pred_len, mode="val"), batch_size=1, shuffle=False)
+    loader_test = DataLoader(TrajectoriesDataset(data_dir, pred_seq_len=model.pred_len, mode="test"), batch_size=1, shuffle=False)
     log("The best validation losses printed below should be the same.")
     log("Validation loss in the checkpoint:  %s" % (stored,))
     val = evaluate(model, loader_val, device, backend=backend)

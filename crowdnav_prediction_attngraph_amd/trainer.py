@@ -230,6 +230,13 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
     torch.manual_seed(seed)
     if pretext_wrapper is None:
         pretext_wrapper = bool(getattr(getattr(config, "env", None), "use_wrapper", False))
+    # the attention policy's kernels take edge widths up to 16 (cn_policy_create), i.e. horizons up to 7: say so here, by name, before the
+    # simulator, the predictor's handle and the storage are built (the DS-RNN baseline takes widths up to 64)
+    steps = int(getattr(getattr(config, "sim", None), "predict_steps", 5))
+    named_base = base if base is not None else getattr(getattr(config, "robot", None), "policy", None)
+    if env_name not in ("CrowdSimVarNum-v0", "CrowdSimVarNumCollect-v0") and named_base != "srnn" and 2 * (steps + 1) > 16:
+        raise NotImplementedError("sim.predict_steps = %d gives spatial edges of width %d, and the attention-graph policy's kernels take at most 16 "
+                                  "(predict_steps <= 7); base='srnn' takes widths up to 64" % (steps, 2 * (steps + 1)))
     envs = make_vec_envs(env_name, seed, num_processes, gamma, None, device, False, config=config, phase="train", pretext_wrapper=bool(pretext_wrapper),
                          predictor=predictor)
     # arguments.py:189, :206: use_self_attn, and sort_humans -- by default whatever the config's args say (it also decides the simulator's row order)
@@ -245,6 +252,8 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
         raise ValueError("sort_humans=False needs the `visible_masks` observation, which %s does not provide" % env_name)
     base_kwargs = dict(env_name=env_name, num_processes=num_processes, num_mini_batch=num_mini_batch, seq_length=num_steps, use_self_attn=use_self_attn,
                        sort_humans=sort_humans, **network_kwargs(network))
+    if env_name in ("CrowdSimPred-v0", "CrowdSimPredRealGST-v0"):
+        base_kwargs["predict_steps"] = steps              # the edge width the network expects of this env is 2 (predict_steps + 1)
     if base is None:
         base = getattr(getattr(config, "robot", None), "policy", None)
         if base not in ("selfAttn_merge_srnn", "srnn"):

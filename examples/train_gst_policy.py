@@ -33,8 +33,9 @@ def fresh_predictor(a, dev):
     if a.device_data:
         log = collect_log(envs, a.collect_steps)
         envs.close()
-        sets = tuple(gst_train.DeviceTrajectories.from_log(log, mode) for mode in ("train", "val"))
-        _, hist = gst_train.train(out_dir=run, dataset=sets, batch_size=a.batch_size, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev)
+        sets = tuple(gst_train.DeviceTrajectories.from_log(log, mode, pred_seq_len=a.predict_steps) for mode in ("train", "val"))
+        _, hist = gst_train.train(out_dir=run, dataset=sets, batch_size=a.batch_size, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev,
+                                  pred_seq_len=a.predict_steps)
         print("predictor (%d + %d sequences of %d envs, batches of %d): val aoe %.4f -> %.4f, val foe %.4f -> %.4f" % (
             len(sets[0]), len(sets[1]), a.collect_envs, a.batch_size, hist["val_aoe_task"][0], hist["val_aoe_task"][-1], hist["val_foe_task"][0], hist["val_foe_task"][-1]), flush=True)
         return run
@@ -45,7 +46,8 @@ def fresh_predictor(a, dev):
     for i in range(min(a.train_files, a.collect_envs)):
         with open(os.path.join(data_dir, "%d.txt" % i), "w") as f:
             f.write("\n".join(lines[i]) + "\n")
-    _, hist = gst_train.train(data_dir, run, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev, batch_size=a.batch_size)
+    _, hist = gst_train.train(data_dir, run, num_epochs=a.epochs, temp_epochs=max(a.epochs, 4), save_epochs=a.epochs, device=dev, batch_size=a.batch_size,
+                              pred_seq_len=a.predict_steps)
     print("predictor: val aoe %.4f -> %.4f, val foe %.4f -> %.4f" % (hist["val_aoe_task"][0], hist["val_aoe_task"][-1], hist["val_foe_task"][0],
                                                                    hist["val_foe_task"][-1]), flush=True)
     return run
@@ -66,6 +68,8 @@ def main():
     ap.add_argument("--eval-interval", type=int, default=100)
     ap.add_argument("--eval-cases", type=int, default=500)
     ap.add_argument("--seed", type=int, default=425)
+    ap.add_argument("--predict-steps", type=int, default=5, help="the prediction horizon P = sim.predict_steps = the predictor's pred_seq_len (1 .. 7 with this policy; "
+                    "a --model-dir must hold a predictor of that horizon)")
     ap.add_argument("--out", default="/tmp/gst_policy")
     a = ap.parse_args()
     logging.basicConfig(level=logging.INFO, stream=sys.stdout)
@@ -74,7 +78,7 @@ def main():
     model_dir = a.model_dir or fresh_predictor(a, dev)
     pred = GSTPredictor.from_checkpoint(find_checkpoint(model_dir), dev)
     t1 = time.time()
-    cfg = C.non_randomized(**{"sim.human_num": 20, "sim.predict_method": "inferred", "env.use_wrapper": True, "pred.model_dir": model_dir})
+    cfg = C.non_randomized(**{"sim.human_num": 20, "sim.predict_method": "inferred", "sim.predict_steps": a.predict_steps, "env.use_wrapper": True, "pred.model_dir": model_dir})
     every = max(a.updates // 12, 1)
     acc = []
 

@@ -712,10 +712,16 @@ typedef struct {
 } cn_gst_weights;
 typedef struct cn_gst cn_gst;
 int cn_gst_create(int human_num, int max_envs, cn_gst **out);
+/* The prediction horizon P = pred_seq_len of the predictor = sim.predict_steps of the env, 1 <= pred_steps <= CN_MAX_PRED: the handle decodes P
+ * steps per forward, out_traj is [E,H,P,5] and the wrapper's edges are 2 (P + 1) wide.  The observed length stays 5 and the parameters
+ * (cn_gst_weights) do not depend on P: the decode is a recurrence.  cn_gst_create is cn_gst_create_horizon with P = 5 -- the same launches and
+ * bits.  cn_gst_pred_steps: the handle's P.  (CN_ABI_VERSION is unchanged: these are additions, no existing signature or struct layout moved.) */
+int cn_gst_create_horizon(int human_num, int max_envs, int pred_steps, cn_gst **out);
+int cn_gst_pred_steps(const cn_gst *g);
 int cn_gst_destroy(cn_gst *g);
 int cn_gst_set_weights(cn_gst *g, const cn_gst_weights *w, void *stream);
-/* in_traj [E,H,5,2] world positions, in_mask [E,H,5] (0/1 float) -> out_traj [E,H,5,5] = cumulative (mu_x, mu_y, sigma_x,
- * sigma_y, corr), positions -999 where the pedestrian is not predicted; out_mask [E,H] (0/1 float). */
+/* in_traj [E,H,5,2] world positions, in_mask [E,H,5] (0/1 float) -> out_traj [E,H,P,5] = cumulative (mu_x, mu_y, sigma_x,
+ * sigma_y, corr), positions -999 where the pedestrian is not predicted; out_mask [E,H] (0/1 float).  P: the handle's horizon. */
 int cn_gst_predict(cn_gst *g, int E, const float *in_traj, const float *in_mask, float *out_traj, float *out_mask, void *stream);
 int cn_gst_wrapper_reset(cn_gst *g, int E, void *stream);
 /* Prediction stride (rl/vec_env/vec_pretext_normalize.py:56-57, :133-134): pred_interval = int(data.pred_timestep // env.time_step); the
@@ -728,10 +734,10 @@ int cn_gst_wrapper_history_len(const cn_gst *g);
  * (cn_env_save) this makes a resumed CrowdSimPredRealGST-v0 run continue bit for bit. */
 int cn_gst_wrapper_save(cn_gst *g, float *traj, uint8_t *mask, void *stream);
 int cn_gst_wrapper_load(cn_gst *g, int E, const float *traj, const uint8_t *mask, void *stream);
-/* obs: the raw CrowdSimPredRealGST-v0 observation (robot_node, spatial_edges [E,H,12] by human id, visible_masks).  Pushes the
- * new positions into the 5-deep history, runs the predictor, adds the social penalty min_{h,k}(collision * penalty / 2^(k+2))
- * to rewards [E] (in place, may be NULL) and writes spatial_edges_out [E,H,12]: predictions in the robot frame where valid,
- * rows sorted by current distance. */
+/* obs: the raw CrowdSimPredRealGST-v0 observation (robot_node, spatial_edges [E,H,2(P+1)] by human id, visible_masks; P = the handle's
+ * horizon, 12 columns at the shipped 5).  Pushes the new positions into the 5-deep history, runs the predictor, adds the social penalty
+ * min_{h, k < P}(collision * penalty / 2^(k+2)) to rewards [E] (in place, may be NULL) and writes spatial_edges_out [E,H,2(P+1)]:
+ * predictions in the robot frame where valid, rows sorted by current distance. */
 int cn_gst_wrapper_step(cn_gst *g, int E, const cn_obs *obs, float robot_plus_human_radius, float collision_penalty, float *rewards,
                         float *spatial_edges_out, void *stream);
 
@@ -748,6 +754,17 @@ int cn_gst_wrapper_step(cn_gst *g, int E, const cn_obs *obs, float robot_plus_hu
 int64_t cn_gst_train_workspace_bytes(int B, int N);
 int cn_gst_train_step(int B, int N, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const cn_gst_weights *grads,
                       float p_drop, uint64_t seed, void *workspace, int64_t workspace_bytes, float *loss_out, float *gauss_out, void *stream);
+/* The same step at a prediction horizon of P = pred_seq_len steps, 1 <= P <= CN_MAX_PRED: v_pred [B,P,N,2], loss_mask_rel [B,N,5+P], gauss_out
+ * [B,P,N,5]; 4 + P encoder-layer passes and LSTM steps per sequence.  The entry points above are these with P = 5 (same launches, same bits).
+ * The dropout stream for general P: the mask of element `idx` of dropout site `site` (0 attention probabilities [8,N,N], 1 out_proj output
+ * [N,64], 2 FFN hidden [N,128], 3 FFN output [N,64]; idx = the element's row-major offset) in encoder-layer pass `call` of sequence b is a
+ * function of (seed + 0x632BE59BD9B4E019 (b + 1), call * 4 + site + 1, idx) alone, where call counts the 4 + P passes in forward order: 0 .. 4 the
+ * observed slices, 4 + tt the pass in front of decode step tt = 1 .. P - 1.  P does not enter: a pass that exists at two horizons draws the
+ * same mask at both. */
+int64_t cn_gst_train_workspace_bytes_horizon(int B, int N, int P);
+int cn_gst_train_step_horizon(int B, int N, int P, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w,
+                              const cn_gst_weights *grads, float p_drop, uint64_t seed, void *workspace, int64_t workspace_bytes, float *loss_out,
+                              float *gauss_out, void *stream);
 
 /* ---- GST predictor EVALUATION step: validation (decode on the mean) and the sampled test protocol, B sequences per call ----
  * Replaces, per sequence, the body of gst_updated/scripts/experiments/eval.py:63-117 (`inference`): st_model.forward (st_model.py:271-455, dropout
@@ -767,6 +784,12 @@ int cn_gst_train_step(int B, int N, const float *v_obs, const float *v_pred, con
 int64_t cn_gst_eval_workspace_bytes(int B, int N, int S);
 int cn_gst_eval_step(int B, int N, int S, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w, const float *noise,
                      void *workspace, int64_t workspace_bytes, float *seq_out, float *ped_out, float *gauss_out, void *stream);
+/* The same at a prediction horizon of P steps, 1 <= P <= CN_MAX_PRED: v_pred [B,P,N,2], loss_mask_rel [B,N,5+P], noise [B,S,P,N,2], gauss_out
+ * [B,R,P,N,5]; the average offset error is over the P steps, and a pedestrian counts when present at all 5 + P.  A sequence lives in LDS:
+ * 133 KB at N = 64, P = 8, the largest case, of the CU's 160 KiB.  The entry points above are these with P = 5. */
+int64_t cn_gst_eval_workspace_bytes_horizon(int B, int N, int S, int P);
+int cn_gst_eval_step_horizon(int B, int N, int S, int P, const float *v_obs, const float *v_pred, const float *loss_mask_rel, const cn_gst_weights *w,
+                             const float *noise, void *workspace, int64_t workspace_bytes, float *seq_out, float *ped_out, float *gauss_out, void *stream);
 
 /* ---- GST predictor training DATA on the device: sequences from the collect batch's observation log, and minibatches of them ----
  * Replaces gst_updated/src/mgnn/trajectories.py:9-160 (TrajectoriesDataset: obs 5, pred 5, skip 1, frame_diff 1, invalid -999) over the text
@@ -809,6 +832,20 @@ int cn_gst_data_fill(int F, int E, int H, int mode, const float *log, const int3
 int cn_gst_gather_batch(int B, int Np, int num_seq, int64_t total_peds, const int32_t *index, const float *cos_sin, const int32_t *seq_start,
                         const int32_t *seq_count, const float *obs_traj_rel, const float *pred_traj_rel, const float *loss_mask_rel,
                         float *v_obs, float *v_pred, float *loss_mask_rel_out, void *stream);
+/* The data calls at a prediction horizon of P = pred_seq_len steps, 1 <= P <= CN_MAX_PRED (TrajectoriesDataset(obs_seq_len=5, pred_seq_len=P)):
+ * read 5 + P for every 10, 4 + P for every 9 and "all 5 + P frames" for "all ten" in the rule above -- F >= 5 + P, W = F - (4 + P) candidates
+ * per env; pred_traj, pred_traj_rel [total_peds,2,P], loss_mask, loss_mask_rel [total_peds,5+P]; the gather writes v_pred [B,P,Np,2] and
+ * loss_mask_rel_out [B,Np,5+P].  A log of fewer than 5 + P samples is refused and launches nothing.  The calls above are these with P = 5. */
+int cn_gst_data_frames_horizon(int F, int E, int H, int P, const float *log, int32_t *visible, float *frame_id, int32_t *status, void *stream);
+int cn_gst_data_count_horizon(int F, int E, int H, int mode, int P, const float *log, const int32_t *visible, const int32_t *listed_before,
+                              const float *frame_id, int32_t *frame_list, int32_t *ped_count, float *first_frame, int32_t *status, void *stream);
+int cn_gst_data_fill_horizon(int F, int E, int H, int mode, int P, const float *log, const int32_t *visible, const int32_t *listed_before,
+                             const float *frame_id, const int32_t *frame_list, const int32_t *ped_count, const int32_t *ped_offset,
+                             int64_t total_peds, float *obs_traj, float *pred_traj, float *obs_traj_rel, float *pred_traj_rel, float *loss_mask,
+                             float *loss_mask_rel, void *stream);
+int cn_gst_gather_batch_horizon(int B, int Np, int P, int num_seq, int64_t total_peds, const int32_t *index, const float *cos_sin,
+                                const int32_t *seq_start, const int32_t *seq_count, const float *obs_traj_rel, const float *pred_traj_rel,
+                                const float *loss_mask_rel, float *v_obs, float *v_pred, float *loss_mask_rel_out, void *stream);
 
 /* ---- rollout math ---- */
 /* rewards [T,N], values [T+1,N], masks [T+1,N] -> returns[t][n] for t < T (row T untouched).  fp32, torch op order. */
