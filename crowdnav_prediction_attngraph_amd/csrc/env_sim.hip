@@ -1054,6 +1054,28 @@ extern "C" int cn_env_set_pregen_budget(cn_env_batch *env, int64_t ticks_10ns)
 
 extern "C" int64_t cn_row_plan_words(int num_envs) { return num_envs > 0 ? (int64_t)rp_words(num_envs) : 0; }
 
+// The row-plan builder on its own, for counts the caller supplies: the rowplan::build the lane kernel hosts, one workgroup per group.
+// (No batch: the groups' arrival counter is header word 7, cleared in front of the launch and left at zero by the last group.)
+__global__ __launch_bounds__(64) void row_plan_kernel(int E, int H, const float *det, int32_t *plan)
+{
+    __shared__ rowplan::Lds lds;
+    rowplan::build((int)blockIdx.x, (int)gridDim.x, E, H, rp_workgroups(E, H), det, plan, lds);
+}
+
+extern "C" int cn_row_plan_build(int num_envs, int rows, const float *detected_human_num, int32_t *row_plan, void *stream)
+{
+    if (int rc = cn_require_device()) return rc;
+    CN_REQUIRE(num_envs > 0 && rows >= 1 && detected_human_num && row_plan, "cn_row_plan_build: null argument or empty batch");
+    CN_REQUIRE((((uintptr_t)detected_human_num | (uintptr_t)row_plan) & 15u) == 0, "cn_row_plan_build: both buffers must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    CN_HIP(hipMemsetAsync(row_plan, 0, RP_HDR * sizeof(int32_t), st));
+    // (a batch the builder does not take -- more than RP_EMAX envs or RP_HMAX rows, a size that is no multiple of four -- leaves word 0 zero)
+    if (num_envs > RP_EMAX) return CN_OK;
+    hipLaunchKernelGGL(row_plan_kernel, dim3(rp_groups(num_envs)), dim3(64), 0, st, num_envs, rows, detected_human_num, row_plan);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 extern "C" int cn_env_destroy(cn_env_batch *env)
 {
     if (!env) return CN_OK;

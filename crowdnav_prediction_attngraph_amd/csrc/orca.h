@@ -4,6 +4,7 @@
 #pragma once
 #include "env_dev.h"
 #include "det_math.h"
+#include <type_traits>
 
 namespace {
 
@@ -460,6 +461,22 @@ __global__ __launch_bounds__(256) void orca_kernel(EnvDev s)
 // and the linear programs are fully unrolled over (line i, earlier line j).  linearProgram3 (the infeasible case, a few agents
 // per thousand) would unroll to O(NB^3) code: those agents are put on a list and redone by the wave-cooperative routine above.
 // Same arithmetic, same operation order as orca_wave / the oracle: results are bit-identical.
+//
+// The launch is a chain of VALU / SALU instructions per wavefront, and a quarter of the SIMDs carry two agent wavefronts (1280 of them on
+// 1024 SIMDs at 4096 x 20): what the agent path does not issue comes off the launch twice.  profiles/HISTORY.md section 23 took out of it
+// what the result does not need, with every operation that defines the result left where it was:
+//   - the staging block converts each record ONCE: (float) px, py, vx, vy as one float4 and the radius (float)(rad + 0.01 + safety); only
+//     the positions stay as doubles as well.  Pass 1 and pass 2 read floats (one ds_read per neighbour) instead of converting 5 doubles
+//     and adding 2 in every turn;
+//   - the exact coincidence test (double positions equal -> the dummy human at (7, 7)) sits behind a float filter, see pass 1;
+//   - pass 1 is unrolled (static slot offsets, static key registers), in scheduling groups of four;
+//   - the neighbour order compares (key bits, slot) as one 64-bit integer: 6 instructions per compare-exchange, none of them control flow
+//     (the short-circuit comparator was 14 with an s_and_saveexec);
+//   - 1 / time horizon and 1 / time step are pinned in registers (the select between them was compiled as a select of the doubles, a
+//     conversion and a full division per neighbour), the selects of pass 2 are bitwise;
+//   - the divisor of the pair walk comes from a lane-computed table, the loop bound from a DPP reduction.
+// Measured (4096 x 20, stamped step, two runs): orca_lane 41.1-41.8 -> 35.1-36.6 us; the launch still ends with the row-plan builders.  Resources of <20,32>: 168 VGPRs, no scratch, 61
+// spilled scalars (parent 69), 25 408 B static LDS (parent 25 920; six workgroups per CU need <= 27 306).
 // ------------------------------------------------------------------------------------------------------------------
 #include "orca_sortnet.inc"
 #include "row_plan.h"
@@ -469,9 +486,10 @@ template <> struct LaneVec<8> { typedef float f __attribute__((ext_vector_type(8
 template <> struct LaneVec<32> { typedef float f __attribute__((ext_vector_type(32))); };
 
 // NB = slots the sorting network orders (>= candidate neighbours incl. self), VW = width of the register vectors that hold the
-// per-lane arrays.  The loops over neighbours / lines are ROLLED with wave-uniform counters: a vector element is then selected by
-// a uniform register index (s_set_gpr_idx), not by 20-32 unrolled copies -- fully unrolled the kernel was 85 KB of straight-line
-// code that every wavefront fetched exactly once (instruction-fetch bound, slower than the cooperative kernel).
+// per-lane arrays.  The loops over the sorted neighbours / the lines (pass 2, the linear program) are ROLLED with wave-uniform counters: a
+// vector element is then selected by a uniform register index (s_set_gpr_idx), not by 20-32 unrolled copies -- fully unrolled the kernel
+// was 85 KB of straight-line code that every wavefront fetched exactly once (instruction-fetch bound, slower than the cooperative kernel).
+// Pass 1 (a dozen instructions per slot) is unrolled.
 template <int NB, int VW>
 __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *plan_det, int32_t *plan, int plan_groups, unsigned long long *plan_stamp)
 {
@@ -500,11 +518,18 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
     // pass 1, a per-lane gather in pass 2 -- is an LDS read instead of an L2 round trip (the kernel is a chain of dependent loads)
     // (the kernel for NB slots serves crowds of more than NB' agents, NB' the next smaller network: at most 63 / (NB' - 1) + 2 envs per wavefront)
     constexpr int NENV = NB == 8 ? 65 : (NB == 20 ? 10 : 5);
-    __shared__ double s_px[128], s_py[128], s_vx[128], s_vy[128], s_rad[128], s_rob[NENV][4];
+    // Per agent: the position as doubles (the own goal vector and the exact coincidence test need them) and, converted ONCE by the lane that
+    // stages the row, what the loops below work on: (float) px, py, vx, vy and the radius as a neighbour's simulator holds it,
+    // (float)(rad + 0.01 + safety).  The robots' words likewise.  (Kept as doubles and converted in every turn of pass 1 and pass 2, a
+    // neighbour cost 5 ds_read_b64, 5 conversions and two double additions per half-plane.)
+    __shared__ double s_px[128], s_py[128], s_rob[NENV][2];
+    __shared__ float4 s_f4[128], s_frob[NENV];
+    __shared__ float s_fr[128];
     // this lane's own words go out in the same batch as the staging loads, not behind the barrier and behind each other: its goal and
     // preferred speed, and its private simulator -- read whether it is still valid or not (a rebuild below overwrites what was read)
     const double *hum = s.hum + (size_t)e * 8 * H;
     const size_t ei = (size_t)e * H + i;
+    const double safety = c.orca_safety_space;
     double sgx, sgy, svpref, shared_nd_in;
     int sim_valid_in, sim_n_in = 0;
     float sim_nd_in, sim_r_in, sim_ms_in;
@@ -531,18 +556,24 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int r = threadIdx.x + 64 * it;
-            if (r < nrows) { s_px[r] = st[it][0]; s_py[r] = st[it][1]; s_vx[r] = st[it][2]; s_vy[r] = st[it][3]; s_rad[r] = st[it][4]; }
+            if (r < nrows) {
+                s_px[r] = st[it][0]; s_py[r] = st[it][1];
+                s_f4[r] = make_float4((float)st[it][0], (float)st[it][1], (float)st[it][2], (float)st[it][3]);
+                s_fr[r] = (float)(st[it][4] + 0.01 + safety);
+            }
         }
         if (c.robot_visible)
             for (int q = threadIdx.x; q <= e1 - e0; q += 64) {
                 const double *rb = s.rob + (size_t)(e0 + q) * 8;
-                s_rob[q][0] = rb[R_PX]; s_rob[q][1] = rb[R_PY]; s_rob[q][2] = rb[R_VX]; s_rob[q][3] = rb[R_VY];
+                const double rx0 = rb[R_PX], ry0 = rb[R_PY], rvx0 = rb[R_VX], rvy0 = rb[R_VY];
+                s_rob[q][0] = rx0; s_rob[q][1] = ry0;
+                s_frob[q] = make_float4((float)rx0, (float)ry0, (float)rvx0, (float)rvy0);
             }
         __syncthreads();
     }
     const int eq = e - (blk * 64) / H, eb = eq * H; // this lane's env inside the staged block
-    const double spx = s_px[eb + i], spy = s_py[eb + i], svx = s_vx[eb + i], svy = s_vy[eb + i], srad = s_rad[eb + i];
-    const double safety = c.orca_safety_space;
+    const double spx = s_px[eb + i], spy = s_py[eb + i];
+    const float4 self4 = s_f4[eb + i];
     const bool rv = c.robot_visible != 0;
     const int n_agents = n + (rv ? 1 : 0);
     // lazily (re)build human i's private simulator: orca.py:80-89
@@ -551,73 +582,122 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
         const bool rebuild = !sim_valid_in || (s.sim_n && sim_n_in != n_agents);
         if (rebuild) {
             nd = (float)shared_nd_in;
-            self_r = (float)(srad + 0.01 + safety);
+            self_r = s_fr[eb + i];
             self_ms = (float)svpref;
             if (s.sim_seen)
-                for (int j = 0; j < n; ++j) s.sim_seen[ei * H + j] = (float)(s_rad[eb + j] + 0.01 + safety);
+                for (int j = 0; j < n; ++j) s.sim_seen[ei * H + j] = s_fr[eb + j];
             s.sim_nd[ei] = nd; s.sim_self_radius[ei] = self_r; s.sim_self_maxspeed[ei] = self_ms; s.sim_valid[ei] = 1;
             if (s.sim_n) s.sim_n[ei] = (uint8_t)n_agents;
         } else {
             nd = sim_nd_in; self_r = sim_r_in; self_ms = sim_ms_in;
         }
     }
-    const float fpx = (float)spx, fpy = (float)spy, fvx = (float)svx, fvy = (float)svy;
-    // pass 1: distance keys of the candidates in index order (slot j = agent j; self and empty slots get +inf)
-    vec key, idx; // idx holds small integers as floats (exact)
+    const float fpx = self4.x, fpy = self4.y, fvx = self4.z, fvy = self4.w;
+    float4 rob4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (rv) rob4 = s_frob[eq];
+    const float rob_r = (float)(c.robot_radius + 0.01 + safety); // fixed for the whole run
+    // pass 1: distance keys of the candidates in index order (slot j = agent j; self and empty slots get +inf).  Fully unrolled: slot j of this
+    // lane's env sits at a fixed offset from the lane's base, the reads go out together and key[j] is a register of its own.
+    // The reference substitutes (7, 7, 0, 0) for a neighbour whose DOUBLE position equals the agent's.  (float) is a function: positions that
+    // differ as floats differ as doubles, so the loop compares the staged floats, and only a wavefront in which some candidate's floats are
+    // equal to its agent's goes through the exact form (the rolled loop behind it, which reads the doubles) -- almost never.
+    vec key, idx; // idx holds the slot numbers' bits
     int nn = 0;
+    unsigned coin = 0u; // bit j: slot j is coincident with this agent (the dummy human)
+    {
+        const float ndSq = nd * nd;
+        bool feq = false;
+        auto pass1 = [&](auto with_robot) {
+#pragma unroll
+            for (int j = 0; j < NB; ++j) {
+                // (slots j >= n read the rows behind the env's, inside the arrays for every crowd size the kernel serves: not candidates)
+                float qx = s_f4[eb + j].x, qy = s_f4[eb + j].y;
+                bool cand = active && j < n && j != i;
+                if constexpr (decltype(with_robot)::value) {
+                    const bool isR = j == n;
+                    qx = isR ? rob4.x : qx; qy = isR ? rob4.y : qy;
+                    cand = cand || (active && isR);
+                }
+                feq |= cand & (qx == fpx) & (qy == fpy); // (bitwise: `||` / `&&` became control flow around each compare)
+                const float ddx0 = fpx - qx, ddy0 = fpy - qy;
+                const float dq = ddx0 * ddx0 + ddy0 * ddy0;
+                const bool inrange = cand && dq < ndSq;
+                key[j] = inrange ? dq : INFINITY;
+                nn += inrange ? 1 : 0;
+                // (groups of four: scheduled as one block, the 20-32 candidate masks are all alive at once and spill scalar registers)
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        if (rv) pass1(std::true_type{}); else pass1(std::false_type{});
+        if (__ballot(feq) != 0ull) {
+            nn = 0;
 #pragma unroll 1
-    for (int j = 0; j < NB; ++j) {
-        const bool isR = rv && j == n;
-        const bool cand = active && ((j < n && j != i) || isR);
-        const int lj = j < n ? j : 0;
-        const double qx = isR ? s_rob[eq][0] : s_px[eb + lj], qy = isR ? s_rob[eq][1] : s_py[eb + lj];
-        const bool coincident = (qx == spx) && (qy == spy);
-        const float opx = coincident ? 7.0f : (float)qx, opy = coincident ? 7.0f : (float)qy;
-        const float ddx0 = fpx - opx, ddy0 = fpy - opy;
-        const float dq = ddx0 * ddx0 + ddy0 * ddy0;
-        const bool inrange = cand && dq < nd * nd;
-        key[j] = inrange ? dq : INFINITY;
-        idx[j] = (float)j;
-        nn += inrange ? 1 : 0;
+            for (int j = 0; j < NB; ++j) {
+                const bool isR = rv && j == n;
+                const bool cand = active && ((j < n && j != i) || isR);
+                const int lj = j < n ? j : 0;
+                const double qxd = isR ? s_rob[eq][0] : s_px[eb + lj], qyd = isR ? s_rob[eq][1] : s_py[eb + lj];
+                const float qx = isR ? rob4.x : s_f4[eb + lj].x, qy = isR ? rob4.y : s_f4[eb + lj].y;
+                const bool coincident = (qxd == spx) && (qyd == spy);
+                if (cand && coincident) coin |= 1u << j;
+                const float opx = coincident ? 7.0f : qx, opy = coincident ? 7.0f : qy;
+                const float ddx0 = fpx - opx, ddy0 = fpy - opy;
+                const float dq = ddx0 * ddx0 + ddy0 * ddy0;
+                const bool inrange = cand && dq < ndSq;
+                key[j] = inrange ? dq : INFINITY;
+                nn += inrange ? 1 : 0;
+            }
+        }
     }
-    // ascending (distSq, index): RVO2's insertion order; the +inf slots end up behind the nn real neighbours
-#define ORCA_CE(a, b)                                                                                  \
-    {                                                                                                  \
-        const float ka0 = key[a], kb0 = key[b], ia0 = idx[a], ib0 = idx[b];                             \
-        const bool sw = kb0 < ka0 || (kb0 == ka0 && ib0 < ia0);                                         \
-        key[a] = sw ? kb0 : ka0; key[b] = sw ? ka0 : kb0; idx[a] = sw ? ib0 : ia0; idx[b] = sw ? ia0 : ib0; \
+    const bool any_coin = __ballot(coin != 0u) != 0ull;
+    // ascending (distSq, index): RVO2's insertion order; the +inf slots end up behind the nn real neighbours.  A key is a sum of squares or
+    // +inf: not negative, no NaN, so its bit pattern orders like the float, and (key bits, slot) as ONE 64-bit integer orders like the pair:
+    // a compare-exchange is one comparison and four selects, without control flow.  Only the slots are used below.
+    {
+        unsigned long long kv[NB];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) kv[j] = ((unsigned long long)__float_as_uint(key[j]) << 32) | (unsigned)j;
+#define ORCA_CE(a, b)                                                  \
+    {                                                                  \
+        const unsigned long long ka0 = kv[a], kb0 = kv[b];             \
+        const bool sw = kb0 < ka0;                                     \
+        kv[a] = sw ? kb0 : ka0; kv[b] = sw ? ka0 : kb0;                \
     }
-    if constexpr (NB == 8) { ORCA_SORTNET_8(ORCA_CE) }
-    else if constexpr (NB == 20) { ORCA_SORTNET_20(ORCA_CE) }
-    else { static_assert(NB == 32, "sorting networks exist for 8, 20 and 32 slots"); ORCA_SORTNET_32(ORCA_CE) }
+        if constexpr (NB == 8) { ORCA_SORTNET_8(ORCA_CE) }
+        else if constexpr (NB == 20) { ORCA_SORTNET_20(ORCA_CE) }
+        else { static_assert(NB == 32, "sorting networks exist for 8, 20 and 32 slots"); ORCA_SORTNET_32(ORCA_CE) }
 #undef ORCA_CE
-    int nmax = nn; // wave-uniform loop bound
-    for (int off = 32; off >= 1; off >>= 1) nmax = max(nmax, __shfl_xor(nmax, off, 64));
-    nmax = __builtin_amdgcn_readfirstlane(nmax);
+#pragma unroll
+        for (int j = 0; j < NB; ++j) idx[j] = __uint_as_float(held((unsigned)kv[j])); // (pinned: or pass 2 indexes kv[] itself, in scratch)
+    }
+    const int nmax = rowplan::wave_max(nn); // wave-uniform loop bound (a DPP reduction: six ds_bpermute round trips as shuffles)
     // pass 2: the ORCA half-plane of the k-th nearest neighbour (Agent::computeNewVelocity), kept in LDS as s_line[k][lane]: the
     // linear program below reads lines of OTHER lanes' agents at per-lane line numbers, which registers cannot do.
     // The three cases of RVO2 (cut-off circle, legs, collision) go through ONE sqrtf and ONE division whose operands are selected per
     // case -- the same operations on the same operands as the branchy form (no contraction in this file), so the same bits, but no
     // divergence: with 64 agents in a wavefront every branch was taken by somebody.
-    const float invTH = 1.0f / (float)c.orca_time_horizon, invDT = 1.0f / (float)c.time_step;
+    // (1 / time horizon and 1 / time step are pinned: left to the compiler, `collide ? invDT : invTH` became a select of the two DOUBLES, a
+    // conversion and a third full division in every turn)
+    const float invTH = held(1.0f / (float)c.orca_time_horizon), invDT = held(1.0f / (float)c.time_step);
     float4 *const s_line = reinterpret_cast<float4 *>(s_raw);
     const int tid = threadIdx.x;
 #pragma unroll 1
     for (int k = 0; k < nmax; ++k) {
         float o_px = 0.0f, o_py = 0.0f, o_dx = 1.0f, o_dy = 0.0f;
-        const int j = (int)idx[k];
+        const int j = (int)__float_as_uint(idx[k]);
         if (k < nn) {
             const bool isR = j == n; // only reachable when rv
             const int lj = isR ? 0 : j;
-            const double qx = isR ? s_rob[eq][0] : s_px[eb + lj], qy = isR ? s_rob[eq][1] : s_py[eb + lj];
-            const double qvx = isR ? s_rob[eq][2] : s_vx[eb + lj], qvy = isR ? s_rob[eq][3] : s_vy[eb + lj];
+            float4 q = s_f4[eb + lj];
             float orad;
-            if (isR) orad = (float)(c.robot_radius + 0.01 + safety); // fixed for the whole run
-            else if (s.sim_seen) orad = s.sim_seen[ei * H + lj];
-            else orad = (float)(s_rad[eb + lj] + 0.01 + safety);
-            const bool coincident = (qx == spx) && (qy == spy);
-            const float opx = coincident ? 7.0f : (float)qx, opy = coincident ? 7.0f : (float)qy;
-            const float ovx = coincident ? 0.0f : (float)qvx, ovy = coincident ? 0.0f : (float)qvy;
+            if (s.sim_seen) orad = s.sim_seen[ei * H + lj];
+            else orad = held(s_fr[eb + lj]); // (pinned: or the two become one flat load through a selected pointer)
+            if (rv) { q.x = isR ? rob4.x : q.x; q.y = isR ? rob4.y : q.y; q.z = isR ? rob4.z : q.z; q.w = isR ? rob4.w : q.w; orad = isR ? rob_r : orad; }
+            if (any_coin) { // (wave-uniform)
+                const bool coincident = (coin >> j) & 1u;
+                q.x = coincident ? 7.0f : q.x; q.y = coincident ? 7.0f : q.y; q.z = coincident ? 0.0f : q.z; q.w = coincident ? 0.0f : q.w;
+            }
+            const float opx = q.x, opy = q.y, ovx = q.z, ovy = q.w;
             const float rpx = opx - fpx, rpy = opy - fpy;   // relativePosition
             const float rvx = fvx - ovx, rvy = fvy - ovy;   // relativeVelocity
             const float distSq = rpx * rpx + rpy * rpy;
@@ -628,7 +708,7 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
             const float wx = rvx - invT * rpx, wy = rvy - invT * rpy;
             const float wLenSq = wx * wx + wy * wy;
             const float dot1 = wx * rpx + wy * rpy;
-            const bool circle = collide || (dot1 < 0.0f && dot1 * dot1 > crSq * wLenSq); // project on the cut-off circle
+            const bool circle = collide | ((dot1 < 0.0f) & (dot1 * dot1 > crSq * wLenSq));  // project on the cut-off circle (bitwise: no control flow)
             const float sq = sqrtf(circle ? wLenSq : distSq - crSq);                        // wLen, or the leg length
             const float inv = 1.0f / (circle ? sq : distSq);                                // 1 / wLen, or 1 / distSq
             // cut-off circle (time horizon, or the time step on collision)
@@ -636,8 +716,9 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
             const float sc = cr * invT - sq;
             // legs
             const bool left = rpx * wy - rpy * wx > 0.0f;
-            const float lgx = left ? (rpx * sq - rpy * cr) * inv : -((rpx * sq + rpy * cr) * inv);
-            const float lgy = left ? (rpx * cr + rpy * sq) * inv : -((-rpx * cr + rpy * sq) * inv);
+            const float lxl = (rpx * sq - rpy * cr) * inv, lxr = -((rpx * sq + rpy * cr) * inv); // (both sides computed, then selected)
+            const float lyl = (rpx * cr + rpy * sq) * inv, lyr = -((-rpx * cr + rpy * sq) * inv);
+            const float lgx = left ? lxl : lxr, lgy = left ? lyl : lyr;
             const float dot2 = rvx * lgx + rvy * lgy;
             const float ldx = circle ? uwy : lgx, ldy = circle ? -uwx : lgy;
             const float ux = circle ? sc * uwx : dot2 * lgx - rvx, uy = circle ? sc * uwy : dot2 * lgy - rvy;
@@ -671,6 +752,9 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
     auto okey_inv = [](unsigned o) { return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xffffffffu)); };
     bool failed = false;
     int line_fail = 0;
+    // lane l: ceil(2^20 / l), the multiplier that divides a pair number by l; a violated line li < 32 fetches lane li's (the division by
+    // the wave-uniform li, done in the loop, was 25 dependent instructions per violated line)
+    const unsigned inv20_of_lane = ((1u << 20) + (unsigned)max(tid, 1) - 1u) / (unsigned)max(tid, 1);
 #pragma unroll 1
     for (int li = 0; li < nmax; ++li) {
         const float4 Li = s_line[li * 64 + tid];
@@ -693,7 +777,7 @@ __global__ __launch_bounds__(64) void orca_lane_kernel(EnvDev s, const float *pl
                 s_vl[rank] = tid; s_tl[tid] = okey(tLeft); s_tr[tid] = okey(tRight); s_pf[tid] = 0;
             }
             __syncthreads(); // (one wavefront: orders the LDS traffic, costs a waitcnt)
-            const unsigned inv20 = ((1u << 20) + (unsigned)li - 1u) / (unsigned)li; // p / li = p * inv20 >> 20 for p (li - 1) < 2^20
+            const unsigned inv20 = (unsigned)__builtin_amdgcn_readlane((int)inv20_of_lane, li); // p / li = p * inv20 >> 20 for p (li - 1) < 2^20
 #pragma unroll 1
             for (int p0 = 0; p0 < npairs; p0 += 64) {
                 const int p = p0 + tid;

@@ -15,6 +15,15 @@
 // of the simulator's ORCA lane kernel (orca.h), i.e. beside work that is on the step's critical path anyway.  Everything they touch
 // more than once lives in registers or LDS (a global round trip costs a lone wavefront 1-2 us, a ds_bpermute 100+ cycles: the scans are DPP).
 //
+// Inside the lane launch a builder takes ~42 us, not 28, and the launch ended with the builders, not with the agents.  On the builder's own
+// timers inside the real launch (RP_TIMING; profiles/HISTORY.md section 23; the timers themselves cost ~15 us) the parent spent 9.3 us on the
+// counts, their scan and the histogram, 4.7 us on the hand-out order, 43 us in the class loop and 0.8 us at the meeting point.  Shortened
+// there, the plan word for word the same (tests/test_gpu_row_plan_words.py): the group's counts are loaded in one batch with the batch's
+// (or ARE the batch's, with one group); the histogram and the position loops run over the entries a lane can hold (8 at 4096 envs), not
+// over 64; the classes' columns are read and scanned eight at a time; the per-class multiplier comes from a lane-computed table.
+// row_plan in the stamped step: 42.4-42.5 -> 37.6-38.6 us (the agents beside it: 35.1-36.6).  The class loop's hand-out (LDS fetch of the ids, then their stores) is what remains:
+// issuing the stores one hand-out late, behind the next fetches, measured SLOWER (39.6 us) and was dropped.
+//
 // Layout (int32 words): header | row_off[E + 1] | tile_cnt[RP_TMAX] | items[RP_TMAX][64], item = env | rows << 16, a tile's list ends with
 // a zero item (or at 64).
 // Tile t belongs to workgroup t % NW; a workgroup walks tiles t = c, c + NW, ...
@@ -117,12 +126,20 @@ __device__ __forceinline__ bool fill(int H, int T, int TB, int rows, int hist, i
     for (int j = 0; j < TBP; ++j) { const int c0 = base + (ln * TB + j < extra ? 1 : 0); cap0[j] = c0 > 63 ? 63 : c0; }
     bool bad = false;
     int rot = 0; // (wave-uniform) lane the next hand-out starts at
+    // lane v: ceil(2^20 / v); floor(r / v) = r * ceil(2^20 / v) >> 20 for r (v - 1) < 2^20.  Computed once by the lanes: the division by the
+    // wave-uniform v inside the class loop was ~25 dependent instructions per size class.  (Up to four tiles per lane, i.e. 256 tiles per group:
+    // the variants for more hold 8 or 16 of everything per lane and are the register peak of the kernel that hosts the builder -- one more
+    // live register there costs that kernel a wavefront per SIMD; they keep the division.)
+    constexpr bool INV_TABLE = TBP <= 4;
+    unsigned inv_of_lane = 0u;
+    if constexpr (INV_TABLE) inv_of_lane = ((1u << 20) + (unsigned)(ln < 1 ? 1 : ln) - 1u) / (unsigned)(ln < 1 ? 1 : ln);
     for (int v = H; v >= 1; --v) {
         const int m = __builtin_amdgcn_readlane(hist, v);
         if (m == 0) continue;
         const int pos0 = __builtin_amdgcn_readlane(cstart, v);
         RP_A0();
-        const unsigned inv = ((1u << 20) + (unsigned)v - 1u) / (unsigned)v; // floor(r / v) = r * ceil(2^20 / v) >> 20 for r (v - 1) < 2^20
+        const unsigned inv = INV_TABLE ? (unsigned)__builtin_amdgcn_readlane((int)inv_of_lane, v) // v <= RP_HMAX < 64
+                                       : ((1u << 20) + (unsigned)v - 1u) / (unsigned)v;
         int placed = 0; // (wave-uniform) envs of the class that have a tile
         // pass 0: dealt EVENLY -- at most ceil(m / T) envs of the class per tile, the lanes in circular order from where the previous
         // class stopped -- so that every tile gets its share of every size (filled in plain first-fit order the first tiles of a group
@@ -189,6 +206,61 @@ __device__ __forceinline__ bool fill(int H, int T, int TB, int rows, int hist, i
     return __ballot(bad) == 0ull;
 }
 
+// The tables of a group from its rows per env c[] (lane l owns the local envs [CHg * l, CHg * l + CHg)): the per-lane size histogram, per size
+// class v (lane v) the number of envs and the first position, and the hand-out order (by rows descending; inside a size class by (lane, i))
+// as lds.ids.  CHGP = CHg rounded up to a power of two: the loops over a lane's envs are unrolled over the entries that can be live (8 at
+// 4096 envs in 8 groups), not over the 64 a lane holds at most.
+template <int CHGP>
+__device__ __forceinline__ void size_histogram(const int (&c)[64], int H, Lds &lds)
+{
+    const int ln = threadIdx.x & 63;
+    // per-lane size histogram in LDS (column `lane` is private to the lane)
+    for (int k = ln; k < (H + 1) * 64; k += 64) lds.tbl[k] = 0;
+#pragma unroll
+    for (int i = 0; i < CHGP; ++i)
+        if (c[i]) __hip_atomic_fetch_add(&lds.tbl[c[i] * 64 + ln], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// tbl[v][lane] becomes the lane's next position.  Eight classes at a time, largest first: their columns are read in one batch and scanned
+// side by side (a class at a time, every class paid an LDS round trip and a scan of its own, one behind the other); the blocks past H
+// are skipped (wave-uniform).
+__device__ __forceinline__ void class_positions(int H, Lds &lds, int &hist, int &cstart)
+{
+    const int ln = threadIdx.x & 63;
+    int at = 0;
+#pragma unroll
+    for (int b = RP_HMAX - 8; b >= 0; b -= 8) {
+        if (b < H) {
+            int mine[8], incl[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) mine[u] = b + 1 + u <= H ? lds.tbl[(b + 1 + u) * 64 + ln] : 0;
+#pragma unroll
+            for (int u = 0; u < 8; ++u) incl[u] = wave_incl_scan(mine[u]);
+#pragma unroll
+            for (int u = 7; u >= 0; --u) {
+                const int v = b + 1 + u;
+                if (v <= H) { // (wave-uniform)
+                    lds.tbl[v * 64 + ln] = at + incl[u] - mine[u];
+                    const int m = __builtin_amdgcn_readlane(incl[u], 63);
+                    if (ln == v) { hist = m; cstart = at; }
+                    at += m;
+                }
+            }
+        }
+    }
+}
+template <int CHGP>
+__device__ __forceinline__ void hand_out_order(const int (&c)[64], int CHg, Lds &lds)
+{
+    const int ln = threadIdx.x & 63;
+    int pos[CHGP];
+#pragma unroll
+    for (int i = 0; i < CHGP; ++i)
+        pos[i] = c[i] ? __hip_atomic_fetch_add(&lds.tbl[c[i] * 64 + ln], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
+#pragma unroll
+    for (int i = 0; i < CHGP; ++i)
+        if (c[i]) lds.ids[pos[i]] = (unsigned short)(ln * CHg + i);   // local index: the group's base is added at the hand-out
+}
+
 // Wavefront g of G (all 64 lanes active; G = rp_groups(E), every wavefront its own workgroup / Lds).  det: detected_human_num of the
 // observation the plan is for.
 // The wavefronts meet once, at the end: each adds itself to the arrival counter (a failed group adds a flag), the last one
@@ -206,14 +278,32 @@ __device__ __forceinline__ void build(int g, int G, int E, int H, int NW, const 
     if (H > RP_HMAX || E > RP_EMAX || (E & 3)) return;
     // ---- rows per env of the WHOLE batch: lane l owns envs [CH * l, CH * l + CH) (CH = 4 * ceil(E / 256) <= 64): totals of every group ----
     const int CH = ((E + 255) >> 8) << 2;
+    // ... and of THIS group: lane l owns local envs [CHg * l, CHg * l + CHg), CHg = 4 * ceil(Eg / 256).  One group: the batch's counts, in the
+    // batch's lanes.  Several: 256 to 512 envs each (rp_groups), one or two float4 per lane, whose addresses follow from g alone -- they go
+    // out in one batch with the batch's (they were a second dependent trip behind the scan: 1-2 us for a lone wavefront)
+    const int Eg = G > 1 ? E / G : E, e_base = G > 1 ? g * Eg : 0;
+    const int CHg = ((Eg + 255) >> 8) << 2;
+    float4 dg[2];
     int mysum = 0;
+    int c[64];
     {
-        int c[64];
+        float4 db[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            float4 d = float4{0.f, 0.f, 0.f, 0.f};
+            db[q] = float4{0.f, 0.f, 0.f, 0.f};
             const int e0 = ln * CH + 4 * q;
-            if (4 * q < CH && e0 < E) d = *reinterpret_cast<const float4 *>(det + e0); // E % 4 == 0: a float4 never straddles the end
+            if (4 * q < CH && e0 < E) db[q] = *reinterpret_cast<const float4 *>(det + e0); // E % 4 == 0: a float4 never straddles the end
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            dg[q] = float4{0.f, 0.f, 0.f, 0.f};
+            const int e0 = ln * CHg + 4 * q;
+            if (G > 1 && 4 * q < CHg && e0 < Eg) dg[q] = *reinterpret_cast<const float4 *>(det + e_base + e0);
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const float4 d = db[q];
+            const int e0 = ln * CH + 4 * q;
             const float dd[4] = {d.x, d.y, d.z, d.w};
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
@@ -244,7 +334,7 @@ __device__ __forceinline__ void build(int g, int G, int E, int H, int NW, const 
     int n = (total + 62 * NW - 1) / (62 * NW);
     n = n < 1 ? 1 : n;
     const int Tall = n * NW;
-    int e_base = 0, Eg = E, t0 = 0, T = Tall, grows = total;
+    int t0 = 0, T = Tall, grows = total;
     if (G > 1) {
         const int LG = 64 / G;
         const int cum0 = g ? __builtin_amdgcn_readlane(mysum, g * LG - 1) : 0, cum1 = __builtin_amdgcn_readlane(mysum, (g + 1) * LG - 1);
@@ -252,55 +342,33 @@ __device__ __forceinline__ void build(int g, int G, int E, int H, int NW, const 
         t0 = (int)(((long long)cum0 * Tall + total / 2) / total);
         const int t1 = g == G - 1 ? Tall : (int)(((long long)cum1 * Tall + total / 2) / total);
         T = t1 - t0;
-        Eg = E / G; e_base = g * Eg;
     }
     bool ok = T >= 1 && Tall <= RP_TMAX; // (too many tiles: no plan, but every group still goes to the meeting point below)
-    int c[64];
     int hist = 0, cstart = 0; // lane v: number of envs of this group with v rows, first position of the class
     if (ok) {
-        // ---- rows per env of THIS group: lane l owns local envs [CHg * l, CHg * l + CHg), CHg = 4 * ceil(Eg / 256) ----
-        const int CHg = ((Eg + 255) >> 8) << 2;
+        if (G > 1) { // (CHg <= 8)
 #pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            float4 d = float4{0.f, 0.f, 0.f, 0.f};
-            const int e0 = ln * CHg + 4 * q;
-            const bool in = 4 * q < CHg && e0 < Eg;
-            if (in) d = *reinterpret_cast<const float4 *>(det + e_base + e0);
-            const float dd[4] = {d.x, d.y, d.z, d.w};
+            for (int q = 0; q < 2; ++q) {
+                const bool in = 4 * q < CHg && ln * CHg + 4 * q < Eg;
+                const float dd[4] = {dg[q].x, dg[q].y, dg[q].z, dg[q].w};
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                int r = (int)dd[u];
-                r = r < 1 ? 1 : (r > H ? H : r);
-                c[4 * q + u] = in ? r : 0;
+                for (int u = 0; u < 4; ++u) {
+                    int r = (int)dd[u];
+                    r = r < 1 ? 1 : (r > H ? H : r);
+                    c[4 * q + u] = in ? r : 0;
+                }
             }
         }
-        // ---- per-lane size histogram in LDS (column `lane` is private to the lane) ----
-        for (int k = ln; k < (H + 1) * 64; k += 64) lds.tbl[k] = 0;
-#pragma unroll
-        for (int i = 0; i < 64; ++i)
-            if (c[i]) __hip_atomic_fetch_add(&lds.tbl[c[i] * 64 + ln], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (CHg <= 8) size_histogram<8>(c, H, lds);
+        else if (CHg <= 16) size_histogram<16>(c, H, lds);
+        else if (CHg <= 32) size_histogram<32>(c, H, lds);
+        else size_histogram<64>(c, H, lds);
         RP_T(1);
-        // ---- hand-out order: by rows descending; inside a size class by (lane, i).  tbl[v][lane] becomes the lane's next position ----
-        {
-            int at = 0;
-            for (int v = H; v >= 1; --v) {
-                const int mine = lds.tbl[v * 64 + ln];
-                const int incl = wave_incl_scan(mine);
-                lds.tbl[v * 64 + ln] = at + incl - mine;
-                const int m = __builtin_amdgcn_readlane(incl, 63);
-                if (ln == v) { hist = m; cstart = at; }
-                at += m;
-            }
-        }
-        {
-            int pos[64];
-#pragma unroll
-            for (int i = 0; i < 64; ++i)
-                pos[i] = c[i] ? __hip_atomic_fetch_add(&lds.tbl[c[i] * 64 + ln], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) : 0;
-#pragma unroll
-            for (int i = 0; i < 64; ++i)
-                if (c[i]) lds.ids[pos[i]] = (unsigned short)(ln * CHg + i);   // local index: the group's base is added at the hand-out
-        }
+        class_positions(H, lds, hist, cstart);
+        if (CHg <= 8) hand_out_order<8>(c, CHg, lds);
+        else if (CHg <= 16) hand_out_order<16>(c, CHg, lds);
+        else if (CHg <= 32) hand_out_order<32>(c, CHg, lds);
+        else hand_out_order<64>(c, CHg, lds);
         RP_T(2);
         const int TB = (T + 63) >> 6;
         int32_t *it = items + (size_t)t0 * 64, *tc = tcnt + t0;

@@ -179,6 +179,10 @@ int cn_env_set_tail_deferral(cn_env_batch *env, int enabled);
 int cn_env_launch_tail(cn_env_batch *env, void *stream);
 /* int32 words of a cn_obs.row_plan buffer for a batch of num_envs envs */
 int64_t cn_row_plan_words(int num_envs);
+/* The row plan of an observation with these detected_human_num [num_envs] float32 (device, 16-byte aligned) and `rows` rows per env, into
+ * row_plan (cn_row_plan_words(num_envs) int32, device, 16-byte aligned): what cn_env_reset / cn_env_step write, for counts of the caller's.
+ * Word 0 stays zero where the builder does not take the batch. */
+int cn_row_plan_build(int num_envs, int rows, const float *detected_human_num, int32_t *row_plan, void *stream);
 int cn_env_reset(cn_env_batch *env, const cn_obs *obs, void *stream);
 /* actions [E,2] float32 (raw policy output; clipped inside like srnn.clip_action).  Outputs: reward [E] float32,
  * done [E] uint8, info [E] uint8 (CN_INFO_*), ep_return [E] float64 and ep_len [E] int32 (valid where done: the
