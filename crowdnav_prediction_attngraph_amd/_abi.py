@@ -274,7 +274,7 @@ ABI_SYMBOLS = [
     "cn_env_trace_append", "cn_trace_metrics", "cn_render_trajectories",
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
     "cn_srnn_create", "cn_srnn_destroy", "cn_srnn_set_weights", "cn_srnn_act", "cn_srnn_get_value", "cn_srnn_get_taps", "cn_srnn_set_gemm_mode",
-    "cn_srnn_seq_workspace_bytes", "cn_srnn_seq_fwd", "cn_srnn_seq_bwd",
+    "cn_srnn_seq_workspace_bytes", "cn_srnn_seq_fwd", "cn_srnn_seq_bwd", "cn_srnn_attn_fwd", "cn_srnn_attn_bwd",
 ]
 
 _lib = None
@@ -349,6 +349,8 @@ def lib():
         L.cn_srnn_seq_workspace_bytes.restype = i64
         L.cn_srnn_seq_fwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, i64, vp]
         L.cn_srnn_seq_bwd.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i64, C.POINTER(SrnnEdgeGrads), vp, vp, vp]
+        L.cn_srnn_attn_fwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.cn_srnn_attn_bwd.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.cn_policy_set_profiling.argtypes = [vp, i32]
         L.cn_policy_set_gemm_mode.argtypes = [vp, i32]
         L.cn_policy_set_self_attention.argtypes = [vp, i32]

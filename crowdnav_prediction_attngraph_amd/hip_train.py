@@ -38,6 +38,69 @@ class SrnnEdgeSequence(torch.autograd.Function):
         return (None, None, None, d_h0, None) + tuple(grads)
 
 
+class SrnnAttention(torch.autograd.Function):
+    """The DS-RNN baseline's edge attention (SRNNBase.attention) over the saved edge states, read in place: (h_all [..., H+1, 256] -- slot 0 the
+    temporal edge, slots 1 .. H the spatial edges --, Wt [64,256], bt [64], Ws [64,256], bs [64]) -> (weighted [..., 256], attn [..., H]) as
+    cn_srnn_attn_fwd / cn_srnn_attn_bwd (plain fp32).  te . (Ws s_j + bs) = (Ws^T te) . s_j + te . bs and the softmax does not see the second
+    term: the kernels never read bs, and its gradient is an exact zero (not None).  The backward writes every element of d_h_all once, as
+    SrnnEdgeSequence.backward takes it; the three weight gradients are sums over all rows on the split-K kernel (cn_linear_wgrad, N = 64,
+    K = 256).  attn is not differentiable (a tap).  with_t = True adds a third output, the temporal rows h_all[..., 0, :] as a tensor of their own:
+    a consumer that uses it instead of a view of h_all hands its gradient to the kernel (d_t_direct) rather than to a zero-filled d_h_all."""
+
+    @staticmethod
+    def forward(ctx, h_all, Wt, bt, Ws, bs, with_t=False):
+        if not (h_all.is_cuda and h_all.dtype == torch.float32):
+            raise A.CnError("SrnnAttention: h_all must be a float32 tensor on the GPU (CPU tensors take SRNNBase.attention), got %s on %s"
+                            % (h_all.dtype, h_all.device))
+        if h_all.dim() < 2 or h_all.shape[-1] != 256 or tuple(Wt.shape) != (64, 256) or tuple(Ws.shape) != (64, 256) or bt.numel() != 64 or bs.numel() != 64:
+            raise A.CnError("SrnnAttention: h_all [..., H+1, 256], Wt / Ws [64,256], bt / bs [64] expected, got %s, %s, %s, %s, %s"
+                            % tuple(list(t.shape) for t in (h_all, Wt, bt, Ws, bs)))
+        h_all = h_all.detach().contiguous()
+        lead, H = h_all.shape[:-2], h_all.shape[-2] - 1
+        B = h_all.numel() // ((H + 1) * 256)
+        wt, b_t, ws = (p.detach().contiguous() for p in (Wt, bt, Ws))
+        dev = h_all.device
+        weighted, attn = torch.empty(B, 256, device=dev), torch.empty(B, H, device=dev)
+        te, u = torch.empty(B, 64, device=dev), torch.empty(B, 256, device=dev)
+        A.call("cn_srnn_attn_fwd", B, H, A.ptr(h_all), A.ptr(wt), A.ptr(b_t), A.ptr(ws), A.ptr(weighted), A.ptr(attn), A.ptr(te), A.ptr(u), A.stream_ptr(),
+               device=dev)
+        ctx.save_for_backward(h_all, wt, ws, attn, te, u)
+        ctx.BH = (B, H)
+        attn = attn.view(*lead, H)
+        ctx.mark_non_differentiable(attn)
+        if with_t:
+            return weighted.view(*lead, 256), attn, h_all[..., 0, :].contiguous()
+        return weighted.view(*lead, 256), attn
+
+    @staticmethod
+    def backward(ctx, d_weighted, _d_attn, d_t=None):
+        h_all, wt, ws, attn, te, u = ctx.saved_tensors
+        B, H = ctx.BH
+        dev = h_all.device
+        d_weighted = d_weighted.contiguous() if d_weighted is not None else torch.zeros(B, 256, device=dev)
+        d_h_all = torch.empty_like(h_all)
+        d_u, d_te = torch.empty(B, 256, device=dev), torch.empty(B, 64, device=dev)
+        d_t = None if d_t is None else d_t.contiguous()
+        A.call("cn_srnn_attn_bwd", B, H, A.ptr(h_all), A.ptr(wt), A.ptr(ws), A.ptr(attn), A.ptr(u), A.ptr(d_weighted), A.ptr(d_t), A.ptr(d_h_all), A.ptr(d_u),
+               A.ptr(d_te), A.stream_ptr(), device=dev)
+        d_ws = _wgrad_ld(te, 64, d_u, 256, B, 64, 256, bias=False)[0]            # dWs = te^T d_u
+        d_wt, d_bt = _wgrad_ld(d_te, 64, h_all, (H + 1) * 256, B, 64, 256)        # dWt = d_te^T t (t in place: row stride (H+1) * 256), dbt
+        return d_h_all, d_wt, d_bt, d_ws, torch.zeros(64, device=dev), None
+
+
+def _wgrad_ld(dy, ldy, x, ldx, M, N, K, bias=True):
+    """(dy^T x [N,K], column sums of dy [N] or None) over M rows of two row-major buffers with the given row strides (cn_linear_wgrad)."""
+    splits = A.lib().cn_linear_wgrad_splits(M, N, K)
+    if splits <= 0:
+        raise A.CnError("cn_linear_wgrad: no split-K plan for a %d x %d weight gradient over %d rows" % (N, K, M))
+    part = torch.empty(splits, N, K, device=x.device)
+    dw = torch.empty(N, K, device=x.device)
+    dbp, db = (torch.empty(splits, N, device=x.device), torch.empty(N, device=x.device)) if bias else (None, None)
+    A.call("cn_linear_wgrad", M, N, K, A.ptr(dy), ldy, None, A.ptr(x), ldx, splits, A.ptr(part), A.ptr(dbp), A.ptr(dw), A.ptr(db), A.stream_ptr(),
+           device=x.device)
+    return dw, db
+
+
 class HHAttention(torch.autograd.Function):
     """softmax(scale * q k^T) v per (sample, head) on compacted rows, forward and backward as HIP kernels
     (cn_hh_attention_fwd / cn_hh_attention_bwd).  qkv [R,1536] float32 cuda, row_off [B+1] int32 cuda."""

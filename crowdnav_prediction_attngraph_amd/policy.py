@@ -502,11 +502,16 @@ class SRNNBase(nn.Module):
     # forward_sequence on GPU tensors: both edge GRUs over all T steps as hip_train.SrnnEdgeSequence (cn_srnn_seq_fwd / cn_srnn_seq_bwd) instead of
     # the torch-op loop, which stays the definition (False, CPU tensors, or a shape cn_srnn_seq_workspace_bytes refuses)
     train_edge_kernels = True
+    # ... and everything behind h_all: the attention as hip_train.SrnnAttention (cn_srnn_attn_fwd / cn_srnn_attn_bwd) on h_all itself, the node GRU
+    # as hip_train.GRUSequence, the products over the T*N rows through HipLinear / WgradLinear (_node_kernels).  False, CPU or non-fp32 tensors,
+    # or no provider: the torch ops below, which stay the definition
+    train_node_kernels = True
 
     def __init__(self, obs_space_dict, args):
         super().__init__()
         self.is_recurrent = True
         self.hip_provider = None            # Policy sets it (_hip_handle): (N, device) -> the HipSrnn handle with the current weights
+        self.gemm_mode_provider = None      # ... and this (_base_gemm_mode): () -> the gemm mode that handle runs in
         self.args = args
         self.human_num = obs_space_dict["spatial_edges"].shape[0]
         self.edge_width = obs_space_dict["spatial_edges"].shape[1]
@@ -591,6 +596,58 @@ class SRNNBase(nn.Module):
             return None
         return self.hip_provider(N, edge_h0.device)
 
+    def _node_kernel_mode(self, inputs, node_h0, edge_h0, masks):
+        """The gemm mode the kernel path behind h_all follows (_node_kernels: the Policy's, which its handle has too), or None where the torch ops
+        run: train_node_kernels off, CPU or non-fp32 tensors, or no provider (a base outside a Policy).  H is inside the kernels' box by
+        construction.  No handle is asked for: these kernels read the parameters themselves."""
+        if not (self.train_node_kernels and self.hip_provider is not None and edge_h0.is_cuda):
+            return None
+        if any(t.dtype != torch.float32 for t in (inputs["robot_node"], inputs["temporal_edges"], inputs["spatial_edges"], node_h0, edge_h0, masks)):
+            return None
+        return self.gemm_mode_provider()
+
+    def _node_kernels(self, mode, h_all, rn, node_h0, m, T, N):
+        """Everything behind the edge GRUs on h_all [T,N,H+1,256]: (value, actor features, node h_T, node output, weighted, attention weights).
+        The attention kernels are plain fp32 and run in both gemm modes.  In 'bf16x3' the node GRU is hip_train.GRUSequence (one launch each
+        way), the products over the T*N rows go through HipLinear (forward, dX and dW on the split-precision kernels) or, where only the weight
+        gradient has a kernel (edge_attention_embed: 64 columns), WgradLinear, and robot_linear -> encoder_linear, two affine maps with nothing
+        in between, is one 7 -> 64 map composed weight by weight (autograd carries the gradient back to both factors).  In 'fp32' those pieces
+        are the torch ops of the definition."""
+        from . import hip_train as K
+        B, node, split = T * N, self.humanNodeRNN, mode == "bf16x3"
+
+        def lin(x, layer):
+            w, b = (layer.weight, layer.bias) if isinstance(layer, nn.Linear) else layer
+            if split and K.linear_supported(x, w):
+                return K.HipLinear.apply(x, w, b, False)
+            if split and K.wgrad_supported(x, w):
+                return K.WgradLinear.apply(x, w, b)
+            return F.linear(x, w, b)
+
+        tl, sl = self.attn.temporal_edge_layer[0], self.attn.spatial_edge_layer[0]
+        weighted, a, ht = K.SrnnAttention.apply(h_all, tl.weight, tl.bias, sl.weight, sl.bias, True)
+        rl, enc = self.robot_linear, node.encoder_linear
+        if split:
+            enc_in = F.linear(rn, K.weight_mm(enc.weight, rl.weight), K.weight_mm(enc.weight, rl.bias) + enc.bias)
+        else:
+            enc_in = F.linear(F.linear(rn, rl.weight, rl.bias), enc.weight, enc.bias)
+        ee = F.relu(lin(torch.cat((ht, weighted), -1).view(B, -1), node.edge_attention_embed))
+        gi_n = lin(torch.cat((F.relu(enc_in), ee), -1), (node.gru.weight_ih_l0, node.gru.bias_ih_l0)).view(T, N, -1)
+        h_n = node_h0.reshape(N, -1)
+        if split:
+            hns = K.GRUSequence.apply(gi_n, h_n, m, node.gru.weight_hh_l0, node.gru.bias_hh_l0)
+            h_n = hns[-1]
+        else:
+            hs = []
+            for t in range(T):
+                h_n = _gru_cell(gi_n[t], h_n * m[t], node.gru.weight_hh_l0, node.gru.bias_hh_l0)
+                hs.append(h_n)
+            hns = torch.stack(hs, 0)
+        out = lin(hns.view(B, -1), node.output_linear)
+        feat = torch.tanh(lin(torch.tanh(lin(out, self.actor[0])), self.actor[2]))
+        crit = torch.tanh(lin(torch.tanh(lin(out, self.critic[0])), self.critic[2]))
+        return _skinny_linear(crit, self.critic_linear.weight, self.critic_linear.bias), feat, h_n, out, weighted, a
+
     def forward_sequence(self, inputs, node_h0, edge_h0, masks, T, N, taps=None):
         """inputs: dict of [T*N, ...] (T-major), node_h0 [N,1,128] or [N,128], edge_h0 [N,H+1,256], masks [T*N,1].
         Returns value [T*N,1], actor features [T*N,256], node h_T [N,128], edge h_T [N,H+1,256].  The state is multiplied by masks[t] at EVERY
@@ -618,6 +675,14 @@ class SRNNBase(nn.Module):
                 hts.append(h_t)
                 hss.append(h_s)
             ht_all, hs_all = torch.stack(hts, 0), torch.stack(hss, 0)                   # [T,N,256], [T,N,H,256]
+        node_mode = self._node_kernel_mode(inputs, node_h0, edge_h0, masks)
+        if node_mode is not None:
+            if hip is None:
+                h_all = torch.cat((ht_all.unsqueeze(2), hs_all), 2)                     # the torch-op edge loop: [T,N,H+1,256] as the kernels read it
+            value, feat, h_n, out, weighted, a = self._node_kernels(node_mode, h_all, rn, node_h0, m, T, N)
+            if taps is not None:
+                taps.update(edge_out=torch.cat((h_t.unsqueeze(1), h_s), 1), attn=a.reshape(B, H), weighted=weighted.reshape(B, -1), node_out=out, actor_feat=feat)
+            return value, feat, h_n, torch.cat((h_t.unsqueeze(1), h_s), 1)
         weighted, a = self.attention(ht_all, hs_all)
         enc = F.relu(F.linear(F.linear(rn, self.robot_linear.weight, self.robot_linear.bias), node.encoder_linear.weight, node.encoder_linear.bias))
         ee = F.relu(F.linear(torch.cat((ht_all, weighted), -1).view(B, -1), node.edge_attention_embed.weight, node.edge_attention_embed.bias))
@@ -647,6 +712,7 @@ class Policy(nn.Module):
         self.base = (SRNNBase if base == "srnn" else AttnGraphBase)(obs_shape, base_kwargs)
         if base == "srnn":
             self.base.hip_provider = self._hip_handle
+            self.base.gemm_mode_provider = self._base_gemm_mode
         self.srnn = True
         self.dist = _DiagGaussian(self.base.output_size, action_space.shape[0])
         self._hip = None
@@ -680,6 +746,9 @@ class Policy(nn.Module):
             self._hip.set_weights(self.state_dict())
             self._hip_version = ver
         return self._hip
+
+    def _base_gemm_mode(self):
+        return getattr(self, self.base.gemm_mode_attr)
 
     _hip_policy = _hip_srnn = _hip_handle     # the per-base names the handle had before: the existing tests reach it through them
 
@@ -749,7 +818,8 @@ class Policy(nn.Module):
     def evaluate_actions(self, inputs, rnn_hxs, masks, action):
         """inputs [T*N,...] (T = seq_length, N = num_processes / num_mini_batch), rnn_hxs at t=0 ([N,...]).  The T-step sequence under
         autograd: on the GPU its heavy stages are HIP kernels behind autograd.Functions (the attention-graph base: the whole of it, below;
-        DS-RNN: the two edge GRUs, SRNNBase.train_edge_kernels), on the CPU everything is torch ops: that graph is the definition."""
+        DS-RNN: the two edge GRUs, SRNNBase.train_edge_kernels, and the attention and node half behind them, SRNNBase.train_node_kernels), on the
+        CPU everything is torch ops: that graph is the definition."""
         B = inputs["robot_node"].shape[0]
         N = rnn_hxs["human_node_rnn"].shape[0]
         T = B // N

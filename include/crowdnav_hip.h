@@ -19,6 +19,7 @@
  *   cn_srnn_create/destroy/set_weights <- rl/networks/model.py:16-46 Policy.__init__ with base='srnn' / load_state_dict
  *   cn_srnn_act                <- rl/networks/model.py:56-74 Policy.act (-> srnn_model.py:389-468 SRNN.forward, infer=True)
  *   cn_srnn_seq_fwd / _bwd      <- rl/ppo/ppo.py evaluate_actions on that base: the edge-GRU sequence of srnn_model.py:418-433 and its backward
+ *   cn_srnn_attn_fwd / _bwd     <- ... the EdgeAttention of srnn_model.py:256-323 over that sequence's edge states and its backward
  *   cn_srnn_get_value          <- rl/networks/model.py:76-80 Policy.get_value on that base
  *   cn_gae                     <- rl/networks/storage.py:123-132 RolloutStorage.compute_returns (use_gae branch)
  *   cn_adv_stats / cn_adv_normalize <- rl/ppo/ppo.py:37-39 advantage normalisation (split so that N GPUs can
@@ -503,6 +504,27 @@ int cn_srnn_seq_fwd(cn_srnn *p, int T, int N, const float *temporal_edges, const
 int cn_srnn_seq_bwd(cn_srnn *p, int T, int N, const float *temporal_edges, const float *spatial_edges, const float *edge_h0, const float *masks,
                     const float *h_all, const float *d_h_all, void *workspace, int64_t workspace_bytes, const cn_srnn_edge_grads *grads,
                     float *d_edge_h0, void *partials, void *stream);
+
+/* ---- DS-RNN baseline: the edge attention of PPO.update (EdgeAttention, srnn_model.py:256-323, over the saved edge states) and its backward ----
+ * h_all [B, H+1, 256] (B = T*N samples, read in place: slot 0 the temporal edge t, slots 1 .. H the spatial edges s_j), Wt / Ws [64,256] the
+ * temporal_edge_layer / spatial_edge_layer weights, bt [64].  Per sample
+ *   te = Wt t + bt;  u = Ws^T te;  score_j = (H / 8) (u . s_j);  a = softmax_j(score) over all H slots, no mask;  weighted = sum_j a_j s_j
+ * which is the reference's te . (Ws s_j + bs) without the term te . bs, the same for every j: the softmax does not see it, so the bias of
+ * spatial_edge_layer is no argument and its gradient is exactly zero.  No [B,H,64] or [B,H,256] temporary exists: the forward reads h_all once,
+ * the backward reads it once and writes d_h_all once.  Plain fp32, one wavefront per sample, fixed summation orders, no atomics: equal
+ * arguments give equal bits, and a sample's outputs do not depend on B or on the other samples.  No workspace.
+ *
+ * cn_srnn_attn_fwd writes weighted [B,256], attn [B,H] and, for the backward, te [B,64] and u [B,256].
+ * cn_srnn_attn_bwd takes d_weighted [B,256] and d_t_direct [B,256] (a gradient that reaches t by another route; may be NULL) and writes
+ * every element of d_h_all [B,H+1,256] exactly once (nothing to zero beforehand): slot 0 = Wt^T d_te + d_t_direct, slot 1 + j =
+ * a_j d_weighted + (H / 8) d_score_j u; plus d_u [B,256] and d_te [B,64], from which the caller sums the weight gradients over the B rows
+ * (dWs = te^T d_u, dWt = d_te^T t, dbt = column sums of d_te: cn_linear_wgrad at N = 64, K = 256, t read in place with ldx = (H+1) * 256).
+ * Box: 1 <= H <= CN_MAX_HUMANS, B >= 1, edge width 256, attention size 64, the [.,256] operands 16-byte aligned; outside it CN_ERR_INVALID
+ * naming the call, and nothing is launched.  (CN_ABI_VERSION is unchanged: these are additions, no existing signature or struct layout moved.) */
+int cn_srnn_attn_fwd(int B, int H, const float *h_all, const float *Wt, const float *bt, const float *Ws, float *weighted, float *attn, float *te,
+                     float *u, void *stream);
+int cn_srnn_attn_bwd(int B, int H, const float *h_all, const float *Wt, const float *Ws, const float *attn, const float *u, const float *d_weighted,
+                     const float *d_t_direct, float *d_h_all, float *d_u, float *d_te, void *stream);
 
 /* ---- device-side launch stamps (measurement aid for bench.py / tools; not part of the reference's interface) ----
  * The kernels of the rollout step (CN_PROF_K_*) stamp the device's 100 MHz wall clock when their first workgroups start and when their

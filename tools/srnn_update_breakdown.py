@@ -15,6 +15,7 @@ belong to, so the run drops a sentinel launch (torch.cuda._sleep: `spin_kernel`)
     (b) attention: S1..S2 and S3..S5
     (c) node GRU, trunks, heads, losses: S2..S3 (forward and backward)
     (d) gather and optimiser: S6..the next S0, and what precedes the first S0 (advantages, the first minibatch's gather)
+With SRNNBase.train_node_kernels the attention is hip_train.SrnnAttention on h_all itself; the same sentinels go around that call.
 A kernel belongs to the interval its start falls into; the sentinels themselves are left out.
 """
 import argparse
@@ -45,6 +46,7 @@ def run(a):
                  base_kwargs=dict(env_name=env_name, num_processes=E, num_mini_batch=2, seq_length=T)).to(dev)
     if a.ops and hasattr(pol.base, "train_edge_kernels"):
         pol.base.train_edge_kernels = False
+        pol.base.train_node_kernels = False
     ro = RolloutStorage(T, E, envs.observation_space.spaces, envs.action_space, 128, 256)
     ro.to(dev)
     ro.materialize_edge_rnn()
@@ -79,6 +81,27 @@ def run(a):
         return step(*args, **kw)
 
     pol.evaluate_actions, pol.base.attention, agent._optimizer_step = evaluate_actions, attention, optimizer_step
+    from crowdnav_prediction_attngraph_amd import hip_train
+    fused = getattr(hip_train, "SrnnAttention", None)
+    if fused is not None and getattr(pol.base, "train_node_kernels", False) and not a.ops:
+        # the kernel route never calls SRNNBase.attention: the same seams around hip_train.SrnnAttention, whose input is h_all itself (its
+        # gradient is the two of h_t and h_s at once: S4 and S5 are neighbours)
+        def both(g):
+            mark()
+            mark()
+
+        class MarkedAttention:
+            @staticmethod
+            def apply(h_all, *rest):
+                mark()                                  # S1
+                if h_all.requires_grad:
+                    h_all.register_hook(both)           # S4, S5
+                out = fused.apply(h_all, *rest)
+                if out[0].requires_grad:
+                    out[0].register_hook(lambda g: mark())      # S3
+                mark()                                  # S2
+                return out
+        hip_train.SrnnAttention = MarkedAttention
     torch.cuda.synchronize()
     mark(); mark(); mark()                      # the marked update lies between two triple sentinels
     agent.update(ro)
