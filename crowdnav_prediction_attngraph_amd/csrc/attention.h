@@ -118,7 +118,7 @@ static int launch_hh_attention(int E, int cap_lo, const float *qkv, const int *r
     int wpb = (int)(65536 / per_wave); wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
     int per_cu = (int)((160 * 1024) / (per_wave * wpb)); per_cu = per_cu > 8 ? 8 : per_cu; // resident blocks per CU (LDS / 32-wave cap)
     int blocks = (E * 8 + wpb - 1) / wpb;
-    if (cls_list && blocks > 256 * per_cu) blocks = 256 * per_cu;
+    if (cls_list && blocks > 256 * per_cu) blocks = 256 * per_cu; // (a new cap: move tests/test_gpu_strided_grids.py, which runs past twice this one)
     hipLaunchKernelGGL(hh_attention_kernel<CAP>, dim3(blocks), dim3(64 * wpb), per_wave * wpb, st, E, cap_lo, qkv, row_off, cls_cnt, cls_list, out, scale);
     CN_CHECK_LAUNCH();
     return CN_OK;
@@ -483,7 +483,7 @@ static int launch_hh_attention_bwd(int B, const float *qkv, const int *row_off, 
         const size_t per_wave = (size_t)(4 * CAP * 68 + CAP * (CAP + 1)) * sizeof(float); // 18.5 KB / 39 KB
         const int wpb = CAP == 16 ? 4 : 2, per_cu = 2;                                    // 8 / 4 wavefronts per CU
         int blocks = (B * 8 + wpb - 1) / wpb;
-        if (blocks > 256 * per_cu) blocks = 256 * per_cu;
+        if (blocks > 256 * per_cu) blocks = 256 * per_cu; // (a new cap: move tests/test_gpu_strided_grids.py, which runs past twice this one)
         if (int rc = cn_lds_opt_in<&hh_attention_bwd_mfma_kernel<NT>>(160 * 1024)) return rc;
         hipLaunchKernelGGL(hh_attention_bwd_mfma_kernel<NT>, dim3(blocks), dim3(64 * wpb), per_wave * wpb, st, B, qkv, row_off, cls + c, cls + 4 + (size_t)c * B,
                            d_out, d_qkv, scale);
@@ -494,7 +494,7 @@ static int launch_hh_attention_bwd(int B, const float *qkv, const int *row_off, 
     int wpb = (int)(65536 / per_wave); wpb = wpb < 1 ? 1 : (wpb > 4 ? 4 : wpb);
     int per_cu = (int)((160 * 1024) / (per_wave * wpb)); per_cu = per_cu > 8 ? 8 : (per_cu < 1 ? 1 : per_cu);
     int blocks = (B * 8 + wpb - 1) / wpb;
-    if (blocks > 256 * per_cu) blocks = 256 * per_cu; // resident-sized grid walking the class list
+    if (blocks > 256 * per_cu) blocks = 256 * per_cu; // resident-sized grid walking the class list (a new cap: move tests/test_gpu_strided_grids.py)
     if (per_wave * wpb > 65536)
         if (int rc = cn_lds_opt_in<&hh_attention_bwd_kernel<CAP>>(160 * 1024)) return rc;
     hipLaunchKernelGGL(hh_attention_bwd_kernel<CAP>, dim3(blocks), dim3(64 * wpb), per_wave * wpb, st, B, qkv, row_off, cls + c, cls + 4 + (size_t)c * B,

