@@ -267,6 +267,7 @@ ABI_SYMBOLS = [
     "cn_gst_wrapper_reset", "cn_gst_wrapper_step", "cn_gst_wrapper_set_interval", "cn_gst_wrapper_history_len", "cn_gst_wrapper_save", "cn_gst_wrapper_load", "cn_gae", "cn_adv_stats", "cn_adv_normalize", "cn_episode_stats_update", "cn_eval_state_words", "cn_eval_accumulate",
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
     "cn_ppo_minibatch_max_rows", "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
+    "cn_ppo_minibatch_workspace_bytes_sized", "cn_ppo_minibatch_step_sized",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
     "cn_gst_train_workspace_bytes_horizon", "cn_gst_train_step_horizon", "cn_gst_eval_workspace_bytes_horizon", "cn_gst_eval_step_horizon",
     "cn_gst_data_frames_horizon", "cn_gst_data_count_horizon", "cn_gst_data_fill_horizon", "cn_gst_gather_batch_horizon",
@@ -447,6 +448,10 @@ def lib():
         L.cn_ppo_minibatch_workspace_bytes.argtypes = [i32, i32, i32, i32, i64]
         L.cn_ppo_row_totals.argtypes = [i32, i32, i32, vp, vp, vp]
         L.cn_ppo_minibatch_step.argtypes = [C.POINTER(PpoBatch), i64, C.POINTER(PolicyWeights), C.POINTER(PolicyWeights), C.POINTER(PpoHyper), vp, i64, vp, vp, vp]
+        L.cn_ppo_minibatch_workspace_bytes_sized.restype = C.c_int64
+        L.cn_ppo_minibatch_workspace_bytes_sized.argtypes = [i32, i32, i32, i32, i64, C.POINTER(PolicyDims)]
+        L.cn_ppo_minibatch_step_sized.argtypes = [C.POINTER(PpoBatch), i64, C.POINTER(PolicyWeights), C.POINTER(PolicyWeights), C.POINTER(PpoHyper),
+                                                  C.POINTER(PolicyDims), vp, i64, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -1,4 +1,4 @@
-// train_step.hip -- cn_ppo_minibatch_step: one PPO minibatch (gather -> train-mode forward -> losses -> backward -> parameter gradients)
+// train_step.hip -- cn_ppo_minibatch_step / cn_ppo_minibatch_step_sized: one PPO minibatch (gather -> train-mode forward -> losses -> backward -> parameter gradients)
 // as ONE boundary call on gfx950 (include/crowdnav_hip.h).  Reference statements it replaces: rl/networks/storage.py:184-253 (one
 // `sample` of recurrent_generator), rl/networks/model.py:82-90 (evaluate_actions), rl/ppo/ppo.py:66-88 (losses, zero_grad, backward).
 //
@@ -12,6 +12,8 @@
 //     cn_small_mm plus autograd's accumulation kernels per optimiser step;
 //   * gradients are written straight into the caller's flat bucket (no zero fill, no accumulation pass).
 // Summation orders are fixed: the step is deterministic.
+// Network sizes: every width behind the human-human block is a function of cn_policy_dims (R, M, A, O) inside the device box of
+// cn_policy_create_sized; the unsized entry points forward to the sized ones with the default tuple (128, 64, 64, 256).
 #include "common.h"
 #include "hh_fused.h"
 
@@ -32,7 +34,7 @@ struct GatherOut {
     int *nd;
 };
 
-__global__ __launch_bounds__(64) void tr_gather_kernel(cn_ppo_batch b, GatherOut o)
+__global__ __launch_bounds__(64) void tr_gather_kernel(cn_ppo_batch b, GatherOut o, int h0_passes)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
     const int t = s / b.N, j = s - t * b.N;
@@ -55,10 +57,10 @@ __global__ __launch_bounds__(64) void tr_gather_kernel(cn_ppo_batch b, GatherOut
     float *dst = o.se + (size_t)s * HD;
     for (int i = lane; i < HD; i += 64) dst[i] = src[i];
     if (t == 0) { // hidden state of the first step only (storage.py:222)
-        const float *hs = b.h0 + (size_t)e * 128;
-        float *hd = o.h0 + (size_t)j * 128;
-        hd[lane] = hs[lane];
-        hd[lane + 64] = hs[lane + 64];
+        const int R = h0_passes * 64; // rnn_size: 64-lane passes over a row of R = 64 / 128 / 192 / 256 floats
+        const float *hs = b.h0 + (size_t)e * R;
+        float *hd = o.h0 + (size_t)j * R;
+        for (int p = 0; p < h0_passes; ++p) hd[lane + 64 * p] = hs[lane + 64 * p];
     }
 }
 
@@ -279,19 +281,33 @@ struct Ws {
     int e0_blocks;
 };
 
-constexpr int RN_SAVED_W[10] = {256, 384, 256, 0 /* H */, 384, 128, 128, 512, 512, 512}; // cn_rn_saved field widths (attn: H)
-
-Ws carve(int T, int N, int H, int D, int64_t rows)
+// The network sizes of the step: cn_policy_dims checked against the device box of cn_policy_create_sized (the default when dims == NULL).
+struct TrDims {
+    int R, M, A, O; // rnn_size, embedding_size, attention_size, output_size
+    bool ok;
+};
+TrDims tr_dims(const cn_policy_dims *d)
 {
+    TrDims q{128, 64, 64, 256, true};
+    if (d) { q.R = d->rnn_size; q.M = d->embedding_size; q.A = d->attention_size; q.O = d->output_size; }
+    q.ok = (q.R == 64 || q.R == 128 || q.R == 192 || q.R == 256) && (q.M == 64 || q.M == 128) && q.O >= 64 && q.O <= 512 && q.O % 64 == 0 && q.A >= 1 && q.A <= 256;
+    return q;
+}
+
+Ws carve(int T, int N, int H, int D, int64_t rows, const TrDims &Q)
+{
+    const cn_policy_dims pd{Q.R, Q.M, Q.A, Q.O};
+    const size_t TE = 256 + (size_t)Q.M, AC = 2 * (size_t)Q.O; // rows of te = [u ; encoder_linear] and of ac0 = (actor.0 ; critic.0) o output_linear
+    const size_t sv_w[10] = {256, 256 + 2 * (size_t)Q.M, 256, (size_t)H, 3 * (size_t)Q.R, (size_t)Q.R, (size_t)Q.R, 4 * (size_t)Q.R, AC, AC}; // cn_rn_saved field widths
     Ws w{};
     size_t off = 0;
     auto f = [&](size_t n_floats) { size_t o = off; off += ((n_floats * 4 + 255) & ~size_t(255)); return o; }; // 256-byte aligned pieces
     const size_t B = (size_t)T * N, R = (size_t)(rows > 0 ? rows : 1);
-    w.rn = f(B * 7); w.te = f(B * 2); w.se = f(B * H * D); w.nd = f(B); w.row_off = f(B + 1); w.h0 = f((size_t)N * 128); w.masks = f(B); w.act = f(B * 2);
+    w.rn = f(B * 7); w.te = f(B * 2); w.se = f(B * H * D); w.nd = f(B); w.row_off = f(B + 1); w.h0 = f((size_t)N * Q.R); w.masks = f(B); w.act = f(B * 2);
     w.vp = f(B); w.ret = f(B); w.olp = f(B); w.adv = f(B); w.xlive = f(R * D);
-    w.qkv_w = f(1536 * 512); w.qkv_b = f(1536); w.os_w = f(256 * 512); w.os_b = f(256); w.te_w = f(320 * 256); w.te_b = f(320); w.ac0_w = f(512 * 128); w.ac0_b = f(512);
-    w.d_qkv_w = f(1536 * 512); w.d_qkv_b = f(1536); w.d_os_w = f(256 * 512); w.d_os_b = f(256); w.d_te_w = f(320 * 256); w.d_te_b = f(320);
-    w.d_ac0_w = f(512 * 128); w.d_ac0_b = f(512);
+    w.qkv_w = f(1536 * 512); w.qkv_b = f(1536); w.os_w = f(256 * 512); w.os_b = f(256); w.te_w = f(TE * 256); w.te_b = f(TE); w.ac0_w = f(AC * Q.R); w.ac0_b = f(AC);
+    w.d_qkv_w = f(1536 * 512); w.d_qkv_b = f(1536); w.d_os_w = f(256 * 512); w.d_os_b = f(256); w.d_te_w = f(TE * 256); w.d_te_b = f(TE);
+    w.d_ac0_w = f(AC * Q.R); w.d_ac0_b = f(AC);
     w.frag = f((size_t)cn_hh_block_workspace_bytes() / 4);
     w.e0 = f(R * 128); w.x = f(R * 512); w.qkv = f(R * 1536); w.attn = f(R * 512); w.out = f(R * 256);
     w.d_out = f(R * 256); w.d_attn = f(R * 512); w.d_qkv = f(R * 1536); w.d_x = f(R * 512); w.d_e0 = f(R * 128);
@@ -307,9 +323,9 @@ Ws carve(int T, int N, int H, int D, int64_t rows)
     w.part = f(pmax ? pmax : 1); w.dbp = f(bmax ? bmax : 1);
     w.e0_blocks = (int)(R < 4096 ? R : 4096);
     w.e0part = f((size_t)w.e0_blocks * 128 * (D + 1)); w.dwb = f((size_t)128 * (D + 1));
-    for (int i = 0; i < 10; ++i) w.sv[i] = f(B * (size_t)(i == 3 ? H : RN_SAVED_W[i]));
+    for (int i = 0; i < 10; ++i) w.sv[i] = f(B * sv_w[i]);
     w.value = f(B); w.logp = f(B); w.d_value = f(B); w.d_logp = f(B);
-    w.rn_fwd = f((size_t)cn_rn_seq_fwd_workspace_floats()); w.rn_bwd = f((size_t)cn_rn_seq_workspace_floats(T, N)); w.d_h0 = f((size_t)N * 128);
+    w.rn_fwd = f((size_t)cn_rn_seq_fwd_workspace_floats_sized(&pd)); w.rn_bwd = f((size_t)cn_rn_seq_workspace_floats_sized(T, N, &pd)); w.d_h0 = f((size_t)N * Q.R);
     w.loss_ws = f((size_t)cn_ppo_loss_workspace_doubles() * 2); w.vl_al = f(4); w.g_losses = f(4);
     w.total = off;
     return w;
@@ -341,10 +357,15 @@ constexpr int64_t TR_MAX_ROWS = ((1LL << 31) - 1) / 1536; // 1 398 101
 
 extern "C" int64_t cn_ppo_minibatch_max_rows(void) { return TR_MAX_ROWS; }
 
+extern "C" int64_t cn_ppo_minibatch_workspace_bytes_sized(int T, int N, int H, int D, int64_t rows, const cn_policy_dims *dims)
+{
+    const TrDims Q = tr_dims(dims);
+    if (!Q.ok || T < 1 || N < 1 || H < 1 || H > 48 || D < 1 || D > 16 || rows < 0 || rows > TR_MAX_ROWS) return 0;
+    return (int64_t)carve(T, N, H, D, rows, Q).total;
+}
 extern "C" int64_t cn_ppo_minibatch_workspace_bytes(int T, int N, int H, int D, int64_t rows)
 {
-    if (T < 1 || N < 1 || H < 1 || H > 48 || D < 1 || D > 16 || rows < 0 || rows > TR_MAX_ROWS) return 0;
-    return (int64_t)carve(T, N, H, D, rows).total;
+    return cn_ppo_minibatch_workspace_bytes_sized(T, N, H, D, rows, nullptr);
 }
 
 extern "C" int cn_ppo_row_totals(int T, int E, int H, const float *detected_human_num, int32_t *totals, void *stream)
@@ -359,6 +380,17 @@ extern "C" int cn_ppo_row_totals(int T, int E, int H, const float *detected_huma
 extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const cn_policy_weights *P, const cn_policy_weights *G, const cn_ppo_hyper *hy,
                                      void *workspace, int64_t workspace_bytes, float *losses_out, float *value_logp_out, void *stream)
 {
+    return cn_ppo_minibatch_step_sized(bp, rows, P, G, hy, nullptr, workspace, workspace_bytes, losses_out, value_logp_out, stream);
+}
+
+extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows, const cn_policy_weights *P, const cn_policy_weights *G, const cn_ppo_hyper *hy,
+                                           const cn_policy_dims *dims, void *workspace, int64_t workspace_bytes, float *losses_out, float *value_logp_out,
+                                           void *stream)
+{
+    const TrDims Q = tr_dims(dims);
+    CN_REQUIRE(Q.ok, "cn_ppo_minibatch_step_sized: (rnn_size %d, embedding_size %d, attention_size %d, output_size %d) outside the device box: rnn_size in "
+               "{64, 128, 192, 256}, embedding_size in {64, 128}, output_size a multiple of 64 in [64, 512], attention_size in [1, 256]", Q.R, Q.M, Q.A, Q.O);
+    const cn_policy_dims pd{Q.R, Q.M, Q.A, Q.O}; // what the sequence's functions read: sizes, and the score temperature H / sqrt(A)
     if (int rc = cn_require_device()) return rc;
     CN_REQUIRE(bp && P && G && hy && workspace && losses_out, "cn_ppo_minibatch_step: null argument");
     const cn_ppo_batch b = *bp;
@@ -376,7 +408,7 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
             CN_REQUIRE(pp[i] && gp[i] && ((uintptr_t)pp[i] & 15) == 0 && ((uintptr_t)gp[i] & 15) == 0,
                        "cn_ppo_minibatch_step: parameter / gradient pointer #%zu is null or not 16-byte aligned", i);
     }
-    const Ws L = carve(b.T, b.N, b.H, b.D, rows);
+    const Ws L = carve(b.T, b.N, b.H, b.D, rows, Q);
     CN_REQUIRE(workspace_bytes >= (int64_t)L.total && ((uintptr_t)workspace & 255) == 0,
                "cn_ppo_minibatch_step: workspace of %lld bytes (256-byte aligned) needed, got %lld", (long long)L.total, (long long)workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
@@ -384,13 +416,14 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
     auto F = [&](size_t off) { return reinterpret_cast<float *>(base + off); };
     auto g = [](const float *p) { return const_cast<float *>(p); }; // the gradient struct reuses cn_policy_weights: its pointers are written
     const int T = b.T, N = b.N, H = b.H, D = b.D, B = (int)Bs, R = (int)rows;
+    const int dR = Q.R, dM = Q.M, dA = Q.A, dO = Q.O;
     int *nd = reinterpret_cast<int *>(base + L.nd), *row_off = reinterpret_cast<int *>(base + L.row_off);
     int rc;
 
     // ---- the minibatch, its row offsets, its compacted input rows ----
     {
         GatherOut o{F(L.rn), F(L.te), F(L.se), F(L.h0), F(L.masks), F(L.act), F(L.vp), F(L.ret), F(L.olp), F(L.adv), nd};
-        hipLaunchKernelGGL(tr_gather_kernel, dim3(B), dim3(64), 0, st, b, o);
+        hipLaunchKernelGGL(tr_gather_kernel, dim3(B), dim3(64), 0, st, b, o, dR / 64);
         CN_CHECK_LAUNCH();
         hipLaunchKernelGGL(tr_scan_kernel, dim3((B + 1023) / 1024), dim3(1024), 0, st, B, H, D, nd, row_off, F(L.se), F(L.xlive));
         CN_CHECK_LAUNCH();
@@ -413,17 +446,18 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
             FoldBuilder::seg(j, 512, P->spatial_linear_w, 512, 1, P->out_proj_b, 1, 0);
             FoldBuilder::plus(j, P->spatial_linear_b, 1);
         }
-        { // u = Ws^T (Wt r + bt): rows 0..255 of te; rows 256..319 = encoder_linear
-            FoldBuilder::seg(fb.add(256, 256, F(L.te_w), 256), 64, P->attn_spatial_w, 1, 256, P->attn_temporal_w, 256, 1);
-            FoldBuilder::seg(fb.add(256, 1, F(L.te_b), 1), 64, P->attn_spatial_w, 1, 256, P->attn_temporal_b, 1, 0);
-            fb.copy(64, 256, F(L.te_w) + 256 * 256, 256, P->enc_w, 256);
-            fb.copy(64, 1, F(L.te_b) + 256, 1, P->enc_b, 1);
+        { // u = Ws^T (Wt r + bt), a K = A segment (unscaled: the sequence takes the temperature H / sqrt(A) from dims): rows 0..255 of te;
+          // rows 256..255+M = encoder_linear
+            FoldBuilder::seg(fb.add(256, 256, F(L.te_w), 256), dA, P->attn_spatial_w, 1, 256, P->attn_temporal_w, 256, 1);
+            FoldBuilder::seg(fb.add(256, 1, F(L.te_b), 1), dA, P->attn_spatial_w, 1, 256, P->attn_temporal_b, 1, 0);
+            fb.copy(dM, 256, F(L.te_w) + 256 * 256, 256, P->enc_w, 256);
+            fb.copy(dM, 1, F(L.te_b) + 256, 1, P->enc_b, 1);
         }
         const float *w0[2] = {P->actor0_w, P->critic0_w}, *b0[2] = {P->actor0_b, P->critic0_b};
-        for (int i = 0; i < 2; ++i) { // (actor.0 ; critic.0) o output_linear
-            FoldBuilder::seg(fb.add(256, 128, F(L.ac0_w) + (size_t)i * 256 * 128, 128), 256, w0[i], 256, 1, P->out_w, 128, 1);
-            FoldJob *j = fb.add(256, 1, F(L.ac0_b) + i * 256, 1);
-            FoldBuilder::seg(j, 256, w0[i], 256, 1, P->out_b, 1, 0);
+        for (int i = 0; i < 2; ++i) { // (actor.0 ; critic.0) [O,O] o output_linear [O,R]
+            FoldBuilder::seg(fb.add(dO, dR, F(L.ac0_w) + (size_t)i * dO * dR, dR), dO, w0[i], dO, 1, P->out_w, dR, 1);
+            FoldJob *j = fb.add(dO, 1, F(L.ac0_b) + i * dO, 1);
+            FoldBuilder::seg(j, dO, w0[i], dO, 1, P->out_b, 1, 0);
             FoldBuilder::plus(j, b0[i], 1);
         }
         if ((rc = fb.launch(st))) return rc;
@@ -438,13 +472,13 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
     cn_rn_saved sv{F(L.sv[0]), F(L.sv[1]), F(L.sv[2]), F(L.sv[3]), F(L.sv[4]), F(L.sv[5]), F(L.sv[6]), F(L.sv[7]), F(L.sv[8]), F(L.sv[9])};
     { // every split-plane image the step needs (the sequence's forward and backward weights, the transposed weights of the block's dX products): one launch
         CnSplitJob jobs[CN_SPLIT_MAX_JOBS];
-        int nj = rn_seq_prep_jobs(&rw, F(L.rn_fwd), F(L.rn_bwd), T, N, jobs);
+        int nj = rn_seq_prep_jobs(&rw, F(L.rn_fwd), F(L.rn_bwd), T, N, jobs, &pd);
         jobs[nj++] = cn_split_job(F(L.os_w), 256, 512, 1, 0, F(L.wT_os));
         jobs[nj++] = cn_split_job(F(L.qkv_w), 1536, 512, 1, 0, F(L.wT_qkv));
         jobs[nj++] = cn_split_job(P->emb2_w, 512, 128, 1, 0, F(L.wT_emb2));
         if ((rc = cn_split_group_launch(jobs, nj, st))) return rc;
     }
-    if ((rc = rn_seq_fwd_impl(T, N, H, F(L.rn), F(L.te), F(L.out), row_off, F(L.h0), F(L.masks), F(L.act), &rw, &sv, F(L.rn_fwd), F(L.value), F(L.logp), stream, true))) return rc;
+    if ((rc = rn_seq_fwd_impl(T, N, H, F(L.rn), F(L.te), F(L.out), row_off, F(L.h0), F(L.masks), F(L.act), &rw, &sv, F(L.rn_fwd), F(L.value), F(L.logp), stream, true, &pd))) return rc;
 
     if (value_logp_out) {
         CN_HIP(hipMemcpyAsync(value_logp_out, F(L.value), (size_t)B * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -463,9 +497,9 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
     cn_rn_grads rg{g(G->robot_linear_w), g(G->robot_linear_b), F(L.d_te_w), F(L.d_te_b), g(G->edge_embed_w), g(G->edge_embed_b), g(G->gru_w_ih), g(G->gru_b_ih),
                    g(G->gru_w_hh), g(G->gru_b_hh), F(L.d_ac0_w), F(L.d_ac0_b), g(G->actor2_w), g(G->actor2_b), g(G->critic2_w), g(G->critic2_b),
                    g(G->critic_linear_w), g(G->critic_linear_b), g(G->fc_mean_w), g(G->fc_mean_b), g(G->logstd)};
-    float *heads = nullptr; // packed head gradients: fc_mean.w [2,256] | critic_linear.w [256] | fc_mean.b [2] | critic_linear.b [1] | logstd [2]
+    float *heads = nullptr; // packed head gradients: fc_mean.w [2,O] | critic_linear.w [O] | fc_mean.b [2] | critic_linear.b [1] | logstd [2]
     if ((rc = rn_seq_bwd_impl(T, N, H, F(L.rn), F(L.te), F(L.out), row_off, F(L.masks), F(L.act), &rw, &sv, F(L.d_value), F(L.d_logp), F(L.rn_bwd), F(L.d_out),
-                              F(L.d_h0), &rg, stream, true, &heads))) return rc;
+                              F(L.d_h0), &rg, stream, true, &heads, &pd))) return rc;
 
     // ---- backward of the human-human block: the per-layer kernels on the saved activations, in reverse order ----
     // out = relu(attn Wos^T + b): d_out is complete since the sequence's attention backward
@@ -501,43 +535,45 @@ extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const
             FoldBuilder::seg(fb.add(512, 512, g(G->out_proj_w), 512), 256, P->spatial_linear_w, 1, 512, F(L.d_os_w), 512, 1);
             FoldBuilder::seg(fb.add(512, 1, g(G->out_proj_b), 1), 256, P->spatial_linear_w, 1, 512, F(L.d_os_b), 1, 0);
         }
-        { // te rows 0..255: U = Ws^T Wt, ub = Ws^T bt.  d Ws = Wt dU^T + bt (x) dub ;  d Wt = Ws dU ;  d bt = Ws dub ;  d bs = 0 (the softmax cannot see it)
-            FoldJob *j = fb.add(64, 256, g(G->attn_spatial_w), 256);
+        { // te rows 0..255: U = Ws^T Wt, ub = Ws^T bt (Ws, Wt [A,256]).  d Ws = Wt dU^T + bt (x) dub ;  d Wt = Ws dU ;  d bt = Ws dub ;
+          // d bs = 0 (the softmax cannot see it)
+            FoldJob *j = fb.add(dA, 256, g(G->attn_spatial_w), 256);
             FoldBuilder::seg(j, 256, P->attn_temporal_w, 256, 1, F(L.d_te_w), 1, 256);
             FoldBuilder::seg(j, 1, P->attn_temporal_b, 1, 0, F(L.d_te_b), 0, 1);
-            FoldBuilder::seg(fb.add(64, 256, g(G->attn_temporal_w), 256), 256, P->attn_spatial_w, 256, 1, F(L.d_te_w), 256, 1);
-            FoldBuilder::seg(fb.add(64, 1, g(G->attn_temporal_b), 1), 256, P->attn_spatial_w, 256, 1, F(L.d_te_b), 1, 0);
-            fb.add(64, 1, g(G->attn_spatial_b), 1); // exact zero
-            fb.copy(64, 256, g(G->enc_w), 256, F(L.d_te_w) + 256 * 256, 256);
-            fb.copy(64, 1, g(G->enc_b), 1, F(L.d_te_b) + 256, 1);
+            FoldBuilder::seg(fb.add(dA, 256, g(G->attn_temporal_w), 256), 256, P->attn_spatial_w, 256, 1, F(L.d_te_w), 256, 1);
+            FoldBuilder::seg(fb.add(dA, 1, g(G->attn_temporal_b), 1), 256, P->attn_spatial_w, 256, 1, F(L.d_te_b), 1, 0);
+            fb.add(dA, 1, g(G->attn_spatial_b), 1); // exact zero
+            fb.copy(dM, 256, g(G->enc_w), 256, F(L.d_te_w) + 256 * 256, 256);
+            fb.copy(dM, 1, g(G->enc_b), 1, F(L.d_te_b) + 256, 1);
         }
-        { // ac0 = (actor.0 ; critic.0) o output_linear
+        { // ac0 = (actor.0 ; critic.0) [O,O] o output_linear [O,R]
             const float *w0[2] = {P->actor0_w, P->critic0_w};
             float *gw0[2] = {g(G->actor0_w), g(G->critic0_w)}, *gb0[2] = {g(G->actor0_b), g(G->critic0_b)};
             for (int i = 0; i < 2; ++i) {
-                const float *dA = F(L.d_ac0_w) + (size_t)i * 256 * 128, *db = F(L.d_ac0_b) + i * 256;
-                FoldJob *j = fb.add(256, 256, gw0[i], 256); // d W0_i = dA_i Wo^T + db_i (x) bo
-                FoldBuilder::seg(j, 128, dA, 128, 1, P->out_w, 1, 128);
+                const float *dA0 = F(L.d_ac0_w) + (size_t)i * dO * dR, *db = F(L.d_ac0_b) + i * dO;
+                FoldJob *j = fb.add(dO, dO, gw0[i], dO); // d W0_i = dA_i Wo^T + db_i (x) bo
+                FoldBuilder::seg(j, dR, dA0, dR, 1, P->out_w, 1, dR);
                 FoldBuilder::seg(j, 1, db, 1, 0, P->out_b, 0, 1);
-                fb.copy(256, 1, gb0[i], 1, db, 1);
+                fb.copy(dO, 1, gb0[i], 1, db, 1);
             }
-            FoldJob *j = fb.add(256, 128, g(G->out_w), 128); // d Wo = actor.0^T dA_actor + critic.0^T dA_critic
-            FoldBuilder::seg(j, 256, w0[0], 1, 256, F(L.d_ac0_w), 128, 1);
-            FoldBuilder::seg(j, 256, w0[1], 1, 256, F(L.d_ac0_w) + 256 * 128, 128, 1);
-            j = fb.add(256, 1, g(G->out_b), 1);
-            FoldBuilder::seg(j, 256, w0[0], 1, 256, F(L.d_ac0_b), 1, 0);
-            FoldBuilder::seg(j, 256, w0[1], 1, 256, F(L.d_ac0_b) + 256, 1, 0);
+            FoldJob *j = fb.add(dO, dR, g(G->out_w), dR); // d Wo = actor.0^T dA_actor + critic.0^T dA_critic
+            FoldBuilder::seg(j, dO, w0[0], 1, dO, F(L.d_ac0_w), dR, 1);
+            FoldBuilder::seg(j, dO, w0[1], 1, dO, F(L.d_ac0_w) + (size_t)dO * dR, dR, 1);
+            j = fb.add(dO, 1, g(G->out_b), 1);
+            FoldBuilder::seg(j, dO, w0[0], 1, dO, F(L.d_ac0_b), 1, 0);
+            FoldBuilder::seg(j, dO, w0[1], 1, dO, F(L.d_ac0_b) + dO, 1, 0);
         }
         // input layer: dwb [128, D + 1] = per output column the D weight gradients, then the bias gradient
         fb.copy(128, D, g(G->emb0_w), D, F(L.dwb), D + 1);
         fb.copy(128, 1, g(G->emb0_b), 1, F(L.dwb) + D, D + 1);
         // heads: scattered from the packed reduction; d(-coef * entropy) / d logstd_k = -coef / 2 on top of the log-prob path's gradient
-        fb.copy(2, 256, g(G->fc_mean_w), 256, heads, 256);
-        fb.copy(1, 256, g(G->critic_linear_w), 256, heads + 512, 256);
-        fb.copy(2, 1, g(G->fc_mean_b), 1, heads + 768, 1);
-        fb.copy(1, 1, g(G->critic_linear_b), 1, heads + 770, 1);
+        // (the packed layout rn_seq_bwd_impl writes for O: fc_mean.w at 0, critic_linear.w at 2 O, fc_mean.b at 3 O, critic_linear.b at 3 O + 2, logstd at 3 O + 3)
+        fb.copy(2, dO, g(G->fc_mean_w), dO, heads, dO);
+        fb.copy(1, dO, g(G->critic_linear_w), dO, heads + 2 * dO, dO);
+        fb.copy(2, 1, g(G->fc_mean_b), 1, heads + 3 * dO, 1);
+        fb.copy(1, 1, g(G->critic_linear_b), 1, heads + 3 * dO + 2, 1);
         fb.add(2, 1, g(G->logstd), 1);
-        FoldBuilder::plus(&fb.t.job[fb.t.njobs - 1], heads + 771, 1);
+        FoldBuilder::plus(&fb.t.job[fb.t.njobs - 1], heads + 3 * dO + 3, 1);
         fb.t.job[fb.t.njobs - 1].add_const = -0.5f * hy->entropy_coef;
         if ((rc = fb.launch(st))) return rc;
     }

@@ -11,5 +11,5 @@ from .hip_env import (HipEnvBatch, StepStamps, orca_solve, prediction_dots, rend
                       trace_metrics)
 from .hip_policy import HipHandle, HipPolicy, HipSrnn, compact_visible  # noqa: F401
 from .hip_train import (Embed0, GRUSequence, HHAttention, HHBlockFused, HipLinear, HRAttention, MinibatchStepper, PPOLoss, RightMatmul,  # noqa: F401
-                        RnSequence, SmallMM, SrnnAttention, SrnnEdgeSequence, WgradLinear, adam_clip_step, adv_normalize, adv_stats, gae, linear_act,
+                        RnSequence, SizedMinibatchStepper, SmallMM, SrnnAttention, SrnnEdgeSequence, WgradLinear, adam_clip_step, adv_normalize, adv_stats, gae, linear_act,
                         linear_supported, split_bf16, weight_mm, wgrad, wgrad_supported)

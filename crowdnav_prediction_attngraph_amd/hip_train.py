@@ -587,7 +587,8 @@ def adv_normalize(returns, values, stats, n, out):
 class MinibatchStepper:
     """One PPO minibatch -- gather from the rollout storage, train-mode forward, losses, backward, every parameter gradient written into the
     caller's flat bucket -- as ONE boundary call (cn_ppo_minibatch_step; rl/networks/storage.py:184-253 + rl/networks/model.py:82-90 +
-    rl/ppo/ppo.py:66-88).  Built by ppo.PPO for the default network; the workspace is one cached byte tensor that grows with the row count."""
+    rl/ppo/ppo.py:66-88).  Built by ppo.PPO for the default network sizes (SizedMinibatchStepper below: every sizes tuple of the device box); the
+    workspace is one cached byte tensor that grows with the row count."""
 
     def __init__(self, policy):
         self.policy = policy
@@ -609,11 +610,16 @@ class MinibatchStepper:
 
     @staticmethod
     def supported(policy, rollouts):
+        """The default sizes only (base.fused_rn_shapes_ok()); SizedMinibatchStepper.supported covers the device box."""
+        return MinibatchStepper._supported(policy, rollouts, lambda base: base.fused_rn_shapes_ok())
+
+    @staticmethod
+    def _supported(policy, rollouts, shapes_ok):
         base = policy.base
         if getattr(policy, "is_srnn_baseline", False):      # DS-RNN: cn_ppo_minibatch_step knows the attention-graph network only
             return False
         if not (base.use_self_attn and base.sort_humans and base.train_gemm_mode == "bf16x3" and base.train_fused_hh and base.train_fused_rn
-                and base.fused_rn_shapes_ok() and base.human_num <= 48 and base.edge_width <= 16):
+                and shapes_ok(base) and base.human_num <= 48 and base.edge_width <= 16):
             return False
         if tuple(base.spatial_attn.embedding_layer[0].weight.shape) != (128, base.edge_width):
             return False
@@ -652,8 +658,7 @@ class MinibatchStepper:
         T, E = rollouts.rewards.shape[0], rollouts.rewards.shape[1]
         N, H, D = int(env_idx.numel()), base.human_num, base.edge_width
         dev = rollouts.rewards.device
-        L = A.lib()
-        need = int(L.cn_ppo_minibatch_workspace_bytes(T, N, H, D, int(rows)))
+        need = self._workspace_bytes(T, N, H, D, int(rows))
         if need <= 0:
             raise A.CnError("cn_ppo_minibatch_workspace_bytes: unsupported shape T=%d N=%d H=%d D=%d rows=%d" % (T, N, H, D, rows))
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
@@ -668,5 +673,36 @@ class MinibatchStepper:
         for k in A.PPO_BATCH_TENSORS:
             setattr(b, k, ts[k].data_ptr())
         hy = A.PpoHyper(float(hyper[0]), float(hyper[1]), float(hyper[2]), int(bool(hyper[3])))
-        A.call("cn_ppo_minibatch_step", C.byref(b), int(rows), C.byref(w), C.byref(g), C.byref(hy), C.c_void_p(self._ws.data_ptr()), int(self._ws.numel()),
-               A.ptr(losses_out), A.ptr(value_logp_out), A.stream_ptr(), device=dev)
+        self._call(C.byref(b), int(rows), C.byref(w), C.byref(g), C.byref(hy), C.c_void_p(self._ws.data_ptr()), int(self._ws.numel()),
+                   A.ptr(losses_out), A.ptr(value_logp_out), A.stream_ptr(), dev)
+
+    # the two boundary calls of step(): what SizedMinibatchStepper replaces
+    def _workspace_bytes(self, T, N, H, D, rows):
+        return int(A.lib().cn_ppo_minibatch_workspace_bytes(T, N, H, D, rows))
+
+    def _call(self, b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev):
+        A.call("cn_ppo_minibatch_step", b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, device=dev)
+
+
+class SizedMinibatchStepper(MinibatchStepper):
+    """MinibatchStepper at the network sizes of policy.base.dims = (R, M, A, O), any tuple inside the device box (_abi.DIMS_BOX):
+    cn_ppo_minibatch_workspace_bytes_sized / cn_ppo_minibatch_step_sized.  At the default tuple the C call is cn_ppo_minibatch_step itself."""
+
+    def __init__(self, policy):
+        super().__init__(policy)
+        try:
+            self.dims = A.policy_dims(policy.base.dims)
+        except NotImplementedError as e:
+            raise A.CnError("SizedMinibatchStepper: %s" % e)
+
+    @staticmethod
+    def supported(policy, rollouts):
+        """An attention-graph policy on GPU tensors whose sizes lie in the device box (base.sized_rn_ok()); otherwise the conditions of
+        MinibatchStepper.supported.  False for the DS-RNN baseline."""
+        return MinibatchStepper._supported(policy, rollouts, lambda base: base.sized_rn_ok())
+
+    def _workspace_bytes(self, T, N, H, D, rows):
+        return int(A.lib().cn_ppo_minibatch_workspace_bytes_sized(T, N, H, D, rows, C.byref(self.dims)))
+
+    def _call(self, b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev):
+        A.call("cn_ppo_minibatch_step_sized", b, rows, w, g, hy, C.byref(self.dims), ws, ws_bytes, losses_out, value_logp_out, stream, device=dev)

@@ -197,8 +197,9 @@ class AttnGraphBase(nn.Module):
 
     @property
     def default_sizes(self):
-        """The reference's default widths: the ones the per-op training Functions of the torch-op route (train_fused_rn = False, 'fp32') and
-        cn_ppo_minibatch_step are specialised to.  The robot-node sequence itself (rn_sequence) runs any sizes in the device box."""
+        """The reference's default widths: the ones the per-op training Functions of the torch-op route (train_fused_rn = False, 'fp32') are
+        specialised to.  The robot-node sequence (rn_sequence) and the one-call minibatch step (cn_ppo_minibatch_step_sized) run any sizes in
+        the device box."""
         from ._abi import DEFAULT_DIMS
         return self.dims == DEFAULT_DIMS
 
@@ -231,9 +232,9 @@ class AttnGraphBase(nn.Module):
         return out
 
     def fused_rn_shapes_ok(self):
-        """The modules have exactly the DEFAULT layer shapes of the robot-node sequence (_abi.RN_WEIGHT_SHAPES): what cn_ppo_minibatch_step is
-        specialised to (hip_train.MinibatchStepper.supported).  evaluate_actions itself asks sized_rn_ok(): hip_train.RnSequence runs every
-        sizes tuple inside the device box."""
+        """The modules have exactly the DEFAULT layer shapes of the robot-node sequence (_abi.RN_WEIGHT_SHAPES): what the unsized
+        cn_ppo_minibatch_step takes (hip_train.MinibatchStepper.supported).  evaluate_actions and hip_train.SizedMinibatchStepper.supported ask
+        sized_rn_ok(): hip_train.RnSequence and cn_ppo_minibatch_step_sized run every sizes tuple inside the device box."""
         rnn, g = self.humanNodeRNN, self.humanNodeRNN.gru
         return (tuple(self.robot_linear[0].weight.shape) == (256, 9) and tuple(rnn.edge_attention_embed.weight.shape) == (64, 256)
                 and tuple(rnn.encoder_linear.weight.shape) == (64, 256) and tuple(self.attn.temporal_edge_layer[0].weight.shape) == (64, 256)
@@ -243,9 +244,10 @@ class AttnGraphBase(nn.Module):
                 and tuple(self.critic_linear.weight.shape) == (1, 256))
 
     def sized_rn_ok(self):
-        """The robot-node sequence (hip_train.RnSequence: cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized) runs at these sizes: every dims tuple inside
-        the device box with the reference's 256-wide edge features.  Wider than fused_rn_shapes_ok(), which keeps meaning "the default shapes"
-        (what cn_ppo_minibatch_step is specialised to, hip_train.MinibatchStepper.supported)."""
+        """The robot-node sequence (hip_train.RnSequence: cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized) and the one-call minibatch step
+        (hip_train.SizedMinibatchStepper: cn_ppo_minibatch_step_sized) run at these sizes: every dims tuple inside the device box with the
+        reference's 256-wide edge features.  Wider than fused_rn_shapes_ok(), which keeps meaning "the default shapes" (what
+        hip_train.MinibatchStepper.supported answers for)."""
         from ._abi import policy_dims
         try:
             policy_dims(self.dims)

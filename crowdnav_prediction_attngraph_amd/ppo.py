@@ -7,7 +7,7 @@ every rank owns a disjoint shard of envs and
   * per optimiser step ONE all-reduce of a single flat fp32 gradient bucket (all parameters, ~10 MB) over RCCL/xGMI,
     averaged, then the grad-norm clip and Adam run identically on every rank.
 The bucket and its optimiser step are flat_adam.FlatAdam, shared with gst_hip.HipGstTrainer.  update() is one epoch / minibatch loop: a
-gradient producer (cn_ppo_minibatch_step, or the autograd-joined graph), then _optimizer_step.
+gradient producer (cn_ppo_minibatch_step / cn_ppo_minibatch_step_sized, or the autograd-joined graph), then _optimizer_step.
 """
 import functools
 
@@ -104,23 +104,34 @@ class PPO():
             value_loss = 0.5 * (returns - values).pow(2).mean()
         return value_loss, action_loss
 
-    # ---- one boundary call per minibatch (default network on the GPU) -------------------------------------------------
+    # ---- one boundary call per minibatch (attention-graph network on the GPU) -----------------------------------------
     # cn_ppo_minibatch_step gathers the minibatch from the storage by env index, runs the train-mode forward, the losses and the whole
     # backward, and WRITES every parameter gradient into the flat bucket: no autograd graph, no framework kernel between the rollout
-    # storage and the Adam step.  use_minibatch_step = False keeps the autograd-joined path below, which the non-default variants
-    # (use_self_attn / sort_humans off, fp32 arithmetic, CPU tensors) always take.
+    # storage and the Adam step.  The default network sizes run it through hip.MinibatchStepper, every other (R, M, A, O) of the device box
+    # through hip.SizedMinibatchStepper (cn_ppo_minibatch_step_sized).  use_minibatch_step = False keeps the autograd-joined path below for
+    # every network; the variants outside the step (use_self_attn / sort_humans off, fp32 arithmetic, crowds of 49 to 64 humans, edge widths
+    # above 16, the DS-RNN baseline, CPU tensors) always take it.
     use_minibatch_step = True
 
+    def _stepper_class(self, rollouts):
+        """hip.MinibatchStepper (default sizes), hip.SizedMinibatchStepper (any other tuple of the device box), or None: no one-call step."""
+        if not (self.actor_critic.is_recurrent and hasattr(self.actor_critic, "base")):
+            return None
+        for cls in (hip.MinibatchStepper, hip.SizedMinibatchStepper):
+            if cls.supported(self.actor_critic, rollouts):
+                return cls
+        return None
+
     def _fast_path(self, rollouts):
-        return (self.use_minibatch_step and self.actor_critic.is_recurrent and hasattr(self.actor_critic, "base")
-                and hip.MinibatchStepper.supported(self.actor_critic, rollouts))
+        return bool(self.use_minibatch_step) and self._stepper_class(rollouts) is not None
 
     def _fast_plan(self, rollouts):
         """(stepper, per-env row totals) when every minibatch this update() can draw fits one cn_ppo_minibatch_step, else None: the update then
         takes the autograd-joined path.  Decided on the host from the one readback update() makes anyway, before the first permutation is
         drawn and before any launch of the step: the npb envs with the most rows together bound every minibatch of every epoch."""
-        if getattr(self, "_stepper", None) is None or self._stepper.policy is not self.actor_critic:
-            self._stepper = hip.MinibatchStepper(self.actor_critic)
+        cls = self._stepper_class(rollouts)
+        if type(getattr(self, "_stepper", None)) is not cls or self._stepper.policy is not self.actor_critic:
+            self._stepper = cls(self.actor_critic)
         E = rollouts.rewards.shape[1]
         assert E >= self.num_mini_batch, "PPO requires the number of processes ({}) to be greater than or equal to the number of PPO mini batches ({}).".format(E, self.num_mini_batch)
         totals = self._stepper.row_totals(rollouts)              # the ONE readback of update(): rows per env -> rows per minibatch on the host

@@ -223,9 +223,10 @@ def train(env_name="CrowdSimVarNum-v0", num_processes=4096, num_steps=30, num_up
     the reference's train.py:94 does, and is 'selfAttn_merge_srnn' otherwise.
     network: a dict of the reference's network-size flags (NETWORK_FLAGS: human_node_rnn_size, human_node_embedding_size, attention_size,
     human_node_output_size) for the attention-graph network; sizes outside the device box (_abi.DIMS_BOX) are refused before the first rollout.
-    The rollout runs on the HIP kernels at any sizes in the box, and so does the update: off the default sizes evaluate_actions is the same two
-    boundary calls each way (cn_hh_block_fwd + the per-layer backward, cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized) joined by autograd; only the
-    one-call minibatch step (cn_ppo_minibatch_step) is still specialised to the default sizes."""
+    The rollout runs on the HIP kernels at any sizes in the box, and so does the update: PPO.update takes one boundary call per minibatch at
+    every tuple of the box (cn_ppo_minibatch_step at the default sizes, cn_ppo_minibatch_step_sized off them).  With
+    PPO.use_minibatch_step = False evaluate_actions is the same two boundary calls each way (cn_hh_block_fwd + the per-layer backward,
+    cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized) joined by autograd."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     torch.manual_seed(seed)
     if pretext_wrapper is None:

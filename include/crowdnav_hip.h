@@ -934,7 +934,8 @@ int cn_adam_clip_step(int64_t n, float *param, float *grad, float *exp_avg, floa
                       float *grad_norm_out, void *stream);
 
 /* ---- one PPO minibatch step as ONE boundary call (rl/ppo/ppo.py:55-95 for one `sample` of the recurrent generator) ----
- * Replaces, for the default network (use_self_attn, sort_humans; crowds of <= 48 humans, edge width <= 16), the statement sequence
+ * Replaces, for the attention-graph network (use_self_attn, sort_humans; crowds of <= 48 humans, edge width <= 16) at the default sizes -- and,
+ * through cn_ppo_minibatch_step_sized below, at every cn_policy_dims tuple of the device box --, the statement sequence
  *   sample = recurrent_generator(...)            rl/networks/storage.py:184-253  (gather of N whole env trajectories by index)
  *   evaluate_actions(...)                        rl/networks/model.py:82-90
  *   value_loss / action_loss / entropy           rl/ppo/ppo.py:66-86
@@ -970,6 +971,19 @@ int cn_ppo_row_totals(int T, int E, int H, const float *detected_human_num, int3
 int cn_ppo_minibatch_step(const cn_ppo_batch *batch, int64_t rows, const cn_policy_weights *params, const cn_policy_weights *grads,
                           const cn_ppo_hyper *hyper, void *workspace, int64_t workspace_bytes, float *losses_out,
                           float *value_logp_out /* optional [2, T * N]: values, log-probs of the minibatch (tests) */, void *stream);
+/* The same step at the network sizes of cn_policy_dims (R, M, A, O) inside the device box of cn_policy_create_sized.  dims == NULL or the default
+ * tuple: cn_ppo_minibatch_step / cn_ppo_minibatch_workspace_bytes themselves (they forward here) -- the same launches on the same buffers, the
+ * same bits, the same workspace size.  Outside the box the step fails with CN_ERR_INVALID naming the box and launches nothing; the workspace
+ * query, which runs on the host, returns 0.  H <= 48, D <= 16 and cn_ppo_minibatch_max_rows() are unchanged (the human-human block in front of
+ * out_sp [rows,256] does not depend on dims).  params / grads have the shapes listed under cn_policy_create_sized; batch->h0 is [E,1,R].
+ * Inside, te = [Ws^T Wt ; encoder_linear] is [256+M,256] (the fold over A is a K = A segment, left unscaled: the sequence takes the score
+ * temperature H / sqrt(A) from dims), ac0 = (actor.0 ; critic.0) o output_linear is [2O,R], the saved activations have the widths listed for
+ * cn_rn_saved under cn_rn_seq_fwd_sized, and the sequence's two workspaces come from cn_rn_seq_*_workspace_floats_sized.
+ * (CN_ABI_VERSION is unchanged: these are additions, no existing signature or struct layout moved.) */
+int64_t cn_ppo_minibatch_workspace_bytes_sized(int T, int N, int H, int D, int64_t rows, const cn_policy_dims *dims);
+int cn_ppo_minibatch_step_sized(const cn_ppo_batch *batch, int64_t rows, const cn_policy_weights *params, const cn_policy_weights *grads,
+                                const cn_ppo_hyper *hyper, const cn_policy_dims *dims, void *workspace, int64_t workspace_bytes,
+                                float *losses_out, float *value_logp_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,8 @@
             stream it once, over the ~34 TB/s aggregate L2 -> CU rate DESIGN.md section 4 quotes for the fused kernels' weight streams.
   update    PPO.update at T = 30, 4096 envs in two minibatches of 2048, for (192, 64, 48, 320), (256, 128, 128, 512) and for the default: update_s of
             trainer.train's updates 1..3 (update 0 is the warm-up).  Off the default sizes the robot-node part of the update runs on the sized
-            sequence (cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized) inside the autograd-joined producer; cn_ppo_minibatch_step is default-only.
+            sequence (cn_rn_seq_fwd_sized / cn_rn_seq_bwd_sized): inside the autograd-joined producer when the recorded figures were taken, inside
+            cn_ppo_minibatch_step_sized since (tools/minibatch_sized_throughput.py records that step).
   update_ab the same update in the tree under --parent-dir and in this tree as alternating child processes (`--rounds` children of three timed
             updates per side and tuple): this tree's sized figures must lie below the parent's with intervals that do not overlap, the default
             tuple's median inside the parent's own range.
