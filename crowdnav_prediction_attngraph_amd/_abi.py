@@ -135,6 +135,18 @@ POLICY_WEIGHT_KEYS = [
 ]
 
 
+def policy_weight_keys(use_self_attn=True):
+    """[(field of cn_policy_weights, state-dict key)] of the attention-graph network: POLICY_WEIGHT_KEYS, or, with use_self_attn off
+    (cn_policy_set_self_attention(p, 0), cn_ppo_variant.self_attn = 0), the remap the library reads in that mode -- the state dict has no
+    spatial_attn.* tensors (those fields stay NULL) and spatial_linear is [.0: 128 x D, .2: 256 x 128].  The one copy of that remap: the rollout
+    handle (hip_policy.HipPolicy._weight_keys) and the minibatch steppers (hip_train.MinibatchStepper) both ask here."""
+    if use_self_attn:
+        return POLICY_WEIGHT_KEYS
+    remap = {"emb0_w": "base.spatial_linear.0.weight", "emb0_b": "base.spatial_linear.0.bias",
+             "spatial_linear_w": "base.spatial_linear.2.weight", "spatial_linear_b": "base.spatial_linear.2.bias"}
+    return [(f, remap.get(f, k)) for f, k in POLICY_WEIGHT_KEYS if f in remap or not k.startswith("base.spatial_attn.")]
+
+
 # order == field order of cn_srnn_weights (DS-RNN baseline, base='srnn'); values == reference state_dict keys.  The three modules no gradient
 # reaches (base.humanNodeRNN.edge_embed, base.human_node_final_linear, base.spatial_linear) are not part of the forward
 SRNN_WEIGHT_KEYS = [
@@ -256,6 +268,12 @@ class PpoHyper(C.Structure):
     _fields_ = [("clip_param", C.c_float), ("value_loss_coef", C.c_float), ("entropy_coef", C.c_float), ("use_clipped_value_loss", C.c_int)]
 
 
+class PpoVariant(C.Structure):
+    """cn_ppo_variant: the two switches of the attention-graph network in the one-call minibatch step; visible_masks = the storage's [T+1,E,H]
+    bool tensor, required exactly when sort_humans == 0."""
+    _fields_ = [("self_attn", C.c_int32), ("sort_humans", C.c_int32), ("visible_masks", C.c_void_p)]
+
+
 # every symbol include/crowdnav_hip.h declares (checked by tests/test_abi_symbols.py)
 ABI_SYMBOLS = [
     "cn_last_error", "cn_version", "cn_device_count", "cn_env_config_default", "cn_env_create", "cn_env_destroy",
@@ -268,6 +286,7 @@ ABI_SYMBOLS = [
     "cn_ppo_loss_workspace_doubles", "cn_ppo_loss_fwd", "cn_ppo_loss_bwd", "cn_adam_workspace_doubles", "cn_adam_clip_step",
     "cn_ppo_minibatch_max_rows", "cn_ppo_minibatch_workspace_bytes", "cn_ppo_row_totals", "cn_ppo_minibatch_step",
     "cn_ppo_minibatch_workspace_bytes_sized", "cn_ppo_minibatch_step_sized",
+    "cn_ppo_minibatch_workspace_bytes_variant", "cn_ppo_minibatch_step_variant", "cn_ppo_row_totals_visible",
     "cn_gst_train_workspace_bytes", "cn_gst_train_step", "cn_gst_eval_workspace_bytes", "cn_gst_eval_step",
     "cn_gst_train_workspace_bytes_horizon", "cn_gst_train_step_horizon", "cn_gst_eval_workspace_bytes_horizon", "cn_gst_eval_step_horizon",
     "cn_gst_data_frames_horizon", "cn_gst_data_count_horizon", "cn_gst_data_fill_horizon", "cn_gst_gather_batch_horizon",
@@ -452,6 +471,11 @@ def lib():
         L.cn_ppo_minibatch_workspace_bytes_sized.argtypes = [i32, i32, i32, i32, i64, C.POINTER(PolicyDims)]
         L.cn_ppo_minibatch_step_sized.argtypes = [C.POINTER(PpoBatch), i64, C.POINTER(PolicyWeights), C.POINTER(PolicyWeights), C.POINTER(PpoHyper),
                                                   C.POINTER(PolicyDims), vp, i64, vp, vp, vp]
+        L.cn_ppo_minibatch_workspace_bytes_variant.restype = C.c_int64
+        L.cn_ppo_minibatch_workspace_bytes_variant.argtypes = [i32, i32, i32, i32, i64, C.POINTER(PolicyDims), C.POINTER(PpoVariant)]
+        L.cn_ppo_minibatch_step_variant.argtypes = [C.POINTER(PpoBatch), i64, C.POINTER(PolicyWeights), C.POINTER(PolicyWeights), C.POINTER(PpoHyper),
+                                                    C.POINTER(PolicyDims), C.POINTER(PpoVariant), vp, i64, vp, vp, vp]
+        L.cn_ppo_row_totals_visible.argtypes = [i32, i32, i32, vp, vp, vp]
         _lib = L
     return _lib
 

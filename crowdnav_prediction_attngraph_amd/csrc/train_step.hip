@@ -12,6 +12,10 @@
 //     cn_small_mm plus autograd's accumulation kernels per optimiser step;
 //   * gradients are written straight into the caller's flat bucket (no zero fill, no accumulation pass).
 // Summation orders are fixed: the step is deterministic.
+// Variants (cn_ppo_variant, cn_ppo_minibatch_step_variant): sort_humans = 0 swaps the gather for tr_gather_visible_kernel, which compacts the
+// visible humans to the front while it gathers (the rule of compact_visible_kernel, policy_kernels.h); self_attn = 0 swaps the human-human
+// block for the two-layer MLP spatial_linear = Linear(D,128) - ReLU - Linear(128,256) - ReLU on the compacted rows (cn_embed0_fwd +
+// cn_linear_fwd forward, the per-layer kernels backward) and drops the block's folds.  v == NULL / {1, 1, NULL}: the launches below, unchanged.
 // Network sizes: every width behind the human-human block is a function of cn_policy_dims (R, M, A, O) inside the device box of
 // cn_policy_create_sized; the unsized entry points forward to the sized ones with the default tuple (128, 64, 64, 256).
 #include "common.h"
@@ -19,6 +23,7 @@
 
 #include "train_internal.h"
 
+#include <cstddef>
 #include <cstring>
 
 namespace {
@@ -58,6 +63,50 @@ __global__ __launch_bounds__(64) void tr_gather_kernel(cn_ppo_batch b, GatherOut
     for (int i = lane; i < HD; i += 64) dst[i] = src[i];
     if (t == 0) { // hidden state of the first step only (storage.py:222)
         const int R = h0_passes * 64; // rnn_size: 64-lane passes over a row of R = 64 / 128 / 192 / 256 floats
+        const float *hs = b.h0 + (size_t)e * R;
+        float *hd = o.h0 + (size_t)j * R;
+        for (int p = 0; p < h0_passes; ++p) hd[lane + 64 * p] = hs[lane + 64 * p];
+    }
+}
+
+// sort_humans = 0 (selfAttn_srnn_temp_node.py:378-383): tr_gather_kernel with the rule of compact_visible_kernel (policy_kernels.h) applied while
+// the spatial edges are gathered -- lane = human, a ballot over the sample's H mask bytes (H <= 48: one wavefront), visible humans to the front in
+// index order, the others behind them in index order, nd = max(1, visible) (an all-invisible sample keeps human 0).  The minibatch's
+// spatial_edges are written once, already compacted; detected_human_num is not read.
+__global__ __launch_bounds__(64) void tr_gather_visible_kernel(cn_ppo_batch b, const uint8_t *__restrict__ vis, GatherOut o, int h0_passes)
+{
+    __shared__ int rank_s[64];
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int t = s / b.N, j = s - t * b.N;
+    const int e = b.env_idx[j];
+    const size_t te_ = (size_t)t * b.E + e;
+    const int H = b.H;
+    const bool isH = lane < H;
+    unsigned long long m = __ballot(isH && vis[te_ * H + (isH ? lane : 0)] != 0);
+    if (m == 0ull) m = 1ull;
+    const unsigned long long valid = (1ull << H) - 1ull; // H <= 48
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int cnt = __popcll(m);
+    rank_s[lane] = ((m >> lane) & 1ull) ? __popcll(m & below) : cnt + __popcll(~m & valid & below);
+    if (lane < 7) o.rn[(size_t)s * 7 + lane] = b.robot_node[te_ * 7 + lane];
+    else if (lane < 9) o.te[(size_t)s * 2 + lane - 7] = b.temporal_edges[te_ * 2 + lane - 7];
+    else if (lane < 11) o.act[(size_t)s * 2 + lane - 9] = b.actions[te_ * 2 + lane - 9];
+    else if (lane == 11) o.masks[s] = b.masks[te_];
+    else if (lane == 12) o.vp[s] = b.value_preds[te_];
+    else if (lane == 13) o.ret[s] = b.returns[te_];
+    else if (lane == 14) o.olp[s] = b.old_logp[te_];
+    else if (lane == 15) o.adv[s] = b.adv[te_];
+    else if (lane == 16) o.nd[s] = cnt; // 1 .. H
+    __syncthreads();
+    const int D = b.D, HD = H * D;
+    const float *src = b.spatial_edges + te_ * HD;
+    float *dst = o.se + (size_t)s * HD;
+    for (int i = lane; i < HD; i += 64) { // coalesced reads; human i / D lands on row rank_s[i / D] < H
+        const int h = i / D;
+        dst[rank_s[h] * D + (i - h * D)] = src[i];
+    }
+    if (t == 0) {
+        const int R = h0_passes * 64;
         const float *hs = b.h0 + (size_t)e * R;
         float *hd = o.h0 + (size_t)j * R;
         for (int p = 0; p < h0_passes; ++p) hd[lane + 64 * p] = hs[lane + 64 * p];
@@ -126,6 +175,21 @@ __global__ __launch_bounds__(256) void tr_row_totals_kernel(int T, int E, int H,
     for (int t = 0; t < T; ++t) {
         int nd = (int)det[(size_t)t * E + e];
         s += nd < 1 ? 1 : (nd > H ? H : nd);
+    }
+    totals[e] = s;
+}
+
+// the same totals from the visibility bytes [T+1, E, H]: sums of max(1, visible) over t < T
+__global__ __launch_bounds__(256) void tr_row_totals_visible_kernel(int T, int E, int H, const uint8_t *__restrict__ vis, int *__restrict__ totals)
+{
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    int s = 0;
+    for (int t = 0; t < T; ++t) {
+        const uint8_t *v = vis + ((size_t)t * E + e) * H;
+        int c = 0;
+        for (int h = 0; h < H; ++h) c += v[h] != 0;
+        s += c < 1 ? 1 : c;
     }
     totals[e] = s;
 }
@@ -273,6 +337,9 @@ struct Ws {
     size_t qkv_w, qkv_b, os_w, os_b, te_w, te_b, ac0_w, ac0_b, d_qkv_w, d_qkv_b, d_os_w, d_os_b, d_te_w, d_te_b, d_ac0_w, d_ac0_b;
     // human-human block: fragment images, saved activations, backward
     size_t frag, e0, x, qkv, attn, out, d_out, d_attn, d_qkv, d_x, d_e0, cls, wT_os, wT_qkv, wT_emb2, part, dbp, e0part, dwb;
+    // self_attn = 0: split planes of spatial_linear.2 [256,128] and of its transpose (the only pieces that variant adds; it reserves none of
+    // qkv_* / os_* / d_qkv_* / d_os_* / frag / x / qkv / attn / d_attn / d_qkv / d_x / cls / wT_*)
+    size_t w2, wT_w2;
     // robot-node sequence
     size_t sv[10], value, logp, d_value, d_logp, rn_fwd, rn_bwd, d_h0;
     // losses
@@ -294,7 +361,18 @@ TrDims tr_dims(const cn_policy_dims *d)
     return q;
 }
 
-Ws carve(int T, int N, int H, int D, int64_t rows, const TrDims &Q)
+// cn_ppo_variant as the step reads it (NULL: today's network)
+struct TrVariant {
+    bool attn, sorted;
+    const uint8_t *vis;
+};
+TrVariant tr_variant(const cn_ppo_variant *v)
+{
+    if (!v) return TrVariant{true, true, nullptr};
+    return TrVariant{v->self_attn != 0, v->sort_humans != 0, v->visible_masks};
+}
+
+Ws carve(int T, int N, int H, int D, int64_t rows, const TrDims &Q, bool attn)
 {
     const cn_policy_dims pd{Q.R, Q.M, Q.A, Q.O};
     const size_t TE = 256 + (size_t)Q.M, AC = 2 * (size_t)Q.O; // rows of te = [u ; encoder_linear] and of ac0 = (actor.0 ; critic.0) o output_linear
@@ -305,17 +383,30 @@ Ws carve(int T, int N, int H, int D, int64_t rows, const TrDims &Q)
     const size_t B = (size_t)T * N, R = (size_t)(rows > 0 ? rows : 1);
     w.rn = f(B * 7); w.te = f(B * 2); w.se = f(B * H * D); w.nd = f(B); w.row_off = f(B + 1); w.h0 = f((size_t)N * Q.R); w.masks = f(B); w.act = f(B * 2);
     w.vp = f(B); w.ret = f(B); w.olp = f(B); w.adv = f(B); w.xlive = f(R * D);
-    w.qkv_w = f(1536 * 512); w.qkv_b = f(1536); w.os_w = f(256 * 512); w.os_b = f(256); w.te_w = f(TE * 256); w.te_b = f(TE); w.ac0_w = f(AC * Q.R); w.ac0_b = f(AC);
-    w.d_qkv_w = f(1536 * 512); w.d_qkv_b = f(1536); w.d_os_w = f(256 * 512); w.d_os_b = f(256); w.d_te_w = f(TE * 256); w.d_te_b = f(TE);
+    if (attn) { w.qkv_w = f(1536 * 512); w.qkv_b = f(1536); w.os_w = f(256 * 512); w.os_b = f(256); }
+    w.te_w = f(TE * 256); w.te_b = f(TE); w.ac0_w = f(AC * Q.R); w.ac0_b = f(AC);
+    if (attn) { w.d_qkv_w = f(1536 * 512); w.d_qkv_b = f(1536); w.d_os_w = f(256 * 512); w.d_os_b = f(256); }
+    w.d_te_w = f(TE * 256); w.d_te_b = f(TE);
     w.d_ac0_w = f(AC * Q.R); w.d_ac0_b = f(AC);
-    w.frag = f((size_t)cn_hh_block_workspace_bytes() / 4);
-    w.e0 = f(R * 128); w.x = f(R * 512); w.qkv = f(R * 1536); w.attn = f(R * 512); w.out = f(R * 256);
-    w.d_out = f(R * 256); w.d_attn = f(R * 512); w.d_qkv = f(R * 1536); w.d_x = f(R * 512); w.d_e0 = f(R * 128);
-    w.cls = f((size_t)cn_hh_attention_workspace_ints((int)B));
-    w.wT_os = f(256 * 512); w.wT_qkv = f(1536 * 512); w.wT_emb2 = f(512 * 128); // hi + lo planes of the transposed weights (N * K bf16 each = N * K floats)
+    if (attn) w.frag = f((size_t)cn_hh_block_workspace_bytes() / 4);
+    w.e0 = f(R * 128);
+    if (attn) { w.x = f(R * 512); w.qkv = f(R * 1536); w.attn = f(R * 512); }
+    w.out = f(R * 256);
+    w.d_out = f(R * 256);
+    if (attn) { w.d_attn = f(R * 512); w.d_qkv = f(R * 1536); w.d_x = f(R * 512); }
+    w.d_e0 = f(R * 128);
+    if (attn) {
+        w.cls = f((size_t)cn_hh_attention_workspace_ints((int)B));
+        w.wT_os = f(256 * 512); w.wT_qkv = f(1536 * 512); w.wT_emb2 = f(512 * 128); // hi + lo planes of the transposed weights (N * K bf16 each = N * K floats)
+    } else {
+        w.w2 = f(256 * 128); w.wT_w2 = f(256 * 128);
+    }
     size_t pmax = 0, bmax = 0;
     const int shp[3][2] = {{256, 512}, {1536, 512}, {512, 128}};
-    for (auto &q : shp) {
+    const int shp_mlp[1][2] = {{256, 128}};
+    const int (*shapes)[2] = attn ? shp : shp_mlp;
+    for (int qi = 0; qi < (attn ? 3 : 1); ++qi) {
+        const int *q = shapes[qi];
         const size_t sp = (size_t)cn_linear_wgrad_splits((int)R, q[0], q[1]);
         pmax = pmax > sp * q[0] * q[1] ? pmax : sp * q[0] * q[1];
         bmax = bmax > sp * q[0] ? bmax : sp * q[0];
@@ -357,11 +448,15 @@ constexpr int64_t TR_MAX_ROWS = ((1LL << 31) - 1) / 1536; // 1 398 101
 
 extern "C" int64_t cn_ppo_minibatch_max_rows(void) { return TR_MAX_ROWS; }
 
-extern "C" int64_t cn_ppo_minibatch_workspace_bytes_sized(int T, int N, int H, int D, int64_t rows, const cn_policy_dims *dims)
+extern "C" int64_t cn_ppo_minibatch_workspace_bytes_variant(int T, int N, int H, int D, int64_t rows, const cn_policy_dims *dims, const cn_ppo_variant *v)
 {
     const TrDims Q = tr_dims(dims);
     if (!Q.ok || T < 1 || N < 1 || H < 1 || H > 48 || D < 1 || D > 16 || rows < 0 || rows > TR_MAX_ROWS) return 0;
-    return (int64_t)carve(T, N, H, D, rows, Q).total;
+    return (int64_t)carve(T, N, H, D, rows, Q, tr_variant(v).attn).total;
+}
+extern "C" int64_t cn_ppo_minibatch_workspace_bytes_sized(int T, int N, int H, int D, int64_t rows, const cn_policy_dims *dims)
+{
+    return cn_ppo_minibatch_workspace_bytes_variant(T, N, H, D, rows, dims, nullptr);
 }
 extern "C" int64_t cn_ppo_minibatch_workspace_bytes(int T, int N, int H, int D, int64_t rows)
 {
@@ -377,6 +472,15 @@ extern "C" int cn_ppo_row_totals(int T, int E, int H, const float *detected_huma
     return CN_OK;
 }
 
+extern "C" int cn_ppo_row_totals_visible(int T, int E, int H, const uint8_t *visible_masks, int32_t *totals, void *stream)
+{
+    if (int rc = cn_require_device()) return rc;
+    CN_REQUIRE(T >= 1 && E >= 1 && H >= 1 && visible_masks && totals, "cn_ppo_row_totals_visible: bad argument");
+    hipLaunchKernelGGL(tr_row_totals_visible_kernel, dim3((E + 255) / 256), dim3(256), 0, (hipStream_t)stream, T, E, H, visible_masks, totals);
+    CN_CHECK_LAUNCH();
+    return CN_OK;
+}
+
 extern "C" int cn_ppo_minibatch_step(const cn_ppo_batch *bp, int64_t rows, const cn_policy_weights *P, const cn_policy_weights *G, const cn_ppo_hyper *hy,
                                      void *workspace, int64_t workspace_bytes, float *losses_out, float *value_logp_out, void *stream)
 {
@@ -387,6 +491,15 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
                                            const cn_policy_dims *dims, void *workspace, int64_t workspace_bytes, float *losses_out, float *value_logp_out,
                                            void *stream)
 {
+    return cn_ppo_minibatch_step_variant(bp, rows, P, G, hy, dims, nullptr, workspace, workspace_bytes, losses_out, value_logp_out, stream);
+}
+
+extern "C" int cn_ppo_minibatch_step_variant(const cn_ppo_batch *bp, int64_t rows, const cn_policy_weights *P, const cn_policy_weights *G, const cn_ppo_hyper *hy,
+                                             const cn_policy_dims *dims, const cn_ppo_variant *var, void *workspace, int64_t workspace_bytes, float *losses_out,
+                                             float *value_logp_out, void *stream)
+{
+    const TrVariant V = tr_variant(var);
+    CN_REQUIRE(V.sorted || V.vis, "cn_ppo_minibatch_step_variant: sort_humans = 0 needs visible_masks (the storage's [T+1, E, H] bytes), got NULL");
     const TrDims Q = tr_dims(dims);
     CN_REQUIRE(Q.ok, "cn_ppo_minibatch_step_sized: (rnn_size %d, embedding_size %d, attention_size %d, output_size %d) outside the device box: rnn_size in "
                "{64, 128, 192, 256}, embedding_size in {64, 128}, output_size a multiple of 64 in [64, 512], attention_size in [1, 256]", Q.R, Q.M, Q.A, Q.O);
@@ -404,11 +517,13 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
                (long long)rows, (long long)TR_MAX_ROWS);
     {
         const void *const *pp = reinterpret_cast<const void *const *>(P), *const *gp = reinterpret_cast<const void *const *>(G);
+        // self_attn = 0: the layers of SpatialEdgeSelfAttn do not exist (their fields may be NULL, as for cn_policy_set_weights)
+        const size_t attn_first = offsetof(cn_policy_weights, emb2_w) / sizeof(void *), attn_last = offsetof(cn_policy_weights, out_proj_b) / sizeof(void *);
         for (size_t i = 0; i < sizeof(cn_policy_weights) / sizeof(void *); ++i)
-            CN_REQUIRE(pp[i] && gp[i] && ((uintptr_t)pp[i] & 15) == 0 && ((uintptr_t)gp[i] & 15) == 0,
+            if (V.attn || i < attn_first || i > attn_last) CN_REQUIRE(pp[i] && gp[i] && ((uintptr_t)pp[i] & 15) == 0 && ((uintptr_t)gp[i] & 15) == 0,
                        "cn_ppo_minibatch_step: parameter / gradient pointer #%zu is null or not 16-byte aligned", i);
     }
-    const Ws L = carve(b.T, b.N, b.H, b.D, rows, Q);
+    const Ws L = carve(b.T, b.N, b.H, b.D, rows, Q, V.attn);
     CN_REQUIRE(workspace_bytes >= (int64_t)L.total && ((uintptr_t)workspace & 255) == 0,
                "cn_ppo_minibatch_step: workspace of %lld bytes (256-byte aligned) needed, got %lld", (long long)L.total, (long long)workspace_bytes);
     hipStream_t st = (hipStream_t)stream;
@@ -423,7 +538,8 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
     // ---- the minibatch, its row offsets, its compacted input rows ----
     {
         GatherOut o{F(L.rn), F(L.te), F(L.se), F(L.h0), F(L.masks), F(L.act), F(L.vp), F(L.ret), F(L.olp), F(L.adv), nd};
-        hipLaunchKernelGGL(tr_gather_kernel, dim3(B), dim3(64), 0, st, b, o, dR / 64);
+        if (V.sorted) hipLaunchKernelGGL(tr_gather_kernel, dim3(B), dim3(64), 0, st, b, o, dR / 64);
+        else hipLaunchKernelGGL(tr_gather_visible_kernel, dim3(B), dim3(64), 0, st, b, V.vis, o, dR / 64);
         CN_CHECK_LAUNCH();
         hipLaunchKernelGGL(tr_scan_kernel, dim3((B + 1023) / 1024), dim3(1024), 0, st, B, H, D, nd, row_off, F(L.se), F(L.xlive));
         CN_CHECK_LAUNCH();
@@ -433,14 +549,14 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
     {
         FoldBuilder fb;
         const float *lin_w[3] = {P->q_w, P->k_w, P->v_w}, *lin_b[3] = {P->q_b, P->k_b, P->v_b};
-        for (int i = 0; i < 3; ++i) { // (q|k|v)_linear o in_proj: Wc_i = W_in[i] W_i, bc_i = W_in[i] b_i + b_in[i]
+        for (int i = 0; V.attn && i < 3; ++i) { // (q|k|v)_linear o in_proj: Wc_i = W_in[i] W_i, bc_i = W_in[i] b_i + b_in[i]
             const float *Wi = P->in_proj_w + (size_t)i * 512 * 512;
             FoldBuilder::seg(fb.add(512, 512, F(L.qkv_w) + (size_t)i * 512 * 512, 512), 512, Wi, 512, 1, lin_w[i], 512, 1);
             FoldJob *j = fb.add(512, 1, F(L.qkv_b) + i * 512, 1);
             FoldBuilder::seg(j, 512, Wi, 512, 1, lin_b[i], 1, 0);
             FoldBuilder::plus(j, P->in_proj_b + i * 512, 1);
         }
-        { // out_proj o spatial_linear
+        if (V.attn) { // out_proj o spatial_linear
             FoldBuilder::seg(fb.add(256, 512, F(L.os_w), 512), 512, P->spatial_linear_w, 512, 1, P->out_proj_w, 512, 1);
             FoldJob *j = fb.add(256, 1, F(L.os_b), 1);
             FoldBuilder::seg(j, 512, P->spatial_linear_w, 512, 1, P->out_proj_b, 1, 0);
@@ -464,8 +580,8 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
     }
 
     // ---- train-mode forward: human-human block (one launch), robot-node sequence ----
-    if ((rc = cn_hh_block_fwd(B, H, D, F(L.se), row_off, P->emb0_w, P->emb0_b, P->emb2_w, P->emb2_b, F(L.qkv_w), F(L.qkv_b), F(L.os_w), F(L.os_b), 0.125f,
-                              base + L.frag, F(L.e0), F(L.x), F(L.qkv), F(L.attn), F(L.out), stream))) return rc;
+    if (V.attn && (rc = cn_hh_block_fwd(B, H, D, F(L.se), row_off, P->emb0_w, P->emb0_b, P->emb2_w, P->emb2_b, F(L.qkv_w), F(L.qkv_b), F(L.os_w), F(L.os_b), 0.125f,
+                                        base + L.frag, F(L.e0), F(L.x), F(L.qkv), F(L.attn), F(L.out), stream))) return rc;
     cn_rn_weights rw{P->robot_linear_w, P->robot_linear_b, F(L.te_w), F(L.te_b), P->edge_embed_w, P->edge_embed_b, P->gru_w_ih, P->gru_b_ih, P->gru_w_hh, P->gru_b_hh,
                      F(L.ac0_w), F(L.ac0_b), P->actor2_w, P->actor2_b, P->critic2_w, P->critic2_b, P->critic_linear_w, P->critic_linear_b, P->fc_mean_w, P->fc_mean_b,
                      P->logstd};
@@ -473,10 +589,20 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
     { // every split-plane image the step needs (the sequence's forward and backward weights, the transposed weights of the block's dX products): one launch
         CnSplitJob jobs[CN_SPLIT_MAX_JOBS];
         int nj = rn_seq_prep_jobs(&rw, F(L.rn_fwd), F(L.rn_bwd), T, N, jobs, &pd);
-        jobs[nj++] = cn_split_job(F(L.os_w), 256, 512, 1, 0, F(L.wT_os));
-        jobs[nj++] = cn_split_job(F(L.qkv_w), 1536, 512, 1, 0, F(L.wT_qkv));
-        jobs[nj++] = cn_split_job(P->emb2_w, 512, 128, 1, 0, F(L.wT_emb2));
+        if (V.attn) {
+            jobs[nj++] = cn_split_job(F(L.os_w), 256, 512, 1, 0, F(L.wT_os));
+            jobs[nj++] = cn_split_job(F(L.qkv_w), 1536, 512, 1, 0, F(L.wT_qkv));
+            jobs[nj++] = cn_split_job(P->emb2_w, 512, 128, 1, 0, F(L.wT_emb2));
+        } else { // spatial_linear.2 [256,128]: its planes for the forward, its transposed planes for dX
+            jobs[nj++] = cn_split_job(P->spatial_linear_w, 256, 128, 0, 0, F(L.w2));
+            jobs[nj++] = cn_split_job(P->spatial_linear_w, 256, 128, 1, 0, F(L.wT_w2));
+        }
         if ((rc = cn_split_group_launch(jobs, nj, st))) return rc;
+    }
+    if (!V.attn) { // out = relu(relu(x W0^T + b0) W2^T + b2) on the compacted rows (selfAttn_srnn_temp_node.py:342-345, :404-408): the rollout's spatial_mlp_forward
+        const uint16_t *hi = reinterpret_cast<const uint16_t *>(F(L.w2)), *lo = hi + (size_t)256 * 128;
+        if ((rc = cn_embed0_fwd(R, D, F(L.xlive), P->emb0_w, P->emb0_b, F(L.e0), stream))) return rc;
+        if ((rc = cn_linear_fwd(R, 256, 128, F(L.e0), 128, nullptr, hi, lo, P->spatial_linear_b, 1, F(L.out), 256, stream))) return rc;
     }
     if ((rc = rn_seq_fwd_impl(T, N, H, F(L.rn), F(L.te), F(L.out), row_off, F(L.h0), F(L.masks), F(L.act), &rw, &sv, F(L.rn_fwd), F(L.value), F(L.logp), stream, true, &pd))) return rc;
 
@@ -503,6 +629,10 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
 
     // ---- backward of the human-human block: the per-layer kernels on the saved activations, in reverse order ----
     // out = relu(attn Wos^T + b): d_out is complete since the sequence's attention backward
+    if (!V.attn) { // out = relu(e0 W2^T + b2), e0 = relu(x W0^T + b0): spatial_linear.2's gradients go straight into the bucket
+        if ((rc = layer_dw(R, 256, 128, F(L.d_out), F(L.out), F(L.e0), g(G->spatial_linear_w), g(G->spatial_linear_b), base, L, st))) return rc;
+        if ((rc = layer_dx(R, 256, 128, F(L.d_out), F(L.out), F(L.wT_w2), F(L.d_e0), st))) return rc;
+    } else {
     if ((rc = layer_dw(R, 256, 512, F(L.d_out), F(L.out), F(L.attn), F(L.d_os_w), F(L.d_os_b), base, L, st))) return rc;
     if ((rc = layer_dx(R, 256, 512, F(L.d_out), F(L.out), F(L.wT_os), F(L.d_attn), st))) return rc;
     if ((rc = cn_hh_attention_bwd(B, H, F(L.qkv), row_off, F(L.d_attn), 0.125f, F(L.d_qkv), reinterpret_cast<int *>(base + L.cls), 0, stream))) return rc;
@@ -510,6 +640,7 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
     if ((rc = layer_dw(R, 1536, 512, F(L.d_qkv), nullptr, F(L.x), F(L.d_qkv_w), F(L.d_qkv_b), base, L, st))) return rc;
     if ((rc = layer_dx(R, 512, 128, F(L.d_x), F(L.x), F(L.wT_emb2), F(L.d_e0), st))) return rc;                                                     // x = relu(e0 W2^T + b2)
     if ((rc = layer_dw(R, 512, 128, F(L.d_x), F(L.x), F(L.e0), g(G->emb2_w), g(G->emb2_b), base, L, st))) return rc;
+    } // V.attn
     if ((rc = cn_embed0_bwd(R, D, F(L.xlive), F(L.e0), F(L.d_e0), L.e0_blocks, F(L.e0part), F(L.dwb), stream))) return rc;
 
     // ---- chain rule of the folds back to the factors + the strided pieces (one grouped launch) ----
@@ -517,7 +648,7 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
         FoldBuilder fb;
         const float *lin_w[3] = {P->q_w, P->k_w, P->v_w}, *lin_b[3] = {P->q_b, P->k_b, P->v_b};
         float *glin_w[3] = {g(G->q_w), g(G->k_w), g(G->v_w)}, *glin_b[3] = {g(G->q_b), g(G->k_b), g(G->v_b)};
-        for (int i = 0; i < 3; ++i) {
+        for (int i = 0; V.attn && i < 3; ++i) {
             const float *Wi = P->in_proj_w + (size_t)i * 512 * 512, *dWc = F(L.d_qkv_w) + (size_t)i * 512 * 512, *dbc = F(L.d_qkv_b) + i * 512;
             // d W_in[i] = dWc_i W_i^T + dbc_i (x) b_i ;  d W_i = W_in[i]^T dWc_i ;  d b_i = W_in[i]^T dbc_i
             FoldJob *j = fb.add(512, 512, g(G->in_proj_w) + (size_t)i * 512 * 512, 512);
@@ -526,8 +657,8 @@ extern "C" int cn_ppo_minibatch_step_sized(const cn_ppo_batch *bp, int64_t rows,
             FoldBuilder::seg(fb.add(512, 512, glin_w[i], 512), 512, Wi, 1, 512, dWc, 512, 1);
             FoldBuilder::seg(fb.add(512, 1, glin_b[i], 1), 512, Wi, 1, 512, dbc, 1, 0);
         }
-        fb.copy(1536, 1, g(G->in_proj_b), 1, F(L.d_qkv_b), 1);
-        { // os = spatial_linear o out_proj
+        if (V.attn) fb.copy(1536, 1, g(G->in_proj_b), 1, F(L.d_qkv_b), 1);
+        if (V.attn) { // os = spatial_linear o out_proj
             FoldJob *j = fb.add(256, 512, g(G->spatial_linear_w), 512);
             FoldBuilder::seg(j, 512, F(L.d_os_w), 512, 1, P->out_proj_w, 1, 512);
             FoldBuilder::seg(j, 1, F(L.d_os_b), 1, 0, P->out_proj_b, 0, 1);

@@ -80,13 +80,7 @@ class HipPolicy(HipHandle):
         self._self_attn = bool(enabled)
 
     def _weight_keys(self):
-        if getattr(self, "_self_attn", True):
-            return A.POLICY_WEIGHT_KEYS
-        # use_self_attn = False: the state dict has no spatial_attn.* tensors (those fields stay NULL) and spatial_linear is
-        # [.0: 128 x D, .2: 256 x 128]
-        remap = {"emb0_w": "base.spatial_linear.0.weight", "emb0_b": "base.spatial_linear.0.bias",
-                 "spatial_linear_w": "base.spatial_linear.2.weight", "spatial_linear_b": "base.spatial_linear.2.bias"}
-        return [(f, remap.get(f, k)) for f, k in A.POLICY_WEIGHT_KEYS if f in remap or not k.startswith("base.spatial_attn.")]
+        return A.policy_weight_keys(getattr(self, "_self_attn", True))     # use_self_attn = False: the remap, no spatial_attn.* entry
 
     def act(self, obs, hxs, masks, eps=None, out=None, row_plan=None):
         """row_plan: HipEnvBatch.row_plan of the batch that produced `obs` with its last reset() / step() (optional; see there)."""

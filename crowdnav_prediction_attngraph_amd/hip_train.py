@@ -588,16 +588,21 @@ class MinibatchStepper:
     """One PPO minibatch -- gather from the rollout storage, train-mode forward, losses, backward, every parameter gradient written into the
     caller's flat bucket -- as ONE boundary call (cn_ppo_minibatch_step; rl/networks/storage.py:184-253 + rl/networks/model.py:82-90 +
     rl/ppo/ppo.py:66-88).  Built by ppo.PPO for the default network sizes (SizedMinibatchStepper below: every sizes tuple of the device box); the
-    workspace is one cached byte tensor that grows with the row count."""
+    workspace is one cached byte tensor that grows with the row count.  The two switches of the network, base.use_self_attn and
+    base.sort_humans, travel as cn_ppo_variant (cn_ppo_minibatch_step_variant); with both on, the calls are the ones without a variant."""
 
     def __init__(self, policy):
         self.policy = policy
         self._ws = None
         self._ptrs = None
+        base = policy.base
+        self.self_attn, self.sort_humans = bool(getattr(base, "use_self_attn", True)), bool(getattr(base, "sort_humans", True))
+        # (field of cn_policy_weights, parameter name): the table the rollout handle sets its weights by (use_self_attn off: the remap)
+        self.weight_keys = A.policy_weight_keys(self.self_attn)
         # Parameters the call does not write: only the ones the loss never reaches (the reference leaves their .grad None).  Their slices of
         # the flat bucket still enter the all-reduce, the clip norm and Adam, so the caller keeps them zero (ppo.PPO._minibatch_step_producer); any
         # OTHER parameter outside cn_policy_weights would silently train on a stale gradient, hence the refusal here.
-        covered = {k for _, k in A.POLICY_WEIGHT_KEYS}
+        covered = {k for _, k in self.weight_keys}
         self.uncovered = [name for name, p in policy.named_parameters() if p.requires_grad and name not in covered]
         stray = [name for name in self.uncovered if not name.startswith("base.human_node_final_linear.")]
         if stray:
@@ -618,11 +623,18 @@ class MinibatchStepper:
         base = policy.base
         if getattr(policy, "is_srnn_baseline", False):      # DS-RNN: cn_ppo_minibatch_step knows the attention-graph network only
             return False
-        if not (base.use_self_attn and base.sort_humans and base.train_gemm_mode == "bf16x3" and base.train_fused_hh and base.train_fused_rn
+        if not (base.train_gemm_mode == "bf16x3" and base.train_fused_hh and base.train_fused_rn
                 and shapes_ok(base) and base.human_num <= 48 and base.edge_width <= 16):
             return False
-        if tuple(base.spatial_attn.embedding_layer[0].weight.shape) != (128, base.edge_width):
-            return False
+        if base.use_self_attn:
+            if tuple(base.spatial_attn.embedding_layer[0].weight.shape) != (128, base.edge_width):
+                return False
+        elif (tuple(base.spatial_linear[0].weight.shape) != (128, base.edge_width) or tuple(base.spatial_linear[2].weight.shape) != (256, 128)):
+            return False                                    # use_self_attn off: spatial_linear is the two-layer MLP the step runs
+        if not base.sort_humans:                            # the gather compacts by the storage's visibility bytes
+            vm = rollouts.obs.get("visible_masks")
+            if vm is None or not (vm.is_cuda and vm.dtype == torch.bool and vm.is_contiguous()):
+                return False
         need = ("robot_node", "temporal_edges", "spatial_edges", "detected_human_num")
         ts = [rollouts.obs.get(k) for k in need] + [rollouts.recurrent_hidden_states["human_node_rnn"], rollouts.masks, rollouts.actions,
                                                     rollouts.value_preds, rollouts.returns, rollouts.action_log_probs]
@@ -631,10 +643,10 @@ class MinibatchStepper:
     def _structs(self):
         """Parameter / gradient pointer structs (views of the flat buckets ppo.PPO binds; re-read whenever a pointer moved)."""
         named = dict(self.policy.named_parameters())
-        key = tuple((named[k].data_ptr(), named[k].grad.data_ptr()) for _, k in A.POLICY_WEIGHT_KEYS)
+        key = tuple((named[k].data_ptr(), named[k].grad.data_ptr()) for _, k in self.weight_keys)
         if self._ptrs is None or self._ptrs[0] != key:
-            w, g = A.PolicyWeights(), A.PolicyWeights()
-            for field, k in A.POLICY_WEIGHT_KEYS:
+            w, g = A.PolicyWeights(), A.PolicyWeights()     # use_self_attn off: the fields of the layers that do not exist stay NULL
+            for field, k in self.weight_keys:
                 p = named[k]
                 if p.dtype != torch.float32 or not p.is_cuda or not p.is_contiguous() or p.grad is None:
                     raise A.CnError("MinibatchStepper: parameter %s must be a contiguous float32 GPU tensor with a bound gradient" % k)
@@ -648,8 +660,23 @@ class MinibatchStepper:
         det = rollouts.obs["detected_human_num"]
         T, E = rollouts.rewards.shape[0], rollouts.rewards.shape[1]
         tot = torch.empty(E, dtype=torch.int32, device=det.device)
-        A.call("cn_ppo_row_totals", T, E, self.policy.base.human_num, A.ptr(det), A.ptr(tot), A.stream_ptr(), device=det.device)
+        if self.sort_humans:
+            A.call("cn_ppo_row_totals", T, E, self.policy.base.human_num, A.ptr(det), A.ptr(tot), A.stream_ptr(), device=det.device)
+        else:                                               # sort_humans off: max(1, visible) per sample, from the visibility bytes
+            A.call("cn_ppo_row_totals_visible", T, E, self.policy.base.human_num, A.ptr(self._visible(rollouts)), A.ptr(tot), A.stream_ptr(), device=det.device)
         return tot.cpu().to(torch.int64)
+
+    def _visible(self, rollouts):
+        vm = rollouts.obs.get("visible_masks")
+        if vm is None or not (vm.is_cuda and vm.dtype == torch.bool and vm.is_contiguous()):
+            raise A.CnError("MinibatchStepper: sort_humans = False needs rollouts.obs['visible_masks'] as a contiguous bool GPU tensor")
+        return vm
+
+    def _variant(self, rollouts):
+        """cn_ppo_variant of this policy on this storage, or None for the network without a variant (both switches on)."""
+        if self.self_attn and self.sort_humans:
+            return None
+        return A.PpoVariant(int(self.self_attn), int(self.sort_humans), None if self.sort_humans else self._visible(rollouts).data_ptr())
 
     def step(self, rollouts, advantages, env_idx, rows, hyper, losses_out, value_logp_out=None):
         """env_idx [N] int32 on the device, rows = their row total, hyper = (clip, value_loss_coef, entropy_coef, use_clipped_value_loss),
@@ -658,7 +685,8 @@ class MinibatchStepper:
         T, E = rollouts.rewards.shape[0], rollouts.rewards.shape[1]
         N, H, D = int(env_idx.numel()), base.human_num, base.edge_width
         dev = rollouts.rewards.device
-        need = self._workspace_bytes(T, N, H, D, int(rows))
+        v = self._variant(rollouts)
+        need = self._workspace_bytes(T, N, H, D, int(rows), v)
         if need <= 0:
             raise A.CnError("cn_ppo_minibatch_workspace_bytes: unsupported shape T=%d N=%d H=%d D=%d rows=%d" % (T, N, H, D, rows))
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
@@ -674,13 +702,19 @@ class MinibatchStepper:
             setattr(b, k, ts[k].data_ptr())
         hy = A.PpoHyper(float(hyper[0]), float(hyper[1]), float(hyper[2]), int(bool(hyper[3])))
         self._call(C.byref(b), int(rows), C.byref(w), C.byref(g), C.byref(hy), C.c_void_p(self._ws.data_ptr()), int(self._ws.numel()),
-                   A.ptr(losses_out), A.ptr(value_logp_out), A.stream_ptr(), dev)
+                   A.ptr(losses_out), A.ptr(value_logp_out), A.stream_ptr(), dev, v)
 
-    # the two boundary calls of step(): what SizedMinibatchStepper replaces
-    def _workspace_bytes(self, T, N, H, D, rows):
+    # the two boundary calls of step(): what SizedMinibatchStepper replaces.  v: the A.PpoVariant of _variant(), or None
+    _dims = None                                            # cn_policy_dims of the variant calls: NULL = the default tuple
+
+    def _workspace_bytes(self, T, N, H, D, rows, v=None):
+        if v is not None:
+            return int(A.lib().cn_ppo_minibatch_workspace_bytes_variant(T, N, H, D, rows, self._dims, C.byref(v)))
         return int(A.lib().cn_ppo_minibatch_workspace_bytes(T, N, H, D, rows))
 
-    def _call(self, b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev):
+    def _call(self, b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev, v=None):
+        if v is not None:
+            return A.call("cn_ppo_minibatch_step_variant", b, rows, w, g, hy, self._dims, C.byref(v), ws, ws_bytes, losses_out, value_logp_out, stream, device=dev)
         A.call("cn_ppo_minibatch_step", b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, device=dev)
 
 
@@ -694,6 +728,7 @@ class SizedMinibatchStepper(MinibatchStepper):
             self.dims = A.policy_dims(policy.base.dims)
         except NotImplementedError as e:
             raise A.CnError("SizedMinibatchStepper: %s" % e)
+        self._dims = C.byref(self.dims)
 
     @staticmethod
     def supported(policy, rollouts):
@@ -701,8 +736,12 @@ class SizedMinibatchStepper(MinibatchStepper):
         MinibatchStepper.supported.  False for the DS-RNN baseline."""
         return MinibatchStepper._supported(policy, rollouts, lambda base: base.sized_rn_ok())
 
-    def _workspace_bytes(self, T, N, H, D, rows):
+    def _workspace_bytes(self, T, N, H, D, rows, v=None):
+        if v is not None:
+            return super()._workspace_bytes(T, N, H, D, rows, v)
         return int(A.lib().cn_ppo_minibatch_workspace_bytes_sized(T, N, H, D, rows, C.byref(self.dims)))
 
-    def _call(self, b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev):
+    def _call(self, b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev, v=None):
+        if v is not None:
+            return super()._call(b, rows, w, g, hy, ws, ws_bytes, losses_out, value_logp_out, stream, dev, v)
         A.call("cn_ppo_minibatch_step_sized", b, rows, w, g, hy, C.byref(self.dims), ws, ws_bytes, losses_out, value_logp_out, stream, device=dev)

@@ -108,9 +108,10 @@ class PPO():
     # cn_ppo_minibatch_step gathers the minibatch from the storage by env index, runs the train-mode forward, the losses and the whole
     # backward, and WRITES every parameter gradient into the flat bucket: no autograd graph, no framework kernel between the rollout
     # storage and the Adam step.  The default network sizes run it through hip.MinibatchStepper, every other (R, M, A, O) of the device box
-    # through hip.SizedMinibatchStepper (cn_ppo_minibatch_step_sized).  use_minibatch_step = False keeps the autograd-joined path below for
-    # every network; the variants outside the step (use_self_attn / sort_humans off, fp32 arithmetic, crowds of 49 to 64 humans, edge widths
-    # above 16, the DS-RNN baseline, CPU tensors) always take it.
+    # through hip.SizedMinibatchStepper (cn_ppo_minibatch_step_sized); with use_self_attn or sort_humans off both pass the switches as
+    # cn_ppo_variant (cn_ppo_minibatch_step_variant).  use_minibatch_step = False keeps the autograd-joined path below for every network;
+    # what lies outside the step (fp32 arithmetic, crowds of 49 to 64 humans, edge widths above 16, the DS-RNN baseline, CPU tensors)
+    # always takes it.
     use_minibatch_step = True
 
     def _stepper_class(self, rollouts):

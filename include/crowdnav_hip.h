@@ -984,6 +984,30 @@ int64_t cn_ppo_minibatch_workspace_bytes_sized(int T, int N, int H, int D, int64
 int cn_ppo_minibatch_step_sized(const cn_ppo_batch *batch, int64_t rows, const cn_policy_weights *params, const cn_policy_weights *grads,
                                 const cn_ppo_hyper *hyper, const cn_policy_dims *dims, void *workspace, int64_t workspace_bytes,
                                 float *losses_out, float *value_logp_out, void *stream);
+/* The same step for the two switches of the attention-graph network the reference accepts besides its sizes (arguments.py:189, :206):
+ *   self_attn = 0    args.use_self_attn = False: no human-human attention.  In place of the human-human block the step runs the two-layer MLP
+ *                    out_sp = relu(relu(x W0^T + b0) W2^T + b2) on the compacted rows (cn_embed0_fwd, then cn_linear_fwd at K = 128, N = 256: the
+ *                    arithmetic of the rollout under cn_policy_set_self_attention(p, 0)) and its per-layer backward.  params / grads are read as
+ *                    cn_policy_set_weights reads them in that mode: emb0_w / emb0_b = base.spatial_linear.0 [128,D], spatial_linear_w / _b =
+ *                    base.spatial_linear.2 [256,128]; the fields emb2_w .. out_proj_b are not read and may be NULL.  The workspace holds none of the
+ *                    block's buffers: cn_ppo_minibatch_workspace_bytes_variant reports the smaller size this variant uses.
+ *   sort_humans = 0  args.sort_humans = False: the storage's spatial_edges are NOT sorted by detection; visible_masks = the storage's
+ *                    [T+1,E,H] visibility bytes (non-zero = visible) is required, detected_human_num is not read.  The gather moves each sample's
+ *                    visible humans to the front in index order, the others behind them in index order (the rule of cn_obs_compact_visible, an
+ *                    all-invisible sample keeps human 0), and counts max(1, visible) rows for it; everything behind the gather is unchanged.
+ *                    rows = sum over the minibatch of max(1, visible): cn_ppo_row_totals_visible gives the per-env totals over t < T.
+ * v == NULL and {1, 1, NULL} are cn_ppo_minibatch_step_sized itself (it forwards here): the same launches, the same bits, the same workspace size.
+ * visible_masks is ignored while sort_humans != 0.  sort_humans = 0 with visible_masks == NULL fails with CN_ERR_INVALID naming the field, like
+ * every other refusal before the first launch.  The shape box (1 <= H <= 48, 1 <= D <= 16, dims inside the device box) and
+ * cn_ppo_minibatch_max_rows() hold for every variant.  Gradients are written, not accumulated; summation orders are fixed.
+ * (CN_ABI_VERSION is unchanged: additions only; cn_ppo_batch and cn_policy_weights keep their layouts.) */
+typedef struct { int32_t self_attn; int32_t sort_humans; const uint8_t *visible_masks; } cn_ppo_variant;
+int64_t cn_ppo_minibatch_workspace_bytes_variant(int T, int N, int H, int D, int64_t rows, const cn_policy_dims *dims, const cn_ppo_variant *v);
+int cn_ppo_minibatch_step_variant(const cn_ppo_batch *batch, int64_t rows, const cn_policy_weights *params, const cn_policy_weights *grads,
+                                  const cn_ppo_hyper *hyper, const cn_policy_dims *dims, const cn_ppo_variant *v, void *workspace,
+                                  int64_t workspace_bytes, float *losses_out, float *value_logp_out, void *stream);
+/* totals [E] int32 (device) = sum over t < T of max(1, visible humans of env e at step t), visible_masks [T+1,E,H] bytes */
+int cn_ppo_row_totals_visible(int T, int E, int H, const uint8_t *visible_masks, int32_t *totals, void *stream);
 
 #ifdef __cplusplus
 }
