@@ -314,6 +314,9 @@ def main():
     if "--rollouts-only" in flags:
         rollout_case("varnum_e4_h5_t6", "CrowdSimVarNum-v0", 4, 5, 2, 6, 2)
         rollout_case("pred_e4_h20_t5", "CrowdSimPred-v0", 4, 20, 12, 5, 2)
+        rollout_case("varnum_e4_h50_t5", "CrowdSimVarNum-v0", 4, 50, 2, 5, 2)
+        rollout_case("varnum_e4_h64_t4", "CrowdSimVarNum-v0", 4, 64, 2, 4, 2)
+        rollout_case("pred_e2_h49_t3", "CrowdSimPred-v0", 2, 49, 12, 3, 1)
         return
     init_case()
     policy_case("varnum_e4_h20", "CrowdSimVarNum-v0", 4, 20, 2)
@@ -322,6 +325,9 @@ def main():
     policy_case("varnum_e3_h50", "CrowdSimVarNum-v0", 3, 50, 2)
     rollout_case("varnum_e4_h5_t6", "CrowdSimVarNum-v0", 4, 5, 2, 6, 2)
     rollout_case("pred_e4_h20_t5", "CrowdSimPred-v0", 4, 20, 12, 5, 2)
+    rollout_case("varnum_e4_h50_t5", "CrowdSimVarNum-v0", 4, 50, 2, 5, 2)
+    rollout_case("varnum_e4_h64_t4", "CrowdSimVarNum-v0", 4, 64, 2, 4, 2)
+    rollout_case("pred_e2_h49_t3", "CrowdSimPred-v0", 2, 49, 12, 3, 1)
 
 
 if __name__ == "__main__":

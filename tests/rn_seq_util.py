@@ -32,6 +32,10 @@ PLAN = {
 # of 32 (the weight gradients' row tail); H = 1 and 5 with ragged detected counts; one case at T = 1.
 SHAPES = [(3, 17, 5), (3, 33, 1), (1, 17, 5)]
 CASES = [(d, SHAPES[0]) for d in DIMS] + [(d, SHAPES[1]) for d in (DIMS[1], DIMS[2], DIMS[5])] + [(DIMS[2], SHAPES[2])]
+# Crowds of 49 to 64 humans: the temperature H / sqrt(A) and the two-pass (> 32 rows) robot-human attention inside the sequence.  Default dims at
+# the box edge H = 64 and at H = 49 past one 16-row GRU workgroup with a row tail (B = 51); A = 128 (the temperature reaches the kernel through
+# the host's scale) with the streamed GRU at H = 64.
+CASES += [(DIMS[3], (2, 5, 64)), (DIMS[3], (3, 17, 49)), (DIMS[1], (2, 5, 64))]
 
 VALUE_BAR = 1e-4              # value, logp, h_T: the project bar, absolute
 GRAD_REL, GRAD_ABS = 3e-4, 1e-7   # gradients: of the tensor's largest fp64 entry (tests/test_gpu_policy_sizes.py:279-282)
