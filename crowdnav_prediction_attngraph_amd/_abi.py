@@ -295,6 +295,7 @@ ABI_SYMBOLS = [
     "cn_gst_data_frames", "cn_gst_data_count", "cn_gst_data_fill", "cn_gst_gather_batch",
     "cn_srnn_create", "cn_srnn_destroy", "cn_srnn_set_weights", "cn_srnn_act", "cn_srnn_get_value", "cn_srnn_get_taps", "cn_srnn_set_gemm_mode",
     "cn_srnn_seq_workspace_bytes", "cn_srnn_seq_fwd", "cn_srnn_seq_bwd", "cn_srnn_attn_fwd", "cn_srnn_attn_bwd",
+    "cn_env_set_scene",
 ]
 
 _lib = None
@@ -337,6 +338,7 @@ def lib():
         L.cn_row_plan_words.argtypes = [C.c_int]
         L.cn_row_plan_build.argtypes = [i32, i32, vp, vp, vp]
         L.cn_env_get_state.argtypes = [vp, vp, vp, vp]
+        L.cn_env_set_scene.argtypes = [vp, vp, vp, vp, C.POINTER(Obs), vp]
         L.cn_env_get_danger_min_dist.argtypes = [vp, vp, vp]
         L.cn_env_set_case_counters.argtypes = [vp, vp, vp]
         L.cn_env_get_human_counts.argtypes = [vp, vp, vp]

@@ -34,6 +34,7 @@
 //                      is staged into LDS only by the (rare) wavefronts that draw from it; the 624-word twist is
 //                      lane-parallel.
 //   env_reset_kernel   reset (cn_env_reset);  env_pregen_kernel: next-episode staging on the side stream;
+//   env_scene_kernel   an episode started from the caller's records (cn_env_set_scene): a reset without the generator;
 //   env_post_kernel    the post-observation updates env_step_kernel deferred;  env_obs_kernel: second half of a split step
 // Reference semantics (file:line under the reference repo) are cited at each block.
 #include "common.h"
@@ -72,6 +73,36 @@ __global__ __launch_bounds__(64) void env_reset_kernel(EnvDev s, cn_obs ob, int 
     store_env(s, e, lane, rb, h);
     if (lane == 0) { s.shared_nd[e] = shared_nd; if (s.nh) s.nh[e] = n; }
     rng_store(R, s, e, lane);
+}
+
+// cn_env_set_scene: the selected envs start an episode from the caller's records (humans [E][H][8], robot [E][8]: cn_env_get_state's layout).
+// One wavefront per env, a lane per human, as in env_reset_kernel; start_episode (episode.h) is the half of a reset that does not generate.
+// Taken: px, py, vx, vy, gx, gy of the humans present, px, py, vx, vy, gx, gy, theta of the robot.  Kept: radius / v_pref (the private ORCA
+// simulators froze them: sim_valid stays as it is), the crowd size, the MT19937 stream (never loaded here, so no rng_store), the case counter,
+// the staged next episode.  An env that is not selected is neither loaded nor stored, and its observation rows are not written: write_obs
+// advances the belief of every human the robot does not see (l0 += l2 * time_step) and overwrites the previous velocities the const-vel
+// predictor reads, so a second observation of an unchanged state would not leave the env as it was.
+__global__ __launch_bounds__(64) void env_scene_kernel(EnvDev s, const uint8_t *select, const double *humans, const double *robot, cn_obs ob, int with_obs)
+{
+    const int lane = threadIdx.x;
+    const int e = blockIdx.x;
+    if (e == 0 && lane == 0) *s.lp3_cnt = 0; // the ORCA pass that follows starts with an empty linearProgram3 list
+    if (select && !select[e]) return;
+    Robot rb;
+    Lane h;
+    load_env(s, e, lane, rb, h);
+    const int H = s.H;
+    const int n = crowd_size(s, e);
+    if (lane < n) {
+        const double *src = humans + ((size_t)e * H + lane) * 8;
+        h.px = src[F_PX]; h.py = src[F_PY]; h.vx = src[F_VX]; h.vy = src[F_VY]; h.gx = src[F_GX]; h.gy = src[F_GY];
+    }
+    const double *r = robot + (size_t)e * 8;
+    rb.px = r[R_PX]; rb.py = r[R_PY]; rb.vx = r[R_VX]; rb.vy = r[R_VY]; rb.gx = r[R_GX]; rb.gy = r[R_GY]; rb.theta = r[R_THETA];
+    rb.pot = -fabs(norm2(rb.gx - rb.px, rb.gy - rb.py)); // as gen_episode
+    start_episode(s, e, lane, n, rb, h, ob, with_obs != 0);
+    if (!with_obs && lane == 0) s.pend[e] = 1;
+    store_env(s, e, lane, rb, h);
 }
 
 // Generates the NEXT episode of every env whose staging slot is empty (side stream, overlapped with the policy forward).
@@ -141,10 +172,12 @@ __global__ __launch_bounds__(64 * W) void env_post_kernel(EnvDev s)
 
 // Second half of a step when the observation needs the 'truth' roll-outs of the state just reached (sim.predict_method = 'truth'):
 // observation (reset or step form), then the post-observation updates of the envs that were not reset.
-__global__ __launch_bounds__(64) void env_obs_kernel(EnvDev s, cn_obs ob)
+// only_pending (cn_env_set_scene): the envs that were not just given a new start are left alone, observation rows included.
+__global__ __launch_bounds__(64) void env_obs_kernel(EnvDev s, cn_obs ob, int only_pending)
 {
     const int lane = threadIdx.x;
     const int e = blockIdx.x;
+    if (only_pending && !s.pend[e]) return;
     Rng R{MT_N, false};
     Robot rb;
     Lane h;
@@ -682,10 +715,10 @@ static int truth_rollout(cn_env_batch *env, hipStream_t st)
 
 // sim.predict_method = 'truth': roll the humans forward P times from the state the first half of the step (or the reset) left, then
 // write the observation and run the post-observation updates
-static int truth_rollout_and_obs(cn_env_batch *env, const cn_obs *obs, hipStream_t st)
+static int truth_rollout_and_obs(cn_env_batch *env, const cn_obs *obs, hipStream_t st, bool only_pending = false)
 {
     if (int rc = truth_rollout(env, st)) return rc;
-    hipLaunchKernelGGL(env_obs_kernel, dim3(env->d.E), dim3(64), 0, st, env->d, *obs);
+    hipLaunchKernelGGL(env_obs_kernel, dim3(env->d.E), dim3(64), 0, st, env->d, *obs, only_pending ? 1 : 0);
     CN_CHECK_LAUNCH();
     return CN_OK;
 }
@@ -1088,14 +1121,15 @@ extern "C" int cn_env_destroy(cn_env_batch *env)
     return CN_OK;
 }
 
-static int check_obs(const cn_obs *obs)
+// who: prefix of the message ("" as cn_env_reset / cn_env_step always reported it, "cn_env_set_scene: " for the call that names itself)
+static int check_obs(const cn_obs *obs, const char *who = "")
 {
     CN_REQUIRE(obs && obs->robot_node && obs->temporal_edges && obs->spatial_edges && obs->detected_human_num,
-               "observation pointers must be non-null (visible_masks may be null)");
+               "%sobservation pointers must be non-null (visible_masks may be null)", who);
     // the plan builder (row_plan.h) writes the plan as int4 (and reads detected_human_num as float4: a count view at an odd offset, e.g. a
     // storage row of a batch whose size is not a multiple of four, simply gets no plan -- prefetch_orca)
     CN_REQUIRE(!obs->row_plan || ((uintptr_t)obs->row_plan & 15u) == 0,
-               "cn_obs.row_plan must be 16-byte aligned and hold cn_row_plan_words(E) int32 words");
+               "%scn_obs.row_plan must be 16-byte aligned and hold cn_row_plan_words(E) int32 words", who);
     return CN_OK;
 }
 
@@ -1111,6 +1145,27 @@ extern "C" int cn_env_reset(cn_env_batch *env, const cn_obs *obs, void *stream)
     CN_CHECK_LAUNCH();
     if (split) { if (int rc = truth_rollout_and_obs(env, obs, st)) return rc; }
     env->reset_done = true;
+    return prefetch_orca(env, st, obs);
+}
+
+extern "C" int cn_env_set_scene(cn_env_batch *env, const uint8_t *select, const double *humans, const double *robot, const cn_obs *obs, void *stream)
+{
+    // every refusal in front of the first launch (and of the first read of *env: the pointers are looked at first)
+    CN_REQUIRE(env, "cn_env_set_scene: null handle");
+    CN_REQUIRE(humans && robot, "cn_env_set_scene: humans [E,H,8] and robot [E,8] are required (device, float64, cn_env_get_state's layout)");
+    if (int rc = check_obs(obs, "cn_env_set_scene: ")) return rc;
+    CN_REQUIRE(env->reset_done, "cn_env_set_scene: the batch was never reset (a scene keeps the radii, speed limits, crowd size and private "
+               "simulators the env's last reset made: call cn_env_reset first)");
+    CN_REQUIRE(env->d.cfg.env_kind != CN_ENV_COLLECT, "cn_env_set_scene: CrowdSimVarNumCollect-v0 takes no scenes");
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = sync_side(env, st)) return rc; // an in-flight prefetch reads the old state
+    const bool split = env->d.cfg.predict_truth != 0;
+    hipLaunchKernelGGL(env_scene_kernel, dim3(env->d.E), dim3(64), 0, st, env->d, select, humans, robot, *obs, split ? 0 : 1);
+    CN_CHECK_LAUNCH();
+    if (split) { if (int rc = truth_rollout_and_obs(env, obs, st, true)) return rc; }
+    // the velocities prefetched for the replaced state are dropped, those of the whole batch with them: one ORCA pass serves every env, and
+    // on an unchanged env it is a pure function of state the scene left alone
+    env->orca_ready = false;
     return prefetch_orca(env, st, obs);
 }
 

@@ -744,22 +744,33 @@ __device__ __forceinline__ void gen_episode(const S &s, Rng &R, int e, int lane,
     rb.pot = -fabs(norm2(rb.gx - rb.px, rb.gy - rb.py));
 }
 
-// the rest of reset(): belief cleared (:108), case counter advanced (:348), episode statistics, first observation
+// The start of an episode from the state in (rb, h), whoever made that state -- the generator (finish_reset) or the caller
+// (env_scene_kernel): belief cleared (:108), step counter and episode statistics zeroed, observation memory emptied, first observation.
+// Nothing here touches the MT19937 stream, the case counter or the staged next episode.
+template <class S>
+__device__ __forceinline__ void start_episode(const S &s, int e, int lane, int n, Robot &rb, Lane &h, const cn_obs &ob, bool with_obs)
+{
+    h.l0 = h.l1 = h.l2 = h.l3 = h.l4 = 0.0;
+    if (lane == 0) {
+        s.step_counter[e] = 0; s.ep_ret[e] = 0.0; s.ep_cnt[e] = 0;
+        if (s.nh) { s.obs_cnt[e] = 0; s.obs_max[e] = -1; } // :327 observed_human_ids = []
+        if (s.max_pid) s.max_pid[e] = n; // crowd_sim_var_num_collect.py:79-81
+    }
+    if (s.pred_id && lane < s.H) { s.pred_id[(size_t)e * s.H + lane] = lane; s.last_obs[(size_t)e * s.H + lane] = 0; }
+    if (with_obs) write_obs(s, e, lane, n, true, rb, h, ob, 0);
+}
+
+// the rest of reset(): what follows from np.random.seed and the case bookkeeping (:348), then the start of the episode
 template <class S>
 __device__ __forceinline__ void finish_reset(const S &s, int e, int lane, int n, uint64_t case_counter, Robot &rb, Lane &h, const cn_obs &ob, bool with_obs = true)
 {
     const auto &c = s.cfg;
-    h.l0 = h.l1 = h.l2 = h.l3 = h.l4 = 0.0;
     const uint64_t case_size = c.phase == CN_PHASE_TRAIN ? (4294967295ull - 2000ull) : (c.phase == CN_PHASE_VAL ? c.val_size : c.test_size);
     if (lane == 0) {
         s.case_counter[e] = (case_counter + (uint64_t)c.nenv) % case_size;
-        s.step_counter[e] = 0; s.ep_ret[e] = 0.0; s.ep_cnt[e] = 0;
-        if (s.nh) { s.obs_cnt[e] = 0; s.obs_max[e] = -1; } // :327 observed_human_ids = []
-        if (s.max_pid) s.max_pid[e] = n; // crowd_sim_var_num_collect.py:79-81
         if (s.wheel) { s.wheel[(size_t)e * 4 + 2] = 0.0; s.wheel[(size_t)e * 4 + 3] = 0.0; } // np.random.seed -> _legacy_seeding: has_gauss = 0
     }
-    if (s.pred_id && lane < s.H) { s.pred_id[(size_t)e * s.H + lane] = lane; s.last_obs[(size_t)e * s.H + lane] = 0; }
-    if (with_obs) write_obs(s, e, lane, n, true, rb, h, ob, 0);
+    start_episode(s, e, lane, n, rb, h, ob, with_obs);
 }
 
 // crowd_sim_var_num.py:303-363 reset.  Uses the pre-generated episode when the side stream has one ready (nx_ready and case_counter: the

@@ -206,7 +206,7 @@ def evaluate_batched(actor_critic, env_name, config, seed, test_size, device=Non
 
 
 def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=None, logging=None, predictor=None, poll_every=16, act_fn=None,
-                      hip_policy=None, use_kernel=True, per_env=None, frame_fn=None, pre_step_fn=None):
+                      hip_policy=None, use_kernel=True, per_env=None, frame_fn=None, pre_step_fn=None, scenes=None, max_steps=None):
     """test_size: the episode count of the sequential protocol (episode k runs case 2 k mod the config's test_size), or a sequence of case
     numbers to run instead (render_episodes).  poll_every: the count of running episodes is read back (the loop's only host synchronisation)
     every that many steps; steps taken after the last episode ended change nothing.  act_fn(t, obs) -> actions [E,2] replaces the policy forward (tests replay recorded actions);
@@ -216,7 +216,10 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     observation it returned, e.g. to draw the state (render_episodes); it must leave both as they are.  pre_step_fn(t, env, acc): called
     immediately BEFORE step t is taken with the HipEnvBatch and the accumulator, whose `active` / `steps` arrays then say which envs' first
     episode is still running and how many steps it has taken -- the moment to record the state a step is taken from (record_episodes;
-    after the step the env of a finished episode already holds its next episode's start); it must leave both as they are."""
+    after the step the env of a finished episode already holds its next episode's start); it must leave both as they are.
+    scenes=(humans [n,H,8], robot [n,8]) (evaluate_scenes): n envs, reset once and then started from these states (HipEnvBatch.set_scene)
+    instead of n test cases; test_size is ignored, per_env["cases"] is range(n), an episode still running after max_steps steps is reported
+    with outcome 0 instead of raising, and the return value is None.  max_steps: the step bound (default: round(time_limit / time_step) + 1)."""
     from .hip_env import HipEnvBatch
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     cfg = to_env_config(config, env_name, 1, "test")          # nenv = 1: case counters advance by one, as in the sequential run
@@ -225,9 +228,13 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
         raise ValueError("actor_critic is None but config.robot.policy is not 'orca'")
     if int(cfg.robot_policy) == 1 and int(cfg.randomize_attributes):
         raise NotImplementedError("an ORCA robot with randomised humans keeps ONE rvo2 simulator (radii / neighbour distance frozen in the "
-                                  "first episode) across the whole sequential run; use evaluate() for that configuration")
+                                  "first episode) across the whole sequential run; use evaluate() for that configuration"
+                                  + ("" if scenes is None else " (scenes: not covered either -- run the ORCA robot on scenes with env.randomize_attributes off)"))
     case_size = int(cfg.test_size)
-    if isinstance(test_size, (list, tuple)):
+    if scenes is not None:
+        case_of = list(range(int(scenes[0].shape[0])))
+        test_size = len(case_of)
+    elif isinstance(test_size, (list, tuple)):
         case_of, test_size = [int(c) for c in test_size], len(test_size)
     else:
         case_of = [(2 * k) % case_size for k in range(test_size)]  # reset() + the vec-env's auto-reset: two resets per episode
@@ -235,7 +242,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     E = len(cases)
     env = HipEnvBatch(cfg, E, int(seed), device=device)
     # env e draws seed offset + counter[e] + (seed + e): counter[e] = case - e  (cases are distinct and sorted, so case >= e)
-    env.set_case_counters(torch.tensor([c - e for e, c in enumerate(cases)], dtype=torch.int64))
+    if scenes is None:
+        env.set_case_counters(torch.tensor([c - e for e, c in enumerate(cases)], dtype=torch.int64))
     pretext = None
     if env_name == "CrowdSimPredRealGST-v0":
         # VecPretextNormalize over the batch: GST predictions into spatial_edges[:, :, 2:], rows sorted by distance.  Every episode evaluated
@@ -248,6 +256,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
                                    float(cfg.collision_penalty), device, pred_interval=interval)
         zero_reward = torch.zeros(E, device=device)
     obs = env.reset()
+    if scenes is not None:
+        obs = env.set_scene(*_scene_tensors(env, scenes[0], scenes[1]))
     if frame_fn is not None:
         frame_fn(0, env, obs)
     pol = None
@@ -260,7 +270,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     acc.start(obs["robot_node"])
     masks = acc.masks
     danger_dist = torch.zeros(E, dtype=torch.float64, device=device)
-    max_steps = int(round(float(cfg.time_limit) / float(cfg.time_step))) + 1
+    if max_steps is None:
+        max_steps = int(round(float(cfg.time_limit) / float(cfg.time_step))) + 1
     poll_every = max(1, int(poll_every))
     for t in range(max_steps):
         if scripted:
@@ -292,6 +303,8 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     r = acc.results()
     if per_env is not None:
         per_env.update(r, cases=cases)
+    if scenes is not None:
+        return None
     if any(o == 0 for o in r["outcome"]):
         raise ValueError("Invalid end signal from environment")
     rew_h = [round(x, 6) for x in r["ep_return"]]
@@ -300,6 +313,51 @@ def _evaluate_batched(actor_critic, env_name, config, seed, test_size, device=No
     pick = lambda xs: [xs[e] for e in order]
     return _summarise(pick(r["outcome"]), pick(r["steps"]), pick(r["path_length"]), pick(r["danger_steps"]), None, pick(rew_h), float(cfg.time_limit),
                       float(cfg.time_step), logging, danger_sums=pick(r["danger_sum"]))
+
+
+def _scene_tensors(env, humans, robot):
+    """Scenes as the caller wrote them -> the float64 device tensors HipEnvBatch.set_scene takes.  humans [n,H,8], or [n,H,6] (px, py, vx, vy,
+    gx, gy: the radius / v_pref columns are filled with the env's own, which a scene keeps anyway); robot [n,8], or [n,7] / [n,6] (the potential
+    is recomputed by the call; a missing theta is pi / 2, the heading a holonomic robot's reset gives it)."""
+    dev = env.device
+    humans = torch.as_tensor(humans, dtype=torch.float64).to(dev)
+    robot = torch.as_tensor(robot, dtype=torch.float64).to(dev)
+    if humans.dim() == 3 and humans.shape[2] == 6 and tuple(humans.shape[:2]) == (env.E, env.H):
+        own, _ = env.get_state()
+        humans = torch.cat([humans, own[:, :, 6:8]], dim=2)
+    if robot.dim() == 2 and robot.shape[1] in (6, 7):
+        pad = torch.zeros(robot.shape[0], 8 - robot.shape[1], dtype=torch.float64, device=dev)
+        if robot.shape[1] == 6:
+            pad[:, 0] = float(np.pi / 2.0)
+        robot = torch.cat([robot, pad], dim=1)
+    return humans.contiguous(), robot.contiguous()
+
+
+def evaluate_scenes(actor_critic, env_name, config, humans, robot, seed=0, act_fn=None, traces=False, max_steps=None, device=None,
+                    predictor=None, batch_invariant=False):
+    """Run a policy on n hand-built (or recorded) situations: the n scenes are the n envs of one batch, which is reset once (that draws each
+    env's radii, speed limits and random stream from `seed`), started from the scenes (HipEnvBatch.set_scene) and then driven by the loop of
+    evaluate_batched through each env's FIRST episode -- the one that starts at the scene: bookkeeping by cn_eval_accumulate, the count of running
+    episodes read back every 16 steps, no synchronisation per step.  Phase 'test', as in evaluate_batched.
+    humans [n,H,8] or [n,H,6], robot [n,8], [n,7] or [n,6] (numpy or torch; see _scene_tensors), H = human_num + human_num_range of the config.
+    actor_critic: a Policy of either base ('selfAttn_merge_srnn', 'srnn'); None with config.robot.policy 'orca' / 'social_force' runs the
+    scripted robot (the ORCA robot with env.randomize_attributes on is refused, as in evaluate_batched); act_fn(t, obs) -> actions [n,2] replaces the forward.  max_steps: step bound (default round(time_limit / time_step) + 1).
+    Returns a dict of per-scene host lists: outcome (the info code: 1 timeout, 2 collision, 3 goal reached; 0: still running after max_steps),
+    steps, ep_return, and from the recorded states (cn_trace_metrics) path_length -- over the states steps were taken FROM, so without the
+    final step's move -- and min_clearance.  traces=True: (that dict, EpisodeTraces) -- .figure() / .frames(scene index) draw them; record 0
+    of scene i is scene i itself."""
+    if env_name == "CrowdSimVarNumCollect-v0":
+        raise ValueError("evaluate_scenes: CrowdSimVarNumCollect-v0 takes no scenes")
+    rec = _TraceRecorder(config, env_name)
+    with _batch_invariant(actor_critic, batch_invariant):
+        _evaluate_batched(actor_critic, env_name, config, seed, 0, device, None, predictor=predictor, act_fn=act_fn, per_env=rec.per_env,
+                          pre_step_fn=rec, scenes=(humans, robot), max_steps=max_steps)
+    tr = rec.finish()
+    m = tr.metrics()
+    r = rec.per_env
+    out = dict(outcome=[int(o) for o in r["outcome"]], steps=[int(x) for x in r["steps"]], ep_return=list(r["ep_return"]),
+               path_length=m["path_length"].tolist(), min_clearance=m["min_clearance"].tolist())
+    return (out, tr) if traces else out
 
 
 FRAME_BUFFER_LIMIT = 4 << 30     # bytes of device memory render_episodes may ask for

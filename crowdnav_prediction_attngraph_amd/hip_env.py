@@ -116,6 +116,39 @@ class HipEnvBatch(HipHandle):
         A.call("cn_env_get_state", self._h, A.ptr(humans), A.ptr(robot), A.stream_ptr(), device=self.device)
         return humans, robot
 
+    def set_scene(self, humans, robot, select=None, obs=None, check=True):
+        """Start a new episode of the selected envs from a state of the caller's (cn_env_set_scene; include/crowdnav_hip.h is the definition):
+        humans [E,H,8] / robot [E,8] float64 device tensors in the layout of get_state() -- `env.set_scene(*other.get_state())` transplants a
+        state.  Taken: px, py, vx, vy, gx, gy of the humans present and px, py, vx, vy, gx, gy, theta of the robot; radius / v_pref and the crowd
+        size stay the env's, the potential is recomputed.  select: bool / uint8 [E] device tensor, None = every env; the rows of `obs` that
+        belong to other envs are left as they are, so with the default buffer (the one reset() / step() write) the result is a complete
+        observation of the batch.  Returns the observation dict.  The batch must have been reset once.
+        check=True (one host read-back; this is not a hot path) raises ValueError naming the env and slot for non-finite values and for
+        radius / v_pref columns that differ from the env's own; check=False goes straight to the launch.  Shapes, dtypes and devices are
+        checked either way (no read-back needed)."""
+        E, H = self.E, self.H
+        if torch.is_tensor(select) and select.dtype == torch.bool:
+            select = select.to(torch.uint8)
+        check_scene_tensors(humans, robot, select, E, H, self.device)
+        humans, robot = humans.contiguous(), robot.contiguous()
+        select = select.contiguous() if select is not None else None
+        if check:
+            own, _ = self.get_state()
+            counts = self.get_human_counts().to(torch.float64)
+            sel = torch.ones(E, dtype=torch.float64, device=self.device) if select is None else select.to(torch.float64)
+            host = torch.cat([humans.reshape(-1), robot.reshape(-1), own[:, :, 6:8].reshape(-1), counts, sel]).cpu().numpy()   # the one read-back
+            o = 0
+            parts = []
+            for n in (E * H * 8, E * 8, E * H * 2, E, E):
+                parts.append(host[o:o + n])
+                o += n
+            check_scene_values(parts[0].reshape(E, H, 8), parts[1].reshape(E, 8), parts[2].reshape(E, H, 2), parts[3].astype("int64"),
+                               parts[4] != 0)
+        obs = self.obs if obs is None else obs
+        o = A.obs_struct(obs, self.row_plan)
+        A.call("cn_env_set_scene", self._h, A.ptr(select), A.ptr(humans), A.ptr(robot), C.byref(o), A.stream_ptr(), device=self.device)
+        return obs
+
     def set_case_counters(self, counters):
         """counters: int64/uint64 [E] tensor; the next reset of env e generates test/train case `counters[e]` (+ its seed)."""
         c = torch.as_tensor(counters, dtype=torch.int64).to(self.device).contiguous()
@@ -207,6 +240,56 @@ class HipEnvBatch(HipHandle):
         return render_scenes(humans, robot, counts=counts, visible=visible, robot_heading=heading.contiguous(), dots=dots, dot_counts=dot_counts,
                              robot_radius=cfg.robot_radius, ring_radius=cfg.sensor_range + cfg.robot_radius + cfg.human_radius, size=size,
                              half_width=cfg.arena_size + 1.0 if half_width is None else half_width, out=out)
+
+
+def _scene_tensor(name, t, shape, dtype, device):
+    """set_scene's refusal of a wrong type, dtype, shape or device, by name (no device needed to decide)."""
+    if not torch.is_tensor(t):
+        raise ValueError("set_scene: %s must be a torch tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != dtype:
+        raise ValueError("set_scene: %s must be %s, got %s" % (name, dtype, t.dtype))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("set_scene: %s must have shape %s, got %s" % (name, list(shape), list(t.shape)))
+    device = torch.device(device)
+    if t.device.type != device.type or (device.index is not None and t.device.index != device.index):
+        raise ValueError("set_scene: %s must live on %s (the batch's device), got %s" % (name, device, t.device))
+
+
+def check_scene_tensors(humans, robot, select, E, H, device):
+    """The shape / dtype / device half of HipEnvBatch.set_scene's checks for a batch of E envs x H slots on `device`: ValueError naming the
+    argument.  select: uint8 [E] or None."""
+    _scene_tensor("humans", humans, (E, H, 8), torch.float64, device)
+    _scene_tensor("robot", robot, (E, 8), torch.float64, device)
+    if select is not None:
+        _scene_tensor("select", select, (E,), torch.uint8, device)
+
+
+def check_scene_values(humans, robot, own_attrs, counts, selected=None):
+    """The value half of set_scene(check=True), on host (numpy) arrays: humans [E,H,8], robot [E,8] as passed, own_attrs [E,H,2] the batch's
+    own radius / v_pref columns, counts [E] its crowd sizes, selected [E] bool (None: all).  ValueError naming the env and slot for a
+    non-finite value in a field the call takes (px .. gy of the humans present, px .. theta of the robot) and for a radius / v_pref that
+    differs from the env's own (a scene does not change them: include/crowdnav_hip.h); unselected envs and slots beyond the crowd are not
+    looked at."""
+    import numpy as np
+    names_h = ("px", "py", "vx", "vy", "gx", "gy", "radius", "v_pref")
+    names_r = ("px", "py", "vx", "vy", "gx", "gy", "theta")
+    E, H = humans.shape[0], humans.shape[1]
+    selected = np.ones(E, dtype=bool) if selected is None else np.asarray(selected, dtype=bool)
+    present = (np.arange(H)[None, :] < np.asarray(counts).reshape(E, 1)) & selected[:, None]
+    bad = np.argwhere(~np.isfinite(humans[:, :, 0:6]) & present[:, :, None])
+    if len(bad):
+        e, j, f = (int(x) for x in bad[0])
+        raise ValueError("set_scene: env %d human slot %d: %s is %r (must be finite)" % (e, j, names_h[f], float(humans[e, j, f])))
+    bad = np.argwhere(~np.isfinite(robot[:, 0:7]) & selected[:, None])
+    if len(bad):
+        e, f = (int(x) for x in bad[0])
+        raise ValueError("set_scene: env %d robot: %s is %r (must be finite)" % (e, names_r[f], float(robot[e, f])))
+    bad = np.argwhere((humans[:, :, 6:8] != own_attrs) & present[:, :, None])
+    if len(bad):
+        e, j, f = (int(x) for x in bad[0])
+        raise ValueError("set_scene: env %d human slot %d: %s is %r, the env's own is %r -- a scene keeps the radii and speed limits the env's "
+                         "last reset made (its private ORCA simulators froze them); take columns 6:8 from get_state()"
+                         % (e, j, names_h[6 + f], float(humans[e, j, 6 + f]), float(own_attrs[e, j, f])))
 
 
 def _check_tensors(who, items):

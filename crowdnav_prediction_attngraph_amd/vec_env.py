@@ -79,6 +79,33 @@ class BatchedCrowdSim(object):
         self._last_obs = obs
         return obs
 
+    def set_scene_device(self, humans, robot, select=None, check=True):
+        """HipEnvBatch.set_scene behind the wrapper processing reset_device applies.  The GST wrapper's observation history can only be reset
+        for the whole batch (VecPretextNormalize.reset()), so with it `select` must be None."""
+        if self._pretext is not None and select is not None:
+            raise ValueError("set_scene: with the GST prediction wrapper a scene is set for the whole batch (select=None): the wrapper's "
+                             "observation history is reset for all envs at once, and an env that kept its episode would lose its own")
+        obs = self._env.set_scene(humans, robot, select=select, check=check)
+        if self._pretext is not None:
+            self._pretext.reset_buffers()
+            obs, _ = self._apply_pretext(obs, torch.zeros(self.num_envs, device=self.device))
+        self._last_obs = obs
+        return obs
+
+    def set_scene(self, humans, robot, select=None):
+        """Start a new episode of every env (or of those `select` marks) from the caller's state and return the observation as reset() does:
+        humans [E,H,8] / robot [E,8] float64 in the layout of get_state().  Not part of the reference's vec-env interface."""
+        dev = self.device
+        humans = torch.as_tensor(humans, dtype=torch.float64).to(dev)
+        robot = torch.as_tensor(robot, dtype=torch.float64).to(dev)
+        if select is not None:
+            select = torch.as_tensor(select).to(dev).to(torch.uint8)
+        return self._export_obs(self.set_scene_device(humans, robot, select=select))
+
+    def get_state(self):
+        """(humans [E,H,8], robot [E,8]) float64 device tensors: what set_scene takes."""
+        return self._env.get_state()
+
     def step_device(self, actions):
         """-> obs dict (internal buffers, overwritten by the next step), reward [E], done [E] u8, info [E] u8, ep_return [E] f64, ep_len [E] i32.
         The Monitor episode return sums the raw env reward (before the GST social penalty), like the reference's wrapper order."""

@@ -199,6 +199,35 @@ int cn_env_join(cn_env_batch *env, void *stream);
 /* Debug/test access to the simulator state: copies humans [E,H,8] (px,py,vx,vy,gx,gy,radius,v_pref) and robot [E,8]
  * (px,py,vx,vy,gx,gy,theta,potential) as float64 into caller DEVICE buffers (either may be NULL). */
 int cn_env_get_state(cn_env_batch *env, double *humans, double *robot, void *stream);
+/* Scenes: the selected envs of a batch start a NEW episode from a state of the caller's -- a crossing built by hand, a recorded state, what
+ * cn_env_get_state gave a moment or a process ago.  What cn_env_get_state gives, this call takes.
+ *   select [E] uint8 (device), or NULL for every env.
+ *   humans [E,H,8] and robot [E,8] float64 (device) in the layout of cn_env_get_state.
+ * TAKEN from each selected env's rows: px, py, vx, vy, gx, gy of the first cn_env_get_human_counts human slots; px, py, vx, vy, gx, gy, theta
+ * of the robot.
+ * NOT TAKEN: human columns 6 and 7 (radius, v_pref) -- the env keeps what its last reset (or a respawn since) made them: every human's
+ * private ORCA simulator froze its own radius and speed limit and the radii it saw when it was built, and the neighbour distance of a
+ * randomised crowd was drawn with them, so other values would need those simulators rebuilt (refused: out of scope, like a change of the
+ * crowd size -- the crowd size stays the env's).  Robot column 7 (the potential) is recomputed as -||p - g||.
+ * For a selected env this is the start of an episode, with the bookkeeping of a reset that had generated exactly this state:
+ *   zeroed     the step counter (global time), the episode return and length;
+ *   reset      the potential; the observation memory a reset initialises -- the robot's beliefs about the humans (last_human_states) and with
+ *              them the previous velocities the const_vel predictor reads, the observed-human list of a varying crowd, human_visibility; and,
+ *              with sim.predict_method = 'truth', the roll-out of the new state behind the observation (as in cn_env_reset);
+ *   kept       the env's MT19937 stream where it stands (cached normal deviate included: the episode's random events -- goal changes,
+ *              respawns, crowd-size changes -- draw from it), its case counter and its pre-generated NEXT episode: the auto-reset that ends
+ *              the scene's episode starts the episode the env would have started next; the private simulators; a unicycle robot's commanded
+ *              speed and wheel filter (the reference never resets them either).
+ * The call then (1) writes the observation of the new state into the selected envs' rows of `obs` in reset form and builds the row plan of the
+ * whole `obs`, (2) drops the prefetched ORCA velocities of the whole batch and (3) prefetches again as cn_env_reset does.
+ * An env that is NOT selected keeps its state bit for bit, and its rows of `obs` are LEFT UNTOUCHED: writing an observation advances the
+ * belief about every human the robot does not see and replaces the velocities the const_vel predictor extrapolates, so it cannot be done
+ * twice for one state.  Pass the buffer that holds the batch's newest observation (what the last cn_env_reset / cn_env_step wrote) and `obs`
+ * is a complete observation of the batch afterwards, row plan included.
+ * No allocation, no host synchronisation.  CN_ERR_INVALID naming the call, before any launch: a NULL handle, humans, robot or obs (or a NULL
+ * required member of obs), a batch that was never reset, CrowdSimVarNumCollect-v0.  The values themselves are the caller's to check (the
+ * Python binding does: HipEnvBatch.set_scene(check=True)). */
+int cn_env_set_scene(cn_env_batch *env, const uint8_t *select, const double *humans, const double *robot, const cn_obs *obs, void *stream);
 /* ORCA velocities of the humans for the CURRENT state (the ones the next cn_env_step will apply; they are computed
  * ahead of time on an internal side stream, overlapped with the caller's policy forward), [E,H,2] float32 */
 int cn_env_get_human_actions(cn_env_batch *env, float *out, void *stream);
